@@ -9,6 +9,7 @@ that is already resident in HBM.  Default workload = BASELINE.json configs[2]: t
 (labels N A C G T X Y), chunksize 10000, batch 512 per GPU (--nbase 5 gives configs[1]).
 
   python bench.py --gpus 1 --steps 3 --warmup 1
+  python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR     (+ what the last timed step returned, as DIR/*.npy)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -30,6 +31,28 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 MFMA_F16_PEAK_TFLOPS = 2500.0  # dense fp16/bf16 MFMA peak
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir, seq, lens):
+    """--dump-outputs: what a caller of the timed path received from its last step, as float32 .npy files under out_dir:
+    seq.npy (chunks, T) the called sequences (ASCII codes, left-packed, zero padded) and seq_len.npy (chunks,).  With N > 1
+    the chunks are the gathered ones, rank by rank.  Outputs past DUMP_LIMIT_BYTES are cut to a fixed seeded sample of whole
+    chunks, in order, whose indices go to rows.npy."""
+    seq = seq.reshape(-1, seq.shape[-1]).cpu().numpy()
+    lens = lens.reshape(-1).cpu().numpy()
+    n, T = seq.shape
+    arrays = {}
+    max_rows = (DUMP_LIMIT_BYTES - 3 * 4096) // (4 * T + 4 + 8)     # a seq row, its length and its index; .npy headers
+    if n > max_rows:
+        rows = np.sort(np.random.default_rng(0).choice(n, max_rows, replace=False))
+        seq, lens = seq[rows], lens[rows]
+        arrays["rows"] = rows.astype(np.float64)
+    arrays["seq"] = seq.astype(np.float32)
+    arrays["seq_len"] = lens.astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(sd, features, n_base, L, chunks, alphabet, repeats=3):
@@ -115,7 +138,12 @@ def main():
                     help="N > 1: xb = xb_gather_called over librccl (C ABI); torch = torch.distributed all_gather")
     ap.add_argument("--force-gather", action="store_true",
                     help="run the deferred side-stream gather plumbing even with one rank (harness self-test)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned to DIR/<name>.npy (float32; inputs are "
+                         "seeded, so two builds can be compared output for output)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     from xna_basecaller_amd import _lib
@@ -189,12 +217,13 @@ def main():
             gather.submit(d_seq[b], d_len[b], ready)         # starts the gather of batch k-1
 
     def fence():
-        if gather is not None:
-            gather.flush()
+        """Wait for everything in flight; returns the last step's gathered (seq, lens) when there is a gather."""
+        gathered = gather.flush() if gather is not None else None
         ctx.synchronize()
         torch.cuda.synchronize()
         xdist.barrier()
         torch.cuda.synchronize()
+        return gathered
 
     for _ in range(args.warmup):
         step()
@@ -204,7 +233,7 @@ def main():
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
-    fence()
+    gathered = fence()
     dt = time.perf_counter() - t0
     if world > 1:
         import torch.distributed as tdist
@@ -213,10 +242,13 @@ def main():
         dt = float(tmax.item())
     stages = ctx.stage_times()
     ctx.set_profiling(False)
-    called = int(d_len[(state["k"] - 1) & 1].sum().item())
+    last = (state["k"] - 1) & 1
+    called = int(d_len[last].sum().item())
 
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *(gathered if gathered is not None else (d_seq[last], d_len[last])))
     K = args.steps
     samples = world * N * L * K
     value = samples / dt

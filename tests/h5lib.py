@@ -1,6 +1,7 @@
 """Test infrastructure: write HDF5 files through the REAL libhdf5 (ctypes), so that hdf5_lite meets files its author did
-not lay out byte by byte.  Only present in build containers that ship libhdf5 (here:
-/opt/conda/lib/libhdf5.so.103, HDF5 1.10.6); the tests skip without it, and nothing here travels into the product."""
+not lay out byte by byte.  Used by tests/golden/make_hdf5_golden.py on a machine that has libhdf5 (the
+stored files were written by HDF5 1.10.6); the tests read those files and need no libhdf5, and nothing here travels into
+the product."""
 import ctypes as C
 import glob
 import os
