@@ -148,6 +148,30 @@ XB_API int xb_decode_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int h
                          const char *alphabet, int8_t *d_labels, int8_t *d_seq, int32_t *d_seq_len);
 
 /*
+ * The same Viterbi decode with per-base qualities and moves (an extension: the reference's Viterbi branch writes the
+ * placeholder 'O' and all-zero moves, crf/basecall.py:60-76).  No reference vectors exist for it: PARITY UNPINNED.
+ * Specification, with the decode's own quantities (scores M, S = nb^sl, E = nb + 1, hi = nb^(sl-1), the Log-semiring alpha,
+ * beta (T+1, S) and logZ exactly as xb_crf_scans returns them, the decode's arithmetic contract):
+ *   path      f_t = the arg-max flat edge j*E + k of step t (the decode's label is k = f_t % E); s_t = f_t / E, the
+ *             destination state, i.e. the path's state at scan index t+1.
+ *   moves     m_t = (k != 0).
+ *   p_t       the k-mer posterior of the beam search, in its order of summation: P(x) = exp((alpha[t+1][x] + beta[t+1][x]) - logZ),
+ *             p = P(s_t); for b = 0..nb-1: p += P(s_t / nb + hi*b); p += P((s_t % hi)*nb + b);  clamped to [0, 1],
+ *             p_t = p > 0 ? exp(0.4 * log p) : 0.
+ *   quality   per emitting step t, over its run t .. u-1 (u = the next emitting step, or T): bp = sum p_u,
+ *             tot = sum (p_u + (nb-1) * ((1 - p_u) / (nb-1))) (the inner sum one term at a time), e = 1 - bp / tot,
+ *             q = e > 0 ? log(e) * -4.3429448190325175 : FLT_MAX, q = q * qscale, q = q + qoffset, clamped to [1, 50],
+ *             character (int)(33.5 + q).  Steps before the first move belong to no base.
+ * Viterbi and beam-search qualities of one model therefore share one scale.
+ *   seq, seq_len  byte-equal to xb_decode's;  qstring (n, T) int8: left-packed and zero-padded in parallel with seq (its i-th
+ *             non-zero byte is the quality of the i-th base);  moves (n, T) uint8 [optional]: m_t per time step (not packed).
+ */
+XB_API int xb_decode_q(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, const char *alphabet, float qscale,
+                       float qoffset, int8_t *seq, int8_t *qstring, uint8_t *moves, int32_t *seq_len);
+XB_API int xb_decode_q_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const char *alphabet, float qscale,
+                           float qoffset, int8_t *d_seq, int8_t *d_qstring, uint8_t *d_moves, int32_t *d_seq_len);
+
+/*
  * The Log-semiring scans of the CRF on their own (seqdist `sparse` operators behind crf/model.py:41-61): any of
  *   alpha (T+1, n, S)  CTC_CRF.forward_scores  (crf/model.py:50-54): alpha_0 = 0, alpha_{t+1}[j] = LSE_k(M[t,j,k] + alpha_t[idx[j,k]])
  *   beta  (T+1, n, S)  CTC_CRF.backward_scores (crf/model.py:56-60): beta_T = 0, beta_t[i] = LSE over edges (j,k) leaving i of
@@ -217,6 +241,9 @@ XB_API int xb_basecall_chunks(xb_ctx *ctx, const float *signal, int n, const cha
                               int8_t *seq, int32_t *seq_len);
 XB_API int xb_basecall_chunks_dev(xb_ctx *ctx, const float *d_signal, int n, const char *alphabet,
                                   int8_t *d_seq, int32_t *d_seq_len);
+/* ... with the qualities and moves of xb_decode_q (moves may be NULL). */
+XB_API int xb_basecall_chunks_q(xb_ctx *ctx, const float *signal, int n, const char *alphabet, float qscale, float qoffset,
+                                int8_t *seq, int8_t *qstring, uint8_t *moves, int32_t *seq_len);
 /* Opt in to the co-scheduling of two calls in flight (see the header comment) and make room for it: the workspaces for
  * max_batch chunks are replaced by twice that -- which waits for everything in flight and takes a second or two, so callers
  * do it once, up front (bench.py: outside its timed region; Model: when the host pipeline starts).  XB_OK also when the
@@ -240,6 +267,14 @@ XB_API int xb_pairing_active(const xb_ctx *ctx);
 #define XB_PIPELINE_SLOTS 4
 XB_API int xb_submit_chunks(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet);
 XB_API int xb_collect_chunks(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len);
+/* The pipeline with the qualities and moves of xb_decode_q: the slot's pinned staging for them is allocated by its first
+ * _q submission.  xb_collect_chunks_q collects a _q submission only (XB_ERR_STATE otherwise; moves may be NULL);
+ * xb_collect_chunks of a _q submission returns its bases alone.  Co-scheduling (xb_reserve_pairing): a _q call pairs only
+ * with a _q call of the same qscale / qoffset, a plain call only with a plain call -- a held call that finds no such partner
+ * runs on its own, so every call produces exactly the bytes it produces unpaired. */
+XB_API int xb_submit_chunks_q(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet, float qscale,
+                              float qoffset);
+XB_API int xb_collect_chunks_q(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len, int8_t *qstring, uint8_t *moves);
 
 XB_API int xb_synchronize(xb_ctx *ctx);
 

@@ -27,6 +27,7 @@ EXPORTS = [
     "xb_comm_unique_id", "xb_comm_create", "xb_comm_destroy", "xb_comm_rank", "xb_comm_world", "xb_comm_last_error",
     "xb_gather_called", "xb_comm_fence", "xb_comm_synchronize", "xb_stream_wait_event", "xb_align_accuracy",
     "xb_beam_search", "xb_beam_search_dev", "xb_basecall_chunks_beam", "xb_reserve_pairing", "xb_pairing_active", "xb_debug_layer_output",
+    "xb_decode_q", "xb_decode_q_dev", "xb_basecall_chunks_q", "xb_submit_chunks_q", "xb_collect_chunks_q",
 ]
 XB_COMM_ID_BYTES = 128
 # xb_status (include/xna_basecaller.h)
@@ -107,6 +108,11 @@ def load():
     lib.xb_ctc_alignments.argtypes = [vp, vp, ip, ip, vp, ip, vp, vp, vp]
     lib.xb_submit_chunks.argtypes = [vp, ip, vp, ip, C.c_char_p]
     lib.xb_collect_chunks.argtypes = [vp, ip, vp, vp]
+    lib.xb_decode_q.argtypes = [vp, vp, ip, ip, ip, C.c_char_p, fl, fl, vp, vp, vp, vp]
+    lib.xb_decode_q_dev.argtypes = [vp, vp, ip, ip, ip, C.c_char_p, fl, fl, vp, vp, vp, vp]
+    lib.xb_basecall_chunks_q.argtypes = [vp, vp, ip, C.c_char_p, fl, fl, vp, vp, vp, vp]
+    lib.xb_submit_chunks_q.argtypes = [vp, ip, vp, ip, C.c_char_p, fl, fl]
+    lib.xb_collect_chunks_q.argtypes = [vp, ip, vp, vp, vp, vp]
     lib.xb_result_stream.argtypes = [vp]
     lib.xb_result_stream.restype = C.c_void_p
     lib.xb_set_profiling.argtypes = [vp, ip]
@@ -312,6 +318,55 @@ class Context:
         self._check(self.lib.xb_basecall_chunks(self.h, signal.ctypes.data, n, "".join(alphabet).encode(),
                                                 seq.ctypes.data, lens.ctypes.data))
         return seq, lens
+
+    # ---- Viterbi decode with qualities and moves (xb_decode_q: an extension, parity unpinned) ----------
+    def decode_q(self, scores, alphabet, qscale=1.0, qoffset=0.0, has_blank=None):
+        """xb_decode_q: scores (T, n, C) -> (seq (n, T) int8, lens (n,), qstring (n, T) int8 left-packed beside seq,
+        moves (n, T) uint8)."""
+        scores = np.ascontiguousarray(scores, dtype=np.float32)
+        T, n, Cin = scores.shape
+        if has_blank is None:
+            has_blank = Cin == self.C_blank
+        if Cin != (self.C_blank if has_blank else self.C_noblank):
+            raise ValueError("scores last dim %d does not match the model (%d with blanks, %d without)"
+                             % (Cin, self.C_blank, self.C_noblank))
+        seq, q, mv = (np.empty((n, T), dtype=np.int8), np.empty((n, T), dtype=np.int8), np.empty((n, T), dtype=np.uint8))
+        lens = np.empty((n,), dtype=np.int32)
+        self._check(self.lib.xb_decode_q(self.h, scores.ctypes.data, T, n, int(bool(has_blank)), "".join(alphabet).encode(),
+                                         float(qscale), float(qoffset), seq.ctypes.data, q.ctypes.data, mv.ctypes.data,
+                                         lens.ctypes.data))
+        return seq, lens, q, mv
+
+    def decode_q_dev(self, d_scores, T, n, has_blank, alphabet, qscale, qoffset, d_seq, d_qstring, d_moves, d_len):
+        self._check(self.lib.xb_decode_q_dev(self.h, _ptr(d_scores), int(T), int(n), int(bool(has_blank)),
+                                             "".join(alphabet).encode(), float(qscale), float(qoffset), _ptr(d_seq),
+                                             _ptr(d_qstring), _ptr(d_moves), _ptr(d_len)))
+
+    def basecall_chunks_q(self, signal, alphabet, qscale=1.0, qoffset=0.0):
+        """xb_basecall_chunks_q: signal (n, chunk_len) -> (seq, lens, qstring, moves) as decode_q returns them."""
+        signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1, self.chunk_len)
+        n = signal.shape[0]
+        seq, q, mv = (np.empty((n, self.T), dtype=np.int8), np.empty((n, self.T), dtype=np.int8),
+                      np.empty((n, self.T), dtype=np.uint8))
+        lens = np.empty((n,), dtype=np.int32)
+        self._check(self.lib.xb_basecall_chunks_q(self.h, signal.ctypes.data, n, "".join(alphabet).encode(), float(qscale),
+                                                  float(qoffset), seq.ctypes.data, q.ctypes.data, mv.ctypes.data,
+                                                  lens.ctypes.data))
+        return seq, lens, q, mv
+
+    def submit_chunks_q(self, slot, signal, alphabet, qscale=1.0, qoffset=0.0):
+        signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1, self.chunk_len)
+        self._check(self.lib.xb_submit_chunks_q(self.h, int(slot), signal.ctypes.data, signal.shape[0],
+                                                "".join(alphabet).encode(), float(qscale), float(qoffset)))
+        return signal.shape[0]
+
+    def collect_chunks_q(self, slot, n):
+        seq, q, mv = (np.empty((n, self.T), dtype=np.int8), np.empty((n, self.T), dtype=np.int8),
+                      np.empty((n, self.T), dtype=np.uint8))
+        lens = np.empty((n,), dtype=np.int32)
+        self._check(self.lib.xb_collect_chunks_q(self.h, int(slot), seq.ctypes.data, lens.ctypes.data, q.ctypes.data,
+                                                 mv.ctypes.data))
+        return seq, lens, q, mv
 
     # ---- beam search with qualities and moves (koi.decode.beam_search at crf/basecall.py:43-46) ----------
     def _beam_out(self, n, T):

@@ -6,7 +6,8 @@ arguments, flags, defaults and stderr lines; FASTQ (or, redirected to `*.sam`, u
 Differences, all outside the hot path: reads come from `*.xsig.npz` signal bundles (no HDF5/VBZ reader in
 this image, see reads.py); --reference / --modified-bases / --save-ctc are rejected (mappy / remora /
 CTCWriter are not on the north-star path); under torchrun (WORLD_SIZE > 1) reads are sharded over the
-ranks and gathered to rank 0 over RCCL before writing.
+ranks and gathered to rank 0 over RCCL before writing.  Extension: --qscores writes the Viterbi decode's device
+qualities (xb_decode_q) in place of the reference's placeholder 'O'; without it the output is unchanged.
 """
 import os
 import sys
@@ -149,10 +150,12 @@ def main(args):
         groups = get_read_groups(args.reads_directory, args.model_directory, recursive=args.recursive,
                                  read_ids=column_to_set(args.read_ids), skip=args.skip, n_proc=n_proc)
 
+    # --qscores (an extension): the Viterbi decode's device qualities instead of the reference's 'O' placeholders
+    extra = {"qscores": True} if args.qscores else {}
     results = basecall(model, reads, reverse=args.revcomp,
                        batchsize=model.config["basecaller"]["batchsize"],
                        chunksize=model.config["basecaller"]["chunksize"],
-                       overlap=model.config["basecaller"]["overlap"])
+                       overlap=model.config["basecaller"]["overlap"], **extra)
 
     t0 = perf_counter()
     if world > 1:
@@ -198,6 +201,9 @@ def argparser():
     parser.add_argument("--skip", action="store_true", default=False)
     parser.add_argument("--save-ctc", action="store_true", default=False)
     parser.add_argument("--revcomp", action="store_true", default=False)
+    parser.add_argument("--qscores", action="store_true", default=False,
+                        help="Viterbi decode: per-base qualities computed on the device (path posteriors, calibrated by the "
+                             "model's [qscore] scale / bias) instead of the placeholder 'O'; not in the reference CLI")
     parser.add_argument("--recursive", action="store_true", default=False)
     quant_parser = parser.add_mutually_exclusive_group(required=False)
     quant_parser.add_argument("--quantize", dest="quantize", action="store_true")

@@ -51,13 +51,16 @@ def stitch_results(results, length, size, overlap, stride, reverse=False):
 
 
 def compute_scores(model, batch, beam_width=32, beam_cut=100.0, scale=1.0, offset=0.0, blank_score=2.0,
-                   reverse=False):
+                   reverse=False, qscores=False):
     """
     crf/basecall.py:27-82: (n,1,L) batch -> {'sequence': int8 (n,T), 'qstring': int8 (n,T), 'moves': bool (n,T)}.
     Viterbi branch (expand_blanks, the only one the reference reaches for XNA alphabets): left-packed ASCII rows, 'O'
-    placeholders, no moves -- one fused device call; the per-character Python loops of the reference are gone.
+    placeholders, no moves -- one fused device call; the per-character Python loops of the reference are gone.  With
+    qscores (an extension, parity unpinned): the device's per-base qualities, left-packed beside the bases, and the
+    per-step moves (xb_basecall_chunks_q; xb_decode_q on the host-reversed scores with reverse), qscale / qoffset from
+    the config's [qscore] section.
     Beam branch (expand_blanks = False, `koi.decode.beam_search`): bases and quality characters at the blocks that emit,
-    real moves -- xb_basecall_chunks_beam, for any alphabet the CRF supports.
+    real moves -- xb_basecall_chunks_beam, for any alphabet the CRF supports.  `qscores` changes nothing there.
     """
     if not model.encoder[-1].expand_blanks:
         own = model.encoder[-1].blank_score
@@ -70,6 +73,14 @@ def compute_scores(model, batch, beam_width=32, beam_cut=100.0, scale=1.0, offse
         else:
             res = model.basecall_chunks_beam(batch, beam_width, beam_cut, scale, offset)
         return {"qstring": res["qstring"], "sequence": res["sequence"], "moves": res["moves"].astype(bool)}
+    if qscores:
+        if reverse:
+            scores = model.seqdist.reverse_complement(model(batch))
+            ctx = model.context(np.asarray(batch).shape[-1], scores.shape[1])
+            sequence, _, qstring, moves = ctx.decode_q(scores, model.alphabet, *model.qscore_params())
+        else:
+            sequence, _, qstring, moves = model.basecall_chunks(batch, qscores=True)
+        return {"qstring": qstring, "sequence": sequence, "moves": moves.astype(bool)}
     if reverse:
         scores = model.seqdist.reverse_complement(model(batch))
         ctx = model.context(np.asarray(batch).shape[-1], scores.shape[1])
@@ -89,7 +100,7 @@ def _scores_dict(sequence):
     }
 
 
-def compute_sequences_pipelined(model, batches, reverse=False):
+def compute_sequences_pipelined(model, batches, reverse=False, qscores=False):
     """
     The device stage of `basecall`: (key, batch) stream -> (key, sequence (n,T) int8 left-packed ASCII) with several batches
     in flight on the device: batch k+1 is submitted (pinned staging, H2D on a copy stream, fused kernels, D2H) before
@@ -98,38 +109,50 @@ def compute_sequences_pipelined(model, batches, reverse=False):
     slots -- batch k+3 is submitted before batch k is collected, so pair (k+2, k+3) is on the device, its H2D copies done,
     while the host waits for pair (k, k+1) -- otherwise two.  Results come out in input order, depth - 1 batches late.
     (compute_scores is the same operator, synchronous, with the reference's full result dict.)
+    With qscores every item is instead compute_scores' dict with the device qualities and moves (Viterbi branch).
     """
     if reverse or not model.encoder[-1].expand_blanks:
         for key, batch in batches:                       # decode of host-side reverse-complemented scores: synchronous
-            yield key, compute_scores(model, batch, reverse=reverse)["sequence"]
+            res = compute_scores(model, batch, reverse=reverse, qscores=qscores)
+            yield key, res if qscores else res["sequence"]
         return
+
+    def submit(slot, batch):
+        return model.submit_chunks(slot, batch, qscores=True) if qscores else model.submit_chunks(slot, batch)
+
+    def collect(handle):
+        out = model.collect_chunks(handle)
+        if qscores:
+            return {"qstring": out[2], "sequence": out[0], "moves": out[3].astype(bool)}
+        return out[0]
+
     pending, slot, depth = deque(), 0, 2
     for key, batch in batches:
         shape = np.asarray(batch).shape
         if pending and not model.context_is_current(shape[-1], shape[0]):
             while pending:                                                # drain before the context is rebuilt
                 k, h = pending.popleft()
-                yield k, model.collect_chunks(h)[0]
+                yield k, collect(h)
         if not pending:
             depth, slot = model.pipeline_depth(shape[-1], shape[0]), 0
-        pending.append((key, model.submit_chunks(slot, batch)))
+        pending.append((key, submit(slot, batch)))
         slot = (slot + 1) % depth
         if len(pending) == depth:                                         # the slot the next batch goes into
             k, h = pending.popleft()
-            yield k, model.collect_chunks(h)[0]
+            yield k, collect(h)
     while pending:
         k, h = pending.popleft()
-        yield k, model.collect_chunks(h)[0]
+        yield k, collect(h)
 
 
-def compute_scores_pipelined(model, batches, reverse=False):
+def compute_scores_pipelined(model, batches, reverse=False, qscores=False):
     """compute_scores over a stream of (key, batch), two batches in flight; yields the reference's result dicts."""
     if not model.encoder[-1].expand_blanks:              # beam search: qualities and moves are real, one batch at a time
         for key, batch in batches:
             yield key, compute_scores(model, batch, reverse=reverse)
         return
-    for key, sequence in compute_sequences_pipelined(model, batches, reverse=reverse):
-        yield key, _scores_dict(sequence)
+    for key, res in compute_sequences_pipelined(model, batches, reverse=reverse, qscores=qscores):
+        yield key, res if qscores else _scores_dict(res)
 
 
 def to_str(x, encoding="ascii"):
@@ -163,22 +186,25 @@ def _called(model, sequence):
 
 
 def _called_beam(model, attrs):
-    """crf/basecall.py:85-93 on stitched beam-search results, plus the mean quality the writers print."""
+    """crf/basecall.py:85-93 on stitched results with real qualities (beam search, or Viterbi with qscores), plus the mean
+    quality the writers print."""
     out = apply_stride_to_moves(model, attrs)
     out["mean_qscore"] = mean_qscore_from_qstring(out["qstring"]) if out["qstring"] else 0.0
     return out
 
 
-def basecall(model, reads, chunksize=4000, overlap=100, batchsize=32, reverse=False):
-    """Basecall `reads` (objects with .signal); yields (read, {'sequence','qstring','sig_move'}) in input order."""
+def basecall(model, reads, chunksize=4000, overlap=100, batchsize=32, reverse=False, qscores=False):
+    """Basecall `reads` (objects with .signal); yields (read, {'sequence','qstring','sig_move'}) in input order.
+    qscores: the Viterbi branch writes the device's per-base qualities (compute_scores) instead of the 'O' placeholders;
+    their rows are stitched like the sequence rows, so len(qstring) == len(sequence), and the moves are stitched in time."""
     chunks = thread_iter(
         ((read, 0, len(read.signal)), chunk(np.asarray(read.signal, dtype=np.float32), chunksize, overlap))
         for read in reads
     )
     batches = thread_iter(batchify(chunks, batchsize=batchsize))
-    if not model.encoder[-1].expand_blanks:
+    if qscores or not model.encoder[-1].expand_blanks:
         # the reference's own five stages (crf/basecall.py:96-122): result dicts are unbatched and stitched plane by plane
-        scores = thread_iter(compute_scores_pipelined(model, batches, reverse=reverse))
+        scores = thread_iter(compute_scores_pipelined(model, batches, reverse=reverse, qscores=qscores))
         results = thread_iter(
             (read, stitch_results(attrs, end - start, chunksize, overlap, model.stride, reverse))
             for ((read, start, end), attrs) in unbatchify(scores)

@@ -53,6 +53,10 @@ struct xb_ctx {
         hipEvent_t h2d = nullptr, done = nullptr;
         int n = 0;
         bool busy = false;
+        // qualities and moves (xb_submit_chunks_q): pinned + device staging, allocated by the slot's first _q submission
+        int8_t *h_q = nullptr, *d_q = nullptr;
+        uint8_t *h_mv = nullptr, *d_mv = nullptr;
+        bool qs = false;                       // the batch in flight was submitted with qualities
     } slots[XB_PIPELINE_SLOTS];
     bool pipeline_failed = false;          // a collected batch reported a lost rendezvous: every batch in flight fails with it
     hipStream_t stream_copy = nullptr;     // H2D of the next batch beside the compute of the current one
@@ -110,6 +114,10 @@ struct xb_ctx {
     uint8_t *beam_moves = nullptr;
     int8_t *labels = nullptr, *seq = nullptr;
     int32_t *seq_len = nullptr;
+    // Viterbi qualities (xb_decode_q, lazily allocated): device staging of the host-pointer calls (max_batch, T) and the
+    // results of a co-scheduled pair of _q calls before they are split (2 max_batch, T)
+    int8_t *q_seq = nullptr, *q_fseq = nullptr;
+    uint8_t *q_moves = nullptr, *q_fmoves = nullptr;
     unsigned *sync = nullptr;    // [64 groups * 32] counters + error word at the end
     unsigned *error = nullptr;
     int lstm_mode = 0;
@@ -149,6 +157,10 @@ struct xb_ctx {
         int slot = -1;                          // host pipeline slot whose D2H copies and done event follow the launch
         void (*after)(void *) = nullptr;        // xb_comm: the gather of this call's results, enqueued right behind it
         void *after_arg = nullptr;
+        int qs = 0;                             // 1: the decode's quality variant (xb_basecall_chunks_q / xb_submit_chunks_q)
+        float qscale = 1.0f, qoffset = 0.0f;
+        int8_t *qstr = nullptr;                 // (n, T) device, required with qs
+        uint8_t *moves = nullptr;               // (n, T) device or nullptr
     };
     int fuse_ok = 1;                            // pairing is possible in this context (schedule, batch size, XB_FUSE)
     int fuse = 0;                               // ... and the caller asked for it (xb_reserve_pairing)
@@ -735,8 +747,16 @@ struct ScanOut {
     float *alpha = nullptr, *beta = nullptr, *logz = nullptr, *post = nullptr;   // device; post has row stride ldq
 };
 
+// qualities and moves of the Viterbi decode (xb_decode_q): the kernel's quality variant, beta rows into the beta stash
+struct QualOut {
+    int8_t *qstr = nullptr;      // (n, T) device
+    uint8_t *moves = nullptr;    // (n, T) device or nullptr
+    float qscale = 1.0f, qoffset = 0.0f;
+};
+
 int run_decode(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, int ld, const char *alphabet,
-               int8_t *d_labels, int8_t *d_seq, int32_t *d_len, hipStream_t st = nullptr, const ScanOut *scan = nullptr)
+               int8_t *d_labels, int8_t *d_seq, int32_t *d_len, hipStream_t st = nullptr, const ScanOut *scan = nullptr,
+               const QualOut *qual = nullptr)
 {
     if (!st) st = ctx->stream;
     const xb_config &c = ctx->cfg;
@@ -755,6 +775,11 @@ int run_decode(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, 
         p.stop_after = (scan->beta || scan->post) ? 2 : 1;
     }
     p.labels = d_labels; p.seq = d_seq; p.seq_len = d_len;
+    if (qual) {
+        if (!qual->qstr || !d_seq) return fail(ctx, XB_ERR_INVALID, "qualities need the seq and qstring outputs");
+        p.qstr = qual->qstr; p.moves = qual->moves; p.qscale = qual->qscale; p.qoffset = qual->qoffset;
+        p.beta_out = ctx->beta;
+    }
     memset(p.alphabet, 0, sizeof p.alphabet);
     if (alphabet) {
         if ((int)strlen(alphabet) < c.n_base + 1) return fail(ctx, XB_ERR_INVALID, "alphabet needs %d symbols", c.n_base + 1);
@@ -783,6 +808,19 @@ int join_async_decode(xb_ctx *ctx)
             ctx->dec_pending[p] = false;
         }
     return XB_OK;
+}
+
+// device staging of the quality calls (once per context)
+int ensure_q_staging(xb_ctx *ctx)
+{
+    const size_t N = (size_t)ctx->cfg.max_batch, T = (size_t)ctx->T;
+    int rc = ctx->q_seq ? XB_OK : dev_alloc(ctx, &ctx->q_seq, N * T);
+    if (!rc && !ctx->q_moves) rc = dev_alloc(ctx, &ctx->q_moves, N * T);
+    if (ctx->fuse_ok) {      // a pair of _q calls (enqueue_call pairs none while these are missing)
+        if (!rc && !ctx->q_fseq) rc = dev_alloc(ctx, &ctx->q_fseq, 2 * N * T);
+        if (!rc && !ctx->q_fmoves) rc = dev_alloc(ctx, &ctx->q_fmoves, 2 * N * T);
+    }
+    return rc;
 }
 
 int sync_all(xb_ctx *ctx)
@@ -960,6 +998,8 @@ XB_API void xb_ctx_destroy(xb_ctx *ctx)
         if (sl.h_seq) (void)hipHostFree(sl.h_seq);
         if (sl.h_len) (void)hipHostFree(sl.h_len);
         if (sl.h_err) (void)hipHostFree(sl.h_err);
+        if (sl.h_q) (void)hipHostFree(sl.h_q);
+        if (sl.h_mv) (void)hipHostFree(sl.h_mv);
         if (sl.h2d) (void)hipEventDestroy(sl.h2d);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
@@ -1188,6 +1228,45 @@ XB_API int xb_decode(xb_ctx *ctx, const float *scores, int T, int n, int has_bla
     if (rc) return rc;
     if (labels) XB_HIP(ctx, hipMemcpyAsync(labels, ctx->labels, (size_t)n * T, hipMemcpyDeviceToHost, ctx->stream));
     if (seq) XB_HIP(ctx, hipMemcpyAsync(seq, ctx->seq, (size_t)n * T, hipMemcpyDeviceToHost, ctx->stream));
+    if (seq_len) XB_HIP(ctx, hipMemcpyAsync(seq_len, ctx->seq_len, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    return xb_synchronize(ctx);
+}
+
+XB_API int xb_decode_q_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const char *alphabet, float qscale,
+                           float qoffset, int8_t *d_seq, int8_t *d_qstring, uint8_t *d_moves, int32_t *d_seq_len)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
+    if (!d_scores || !d_seq || !d_qstring || !alphabet) return fail(ctx, XB_ERR_INVALID, "null argument");
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = join_async_decode(ctx)) return rc;
+    ctx->result_stream = ctx->stream;
+    const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
+    QualOut q;
+    q.qstr = d_qstring; q.moves = d_moves; q.qscale = qscale; q.qoffset = qoffset;
+    return run_decode(ctx, d_scores, T, n, has_blank ? 1 : 0, ld, alphabet, nullptr, d_seq, d_seq_len, nullptr, nullptr, &q);
+}
+
+XB_API int xb_decode_q(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, const char *alphabet, float qscale,
+                       float qoffset, int8_t *seq, int8_t *qstring, uint8_t *moves, int32_t *seq_len)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
+    if (!scores || !seq || !qstring || !alphabet) return fail(ctx, XB_ERR_INVALID, "null argument");
+    if (T < 1 || T > ctx->T) return fail(ctx, XB_ERR_INVALID, "T=%d outside [1, %d]", T, ctx->T);
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcj = join_async_decode(ctx)) return rcj;
+    if (int rcs = ensure_q_staging(ctx)) return rcs;
+    const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
+    XB_HIP(ctx, hipMemcpyAsync(ctx->scores, scores, sizeof(float) * (size_t)T * n * ld, hipMemcpyHostToDevice, ctx->stream));
+    QualOut q;
+    q.qstr = ctx->q_seq; q.moves = moves ? ctx->q_moves : nullptr; q.qscale = qscale; q.qoffset = qoffset;
+    int rc = run_decode(ctx, ctx->scores, T, n, has_blank ? 1 : 0, ld, alphabet, nullptr, ctx->seq, ctx->seq_len, nullptr, nullptr, &q);
+    if (rc) return rc;
+    const size_t nt = (size_t)n * T;
+    XB_HIP(ctx, hipMemcpyAsync(seq, ctx->seq, nt, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(qstring, ctx->q_seq, nt, hipMemcpyDeviceToHost, ctx->stream));
+    if (moves) XB_HIP(ctx, hipMemcpyAsync(moves, ctx->q_moves, nt, hipMemcpyDeviceToHost, ctx->stream));
     if (seq_len) XB_HIP(ctx, hipMemcpyAsync(seq_len, ctx->seq_len, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     return xb_synchronize(ctx);
 }
@@ -1501,6 +1580,10 @@ static int call_post_actions(xb_ctx *ctx, const xb_ctx::Call &c, hipStream_t rs)
         // the error word as THIS batch left it (stream order: behind its recurrences and its decode), not as whatever batch
         // happens to be running when the slot is collected finds it
         XB_HIP(ctx, hipMemcpyAsync(sl.h_err, ctx->error, sizeof(unsigned), hipMemcpyDeviceToHost, rs));
+        if (c.qs) {
+            XB_HIP(ctx, hipMemcpyAsync(sl.h_q, sl.d_q, (size_t)c.n * ctx->T, hipMemcpyDeviceToHost, rs));
+            XB_HIP(ctx, hipMemcpyAsync(sl.h_mv, sl.d_mv, (size_t)c.n * ctx->T, hipMemcpyDeviceToHost, rs));
+        }
         XB_HIP(ctx, hipEventRecord(sl.done, rs));
     }
     if (c.after) c.after(c.after_arg);
@@ -1514,13 +1597,22 @@ static int launch_calls(xb_ctx *ctx, const xb_ctx::Call &a, const xb_ctx::Call *
     int8_t *d_seq = b ? ctx->fseq : a.seq;
     int32_t *d_len = b ? ctx->flen : a.len;
     const float *sig2 = b ? b->signal : nullptr;
+    // a pair is two plain calls or two _q calls of the same qscale / qoffset (enqueue_call)
+    QualOut qo;
+    const QualOut *qual = nullptr;
+    if (a.qs) {
+        qo.qstr = b ? ctx->q_fseq : a.qstr;
+        qo.moves = b ? ctx->q_fmoves : a.moves;
+        qo.qscale = a.qscale; qo.qoffset = a.qoffset;
+        qual = &qo;
+    }
     int rc;
     hipStream_t rs;
     if (!ctx->overlap || !ctx->stream3 || !ctx->scores2 || !ctx->decode_async) {
         rs = ctx->result_stream = ctx->stream;
         rc = run_encoder(ctx, a.signal, n, 0, ctx->scores, ctx->ld_nb, sig2, a.n);
         if (rc) return rc;
-        rc = run_decode(ctx, ctx->scores, ctx->T, n, 0, ctx->ld_nb, a.alphabet, nullptr, d_seq, d_len);
+        rc = run_decode(ctx, ctx->scores, ctx->T, n, 0, ctx->ld_nb, a.alphabet, nullptr, d_seq, d_len, nullptr, nullptr, qual);
         if (rc) return rc;
     } else {
         // asynchronous decode: the encoder of this batch writes score buffer p while the decode of the previous batch may
@@ -1535,7 +1627,7 @@ static int launch_calls(xb_ctx *ctx, const xb_ctx::Call &a, const xb_ctx::Call *
         if ((rc = next_dep(ctx, &enc))) return rc;
         XB_HIP(ctx, hipEventRecord(enc, ctx->stream));
         XB_HIP(ctx, hipStreamWaitEvent(ctx->stream3, enc, 0));
-        rc = run_decode(ctx, sc, ctx->T, n, 0, ctx->ld_nb, a.alphabet, nullptr, d_seq, d_len, ctx->stream3);
+        rc = run_decode(ctx, sc, ctx->T, n, 0, ctx->ld_nb, a.alphabet, nullptr, d_seq, d_len, ctx->stream3, nullptr, qual);
         if (rc) return rc;
     }
     if (b) {        // the pair's rows back to where each caller wants them
@@ -1544,6 +1636,13 @@ static int launch_calls(xb_ctx *ctx, const xb_ctx::Call &a, const xb_ctx::Call *
         XB_HIP(ctx, hipMemcpyAsync(b->seq, ctx->fseq + (size_t)a.n * T, (size_t)b->n * T, hipMemcpyDeviceToDevice, rs));
         if (a.len) XB_HIP(ctx, hipMemcpyAsync(a.len, ctx->flen, sizeof(int32_t) * (size_t)a.n, hipMemcpyDeviceToDevice, rs));
         if (b->len) XB_HIP(ctx, hipMemcpyAsync(b->len, ctx->flen + a.n, sizeof(int32_t) * (size_t)b->n, hipMemcpyDeviceToDevice, rs));
+        if (a.qs) {
+            XB_HIP(ctx, hipMemcpyAsync(a.qstr, ctx->q_fseq, (size_t)a.n * T, hipMemcpyDeviceToDevice, rs));
+            XB_HIP(ctx, hipMemcpyAsync(b->qstr, ctx->q_fseq + (size_t)a.n * T, (size_t)b->n * T, hipMemcpyDeviceToDevice, rs));
+            if (a.moves) XB_HIP(ctx, hipMemcpyAsync(a.moves, ctx->q_fmoves, (size_t)a.n * T, hipMemcpyDeviceToDevice, rs));
+            if (b->moves)
+                XB_HIP(ctx, hipMemcpyAsync(b->moves, ctx->q_fmoves + (size_t)a.n * T, (size_t)b->n * T, hipMemcpyDeviceToDevice, rs));
+        }
     }
     if (rs == ctx->stream3) {
         const int pb = (int)((ctx->batch_idx - 1) & 1u);
@@ -1582,6 +1681,8 @@ static int enqueue_call(xb_ctx *ctx, const xb_ctx::Call &c)
         const xb_ctx::Call h = ctx->held;
         ctx->holding = false;
         bool pair = ctx->fuse && h.n + c.n <= 2 * ctx->cfg.max_batch && strcmp(h.alphabet, c.alphabet) == 0 && h.seq != c.seq;
+        // qualities: only with a call of the same mode and the same qscale / qoffset (one decode pass serves both)
+        pair = pair && h.qs == c.qs && (!c.qs || (h.qscale == c.qscale && h.qoffset == c.qoffset && h.qstr != c.qstr && ctx->q_fseq));
         if (pair && h.n + c.n > ctx->cap && reserve_pairing(ctx) != XB_OK) pair = false;     // no room for both: one by one
         if (pair) {
             const int rc = launch_calls(ctx, h, &c);
@@ -1631,6 +1732,32 @@ XB_API int xb_basecall_chunks(xb_ctx *ctx, const float *signal, int n, const cha
     return xb_synchronize(ctx);
 }
 
+XB_API int xb_basecall_chunks_q(xb_ctx *ctx, const float *signal, int n, const char *alphabet, float qscale, float qoffset,
+                                int8_t *seq, int8_t *qstring, uint8_t *moves, int32_t *seq_len)
+{
+    int rc = check_ready(ctx, n);
+    if (rc) return rc;
+    if (!signal || !seq || !qstring || !alphabet) return fail(ctx, XB_ERR_INVALID, "null argument");
+    if ((int)strlen(alphabet) < ctx->cfg.n_base + 1 || strlen(alphabet) >= sizeof(xb_ctx::Call{}.alphabet))
+        return fail(ctx, XB_ERR_INVALID, "alphabet needs %d symbols", ctx->cfg.n_base + 1);
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if ((rc = ensure_q_staging(ctx))) return rc;
+    XB_HIP(ctx, hipMemcpyAsync(ctx->d_signal, signal, sizeof(float) * (size_t)n * ctx->cfg.chunk_len,
+                               hipMemcpyHostToDevice, ctx->stream));
+    xb_ctx::Call c;
+    c.signal = ctx->d_signal; c.n = n; c.seq = ctx->seq; c.len = ctx->seq_len;
+    c.qs = 1; c.qscale = qscale; c.qoffset = qoffset; c.qstr = ctx->q_seq; c.moves = moves ? ctx->q_moves : nullptr;
+    strcpy(c.alphabet, alphabet);
+    if ((rc = enqueue_call(ctx, c))) return rc;
+    if ((rc = join_async_decode(ctx))) return rc;
+    const size_t nt = (size_t)n * ctx->T;
+    XB_HIP(ctx, hipMemcpyAsync(seq, ctx->seq, nt, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(qstring, ctx->q_seq, nt, hipMemcpyDeviceToHost, ctx->stream));
+    if (moves) XB_HIP(ctx, hipMemcpyAsync(moves, ctx->q_moves, nt, hipMemcpyDeviceToHost, ctx->stream));
+    if (seq_len) XB_HIP(ctx, hipMemcpyAsync(seq_len, ctx->seq_len, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    return xb_synchronize(ctx);
+}
+
 // lazily created: most contexts (tests, bench) never use the host pipeline
 static int ensure_slot(xb_ctx *ctx, int slot)
 {
@@ -1651,13 +1778,27 @@ static int ensure_slot(xb_ctx *ctx, int slot)
     return XB_OK;
 }
 
-XB_API int xb_submit_chunks(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet)
+// the slot's staging of qualities and moves, on its first _q submission
+static int ensure_slot_q(xb_ctx *ctx, int slot)
+{
+    xb_ctx::Slot &sl = ctx->slots[slot];
+    const size_t NT = (size_t)ctx->cfg.max_batch * ctx->T;
+    if (!sl.h_q) XB_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&sl.h_q), NT, hipHostMallocDefault));
+    if (!sl.h_mv) XB_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&sl.h_mv), NT, hipHostMallocDefault));
+    int rc = sl.d_q ? XB_OK : dev_alloc(ctx, &sl.d_q, NT);
+    if (!rc && !sl.d_mv) rc = dev_alloc(ctx, &sl.d_mv, NT);
+    if (!rc) rc = ensure_q_staging(ctx);
+    return rc;
+}
+
+static int submit_chunks(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet, const xb_ctx::Call *q)
 {
     int rc = check_ready(ctx, n);
     if (rc) return rc;
     if (slot < 0 || slot >= XB_PIPELINE_SLOTS || !signal || !alphabet) return fail(ctx, XB_ERR_INVALID, "bad slot / null argument");
     XB_HIP(ctx, hipSetDevice(ctx->device));
     if ((rc = ensure_slot(ctx, slot))) return rc;
+    if (q && (rc = ensure_slot_q(ctx, slot))) return rc;
     xb_ctx::Slot &sl = ctx->slots[slot];
     if (sl.busy) return fail(ctx, XB_ERR_STATE, "slot %d was submitted and not collected", slot);
     const size_t bytes = sizeof(float) * (size_t)n * ctx->cfg.chunk_len;
@@ -1671,11 +1812,42 @@ XB_API int xb_submit_chunks(xb_ctx *ctx, int slot, const float *signal, int n, c
     // (call_post_actions) -- which may be held back until the next submit so that the two batches share one pass
     xb_ctx::Call c;
     c.signal = sl.d_signal; c.n = n; c.seq = sl.d_seq; c.len = sl.d_len; c.slot = slot;
+    if (q) {
+        c.qs = 1; c.qscale = q->qscale; c.qoffset = q->qoffset; c.qstr = sl.d_q; c.moves = sl.d_mv;
+    }
     strcpy(c.alphabet, alphabet);
     rc = enqueue_call(ctx, c);
     if (rc) return rc;
     sl.n = n;
     sl.busy = true;
+    sl.qs = q != nullptr;
+    return XB_OK;
+}
+
+XB_API int xb_submit_chunks(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet)
+{
+    return submit_chunks(ctx, slot, signal, n, alphabet, nullptr);
+}
+
+XB_API int xb_submit_chunks_q(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet, float qscale,
+                              float qoffset)
+{
+    xb_ctx::Call q;
+    q.qscale = qscale; q.qoffset = qoffset;
+    return submit_chunks(ctx, slot, signal, n, alphabet, &q);
+}
+
+XB_API int xb_collect_chunks_q(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len, int8_t *qstring, uint8_t *moves)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    if (slot < 0 || slot >= XB_PIPELINE_SLOTS || !seq || !qstring) return fail(ctx, XB_ERR_INVALID, "bad slot / null argument");
+    xb_ctx::Slot &sl = ctx->slots[slot];
+    if (!sl.busy || !sl.qs) return fail(ctx, XB_ERR_STATE, "slot %d has no submission with qualities in flight", slot);
+    const int n = sl.n;
+    const int rc = xb_collect_chunks(ctx, slot, seq, seq_len);
+    if (rc) return rc;
+    memcpy(qstring, sl.h_q, (size_t)n * ctx->T);
+    if (moves) memcpy(moves, sl.h_mv, (size_t)n * ctx->T);
     return XB_OK;
 }
 

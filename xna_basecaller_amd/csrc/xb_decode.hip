@@ -14,6 +14,8 @@
 //      Q = log(P + 1e-8) of every edge, (T, N, S*E) fp32, scattered by destination edge into an LDS row and stored as
 //      coalesced rows one step late
 //   3. Max forward over Q + per-step arg-max of the max-marginals (read Q, bmax), then pack.
+// The quality variant (QS, xb_decode_q) adds a fourth phase after sweep 3: per-step path posteriors from the stashed
+// alpha / beta rows, then per-base quality characters, packed beside the bases (see "qualities" below).
 //
 // What bounds a step is the LENGTH OF ITS DEPENDENCY CHAIN, not bytes or instruction count (a dependent VALU
 // instruction issues every ~8 cycles, independent ones every ~2.4 per SIMD: tools/valu_probe.hip), so the kernel is
@@ -306,7 +308,9 @@ struct Edges {
 // VW: 4 = 16-byte staging loads in sweep 2 (row stride and base 16-byte aligned), 1 = 4-byte loads
 // SCAN = true: the xb_crf_scans variant (optional beta / posterior outputs, early return after sweep 1 or 2); the decode
 // proper is compiled without those paths (measured: 1-2 % of the decode time when they are run-time branches).
-template <int NB, int BS, bool HB, int LPS, int VW, bool SCAN>
+// QS = true: the xb_decode_q variant -- sweep 2 stores the Log backward rows (beta_out), sweep 3 keeps the arg-max state of
+// every step, and phase 4 turns them into per-base qualities and moves.  The instantiations with QS = false compile none of it.
+template <int NB, int BS, bool HB, int LPS, int VW, bool SCAN, bool QS>
 __global__ __launch_bounds__(BS) XB_DEC_WAVES_ATTR void crf_decode_kernel(xb::DecodeParams p)
 {
     constexpr int E = NB + 1;
@@ -345,6 +349,7 @@ __global__ __launch_bounds__(BS) XB_DEC_WAVES_ATTR void crf_decode_kernel(xb::De
     int *sRi = reinterpret_cast<int *>(sRv + LRING * NW);         // [LRING][NW] arg-max partials: flat edge index
     float *sBc = reinterpret_cast<float *>(sRi + LRING * NW);     // [4] broadcast scratch
     int8_t *sLab = reinterpret_cast<int8_t *>(sBc + 4);           // [T]
+    int16_t *sPath = reinterpret_cast<int16_t *>(sLab + ((T + 1) & ~1));   // [T] QS only: arg-max state per step (S <= 1024)
 
     const float *sc = p.scores + (size_t)n * p.ld;
     const size_t tstride = (size_t)N * p.ld;
@@ -474,7 +479,7 @@ __global__ __launch_bounds__(BS) XB_DEC_WAVES_ATTR void crf_decode_kernel(xb::De
         const int i = (stc % NB) * hi + stc / NB;
         const int kk = stc % NB + 1;                               // = i / hi + 1: column of the new-base edges
         const int jb = (stc / NB) * NB;                            // = (i % hi) * NB: first destination
-        float *beta_out = SCAN && p.beta_out ? p.beta_out + (size_t)n * S : nullptr;     // uniform
+        float *beta_out = (SCAN || QS) && p.beta_out ? p.beta_out + (size_t)n * S : nullptr;     // uniform
         const bool post_mode = SCAN && p.post_mode != 0;
         if (tid < S) {
             sA[(T & 1) * S + tid] = 0.0f;
@@ -641,6 +646,7 @@ __global__ __launch_bounds__(BS) XB_DEC_WAVES_ATTR void crf_decode_kernel(xb::De
                     if (v > bv || (v == bv && c < bi)) { bv = v; bi = c; }
                 }
                 sLab[t] = (int8_t)(bi % E);
+                if constexpr (QS) sPath[t] = (int16_t)(bi / E);     // the destination state: the path's state at t + 1
             }
         };
         float aown = 0.0f;
@@ -722,6 +728,67 @@ __global__ __launch_bounds__(BS) XB_DEC_WAVES_ATTR void crf_decode_kernel(xb::De
         __syncthreads();
     }
 
+    // ------------------------------------------------ phase 4 (QS): qualities
+    // Per step t the posterior mass of the path state s = sPath[t] and of its nb left- and nb right-shifted neighbours at
+    // scan index t + 1, P(x) = exp((alpha_{t+1}[x] + beta_{t+1}[x]) - logZ), summed in the beam search's order (xb_beam.hip),
+    // clamped to [0, 1] and raised to 0.4.  Steps are spread over the workgroup; p_t goes to this chunk's slice of the Q
+    // buffer, which sweep 3 has finished with (step t at row t / ldq, column t % ldq: ldq contiguous floats per row).
+    // The per-base characters are formed in the pack below, one base per emitting step.
+    auto pslot = [&](int t) -> float * { return qrow + (size_t)(t / ldq) * qstride + (t % ldq); };
+    if constexpr (QS) {
+        constexpr int NG = 2 * NB + 1;
+        for (int t = tid; t < T; t += BS) {
+            const int s = sPath[t];
+            const int l0 = s / NB, r0 = (s % hi) * NB;
+            const float *a1 = alpha + (size_t)(t + 1) * sstride, *b1 = p.beta_out + (size_t)n * S + (size_t)(t + 1) * sstride;
+            int xs[NG];
+            xs[0] = s;
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                xs[1 + 2 * b] = l0 + hi * b;
+                xs[2 + 2 * b] = r0 + b;
+            }
+            float av[NG], bv[NG], x[NG], P[NG];
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                av[g] = a1[xs[g]];
+                bv[g] = b1[xs[g]];
+            }
+#pragma unroll
+            for (int g = 0; g < NG; ++g) x[g] = (av[g] + bv[g]) - logZ;
+            xb_exp_n<NG>(x, P);
+            float pr = P[0];
+#pragma unroll
+            for (int g = 1; g < NG; ++g) pr = pr + P[g];
+            pr = pr > 1.0f ? 1.0f : pr;
+            pr = pr < 0.0f ? 0.0f : pr;
+            *pslot(t) = pr > 0.0f ? xb_expf(0.4f * xb_logf(pr)) : 0.0f;
+        }
+        if (p.moves)
+            for (int t = tid; t < T; t += BS) p.moves[(size_t)n * T + t] = sLab[t] != 0 ? 1 : 0;
+        __syncthreads();
+    }
+    // quality character of the base emitted at step t: its run is t .. u-1, u = the next emitting step (or T)
+    auto qchar = [&](int t) -> int8_t {
+        float bp = 0.0f, tot = 0.0f;
+        for (int u = t; u < T && (u == t || sLab[u] == 0); ++u) {
+            const float pr = *pslot(u), wrong = (1.0f - pr) / (float)(NB - 1);
+            bp = bp + pr;
+            float one = pr;
+#pragma unroll
+            for (int j = 1; j < NB; ++j) one = one + wrong;
+            tot = tot + one;
+        }
+        const float e = 1.0f - bp / tot;
+        float q = e > 0.0f ? xb_logf(e) * -4.3429448190325175f : 3.402823466e+38f;
+        q = q * p.qscale;
+        q = q + p.qoffset;
+        q = q < 1.0f ? 1.0f : q;
+        q = q > 50.0f ? 50.0f : q;
+        return (int8_t)(int)(33.5f + q);
+    };
+    (void)qchar;
+
     // ------------------------------------------------ labels out + path_to_str + left-pack
     if (p.labels)
         for (int t = tid; t < T; t += BS) p.labels[(size_t)n * T + t] = sLab[t];
@@ -744,15 +811,20 @@ __global__ __launch_bounds__(BS) XB_DEC_WAVES_ATTR void crf_decode_kernel(xb::De
             int pos = sCnt[tid];
             for (int t = lo; t < hiT; ++t) {
                 const int l = sLab[t];
-                if (l != 0) out[pos++] = (int8_t)p.alphabet[l];
+                if (l != 0) {
+                    if constexpr (QS) p.qstr[(size_t)n * T + pos] = qchar(t);     // packed in parallel with the bases
+                    out[pos++] = (int8_t)p.alphabet[l];
+                }
             }
             for (int t = total + tid; t < T; t += BS) out[t] = 0;
+            if constexpr (QS)
+                for (int t = total + tid; t < T; t += BS) p.qstr[(size_t)n * T + t] = 0;
         }
         if (p.seq_len && tid == 0) p.seq_len[n] = total;
     }
 }
 
-template <int NB, int BS, int LPS, bool SCAN>
+template <int NB, int BS, int LPS, bool SCAN, bool QS>
 hipError_t launch_nb_bs(const xb::DecodeParams &p, int vw, hipStream_t stream)
 {
     // must mirror the kernel's LDS carve
@@ -760,8 +832,9 @@ hipError_t launch_nb_bs(const xb::DecodeParams &p, int vw, hipStream_t stream)
     auto lds_bytes = [&](int w) {
         const int nrs = w == 4 ? (E + 4 * LPS - 1) / (4 * LPS) : (E + LPS - 1) / LPS;      // the kernel's NRS
         const size_t cpad = (size_t)BS * nrs * w;
-        const size_t b = sizeof(float) * (4 * cpad + 5 * (size_t)p.S + (size_t)LRING * (BS / 64)) +
-                         sizeof(int) * (size_t)LRING * (BS / 64) + sizeof(float) * 4 + (size_t)p.T;
+        size_t b = sizeof(float) * (4 * cpad + 5 * (size_t)p.S + (size_t)LRING * (BS / 64)) +
+                   sizeof(int) * (size_t)LRING * (BS / 64) + sizeof(float) * 4 + (size_t)p.T;
+        if (QS) b += 1 + sizeof(int16_t) * (size_t)p.T;        // sPath behind sLab, at the next even byte
         return (b + 15) & ~(size_t)15;
     };
     // the four-wide row loads pad a state's edges to a multiple of four: where that no longer fits (4^5 states), one by one
@@ -771,9 +844,9 @@ hipError_t launch_nb_bs(const xb::DecodeParams &p, int vw, hipStream_t stream)
     dim3 grid(p.N), block(BS);
 #define XB_LAUNCH(HB, VW)                                                                                          \
     do {                                                                                                           \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&crf_decode_kernel<NB, BS, HB, LPS, VW, SCAN>),         \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&crf_decode_kernel<NB, BS, HB, LPS, VW, SCAN, QS>),         \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
-        hipLaunchKernelGGL((crf_decode_kernel<NB, BS, HB, LPS, VW, SCAN>), grid, block, lds, stream, p);                 \
+        hipLaunchKernelGGL((crf_decode_kernel<NB, BS, HB, LPS, VW, SCAN, QS>), grid, block, lds, stream, p);                 \
     } while (0)
     if (p.has_blank) {
         if (vw == 4) XB_LAUNCH(true, 4); else XB_LAUNCH(true, 1);
@@ -785,19 +858,19 @@ hipError_t launch_nb_bs(const xb::DecodeParams &p, int vw, hipStream_t stream)
 }
 
 // Block = smallest multiple of 64 threads (from a short list, pruned per alphabet) that holds LPS lanes for each state.
-template <int NB, int LPS, bool SCAN>
+template <int NB, int LPS, bool SCAN, bool QS = false>
 hipError_t launch_nb_lps(const xb::DecodeParams &p, int vw, hipStream_t stream)
 {
     const int need = LPS * p.S;
-    if (need <= 64) return launch_nb_bs<NB, 64, LPS, SCAN>(p, vw, stream);
-    if (need <= 128) return launch_nb_bs<NB, 128, LPS, SCAN>(p, vw, stream);
-    if (need <= 256) return launch_nb_bs<NB, 256, LPS, SCAN>(p, vw, stream);
+    if (need <= 64) return launch_nb_bs<NB, 64, LPS, SCAN, QS>(p, vw, stream);
+    if (need <= 128) return launch_nb_bs<NB, 128, LPS, SCAN, QS>(p, vw, stream);
+    if (need <= 256) return launch_nb_bs<NB, 256, LPS, SCAN, QS>(p, vw, stream);
     if constexpr (NB == 6) {
-        if (need <= 448) return launch_nb_bs<NB, 448, LPS, SCAN>(p, vw, stream);     // 2 x 216 states
+        if (need <= 448) return launch_nb_bs<NB, 448, LPS, SCAN, QS>(p, vw, stream);     // 2 x 216 states
     } else {
-        if (need <= 640) return launch_nb_bs<NB, 640, LPS, SCAN>(p, vw, stream);     // 5^4 states / 2 x 4^4
+        if (need <= 640) return launch_nb_bs<NB, 640, LPS, SCAN, QS>(p, vw, stream);     // 5^4 states / 2 x 4^4
         if constexpr (NB == 4 && LPS == 1) {
-            if (need <= 1024) return launch_nb_bs<NB, 1024, LPS, SCAN>(p, vw, stream);   // 4^5 states
+            if (need <= 1024) return launch_nb_bs<NB, 1024, LPS, SCAN, QS>(p, vw, stream);   // 4^5 states
         }
     }
     return hipErrorInvalidValue;
@@ -805,6 +878,11 @@ hipError_t launch_nb_lps(const xb::DecodeParams &p, int vw, hipStream_t stream)
 template <int NB>
 hipError_t launch_nb(const xb::DecodeParams &p, int vw, hipStream_t stream)
 {
+    // the quality variant, with either lane split (validated by launch_crf_decode: full decode, beta_out and seq set)
+    if (p.qstr) {
+        if (xb::decode_lanes_per_state(p.S, p.N) == 2) return launch_nb_lps<NB, 2, false, true>(p, vw, stream);
+        return launch_nb_lps<NB, 1, false, true>(p, vw, stream);
+    }
     // the scan variant exists with one lane per state only (the results do not depend on the lane split)
     if (p.stop_after || p.beta_out || p.post_mode) return launch_nb_lps<NB, 1, true>(p, vw, stream);
     if (xb::decode_lanes_per_state(p.S, p.N) == 2) return launch_nb_lps<NB, 2, false>(p, vw, stream);
@@ -994,6 +1072,7 @@ hipError_t launch_crf_decode(const DecodeParams &p, hipStream_t stream)
     const int E = p.nb + 1;
     if (p.cin != (p.has_blank ? p.S * E : p.S * p.nb) || p.ld < p.cin) return hipErrorInvalidValue;
     if (!p.qbuf || p.ldq % 4 != 0 || p.ldq < p.S * E || reinterpret_cast<uintptr_t>(p.qbuf) % 16 != 0) return hipErrorInvalidValue;
+    if (p.qstr && (!p.seq || !p.beta_out || p.stop_after || p.post_mode)) return hipErrorInvalidValue;
     int vw = 1;
     const uintptr_t a = reinterpret_cast<uintptr_t>(p.scores);
     // vector loads may run into the row's padding columns (ld >= cin rounded up), never past the row

@@ -27,6 +27,10 @@ struct DecodeParams {
     char alphabet[8];
     int debug_stop;               // diagnostic builds only (XB_LSTM_STAMPS): return after sweep 1 / 2
     int debug_lds;                // diagnostic builds only: sweep 2 with lane-linear (conflict-free) LDS addresses, WRONG results
+    // qualities (xb_decode_q): set qstr to run the quality variant -- it needs seq and beta_out ((T+1, N, S) workspace) too
+    int8_t *qstr;                 // (N, T) or nullptr: quality characters, left-packed in parallel with seq, zero-padded
+    uint8_t *moves;               // (N, T) or nullptr (quality variant only): 1 where the step emits a base
+    float qscale, qoffset;        // q = -10 log10(error) * qscale + qoffset, before the clamp to [1, 50]
 };
 hipError_t launch_crf_decode(const DecodeParams &p, hipStream_t stream);
 int decode_lanes_per_state(int S, int N);   // 1, 2 or 4 lanes serve one CRF state (env XB_DECODE_LPS overrides for tests)
