@@ -172,6 +172,32 @@ XB_API int xb_decode_q_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int
                            float qoffset, int8_t *d_seq, int8_t *d_qstring, uint8_t *d_moves, int32_t *d_seq_len);
 
 /*
+ * xb_decode_q with per-base letter probabilities (an extension for calling unnatural bases: how sure the decode is of each
+ * letter of the alphabet at every called base).  No reference vectors exist for it: PARITY UNPINNED.  Specification, with
+ * the quantities of xb_decode_q (scores M, S, E, hi, idx(j, k) = (k - 1) * hi + j / nb for k >= 1, Log alpha / beta, logZ):
+ *   P_t(j, k)   the edge posterior exp(((alpha[t][idx(j, k)] + M[t][j][k]) + beta[t+1][j]) - logZ), bit-equal to
+ *               xb_crf_scans' post.
+ *   m_t[i]      move mass of source state i: its nb move edges (j = (i % hi) * nb + e - 1, k = i / hi + 1, e = 1..nb)
+ *               summed in edge order: ((0 + P_t(e = 1)) + P_t(e = 2)) + .. + P_t(e = nb).  Stays emit nothing.
+ *   e_t[b]      letter mass of step t, b = 0..nb-1 (every move edge out of i emits letter i / hi + 1): over the hi sources
+ *               i = b * hi + q, lane g = 0..15 first sums x_g = 0 + m_t[b*hi + g] + m_t[b*hi + g + 16] + .. (increasing q);
+ *               then four rounds of x_g = x_{g-d} + x_g for g >= d, d = 1, 2, 4, 8 (all g of a round at once); e_t[b] = x_15.
+ *   bases       the emitting steps t_1 < .. < t_L of the decode's own path (m_t = 1 of xb_decode_q): the packed sequence.
+ *   window      of base i: W_i = t_{i-1} + 1 .. t_{i+1} - 1 with t_0 = -1, t_{L+1} = T (neighbouring windows overlap).
+ *   mass_i[b] = 0 + e_u[b] summed over u in W_i in increasing u;  tot_i = mass_i[0] + mass_i[1] + .. (letter order).
+ *   prob_i[b] = mass_i[b] / tot_i, or 0 for every letter when tot_i = 0 (everything underflowed: no information).
+ *   byte        v = min(255, (int)(256 * prob_i[b])): SAM ML's 1/256 binning.
+ *   probs (n, nb, T) uint8: plane b is letter alphabet[1 + b], left-packed and zero-padded in parallel with seq exactly as
+ *             qstring is (the i-th byte of a chunk's row in plane b belongs to base i).  seq, seq_len, qstring and moves are
+ *             byte-equal to xb_decode_q's (moves may be NULL).
+ */
+XB_API int xb_decode_ub(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, const char *alphabet, float qscale,
+                        float qoffset, int8_t *seq, int8_t *qstring, uint8_t *moves, uint8_t *probs, int32_t *seq_len);
+XB_API int xb_decode_ub_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const char *alphabet,
+                            float qscale, float qoffset, int8_t *d_seq, int8_t *d_qstring, uint8_t *d_moves, uint8_t *d_probs,
+                            int32_t *d_seq_len);
+
+/*
  * The Log-semiring scans of the CRF on their own (seqdist `sparse` operators behind crf/model.py:41-61): any of
  *   alpha (T+1, n, S)  CTC_CRF.forward_scores  (crf/model.py:50-54): alpha_0 = 0, alpha_{t+1}[j] = LSE_k(M[t,j,k] + alpha_t[idx[j,k]])
  *   beta  (T+1, n, S)  CTC_CRF.backward_scores (crf/model.py:56-60): beta_T = 0, beta_t[i] = LSE over edges (j,k) leaving i of
@@ -244,6 +270,9 @@ XB_API int xb_basecall_chunks_dev(xb_ctx *ctx, const float *d_signal, int n, con
 /* ... with the qualities and moves of xb_decode_q (moves may be NULL). */
 XB_API int xb_basecall_chunks_q(xb_ctx *ctx, const float *signal, int n, const char *alphabet, float qscale, float qoffset,
                                 int8_t *seq, int8_t *qstring, uint8_t *moves, int32_t *seq_len);
+/* ... with the qualities, moves and letter probabilities of xb_decode_ub (moves may be NULL; probs (n, nb, T)). */
+XB_API int xb_basecall_chunks_ub(xb_ctx *ctx, const float *signal, int n, const char *alphabet, float qscale, float qoffset,
+                                 int8_t *seq, int8_t *qstring, uint8_t *moves, uint8_t *probs, int32_t *seq_len);
 /* Opt in to the co-scheduling of two calls in flight (see the header comment) and make room for it: the workspaces for
  * max_batch chunks are replaced by twice that -- which waits for everything in flight and takes a second or two, so callers
  * do it once, up front (bench.py: outside its timed region; Model: when the host pipeline starts).  XB_OK also when the
@@ -275,6 +304,14 @@ XB_API int xb_collect_chunks(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_le
 XB_API int xb_submit_chunks_q(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet, float qscale,
                               float qoffset);
 XB_API int xb_collect_chunks_q(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len, int8_t *qstring, uint8_t *moves);
+/* The pipeline with the letter probabilities of xb_decode_ub: the slot's pinned staging for them is allocated by its first
+ * _ub submission.  xb_collect_chunks_ub collects a _ub submission only (XB_ERR_STATE otherwise; moves may be NULL);
+ * xb_collect_chunks_q / xb_collect_chunks of a _ub submission return its qualities / bases alone.  Co-scheduling: a _ub call
+ * pairs only with a _ub call of the same qscale / qoffset, so every call produces exactly the bytes it produces unpaired. */
+XB_API int xb_submit_chunks_ub(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet, float qscale,
+                               float qoffset);
+XB_API int xb_collect_chunks_ub(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len, int8_t *qstring, uint8_t *moves,
+                                uint8_t *probs);
 
 XB_API int xb_synchronize(xb_ctx *ctx);
 

@@ -28,6 +28,7 @@ EXPORTS = [
     "xb_gather_called", "xb_comm_fence", "xb_comm_synchronize", "xb_stream_wait_event", "xb_align_accuracy",
     "xb_beam_search", "xb_beam_search_dev", "xb_basecall_chunks_beam", "xb_reserve_pairing", "xb_pairing_active", "xb_debug_layer_output",
     "xb_decode_q", "xb_decode_q_dev", "xb_basecall_chunks_q", "xb_submit_chunks_q", "xb_collect_chunks_q",
+    "xb_decode_ub", "xb_decode_ub_dev", "xb_basecall_chunks_ub", "xb_submit_chunks_ub", "xb_collect_chunks_ub",
 ]
 XB_COMM_ID_BYTES = 128
 # xb_status (include/xna_basecaller.h)
@@ -113,6 +114,11 @@ def load():
     lib.xb_basecall_chunks_q.argtypes = [vp, vp, ip, C.c_char_p, fl, fl, vp, vp, vp, vp]
     lib.xb_submit_chunks_q.argtypes = [vp, ip, vp, ip, C.c_char_p, fl, fl]
     lib.xb_collect_chunks_q.argtypes = [vp, ip, vp, vp, vp, vp]
+    lib.xb_decode_ub.argtypes = [vp, vp, ip, ip, ip, C.c_char_p, fl, fl, vp, vp, vp, vp, vp]
+    lib.xb_decode_ub_dev.argtypes = [vp, vp, ip, ip, ip, C.c_char_p, fl, fl, vp, vp, vp, vp, vp]
+    lib.xb_basecall_chunks_ub.argtypes = [vp, vp, ip, C.c_char_p, fl, fl, vp, vp, vp, vp, vp]
+    lib.xb_submit_chunks_ub.argtypes = [vp, ip, vp, ip, C.c_char_p, fl, fl]
+    lib.xb_collect_chunks_ub.argtypes = [vp, ip, vp, vp, vp, vp, vp]
     lib.xb_result_stream.argtypes = [vp]
     lib.xb_result_stream.restype = C.c_void_p
     lib.xb_set_profiling.argtypes = [vp, ip]
@@ -367,6 +373,54 @@ class Context:
         self._check(self.lib.xb_collect_chunks_q(self.h, int(slot), seq.ctypes.data, lens.ctypes.data, q.ctypes.data,
                                                  mv.ctypes.data))
         return seq, lens, q, mv
+
+    # ---- ... and with per-base letter probabilities (xb_decode_ub: an extension, parity unpinned) ----------
+    def _ub_out(self, n, T):
+        return (np.empty((n, T), dtype=np.int8), np.empty((n,), dtype=np.int32), np.empty((n, T), dtype=np.int8),
+                np.empty((n, T), dtype=np.uint8), np.empty((n, self.n_base, T), dtype=np.uint8))
+
+    def decode_ub(self, scores, alphabet, qscale=1.0, qoffset=0.0, has_blank=None):
+        """xb_decode_ub: scores (T, n, C) -> (seq, lens, qstring, moves) as decode_q returns them, plus probs (n, nb, T)
+        uint8: plane b holds the probability byte of letter alphabet[1 + b] per base, left-packed beside seq."""
+        scores = np.ascontiguousarray(scores, dtype=np.float32)
+        T, n, Cin = scores.shape
+        if has_blank is None:
+            has_blank = Cin == self.C_blank
+        if Cin != (self.C_blank if has_blank else self.C_noblank):
+            raise ValueError("scores last dim %d does not match the model (%d with blanks, %d without)"
+                             % (Cin, self.C_blank, self.C_noblank))
+        seq, lens, q, mv, pr = self._ub_out(n, T)
+        self._check(self.lib.xb_decode_ub(self.h, scores.ctypes.data, T, n, int(bool(has_blank)), "".join(alphabet).encode(),
+                                          float(qscale), float(qoffset), seq.ctypes.data, q.ctypes.data, mv.ctypes.data,
+                                          pr.ctypes.data, lens.ctypes.data))
+        return seq, lens, q, mv, pr
+
+    def decode_ub_dev(self, d_scores, T, n, has_blank, alphabet, qscale, qoffset, d_seq, d_qstring, d_moves, d_probs, d_len):
+        self._check(self.lib.xb_decode_ub_dev(self.h, _ptr(d_scores), int(T), int(n), int(bool(has_blank)),
+                                              "".join(alphabet).encode(), float(qscale), float(qoffset), _ptr(d_seq),
+                                              _ptr(d_qstring), _ptr(d_moves), _ptr(d_probs), _ptr(d_len)))
+
+    def basecall_chunks_ub(self, signal, alphabet, qscale=1.0, qoffset=0.0):
+        """xb_basecall_chunks_ub: signal (n, chunk_len) -> (seq, lens, qstring, moves, probs) as decode_ub returns them."""
+        signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1, self.chunk_len)
+        n = signal.shape[0]
+        seq, lens, q, mv, pr = self._ub_out(n, self.T)
+        self._check(self.lib.xb_basecall_chunks_ub(self.h, signal.ctypes.data, n, "".join(alphabet).encode(), float(qscale),
+                                                   float(qoffset), seq.ctypes.data, q.ctypes.data, mv.ctypes.data,
+                                                   pr.ctypes.data, lens.ctypes.data))
+        return seq, lens, q, mv, pr
+
+    def submit_chunks_ub(self, slot, signal, alphabet, qscale=1.0, qoffset=0.0):
+        signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1, self.chunk_len)
+        self._check(self.lib.xb_submit_chunks_ub(self.h, int(slot), signal.ctypes.data, signal.shape[0],
+                                                 "".join(alphabet).encode(), float(qscale), float(qoffset)))
+        return signal.shape[0]
+
+    def collect_chunks_ub(self, slot, n):
+        seq, lens, q, mv, pr = self._ub_out(n, self.T)
+        self._check(self.lib.xb_collect_chunks_ub(self.h, int(slot), seq.ctypes.data, lens.ctypes.data, q.ctypes.data,
+                                                  mv.ctypes.data, pr.ctypes.data))
+        return seq, lens, q, mv, pr
 
     # ---- beam search with qualities and moves (koi.decode.beam_search at crf/basecall.py:43-46) ----------
     def _beam_out(self, n, T):

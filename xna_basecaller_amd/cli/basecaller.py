@@ -7,7 +7,8 @@ Differences, all outside the hot path: reads come from `*.xsig.npz` signal bundl
 this image, see reads.py); --reference / --modified-bases / --save-ctc are rejected (mappy / remora /
 CTCWriter are not on the north-star path); under torchrun (WORLD_SIZE > 1) reads are sharded over the
 ranks and gathered to rank 0 over RCCL before writing.  Extension: --qscores writes the Viterbi decode's device
-qualities (xb_decode_q) in place of the reference's placeholder 'O'; without it the output is unchanged.
+qualities (xb_decode_q) in place of the reference's placeholder 'O'; --ub-probs adds per-base probabilities of every
+letter outside A, C, G, T as `u<letter>:B:C` tags (xb_decode_ub); without them the output is unchanged.
 """
 import os
 import sys
@@ -70,7 +71,7 @@ def _gathered_results(results, loader, rank, world, window=256):
                 held = item
                 break
             batch.append((read.index, tuple(getattr(read, k) for k in READ_FIELDS), read.tagdata(), len(read.signal),
-                          res["sequence"], res["qstring"]))
+                          res["sequence"], res["qstring"], res.get("mods", [])))
         payload = ("error", repr(failure)) if failure is not None else ("ok", batch)
         gathered = [None] * world if rank == 0 else None
         tdist.gather_object(payload, gathered, dst=0)
@@ -81,10 +82,24 @@ def _gathered_results(results, loader, rank, world, window=256):
                 failure = RuntimeError("a rank failed while basecalling: %s" % "; ".join(bad))
                 continue
             merged = sorted((rec for p in gathered for rec in p[1]), key=lambda rec: rec[0])
-            for _, fields, tags, n_samples, seq, qstring in merged:
-                yield _CalledRead(fields, tags, n_samples), {"sequence": seq, "qstring": qstring}
+            for _, fields, tags, n_samples, seq, qstring, mods in merged:
+                res = {"sequence": seq, "qstring": qstring}
+                if mods:
+                    res["mods"] = mods
+                yield _CalledRead(fields, tags, n_samples), res
     if failure is not None:
         raise failure
+
+
+def ub_probs_refusal(model):
+    """Why `--ub-probs` cannot run on `model` (a message), or None: the letter probabilities come from the Viterbi decode,
+    and they are reported for the letters outside A, C, G, T only."""
+    from ..crf.basecall import ub_letters
+    if not model.encoder[-1].expand_blanks:
+        return "--ub-probs needs the Viterbi decode; this model takes the beam search"
+    if not ub_letters(model):
+        return "--ub-probs reports letters outside A, C, G, T; the alphabet %s has none" % "".join(model.alphabet[1:])
+    return None
 
 
 def reader_procs(world=1):
@@ -138,6 +153,11 @@ def main(args):
     if args.reference or args.modified_bases or args.modified_base_model or args.save_ctc:
         sys.stderr.write("> error: --reference/--modified-bases/--save-ctc are not part of the MI355X path\n")
         exit(1)
+    if args.ub_probs:
+        why = ub_probs_refusal(model)
+        if why is not None:
+            sys.stderr.write("> error: %s\n" % why)
+            exit(1)
     fmt = biofmt(aligned=False)
     sys.stderr.write(f"> outputting {fmt.aligned} {fmt.name}\n")
     if fmt.name not in ("fastq", "sam"):
@@ -152,6 +172,8 @@ def main(args):
 
     # --qscores (an extension): the Viterbi decode's device qualities instead of the reference's 'O' placeholders
     extra = {"qscores": True} if args.qscores else {}
+    if args.ub_probs:                   # --ub-probs (an extension): per-base letter probabilities as u<letter>:B:C tags
+        extra["ub_probs"] = True
     results = basecall(model, reads, reverse=args.revcomp,
                        batchsize=model.config["basecaller"]["batchsize"],
                        chunksize=model.config["basecaller"]["chunksize"],
@@ -204,6 +226,10 @@ def argparser():
     parser.add_argument("--qscores", action="store_true", default=False,
                         help="Viterbi decode: per-base qualities computed on the device (path posteriors, calibrated by the "
                              "model's [qscore] scale / bias) instead of the placeholder 'O'; not in the reference CLI")
+    parser.add_argument("--ub-probs", action="store_true", default=False,
+                        help="Viterbi decode: per-base probability of every alphabet letter outside A, C, G, T, computed on "
+                             "the device from the decode's posteriors, as u<letter>:B:C tags (1/256 bins); not in the "
+                             "reference CLI")
     parser.add_argument("--recursive", action="store_true", default=False)
     quant_parser = parser.add_mutually_exclusive_group(required=False)
     quant_parser.add_argument("--quantize", dest="quantize", action="store_true")

@@ -51,7 +51,7 @@ def stitch_results(results, length, size, overlap, stride, reverse=False):
 
 
 def compute_scores(model, batch, beam_width=32, beam_cut=100.0, scale=1.0, offset=0.0, blank_score=2.0,
-                   reverse=False, qscores=False):
+                   reverse=False, qscores=False, ub_probs=False):
     """
     crf/basecall.py:27-82: (n,1,L) batch -> {'sequence': int8 (n,T), 'qstring': int8 (n,T), 'moves': bool (n,T)}.
     Viterbi branch (expand_blanks, the only one the reference reaches for XNA alphabets): left-packed ASCII rows, 'O'
@@ -61,7 +61,20 @@ def compute_scores(model, batch, beam_width=32, beam_cut=100.0, scale=1.0, offse
     the config's [qscore] section.
     Beam branch (expand_blanks = False, `koi.decode.beam_search`): bases and quality characters at the blocks that emit,
     real moves -- xb_basecall_chunks_beam, for any alphabet the CRF supports.  `qscores` changes nothing there.
+    With ub_probs (an extension, parity unpinned, Viterbi branch only): also 'probs' (n, nb, T) uint8, per base the
+    probability byte of every letter alphabet[1 + b], left-packed beside the bases (xb_basecall_chunks_ub; xb_decode_ub with
+    reverse); the qualities and moves are the device's with qscores, else the placeholders.
     """
+    if ub_probs:
+        if not model.encoder[-1].expand_blanks:
+            raise ValueError("letter probabilities come from the Viterbi decode; this model takes the beam search")
+        if reverse:
+            scores = model.seqdist.reverse_complement(model(batch))
+            ctx = model.context(np.asarray(batch).shape[-1], scores.shape[1])
+            sequence, _, qstring, moves, probs = ctx.decode_ub(scores, model.alphabet, *model.qscore_params())
+        else:
+            sequence, _, qstring, moves, probs = model.basecall_chunks(batch, ub_probs=True)
+        return _ub_dict(sequence, qstring, moves, probs, qscores)
     if not model.encoder[-1].expand_blanks:
         own = model.encoder[-1].blank_score
         if own is None or float(own) != float(blank_score):
@@ -100,7 +113,15 @@ def _scores_dict(sequence):
     }
 
 
-def compute_sequences_pipelined(model, batches, reverse=False, qscores=False):
+def _ub_dict(sequence, qstring, moves, probs, qscores):
+    """compute_scores' dict of a letter-probability decode: the device qualities and moves with qscores, else the
+    placeholders of _scores_dict (the bytes of a run without qualities)."""
+    out = {"qstring": qstring, "sequence": sequence, "moves": moves.astype(bool)} if qscores else _scores_dict(sequence)
+    out["probs"] = probs
+    return out
+
+
+def compute_sequences_pipelined(model, batches, reverse=False, qscores=False, ub_probs=False):
     """
     The device stage of `basecall`: (key, batch) stream -> (key, sequence (n,T) int8 left-packed ASCII) with several batches
     in flight on the device: batch k+1 is submitted (pinned staging, H2D on a copy stream, fused kernels, D2H) before
@@ -109,19 +130,25 @@ def compute_sequences_pipelined(model, batches, reverse=False, qscores=False):
     slots -- batch k+3 is submitted before batch k is collected, so pair (k+2, k+3) is on the device, its H2D copies done,
     while the host waits for pair (k, k+1) -- otherwise two.  Results come out in input order, depth - 1 batches late.
     (compute_scores is the same operator, synchronous, with the reference's full result dict.)
-    With qscores every item is instead compute_scores' dict with the device qualities and moves (Viterbi branch).
+    With qscores every item is instead compute_scores' dict with the device qualities and moves (Viterbi branch), with
+    ub_probs compute_scores' dict with the letter-probability planes.
     """
+    as_dict = qscores or ub_probs
     if reverse or not model.encoder[-1].expand_blanks:
         for key, batch in batches:                       # decode of host-side reverse-complemented scores: synchronous
-            res = compute_scores(model, batch, reverse=reverse, qscores=qscores)
-            yield key, res if qscores else res["sequence"]
+            res = compute_scores(model, batch, reverse=reverse, qscores=qscores, ub_probs=ub_probs)
+            yield key, res if as_dict else res["sequence"]
         return
 
     def submit(slot, batch):
+        if ub_probs:
+            return model.submit_chunks(slot, batch, ub_probs=True)
         return model.submit_chunks(slot, batch, qscores=True) if qscores else model.submit_chunks(slot, batch)
 
     def collect(handle):
         out = model.collect_chunks(handle)
+        if ub_probs:
+            return _ub_dict(out[0], out[2], out[3], out[4], qscores)
         if qscores:
             return {"qstring": out[2], "sequence": out[0], "moves": out[3].astype(bool)}
         return out[0]
@@ -145,14 +172,14 @@ def compute_sequences_pipelined(model, batches, reverse=False, qscores=False):
         yield k, collect(h)
 
 
-def compute_scores_pipelined(model, batches, reverse=False, qscores=False):
+def compute_scores_pipelined(model, batches, reverse=False, qscores=False, ub_probs=False):
     """compute_scores over a stream of (key, batch), two batches in flight; yields the reference's result dicts."""
     if not model.encoder[-1].expand_blanks:              # beam search: qualities and moves are real, one batch at a time
         for key, batch in batches:
-            yield key, compute_scores(model, batch, reverse=reverse)
+            yield key, compute_scores(model, batch, reverse=reverse, ub_probs=ub_probs)
         return
-    for key, res in compute_sequences_pipelined(model, batches, reverse=reverse, qscores=qscores):
-        yield key, res if qscores else _scores_dict(res)
+    for key, res in compute_sequences_pipelined(model, batches, reverse=reverse, qscores=qscores, ub_probs=ub_probs):
+        yield key, res if (qscores or ub_probs) else _scores_dict(res)
 
 
 def to_str(x, encoding="ascii"):
@@ -193,23 +220,63 @@ def _called_beam(model, attrs):
     return out
 
 
-def basecall(model, reads, chunksize=4000, overlap=100, batchsize=32, reverse=False, qscores=False):
+NATURAL = "ACGT"
+
+
+def ub_letters(model):
+    """(plane index b, letter) of the model's alphabet letters outside A, C, G, T: the letters `ub_probs` reports."""
+    return [(b, c) for b, c in enumerate(model.alphabet[1:]) if c not in NATURAL]
+
+
+def _planes(res):
+    """compute_scores' (n, nb, T) 'probs' as one (n, T) row set per plane, stitched like the sequence rows."""
+    if "probs" not in res:
+        return res
+    out = dict(res)
+    probs = out.pop("probs")
+    out["probs"] = {b: probs[:, b] for b in range(probs.shape[1])}
+    return out
+
+
+def ub_tags(model, attrs):
+    """SAM / FASTQ tags of the stitched planes: `u<letter>:B:C,v1,..,vL` per letter outside A, C, G, T, one value per
+    called base (the plane bytes where the stitched sequence row holds a base)."""
+    called = np.asarray(attrs["sequence"]) != 0
+    tags = []
+    for b, letter in ub_letters(model):
+        vals = np.asarray(attrs["probs"][b])[called]
+        tags.append("u%s:B:C,%s" % (letter, ",".join(map(str, vals.tolist()))))
+    return tags
+
+
+def _called_ub(model, attrs):
+    out = _called_beam(model, attrs)
+    if out["sequence"]:
+        out["mods"] = ub_tags(model, attrs)
+    return out
+
+
+def basecall(model, reads, chunksize=4000, overlap=100, batchsize=32, reverse=False, qscores=False, ub_probs=False):
     """Basecall `reads` (objects with .signal); yields (read, {'sequence','qstring','sig_move'}) in input order.
     qscores: the Viterbi branch writes the device's per-base qualities (compute_scores) instead of the 'O' placeholders;
-    their rows are stitched like the sequence rows, so len(qstring) == len(sequence), and the moves are stitched in time."""
+    their rows are stitched like the sequence rows, so len(qstring) == len(sequence), and the moves are stitched in time.
+    ub_probs: the letter-probability planes are stitched like the sequence rows too (reverse included), and every read's
+    result carries their tags in 'mods' (ub_tags), the slot the writers append to a record's tags."""
     chunks = thread_iter(
         ((read, 0, len(read.signal)), chunk(np.asarray(read.signal, dtype=np.float32), chunksize, overlap))
         for read in reads
     )
     batches = thread_iter(batchify(chunks, batchsize=batchsize))
-    if qscores or not model.encoder[-1].expand_blanks:
+    if qscores or ub_probs or not model.encoder[-1].expand_blanks:
         # the reference's own five stages (crf/basecall.py:96-122): result dicts are unbatched and stitched plane by plane
-        scores = thread_iter(compute_scores_pipelined(model, batches, reverse=reverse, qscores=qscores))
+        scores = thread_iter((key, _planes(res)) for key, res in
+                             compute_scores_pipelined(model, batches, reverse=reverse, qscores=qscores, ub_probs=ub_probs))
         results = thread_iter(
             (read, stitch_results(attrs, end - start, chunksize, overlap, model.stride, reverse))
             for ((read, start, end), attrs) in unbatchify(scores)
         )
-        return thread_iter((read, _called_beam(model, attrs)) for read, attrs in results)
+        called = _called_ub if ub_probs else _called_beam
+        return thread_iter((read, called(model, attrs)) for read, attrs in results)
     sequences = thread_iter(compute_sequences_pipelined(model, batches, reverse=reverse))
     results = thread_iter(
         (read, stitch(seq, chunksize, overlap, end - start, model.stride, reverse=reverse))

@@ -401,11 +401,14 @@ class Model(torch.nn.Module):
         q = self.config.get("qscore", {}) or {}
         return float(q.get("scale", 1.0)), float(q.get("bias", 0.0))
 
-    def basecall_chunks(self, batch, qscores=False):
+    def basecall_chunks(self, batch, qscores=False, ub_probs=False):
         """Fused encode + decode of a (N,1,L) batch -> (seq (N,T) int8 left-packed ASCII, lens (N,)); with qscores also
-        qstring (N,T) int8 (left-packed beside seq) and moves (N,T) uint8 (xb_basecall_chunks_q)."""
+        qstring (N,T) int8 (left-packed beside seq) and moves (N,T) uint8 (xb_basecall_chunks_q); with ub_probs (qualities
+        included) also probs (N,nb,T) uint8, the letter-probability planes left-packed beside seq (xb_basecall_chunks_ub)."""
         sig = self._as_signal(batch)
         ctx = self.context(sig.shape[1], sig.shape[0])
+        if ub_probs:
+            return ctx.basecall_chunks_ub(sig, self.alphabet, *self.qscore_params())
         if qscores:
             return ctx.basecall_chunks_q(sig, self.alphabet, *self.qscore_params())
         return ctx.basecall_chunks(sig, self.alphabet)
@@ -417,6 +420,15 @@ class Model(torch.nn.Module):
         scores = np.ascontiguousarray(scores, dtype=np.float32)
         T, N, _ = scores.shape
         return self.context(T * self.stride, N).decode_q(scores, self.alphabet, *self.qscore_params())
+
+    def decode_ub(self, scores):
+        """(T,N,C) host scores -> (seq, lens, qstring, moves, probs) of the Viterbi decode with qualities and letter
+        probabilities (xb_decode_ub)."""
+        if hasattr(scores, "detach"):
+            scores = scores.detach().to(torch.float32).cpu().numpy()
+        scores = np.ascontiguousarray(scores, dtype=np.float32)
+        T, N, _ = scores.shape
+        return self.context(T * self.stride, N).decode_ub(scores, self.alphabet, *self.qscore_params())
 
     def basecall_chunks_beam(self, batch, beam_width=32, beam_cut=100.0, scale=1.0, offset=0.0):
         """Fused encode + beam search of a (N,1,L) batch -> {'sequence', 'qstring' (N,T) int8, 'moves' (N,T) uint8, 'score'}:
@@ -433,13 +445,16 @@ class Model(torch.nn.Module):
         T, N, _ = scores.shape
         return self.context(T * self.stride, N).beam_search(scores, self.alphabet, beam_width, beam_cut, scale, offset)
 
-    def submit_chunks(self, slot, batch, qscores=False):
+    def submit_chunks(self, slot, batch, qscores=False, ub_probs=False):
         """Enqueue the fused encode + decode of a (N,1,L) batch in pipeline slot 0 .. 3 without waiting; returns a handle
         for collect_chunks.  The caller keeps at most one handle per slot in flight.  qscores: the decode with qualities
-        (xb_submit_chunks_q); collect_chunks then returns (seq, lens, qstring, moves)."""
+        (xb_submit_chunks_q); collect_chunks then returns (seq, lens, qstring, moves).  ub_probs: with qualities and letter
+        probabilities (xb_submit_chunks_ub); collect_chunks then returns (seq, lens, qstring, moves, probs)."""
         sig = self._as_signal(batch)
         ctx = self.context(sig.shape[1], sig.shape[0])
         self.chunks_submitted = getattr(self, "chunks_submitted", 0) + sig.shape[0]
+        if ub_probs:
+            return ctx, slot, ctx.submit_chunks_ub(slot, sig, self.alphabet, *self.qscore_params()), "ub"
         if qscores:
             return ctx, slot, ctx.submit_chunks_q(slot, sig, self.alphabet, *self.qscore_params()), True
         return ctx, slot, ctx.submit_chunks(slot, sig, self.alphabet)
@@ -462,6 +477,8 @@ class Model(torch.nn.Module):
     @staticmethod
     def collect_chunks(handle):
         ctx, slot, n = handle[:3]
+        if len(handle) > 3 and handle[3] == "ub":       # submitted with letter probabilities
+            return ctx.collect_chunks_ub(slot, n)
         if len(handle) > 3:                     # submitted with qualities
             return ctx.collect_chunks_q(slot, n)
         return ctx.collect_chunks(slot, n)

@@ -57,6 +57,9 @@ struct xb_ctx {
         int8_t *h_q = nullptr, *d_q = nullptr;
         uint8_t *h_mv = nullptr, *d_mv = nullptr;
         bool qs = false;                       // the batch in flight was submitted with qualities
+        // letter probabilities (xb_submit_chunks_ub): pinned + device staging (max_batch, nb, T), allocated by the first _ub submission
+        uint8_t *h_p = nullptr, *d_p = nullptr;
+        bool ub = false;                       // the batch in flight was submitted with letter probabilities
     } slots[XB_PIPELINE_SLOTS];
     bool pipeline_failed = false;          // a collected batch reported a lost rendezvous: every batch in flight fails with it
     hipStream_t stream_copy = nullptr;     // H2D of the next batch beside the compute of the current one
@@ -118,6 +121,10 @@ struct xb_ctx {
     // results of a co-scheduled pair of _q calls before they are split (2 max_batch, T)
     int8_t *q_seq = nullptr, *q_fseq = nullptr;
     uint8_t *q_moves = nullptr, *q_fmoves = nullptr;
+    // letter probabilities (xb_decode_ub, lazily allocated): the per-step letter mass workspace (cap, T, nb) fp32, the device
+    // staging of the host-pointer calls (max_batch, nb, T) and the planes of a co-scheduled pair before they are split
+    float *u_buf = nullptr;
+    uint8_t *u_probs = nullptr, *u_fprobs = nullptr;
     unsigned *sync = nullptr;    // [64 groups * 32] counters + error word at the end
     unsigned *error = nullptr;
     int lstm_mode = 0;
@@ -161,6 +168,8 @@ struct xb_ctx {
         float qscale = 1.0f, qoffset = 0.0f;
         int8_t *qstr = nullptr;                 // (n, T) device, required with qs
         uint8_t *moves = nullptr;               // (n, T) device or nullptr
+        int ub = 0;                             // 1 (with qs): the letter-probability variant (xb_basecall_chunks_ub / xb_submit_chunks_ub)
+        uint8_t *probs = nullptr;               // (n, nb, T) device, required with ub
     };
     int fuse_ok = 1;                            // pairing is possible in this context (schedule, batch size, XB_FUSE)
     int fuse = 0;                               // ... and the caller asked for it (xb_reserve_pairing)
@@ -752,6 +761,7 @@ struct QualOut {
     int8_t *qstr = nullptr;      // (n, T) device
     uint8_t *moves = nullptr;    // (n, T) device or nullptr
     float qscale = 1.0f, qoffset = 0.0f;
+    uint8_t *probs = nullptr;    // (n, nb, T) device or nullptr: the letter-probability variant (xb_decode_ub)
 };
 
 int run_decode(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, int ld, const char *alphabet,
@@ -779,6 +789,10 @@ int run_decode(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, 
         if (!qual->qstr || !d_seq) return fail(ctx, XB_ERR_INVALID, "qualities need the seq and qstring outputs");
         p.qstr = qual->qstr; p.moves = qual->moves; p.qscale = qual->qscale; p.qoffset = qual->qoffset;
         p.beta_out = ctx->beta;
+        if (qual->probs) {
+            if (!ctx->u_buf) return fail(ctx, XB_ERR_INVALID, "letter probabilities need their workspace");
+            p.probs = qual->probs; p.ubuf = ctx->u_buf;
+        }
     }
     memset(p.alphabet, 0, sizeof p.alphabet);
     if (alphabet) {
@@ -820,6 +834,17 @@ int ensure_q_staging(xb_ctx *ctx)
         if (!rc && !ctx->q_fseq) rc = dev_alloc(ctx, &ctx->q_fseq, 2 * N * T);
         if (!rc && !ctx->q_fmoves) rc = dev_alloc(ctx, &ctx->q_fmoves, 2 * N * T);
     }
+    return rc;
+}
+
+// device workspace and staging of the letter-probability calls (once per context; the quality staging too)
+int ensure_ub_staging(xb_ctx *ctx)
+{
+    const size_t N = (size_t)ctx->cfg.max_batch, T = (size_t)ctx->T, nb = (size_t)ctx->cfg.n_base;
+    int rc = ensure_q_staging(ctx);
+    if (!rc && !ctx->u_buf) rc = dev_alloc(ctx, &ctx->u_buf, (ctx->fuse_ok ? 2 : 1) * N * T * nb);
+    if (!rc && !ctx->u_probs) rc = dev_alloc(ctx, &ctx->u_probs, N * nb * T);
+    if (ctx->fuse_ok && !rc && !ctx->u_fprobs) rc = dev_alloc(ctx, &ctx->u_fprobs, 2 * N * nb * T);
     return rc;
 }
 
@@ -1000,6 +1025,7 @@ XB_API void xb_ctx_destroy(xb_ctx *ctx)
         if (sl.h_err) (void)hipHostFree(sl.h_err);
         if (sl.h_q) (void)hipHostFree(sl.h_q);
         if (sl.h_mv) (void)hipHostFree(sl.h_mv);
+        if (sl.h_p) (void)hipHostFree(sl.h_p);
         if (sl.h2d) (void)hipEventDestroy(sl.h2d);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
@@ -1267,6 +1293,48 @@ XB_API int xb_decode_q(xb_ctx *ctx, const float *scores, int T, int n, int has_b
     XB_HIP(ctx, hipMemcpyAsync(seq, ctx->seq, nt, hipMemcpyDeviceToHost, ctx->stream));
     XB_HIP(ctx, hipMemcpyAsync(qstring, ctx->q_seq, nt, hipMemcpyDeviceToHost, ctx->stream));
     if (moves) XB_HIP(ctx, hipMemcpyAsync(moves, ctx->q_moves, nt, hipMemcpyDeviceToHost, ctx->stream));
+    if (seq_len) XB_HIP(ctx, hipMemcpyAsync(seq_len, ctx->seq_len, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    return xb_synchronize(ctx);
+}
+
+XB_API int xb_decode_ub_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const char *alphabet,
+                            float qscale, float qoffset, int8_t *d_seq, int8_t *d_qstring, uint8_t *d_moves, uint8_t *d_probs,
+                            int32_t *d_seq_len)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
+    if (!d_scores || !d_seq || !d_qstring || !d_probs || !alphabet) return fail(ctx, XB_ERR_INVALID, "null argument");
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = join_async_decode(ctx)) return rc;
+    if (int rc = ensure_ub_staging(ctx)) return rc;
+    ctx->result_stream = ctx->stream;
+    const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
+    QualOut q;
+    q.qstr = d_qstring; q.moves = d_moves; q.qscale = qscale; q.qoffset = qoffset; q.probs = d_probs;
+    return run_decode(ctx, d_scores, T, n, has_blank ? 1 : 0, ld, alphabet, nullptr, d_seq, d_seq_len, nullptr, nullptr, &q);
+}
+
+XB_API int xb_decode_ub(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, const char *alphabet, float qscale,
+                        float qoffset, int8_t *seq, int8_t *qstring, uint8_t *moves, uint8_t *probs, int32_t *seq_len)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
+    if (!scores || !seq || !qstring || !probs || !alphabet) return fail(ctx, XB_ERR_INVALID, "null argument");
+    if (T < 1 || T > ctx->T) return fail(ctx, XB_ERR_INVALID, "T=%d outside [1, %d]", T, ctx->T);
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcj = join_async_decode(ctx)) return rcj;
+    if (int rcs = ensure_ub_staging(ctx)) return rcs;
+    const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
+    XB_HIP(ctx, hipMemcpyAsync(ctx->scores, scores, sizeof(float) * (size_t)T * n * ld, hipMemcpyHostToDevice, ctx->stream));
+    QualOut q;
+    q.qstr = ctx->q_seq; q.moves = moves ? ctx->q_moves : nullptr; q.qscale = qscale; q.qoffset = qoffset; q.probs = ctx->u_probs;
+    int rc = run_decode(ctx, ctx->scores, T, n, has_blank ? 1 : 0, ld, alphabet, nullptr, ctx->seq, ctx->seq_len, nullptr, nullptr, &q);
+    if (rc) return rc;
+    const size_t nt = (size_t)n * T;
+    XB_HIP(ctx, hipMemcpyAsync(seq, ctx->seq, nt, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(qstring, ctx->q_seq, nt, hipMemcpyDeviceToHost, ctx->stream));
+    if (moves) XB_HIP(ctx, hipMemcpyAsync(moves, ctx->q_moves, nt, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(probs, ctx->u_probs, nt * ctx->cfg.n_base, hipMemcpyDeviceToHost, ctx->stream));
     if (seq_len) XB_HIP(ctx, hipMemcpyAsync(seq_len, ctx->seq_len, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     return xb_synchronize(ctx);
 }
@@ -1584,6 +1652,8 @@ static int call_post_actions(xb_ctx *ctx, const xb_ctx::Call &c, hipStream_t rs)
             XB_HIP(ctx, hipMemcpyAsync(sl.h_q, sl.d_q, (size_t)c.n * ctx->T, hipMemcpyDeviceToHost, rs));
             XB_HIP(ctx, hipMemcpyAsync(sl.h_mv, sl.d_mv, (size_t)c.n * ctx->T, hipMemcpyDeviceToHost, rs));
         }
+        if (c.ub)
+            XB_HIP(ctx, hipMemcpyAsync(sl.h_p, sl.d_p, (size_t)c.n * ctx->cfg.n_base * ctx->T, hipMemcpyDeviceToHost, rs));
         XB_HIP(ctx, hipEventRecord(sl.done, rs));
     }
     if (c.after) c.after(c.after_arg);
@@ -1604,6 +1674,7 @@ static int launch_calls(xb_ctx *ctx, const xb_ctx::Call &a, const xb_ctx::Call *
         qo.qstr = b ? ctx->q_fseq : a.qstr;
         qo.moves = b ? ctx->q_fmoves : a.moves;
         qo.qscale = a.qscale; qo.qoffset = a.qoffset;
+        if (a.ub) qo.probs = b ? ctx->u_fprobs : a.probs;
         qual = &qo;
     }
     int rc;
@@ -1642,6 +1713,11 @@ static int launch_calls(xb_ctx *ctx, const xb_ctx::Call &a, const xb_ctx::Call *
             if (a.moves) XB_HIP(ctx, hipMemcpyAsync(a.moves, ctx->q_fmoves, (size_t)a.n * T, hipMemcpyDeviceToDevice, rs));
             if (b->moves)
                 XB_HIP(ctx, hipMemcpyAsync(b->moves, ctx->q_fmoves + (size_t)a.n * T, (size_t)b->n * T, hipMemcpyDeviceToDevice, rs));
+        }
+        if (a.ub) {      // (n, nb, T) planes: a's chunks first
+            const size_t pt = (size_t)ctx->cfg.n_base * T;
+            XB_HIP(ctx, hipMemcpyAsync(a.probs, ctx->u_fprobs, (size_t)a.n * pt, hipMemcpyDeviceToDevice, rs));
+            XB_HIP(ctx, hipMemcpyAsync(b->probs, ctx->u_fprobs + (size_t)a.n * pt, (size_t)b->n * pt, hipMemcpyDeviceToDevice, rs));
         }
     }
     if (rs == ctx->stream3) {
@@ -1683,6 +1759,8 @@ static int enqueue_call(xb_ctx *ctx, const xb_ctx::Call &c)
         bool pair = ctx->fuse && h.n + c.n <= 2 * ctx->cfg.max_batch && strcmp(h.alphabet, c.alphabet) == 0 && h.seq != c.seq;
         // qualities: only with a call of the same mode and the same qscale / qoffset (one decode pass serves both)
         pair = pair && h.qs == c.qs && (!c.qs || (h.qscale == c.qscale && h.qoffset == c.qoffset && h.qstr != c.qstr && ctx->q_fseq));
+        // letter probabilities: only with another _ub call (of the same qscale / qoffset, above)
+        pair = pair && h.ub == c.ub && (!c.ub || (h.probs != c.probs && ctx->u_fprobs));
         if (pair && h.n + c.n > ctx->cap && reserve_pairing(ctx) != XB_OK) pair = false;     // no room for both: one by one
         if (pair) {
             const int rc = launch_calls(ctx, h, &c);
@@ -1758,6 +1836,34 @@ XB_API int xb_basecall_chunks_q(xb_ctx *ctx, const float *signal, int n, const c
     return xb_synchronize(ctx);
 }
 
+XB_API int xb_basecall_chunks_ub(xb_ctx *ctx, const float *signal, int n, const char *alphabet, float qscale, float qoffset,
+                                 int8_t *seq, int8_t *qstring, uint8_t *moves, uint8_t *probs, int32_t *seq_len)
+{
+    int rc = check_ready(ctx, n);
+    if (rc) return rc;
+    if (!signal || !seq || !qstring || !probs || !alphabet) return fail(ctx, XB_ERR_INVALID, "null argument");
+    if ((int)strlen(alphabet) < ctx->cfg.n_base + 1 || strlen(alphabet) >= sizeof(xb_ctx::Call{}.alphabet))
+        return fail(ctx, XB_ERR_INVALID, "alphabet needs %d symbols", ctx->cfg.n_base + 1);
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if ((rc = ensure_ub_staging(ctx))) return rc;
+    XB_HIP(ctx, hipMemcpyAsync(ctx->d_signal, signal, sizeof(float) * (size_t)n * ctx->cfg.chunk_len,
+                               hipMemcpyHostToDevice, ctx->stream));
+    xb_ctx::Call c;
+    c.signal = ctx->d_signal; c.n = n; c.seq = ctx->seq; c.len = ctx->seq_len;
+    c.qs = 1; c.qscale = qscale; c.qoffset = qoffset; c.qstr = ctx->q_seq; c.moves = moves ? ctx->q_moves : nullptr;
+    c.ub = 1; c.probs = ctx->u_probs;
+    strcpy(c.alphabet, alphabet);
+    if ((rc = enqueue_call(ctx, c))) return rc;
+    if ((rc = join_async_decode(ctx))) return rc;
+    const size_t nt = (size_t)n * ctx->T;
+    XB_HIP(ctx, hipMemcpyAsync(seq, ctx->seq, nt, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(qstring, ctx->q_seq, nt, hipMemcpyDeviceToHost, ctx->stream));
+    if (moves) XB_HIP(ctx, hipMemcpyAsync(moves, ctx->q_moves, nt, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(probs, ctx->u_probs, nt * ctx->cfg.n_base, hipMemcpyDeviceToHost, ctx->stream));
+    if (seq_len) XB_HIP(ctx, hipMemcpyAsync(seq_len, ctx->seq_len, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    return xb_synchronize(ctx);
+}
+
 // lazily created: most contexts (tests, bench) never use the host pipeline
 static int ensure_slot(xb_ctx *ctx, int slot)
 {
@@ -1791,6 +1897,17 @@ static int ensure_slot_q(xb_ctx *ctx, int slot)
     return rc;
 }
 
+// the slot's staging of letter probabilities, on its first _ub submission
+static int ensure_slot_ub(xb_ctx *ctx, int slot)
+{
+    xb_ctx::Slot &sl = ctx->slots[slot];
+    const size_t NPT = (size_t)ctx->cfg.max_batch * ctx->cfg.n_base * ctx->T;
+    if (!sl.h_p) XB_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&sl.h_p), NPT, hipHostMallocDefault));
+    int rc = sl.d_p ? XB_OK : dev_alloc(ctx, &sl.d_p, NPT);
+    if (!rc) rc = ensure_ub_staging(ctx);
+    return rc;
+}
+
 static int submit_chunks(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet, const xb_ctx::Call *q)
 {
     int rc = check_ready(ctx, n);
@@ -1799,6 +1916,7 @@ static int submit_chunks(xb_ctx *ctx, int slot, const float *signal, int n, cons
     XB_HIP(ctx, hipSetDevice(ctx->device));
     if ((rc = ensure_slot(ctx, slot))) return rc;
     if (q && (rc = ensure_slot_q(ctx, slot))) return rc;
+    if (q && q->ub && (rc = ensure_slot_ub(ctx, slot))) return rc;
     xb_ctx::Slot &sl = ctx->slots[slot];
     if (sl.busy) return fail(ctx, XB_ERR_STATE, "slot %d was submitted and not collected", slot);
     const size_t bytes = sizeof(float) * (size_t)n * ctx->cfg.chunk_len;
@@ -1814,6 +1932,7 @@ static int submit_chunks(xb_ctx *ctx, int slot, const float *signal, int n, cons
     c.signal = sl.d_signal; c.n = n; c.seq = sl.d_seq; c.len = sl.d_len; c.slot = slot;
     if (q) {
         c.qs = 1; c.qscale = q->qscale; c.qoffset = q->qoffset; c.qstr = sl.d_q; c.moves = sl.d_mv;
+        if (q->ub) { c.ub = 1; c.probs = sl.d_p; }
     }
     strcpy(c.alphabet, alphabet);
     rc = enqueue_call(ctx, c);
@@ -1821,6 +1940,7 @@ static int submit_chunks(xb_ctx *ctx, int slot, const float *signal, int n, cons
     sl.n = n;
     sl.busy = true;
     sl.qs = q != nullptr;
+    sl.ub = q != nullptr && q->ub;
     return XB_OK;
 }
 
@@ -1835,6 +1955,29 @@ XB_API int xb_submit_chunks_q(xb_ctx *ctx, int slot, const float *signal, int n,
     xb_ctx::Call q;
     q.qscale = qscale; q.qoffset = qoffset;
     return submit_chunks(ctx, slot, signal, n, alphabet, &q);
+}
+
+XB_API int xb_submit_chunks_ub(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet, float qscale,
+                               float qoffset)
+{
+    xb_ctx::Call q;
+    q.qscale = qscale; q.qoffset = qoffset; q.ub = 1;
+    return submit_chunks(ctx, slot, signal, n, alphabet, &q);
+}
+
+XB_API int xb_collect_chunks_ub(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len, int8_t *qstring, uint8_t *moves,
+                                uint8_t *probs)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    if (slot < 0 || slot >= XB_PIPELINE_SLOTS || !seq || !qstring || !probs)
+        return fail(ctx, XB_ERR_INVALID, "bad slot / null argument");
+    xb_ctx::Slot &sl = ctx->slots[slot];
+    if (!sl.busy || !sl.ub) return fail(ctx, XB_ERR_STATE, "slot %d has no submission with letter probabilities in flight", slot);
+    const int n = sl.n;
+    const int rc = xb_collect_chunks_q(ctx, slot, seq, seq_len, qstring, moves);
+    if (rc) return rc;
+    memcpy(probs, sl.h_p, (size_t)n * ctx->cfg.n_base * ctx->T);
+    return XB_OK;
 }
 
 XB_API int xb_collect_chunks_q(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len, int8_t *qstring, uint8_t *moves)

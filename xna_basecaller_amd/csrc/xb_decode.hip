@@ -16,6 +16,9 @@
 //   3. Max forward over Q + per-step arg-max of the max-marginals (read Q, bmax), then pack.
 // The quality variant (QS, xb_decode_q) adds a fourth phase after sweep 3: per-step path posteriors from the stashed
 // alpha / beta rows, then per-base quality characters, packed beside the bases (see "qualities" below).
+// The letter-probability variant (UB, xb_decode_ub; implies QS) also sums, in sweep 2, each step's move-edge posteriors
+// per emitted letter (nb floats per step into a per-chunk workspace) and, in the pack, turns them into per-base windowed
+// probability bytes of every letter (see "letter probabilities" below).
 //
 // What bounds a step is the LENGTH OF ITS DEPENDENCY CHAIN, not bytes or instruction count (a dependent VALU
 // instruction issues every ~8 cycles, independent ones every ~2.4 per SIMD: tools/valu_probe.hip), so the kernel is
@@ -219,6 +222,24 @@ __device__ __forceinline__ float pair_sum_ordered(const float (&ex)[(E + 1) / 2]
 #undef XB_BC0
 #undef XB_BC1
 
+// Inclusive sum scan over each 16-lane DPP row (Hillis-Steele: x[l] = x[l - d] + x[l] for l >= d, d = 1, 2, 4, 8; a lane
+// without a source in its row keeps its value), so that lane 15 of a row ends with the row's sum in that tree order
+__device__ __forceinline__ float row16_scan(float v)
+{
+    asm volatile(
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1"
+        : "+v"(v));
+    return v;
+}
+
 // CNT consecutive floats from a 4-byte aligned address in the widest pieces (global_load_dwordx4 / x2 / dword)
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
@@ -310,7 +331,9 @@ struct Edges {
 // proper is compiled without those paths (measured: 1-2 % of the decode time when they are run-time branches).
 // QS = true: the xb_decode_q variant -- sweep 2 stores the Log backward rows (beta_out), sweep 3 keeps the arg-max state of
 // every step, and phase 4 turns them into per-base qualities and moves.  The instantiations with QS = false compile none of it.
-template <int NB, int BS, bool HB, int LPS, int VW, bool SCAN, bool QS>
+// UB = true (with QS): the xb_decode_ub variant -- sweep 2 also reduces each step's move-edge posteriors per letter into
+// p.ubuf, and the pack writes every base's letter-probability bytes.  The instantiations with UB = false compile none of it.
+template <int NB, int BS, bool HB, int LPS, int VW, bool SCAN, bool QS, bool UB>
 __global__ __launch_bounds__(BS) XB_DEC_WAVES_ATTR void crf_decode_kernel(xb::DecodeParams p)
 {
     constexpr int E = NB + 1;
@@ -350,6 +373,8 @@ __global__ __launch_bounds__(BS) XB_DEC_WAVES_ATTR void crf_decode_kernel(xb::De
     float *sBc = reinterpret_cast<float *>(sRi + LRING * NW);     // [4] broadcast scratch
     int8_t *sLab = reinterpret_cast<int8_t *>(sBc + 4);           // [T]
     int16_t *sPath = reinterpret_cast<int16_t *>(sLab + ((T + 1) & ~1));   // [T] QS only: arg-max state per step (S <= 1024)
+    // [2][S] UB only: move mass of every source state per step (sweep 2), at the next 4-byte boundary behind sPath
+    float *sU = reinterpret_cast<float *>(reinterpret_cast<uintptr_t>(sPath + T + 1) & ~(uintptr_t)3);
 
     const float *sc = p.scores + (size_t)n * p.ld;
     const size_t tstride = (size_t)N * p.ld;
@@ -522,6 +547,24 @@ __global__ __launch_bounds__(BS) XB_DEC_WAVES_ATTR void crf_decode_kernel(xb::De
             for (int g = tid * 4; g < ldq; g += BS * 4)
                 *reinterpret_cast<f32x4 *>(dst + g) = *reinterpret_cast<const f32x4 *>(src + g);
         };
+        // UB: e_t[b] of step t from the move masses of its hi sources b*hi .. b*hi+hi-1 (source order in sU), once every
+        // thread has passed the barrier of step t-1.  Lane 16 b + g sums the sources g, g + 16, .. of letter b in increasing
+        // order from 0; row16_scan then adds the 16 lanes of the row and lane 15 stores e_t[b] to the chunk's ubuf slice.
+        auto ub_reduce = [&](int t) {
+            if constexpr (UB) {
+#pragma unroll
+                for (int l0 = 0; l0 < NB * 16; l0 += BS) {
+                    if (l0 + wave * 64 < NB * 16) {              // wave-uniform
+                        const int c = l0 + tid, b = c >> 4, g = c & 15;
+                        const float *row = sU + (t & 1) * S + (b < NB ? b : 0) * hi;
+                        float x = 0.0f;
+                        for (int q = g; q < hi; q += 16) x += row[q];
+                        x = row16_scan(x);
+                        if (g == 15 && b < NB) p.ubuf[((size_t)n * T + t) * NB + b] = x;
+                    }
+                }
+            }
+        };
         typename std::conditional<VW == 4, RowRegs<NRS, BS>, RowRegs1<NRS, BS>>::type ring[RDEPTH];
         float aring[RDEPTH];
 #pragma unroll
@@ -544,6 +587,7 @@ __global__ __launch_bounds__(BS) XB_DEC_WAVES_ATTR void crf_decode_kernel(xb::De
             }
             lds_barrier();
             if (t >= 0 && t + 1 < T) store_qrow(t + 1);
+            if (UB && t >= 0 && t + 1 < T) ub_reduce(t + 1);
             if (t >= 0) {                                        // block-uniform
                 float *qs = sQ + (t & 1) * cpad;
                 const float *b1 = sA + ((t + 1) & 1) * S;
@@ -578,6 +622,22 @@ __global__ __launch_bounds__(BS) XB_DEC_WAVES_ATTR void crf_decode_kernel(xb::De
                 } else {
                     sm = pair_sum_ordered<E>(ex);
                 }
+                if constexpr (UB) {
+                    // move mass of source i: its nb move edges' posteriors summed in edge order 1..nb (from an exact 0 in
+                    // place of the stay edge), both halves of a pair in one chain
+                    float pm[EPER];
+#pragma unroll
+                    for (int r = 0; r < EPER; ++r) pm[r] = (r == 0 && stay0) ? 0.0f : P[r];
+                    float ms;
+                    if constexpr (LPS == 1) {
+                        ms = pm[0];
+#pragma unroll
+                        for (int r = 1; r < EPER; ++r) ms += pm[r];
+                    } else {
+                        ms = pair_sum_ordered<E>(pm);
+                    }
+                    if (ph == 0 && act) sU[(t & 1) * S + i] = ms;
+                }
                 if (post_mode) {                                 // uniform, xb_crf_scans: the row carries P itself (stored here,
 #pragma unroll                                                   // so that P is dead before the logs in the decode proper)
                     for (int r = 0; r < EPER; ++r)
@@ -609,6 +669,7 @@ __global__ __launch_bounds__(BS) XB_DEC_WAVES_ATTR void crf_decode_kernel(xb::De
         }
         lds_barrier();
         store_qrow(0);
+        if (UB) ub_reduce(0);
         __syncthreads();
     }
 
@@ -788,6 +849,36 @@ __global__ __launch_bounds__(BS) XB_DEC_WAVES_ATTR void crf_decode_kernel(xb::De
         return (int8_t)(int)(33.5f + q);
     };
     (void)qchar;
+    // letter probabilities (UB) of the base emitted at step t, its i-th: window = the steps after the previous emitting step
+    // up to before the next one (or 0 / T-1 at the chunk ends); mass[b] = e_u[b] summed over the window in increasing u,
+    // tot = mass summed in letter order, byte = min(255, (int)(256 * mass / tot)), all 0 when tot = 0
+    auto ubytes = [&](int t, int pos) {
+        int u0 = t - 1;
+        while (u0 >= 0 && sLab[u0] == 0) --u0;
+        int u1 = t + 1;
+        while (u1 < T && sLab[u1] == 0) ++u1;
+        const float *e = p.ubuf + (size_t)n * T * NB;
+        float mass[NB];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) mass[b] = 0.0f;
+        for (int u = u0 + 1; u < u1; ++u) {
+#pragma unroll
+            for (int b = 0; b < NB; ++b) mass[b] = mass[b] + e[(size_t)u * NB + b];
+        }
+        float tot = mass[0];
+#pragma unroll
+        for (int b = 1; b < NB; ++b) tot = tot + mass[b];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            int v = 0;
+            if (tot > 0.0f) {
+                v = (int)(256.0f * (mass[b] / tot));
+                v = v > 255 ? 255 : v;
+            }
+            p.probs[((size_t)n * NB + b) * T + pos] = (uint8_t)v;
+        }
+    };
+    (void)ubytes;
 
     // ------------------------------------------------ labels out + path_to_str + left-pack
     if (p.labels)
@@ -813,18 +904,22 @@ __global__ __launch_bounds__(BS) XB_DEC_WAVES_ATTR void crf_decode_kernel(xb::De
                 const int l = sLab[t];
                 if (l != 0) {
                     if constexpr (QS) p.qstr[(size_t)n * T + pos] = qchar(t);     // packed in parallel with the bases
+                    if constexpr (UB) ubytes(t, pos);
                     out[pos++] = (int8_t)p.alphabet[l];
                 }
             }
             for (int t = total + tid; t < T; t += BS) out[t] = 0;
             if constexpr (QS)
                 for (int t = total + tid; t < T; t += BS) p.qstr[(size_t)n * T + t] = 0;
+            if constexpr (UB)
+                for (int b = 0; b < NB; ++b)
+                    for (int t = total + tid; t < T; t += BS) p.probs[((size_t)n * NB + b) * T + t] = 0;
         }
         if (p.seq_len && tid == 0) p.seq_len[n] = total;
     }
 }
 
-template <int NB, int BS, int LPS, bool SCAN, bool QS>
+template <int NB, int BS, int LPS, bool SCAN, bool QS, bool UB>
 hipError_t launch_nb_bs(const xb::DecodeParams &p, int vw, hipStream_t stream)
 {
     // must mirror the kernel's LDS carve
@@ -835,6 +930,7 @@ hipError_t launch_nb_bs(const xb::DecodeParams &p, int vw, hipStream_t stream)
         size_t b = sizeof(float) * (4 * cpad + 5 * (size_t)p.S + (size_t)LRING * (BS / 64)) +
                    sizeof(int) * (size_t)LRING * (BS / 64) + sizeof(float) * 4 + (size_t)p.T;
         if (QS) b += 1 + sizeof(int16_t) * (size_t)p.T;        // sPath behind sLab, at the next even byte
+        if (UB) b = ((b + 3) & ~(size_t)3) + sizeof(float) * 2 * (size_t)p.S;   // sU behind sPath, at the next 4-byte boundary
         return (b + 15) & ~(size_t)15;
     };
     // the four-wide row loads pad a state's edges to a multiple of four: where that no longer fits (4^5 states), one by one
@@ -844,9 +940,9 @@ hipError_t launch_nb_bs(const xb::DecodeParams &p, int vw, hipStream_t stream)
     dim3 grid(p.N), block(BS);
 #define XB_LAUNCH(HB, VW)                                                                                          \
     do {                                                                                                           \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&crf_decode_kernel<NB, BS, HB, LPS, VW, SCAN, QS>),         \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&crf_decode_kernel<NB, BS, HB, LPS, VW, SCAN, QS, UB>),         \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
-        hipLaunchKernelGGL((crf_decode_kernel<NB, BS, HB, LPS, VW, SCAN, QS>), grid, block, lds, stream, p);                 \
+        hipLaunchKernelGGL((crf_decode_kernel<NB, BS, HB, LPS, VW, SCAN, QS, UB>), grid, block, lds, stream, p);                 \
     } while (0)
     if (p.has_blank) {
         if (vw == 4) XB_LAUNCH(true, 4); else XB_LAUNCH(true, 1);
@@ -858,19 +954,19 @@ hipError_t launch_nb_bs(const xb::DecodeParams &p, int vw, hipStream_t stream)
 }
 
 // Block = smallest multiple of 64 threads (from a short list, pruned per alphabet) that holds LPS lanes for each state.
-template <int NB, int LPS, bool SCAN, bool QS = false>
+template <int NB, int LPS, bool SCAN, bool QS = false, bool UB = false>
 hipError_t launch_nb_lps(const xb::DecodeParams &p, int vw, hipStream_t stream)
 {
     const int need = LPS * p.S;
-    if (need <= 64) return launch_nb_bs<NB, 64, LPS, SCAN, QS>(p, vw, stream);
-    if (need <= 128) return launch_nb_bs<NB, 128, LPS, SCAN, QS>(p, vw, stream);
-    if (need <= 256) return launch_nb_bs<NB, 256, LPS, SCAN, QS>(p, vw, stream);
+    if (need <= 64) return launch_nb_bs<NB, 64, LPS, SCAN, QS, UB>(p, vw, stream);
+    if (need <= 128) return launch_nb_bs<NB, 128, LPS, SCAN, QS, UB>(p, vw, stream);
+    if (need <= 256) return launch_nb_bs<NB, 256, LPS, SCAN, QS, UB>(p, vw, stream);
     if constexpr (NB == 6) {
-        if (need <= 448) return launch_nb_bs<NB, 448, LPS, SCAN, QS>(p, vw, stream);     // 2 x 216 states
+        if (need <= 448) return launch_nb_bs<NB, 448, LPS, SCAN, QS, UB>(p, vw, stream);     // 2 x 216 states
     } else {
-        if (need <= 640) return launch_nb_bs<NB, 640, LPS, SCAN, QS>(p, vw, stream);     // 5^4 states / 2 x 4^4
+        if (need <= 640) return launch_nb_bs<NB, 640, LPS, SCAN, QS, UB>(p, vw, stream);     // 5^4 states / 2 x 4^4
         if constexpr (NB == 4 && LPS == 1) {
-            if (need <= 1024) return launch_nb_bs<NB, 1024, LPS, SCAN, QS>(p, vw, stream);   // 4^5 states
+            if (need <= 1024) return launch_nb_bs<NB, 1024, LPS, SCAN, QS, UB>(p, vw, stream);   // 4^5 states
         }
     }
     return hipErrorInvalidValue;
@@ -878,6 +974,11 @@ hipError_t launch_nb_lps(const xb::DecodeParams &p, int vw, hipStream_t stream)
 template <int NB>
 hipError_t launch_nb(const xb::DecodeParams &p, int vw, hipStream_t stream)
 {
+    // the letter-probability variant (validated by launch_crf_decode: the quality variant's outputs and ubuf set)
+    if (p.probs) {
+        if (xb::decode_lanes_per_state(p.S, p.N) == 2) return launch_nb_lps<NB, 2, false, true, true>(p, vw, stream);
+        return launch_nb_lps<NB, 1, false, true, true>(p, vw, stream);
+    }
     // the quality variant, with either lane split (validated by launch_crf_decode: full decode, beta_out and seq set)
     if (p.qstr) {
         if (xb::decode_lanes_per_state(p.S, p.N) == 2) return launch_nb_lps<NB, 2, false, true>(p, vw, stream);
@@ -1073,6 +1174,7 @@ hipError_t launch_crf_decode(const DecodeParams &p, hipStream_t stream)
     if (p.cin != (p.has_blank ? p.S * E : p.S * p.nb) || p.ld < p.cin) return hipErrorInvalidValue;
     if (!p.qbuf || p.ldq % 4 != 0 || p.ldq < p.S * E || reinterpret_cast<uintptr_t>(p.qbuf) % 16 != 0) return hipErrorInvalidValue;
     if (p.qstr && (!p.seq || !p.beta_out || p.stop_after || p.post_mode)) return hipErrorInvalidValue;
+    if (p.probs && (!p.qstr || !p.ubuf)) return hipErrorInvalidValue;
     int vw = 1;
     const uintptr_t a = reinterpret_cast<uintptr_t>(p.scores);
     // vector loads may run into the row's padding columns (ld >= cin rounded up), never past the row

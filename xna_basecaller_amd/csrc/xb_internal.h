@@ -31,6 +31,10 @@ struct DecodeParams {
     int8_t *qstr;                 // (N, T) or nullptr: quality characters, left-packed in parallel with seq, zero-padded
     uint8_t *moves;               // (N, T) or nullptr (quality variant only): 1 where the step emits a base
     float qscale, qoffset;        // q = -10 log10(error) * qscale + qoffset, before the clamp to [1, 50]
+    // letter probabilities (xb_decode_ub): set probs to run the UB variant -- the quality variant plus the per-step letter
+    // mass of the move edges, stored by sweep 2 into ubuf, and per base the windowed probability bytes of every letter
+    float *ubuf;                  // (N, T, nb) fp32 workspace: e_t[b] per chunk and step
+    uint8_t *probs;               // (N, nb, T) or nullptr: plane b = letter alphabet[1 + b], left-packed beside seq, zero-padded
 };
 hipError_t launch_crf_decode(const DecodeParams &p, hipStream_t stream);
 int decode_lanes_per_state(int S, int N);   // 1, 2 or 4 lanes serve one CRF state (env XB_DECODE_LPS overrides for tests)
