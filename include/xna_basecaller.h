@@ -296,18 +296,15 @@ XB_API int xb_pairing_active(const xb_ctx *ctx);
 #define XB_PIPELINE_SLOTS 4
 XB_API int xb_submit_chunks(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet);
 XB_API int xb_collect_chunks(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len);
-/* The pipeline with the qualities and moves of xb_decode_q: the slot's pinned staging for them is allocated by its first
- * _q submission.  xb_collect_chunks_q collects a _q submission only (XB_ERR_STATE otherwise; moves may be NULL);
- * xb_collect_chunks of a _q submission returns its bases alone.  Co-scheduling (xb_reserve_pairing): a _q call pairs only
- * with a _q call of the same qscale / qoffset, a plain call only with a plain call -- a held call that finds no such partner
+/* The pipeline with the qualities and moves of xb_decode_q (_q) and with those and the letter probabilities of xb_decode_ub
+ * (_ub): a slot's pinned staging for them is allocated by its first such submission.  A collect takes a submission of its
+ * own kind or a richer one (XB_ERR_STATE otherwise; moves may be NULL): xb_collect_chunks_q of a _ub submission returns its
+ * qualities, xb_collect_chunks of a _q or _ub submission its bases alone.  Co-scheduling (xb_reserve_pairing): a call pairs
+ * only with a call of its own kind and, for _q / _ub, the same qscale / qoffset -- a held call that finds no such partner
  * runs on its own, so every call produces exactly the bytes it produces unpaired. */
 XB_API int xb_submit_chunks_q(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet, float qscale,
                               float qoffset);
 XB_API int xb_collect_chunks_q(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len, int8_t *qstring, uint8_t *moves);
-/* The pipeline with the letter probabilities of xb_decode_ub: the slot's pinned staging for them is allocated by its first
- * _ub submission.  xb_collect_chunks_ub collects a _ub submission only (XB_ERR_STATE otherwise; moves may be NULL);
- * xb_collect_chunks_q / xb_collect_chunks of a _ub submission return its qualities / bases alone.  Co-scheduling: a _ub call
- * pairs only with a _ub call of the same qscale / qoffset, so every call produces exactly the bytes it produces unpaired. */
 XB_API int xb_submit_chunks_ub(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet, float qscale,
                                float qoffset);
 XB_API int xb_collect_chunks_ub(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len, int8_t *qstring, uint8_t *moves,

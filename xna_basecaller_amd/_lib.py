@@ -173,6 +173,21 @@ def _ptr(a):
     return int(a)          # raw device pointer (e.g. torch.Tensor.data_ptr())
 
 
+def output_level(qscores=False, ub_probs=False):
+    """Output level of the Viterbi decode: 0 the bases, 1 also qualities and moves (the _q entry points), 2 also the letter
+    probabilities (_ub; they imply the qualities)."""
+    return 2 if ub_probs else int(bool(qscores))
+
+
+def _lens_last(out):
+    """An output tuple (seq, lens[, qstring, moves[, probs]]) as the pointers of the decode / basecall entry points: lens last."""
+    return [_ptr(a) for a in out[:1] + out[2:] + out[1:2]]
+
+
+def _calib(level, qscale, qoffset):
+    return (float(qscale), float(qoffset)) if level else ()
+
+
 class Context:
     """One xb_ctx: a GPU, a stream, the device copies of the weights and all workspaces."""
 
@@ -206,6 +221,27 @@ class Context:
         except Exception:
             pass
 
+    def _scores(self, scores, has_blank):
+        """(T, n, C) scores as contiguous fp32 and the has_blank flag (0 / 1) of their layout, checked against the model."""
+        scores = np.ascontiguousarray(scores, dtype=np.float32)
+        Cin = scores.shape[2]
+        if has_blank is None:
+            has_blank = Cin == self.C_blank
+        if Cin != (self.C_blank if has_blank else self.C_noblank):
+            raise ValueError("scores last dim %d does not match the model (%d with blanks, %d without)"
+                             % (Cin, self.C_blank, self.C_noblank))
+        return scores, int(bool(has_blank))
+
+    def _outputs(self, level, n, T):
+        """Host outputs of an output level: (seq (n, T) int8, lens (n,) int32[, qstring (n, T) int8, moves (n, T) uint8[,
+        probs (n, nb, T) uint8]])."""
+        out = (np.empty((n, T), dtype=np.int8), np.empty((n,), dtype=np.int32))
+        if level >= 1:
+            out += (np.empty((n, T), dtype=np.int8), np.empty((n, T), dtype=np.uint8))
+        if level == 2:
+            out += (np.empty((n, self.n_base, T), dtype=np.uint8),)
+        return out
+
     def load_state_dict(self, state_dict):
         """state_dict: name -> fp32 array in PyTorch layout (the 28 inference-encoder tensors)."""
         for k, v in state_dict.items():
@@ -230,47 +266,31 @@ class Context:
         return scores
 
     def decode(self, scores, alphabet, has_blank=None, want_labels=False):
-        scores = np.ascontiguousarray(scores, dtype=np.float32)
-        T, n, Cin = scores.shape
-        if has_blank is None:
-            has_blank = Cin == self.C_blank
-        if Cin != (self.C_blank if has_blank else self.C_noblank):
-            raise ValueError("scores last dim %d does not match the model (%d with blanks, %d without)"
-                             % (Cin, self.C_blank, self.C_noblank))
+        scores, has_blank = self._scores(scores, has_blank)
+        T, n, _ = scores.shape
         labels = np.empty((n, T), dtype=np.int8) if want_labels else None
-        seq = np.empty((n, T), dtype=np.int8)
-        lens = np.empty((n,), dtype=np.int32)
-        self._check(self.lib.xb_decode(self.h, scores.ctypes.data, T, n, int(bool(has_blank)),
-                                       "".join(alphabet).encode(), _ptr(labels), seq.ctypes.data, lens.ctypes.data))
+        seq, lens = self._outputs(0, n, T)
+        self._check(self.lib.xb_decode(self.h, scores.ctypes.data, T, n, has_blank, "".join(alphabet).encode(), _ptr(labels),
+                                       seq.ctypes.data, lens.ctypes.data))
         return (seq, lens, labels) if want_labels else (seq, lens)
 
     def crf_logz(self, scores, has_blank=None):
         """(T, n, C) scores -> (n,) fp32 log partition function (CTC_CRF.logZ, crf/model.py:41-46)."""
-        scores = np.ascontiguousarray(scores, dtype=np.float32)
-        T, n, Cin = scores.shape
-        if has_blank is None:
-            has_blank = Cin == self.C_blank
-        if Cin != (self.C_blank if has_blank else self.C_noblank):
-            raise ValueError("scores last dim %d does not match the model (%d with blanks, %d without)"
-                             % (Cin, self.C_blank, self.C_noblank))
+        scores, has_blank = self._scores(scores, has_blank)
+        T, n, _ = scores.shape
         logz = np.empty((n,), dtype=np.float32)
-        self._check(self.lib.xb_crf_logz(self.h, scores.ctypes.data, T, n, int(bool(has_blank)), logz.ctypes.data))
+        self._check(self.lib.xb_crf_logz(self.h, scores.ctypes.data, T, n, has_blank, logz.ctypes.data))
         return logz
 
     def crf_scans(self, scores, want=("alpha", "beta", "logz", "post"), has_blank=None):
         """(T, n, C) scores -> dict of the Log scans (xb_crf_scans): 'alpha', 'beta' (T+1, n, S), 'logz' (n,),
         'post' (T, n, S*(n_base+1))."""
-        scores = np.ascontiguousarray(scores, dtype=np.float32)
-        T, n, Cin = scores.shape
-        if has_blank is None:
-            has_blank = Cin == self.C_blank
-        if Cin != (self.C_blank if has_blank else self.C_noblank):
-            raise ValueError("scores last dim %d does not match the model (%d with blanks, %d without)"
-                             % (Cin, self.C_blank, self.C_noblank))
+        scores, has_blank = self._scores(scores, has_blank)
+        T, n, _ = scores.shape
         S = self.C_blank // (self.n_base + 1)
         shapes = {"alpha": (T + 1, n, S), "beta": (T + 1, n, S), "logz": (n,), "post": (T, n, self.C_blank)}
         out = {k: np.empty(shapes[k], dtype=np.float32) for k in want}
-        self._check(self.lib.xb_crf_scans(self.h, scores.ctypes.data, T, n, int(bool(has_blank)), _ptr(out.get("alpha")),
+        self._check(self.lib.xb_crf_scans(self.h, scores.ctypes.data, T, n, has_blank, _ptr(out.get("alpha")),
                                           _ptr(out.get("beta")), _ptr(out.get("logz")), _ptr(out.get("post"))))
         return out
 
@@ -316,111 +336,68 @@ class Context:
     def crf_logz_dev(self, d_scores, T, n, has_blank, d_logz):
         self._check(self.lib.xb_crf_logz_dev(self.h, _ptr(d_scores), T, n, int(bool(has_blank)), _ptr(d_logz)))
 
-    def basecall_chunks(self, signal, alphabet):
+    # ---- the Viterbi basecall at an output level (output_level): 0 xb_basecall_chunks, 1 _q, 2 _ub ----------
+    def basecall_chunks(self, signal, alphabet, qscale=1.0, qoffset=0.0, level=0):
+        """signal (n, chunk_len) -> (seq (n, T) int8 left-packed ASCII, lens (n,)), at level 1 also (qstring, moves) and at level
+        2 also probs, as decode_q / decode_ub return them."""
         signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1, self.chunk_len)
         n = signal.shape[0]
-        seq = np.empty((n, self.T), dtype=np.int8)
-        lens = np.empty((n,), dtype=np.int32)
-        self._check(self.lib.xb_basecall_chunks(self.h, signal.ctypes.data, n, "".join(alphabet).encode(),
-                                                seq.ctypes.data, lens.ctypes.data))
-        return seq, lens
+        out = self._outputs(level, n, self.T)
+        fn = (self.lib.xb_basecall_chunks, self.lib.xb_basecall_chunks_q, self.lib.xb_basecall_chunks_ub)[level]
+        self._check(fn(self.h, signal.ctypes.data, n, "".join(alphabet).encode(), *_calib(level, qscale, qoffset),
+                       *_lens_last(out)))
+        return out
 
-    # ---- Viterbi decode with qualities and moves (xb_decode_q: an extension, parity unpinned) ----------
+    # ---- Viterbi decode with qualities and moves (xb_decode_q), and with per-base letter probabilities (xb_decode_ub):
+    #      extensions, parity unpinned ----------
+    def _decode_level(self, level, scores, alphabet, qscale, qoffset, has_blank):
+        scores, has_blank = self._scores(scores, has_blank)
+        T, n, _ = scores.shape
+        out = self._outputs(level, n, T)
+        fn = (self.lib.xb_decode_q, self.lib.xb_decode_ub)[level - 1]
+        self._check(fn(self.h, scores.ctypes.data, T, n, has_blank, "".join(alphabet).encode(), float(qscale), float(qoffset),
+                       *_lens_last(out)))
+        return out
+
     def decode_q(self, scores, alphabet, qscale=1.0, qoffset=0.0, has_blank=None):
         """xb_decode_q: scores (T, n, C) -> (seq (n, T) int8, lens (n,), qstring (n, T) int8 left-packed beside seq,
         moves (n, T) uint8)."""
-        scores = np.ascontiguousarray(scores, dtype=np.float32)
-        T, n, Cin = scores.shape
-        if has_blank is None:
-            has_blank = Cin == self.C_blank
-        if Cin != (self.C_blank if has_blank else self.C_noblank):
-            raise ValueError("scores last dim %d does not match the model (%d with blanks, %d without)"
-                             % (Cin, self.C_blank, self.C_noblank))
-        seq, q, mv = (np.empty((n, T), dtype=np.int8), np.empty((n, T), dtype=np.int8), np.empty((n, T), dtype=np.uint8))
-        lens = np.empty((n,), dtype=np.int32)
-        self._check(self.lib.xb_decode_q(self.h, scores.ctypes.data, T, n, int(bool(has_blank)), "".join(alphabet).encode(),
-                                         float(qscale), float(qoffset), seq.ctypes.data, q.ctypes.data, mv.ctypes.data,
-                                         lens.ctypes.data))
-        return seq, lens, q, mv
+        return self._decode_level(1, scores, alphabet, qscale, qoffset, has_blank)
+
+    def decode_ub(self, scores, alphabet, qscale=1.0, qoffset=0.0, has_blank=None):
+        """xb_decode_ub: scores (T, n, C) -> (seq, lens, qstring, moves) as decode_q returns them, plus probs (n, nb, T)
+        uint8: plane b holds the probability byte of letter alphabet[1 + b] per base, left-packed beside seq."""
+        return self._decode_level(2, scores, alphabet, qscale, qoffset, has_blank)
 
     def decode_q_dev(self, d_scores, T, n, has_blank, alphabet, qscale, qoffset, d_seq, d_qstring, d_moves, d_len):
         self._check(self.lib.xb_decode_q_dev(self.h, _ptr(d_scores), int(T), int(n), int(bool(has_blank)),
                                              "".join(alphabet).encode(), float(qscale), float(qoffset), _ptr(d_seq),
                                              _ptr(d_qstring), _ptr(d_moves), _ptr(d_len)))
 
-    def basecall_chunks_q(self, signal, alphabet, qscale=1.0, qoffset=0.0):
-        """xb_basecall_chunks_q: signal (n, chunk_len) -> (seq, lens, qstring, moves) as decode_q returns them."""
-        signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1, self.chunk_len)
-        n = signal.shape[0]
-        seq, q, mv = (np.empty((n, self.T), dtype=np.int8), np.empty((n, self.T), dtype=np.int8),
-                      np.empty((n, self.T), dtype=np.uint8))
-        lens = np.empty((n,), dtype=np.int32)
-        self._check(self.lib.xb_basecall_chunks_q(self.h, signal.ctypes.data, n, "".join(alphabet).encode(), float(qscale),
-                                                  float(qoffset), seq.ctypes.data, q.ctypes.data, mv.ctypes.data,
-                                                  lens.ctypes.data))
-        return seq, lens, q, mv
-
-    def submit_chunks_q(self, slot, signal, alphabet, qscale=1.0, qoffset=0.0):
-        signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1, self.chunk_len)
-        self._check(self.lib.xb_submit_chunks_q(self.h, int(slot), signal.ctypes.data, signal.shape[0],
-                                                "".join(alphabet).encode(), float(qscale), float(qoffset)))
-        return signal.shape[0]
-
-    def collect_chunks_q(self, slot, n):
-        seq, q, mv = (np.empty((n, self.T), dtype=np.int8), np.empty((n, self.T), dtype=np.int8),
-                      np.empty((n, self.T), dtype=np.uint8))
-        lens = np.empty((n,), dtype=np.int32)
-        self._check(self.lib.xb_collect_chunks_q(self.h, int(slot), seq.ctypes.data, lens.ctypes.data, q.ctypes.data,
-                                                 mv.ctypes.data))
-        return seq, lens, q, mv
-
-    # ---- ... and with per-base letter probabilities (xb_decode_ub: an extension, parity unpinned) ----------
-    def _ub_out(self, n, T):
-        return (np.empty((n, T), dtype=np.int8), np.empty((n,), dtype=np.int32), np.empty((n, T), dtype=np.int8),
-                np.empty((n, T), dtype=np.uint8), np.empty((n, self.n_base, T), dtype=np.uint8))
-
-    def decode_ub(self, scores, alphabet, qscale=1.0, qoffset=0.0, has_blank=None):
-        """xb_decode_ub: scores (T, n, C) -> (seq, lens, qstring, moves) as decode_q returns them, plus probs (n, nb, T)
-        uint8: plane b holds the probability byte of letter alphabet[1 + b] per base, left-packed beside seq."""
-        scores = np.ascontiguousarray(scores, dtype=np.float32)
-        T, n, Cin = scores.shape
-        if has_blank is None:
-            has_blank = Cin == self.C_blank
-        if Cin != (self.C_blank if has_blank else self.C_noblank):
-            raise ValueError("scores last dim %d does not match the model (%d with blanks, %d without)"
-                             % (Cin, self.C_blank, self.C_noblank))
-        seq, lens, q, mv, pr = self._ub_out(n, T)
-        self._check(self.lib.xb_decode_ub(self.h, scores.ctypes.data, T, n, int(bool(has_blank)), "".join(alphabet).encode(),
-                                          float(qscale), float(qoffset), seq.ctypes.data, q.ctypes.data, mv.ctypes.data,
-                                          pr.ctypes.data, lens.ctypes.data))
-        return seq, lens, q, mv, pr
-
     def decode_ub_dev(self, d_scores, T, n, has_blank, alphabet, qscale, qoffset, d_seq, d_qstring, d_moves, d_probs, d_len):
         self._check(self.lib.xb_decode_ub_dev(self.h, _ptr(d_scores), int(T), int(n), int(bool(has_blank)),
                                               "".join(alphabet).encode(), float(qscale), float(qoffset), _ptr(d_seq),
                                               _ptr(d_qstring), _ptr(d_moves), _ptr(d_probs), _ptr(d_len)))
 
+    def basecall_chunks_q(self, signal, alphabet, qscale=1.0, qoffset=0.0):
+        """xb_basecall_chunks_q: signal (n, chunk_len) -> (seq, lens, qstring, moves) as decode_q returns them."""
+        return self.basecall_chunks(signal, alphabet, qscale, qoffset, level=1)
+
     def basecall_chunks_ub(self, signal, alphabet, qscale=1.0, qoffset=0.0):
         """xb_basecall_chunks_ub: signal (n, chunk_len) -> (seq, lens, qstring, moves, probs) as decode_ub returns them."""
-        signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1, self.chunk_len)
-        n = signal.shape[0]
-        seq, lens, q, mv, pr = self._ub_out(n, self.T)
-        self._check(self.lib.xb_basecall_chunks_ub(self.h, signal.ctypes.data, n, "".join(alphabet).encode(), float(qscale),
-                                                   float(qoffset), seq.ctypes.data, q.ctypes.data, mv.ctypes.data,
-                                                   pr.ctypes.data, lens.ctypes.data))
-        return seq, lens, q, mv, pr
+        return self.basecall_chunks(signal, alphabet, qscale, qoffset, level=2)
+
+    def submit_chunks_q(self, slot, signal, alphabet, qscale=1.0, qoffset=0.0):
+        return self.submit_chunks(slot, signal, alphabet, qscale, qoffset, level=1)
+
+    def collect_chunks_q(self, slot, n):
+        return self.collect_chunks(slot, n, level=1)
 
     def submit_chunks_ub(self, slot, signal, alphabet, qscale=1.0, qoffset=0.0):
-        signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1, self.chunk_len)
-        self._check(self.lib.xb_submit_chunks_ub(self.h, int(slot), signal.ctypes.data, signal.shape[0],
-                                                 "".join(alphabet).encode(), float(qscale), float(qoffset)))
-        return signal.shape[0]
+        return self.submit_chunks(slot, signal, alphabet, qscale, qoffset, level=2)
 
     def collect_chunks_ub(self, slot, n):
-        seq, lens, q, mv, pr = self._ub_out(n, self.T)
-        self._check(self.lib.xb_collect_chunks_ub(self.h, int(slot), seq.ctypes.data, lens.ctypes.data, q.ctypes.data,
-                                                  mv.ctypes.data, pr.ctypes.data))
-        return seq, lens, q, mv, pr
+        return self.collect_chunks(slot, n, level=2)
 
     # ---- beam search with qualities and moves (koi.decode.beam_search at crf/basecall.py:43-46) ----------
     def _beam_out(self, n, T):
@@ -457,17 +434,20 @@ class Context:
                                                 float(offset), _ptr(d_sequence), _ptr(d_qstring), _ptr(d_moves), _ptr(d_score)))
 
     # ---- host pipeline: two batches in flight (xb_submit_chunks / xb_collect_chunks) ----------
-    def submit_chunks(self, slot, signal, alphabet):
+    def submit_chunks(self, slot, signal, alphabet, qscale=1.0, qoffset=0.0, level=0):
+        """Enqueue the basecall of signal at an output level in pipeline slot `slot` (xb_submit_chunks[_q|_ub]); returns n."""
         signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1, self.chunk_len)
-        self._check(self.lib.xb_submit_chunks(self.h, int(slot), signal.ctypes.data, signal.shape[0],
-                                              "".join(alphabet).encode()))
+        fn = (self.lib.xb_submit_chunks, self.lib.xb_submit_chunks_q, self.lib.xb_submit_chunks_ub)[level]
+        self._check(fn(self.h, int(slot), signal.ctypes.data, signal.shape[0], "".join(alphabet).encode(),
+                       *_calib(level, qscale, qoffset)))
         return signal.shape[0]
 
-    def collect_chunks(self, slot, n):
-        seq = np.empty((n, self.T), dtype=np.int8)
-        lens = np.empty((n,), dtype=np.int32)
-        self._check(self.lib.xb_collect_chunks(self.h, int(slot), seq.ctypes.data, lens.ctypes.data))
-        return seq, lens
+    def collect_chunks(self, slot, n, level=0):
+        """The outputs of a level (basecall_chunks' tuple) of slot's submission, made at that level or above."""
+        out = self._outputs(level, n, self.T)
+        fn = (self.lib.xb_collect_chunks, self.lib.xb_collect_chunks_q, self.lib.xb_collect_chunks_ub)[level]
+        self._check(fn(self.h, int(slot), *[_ptr(a) for a in out]))
+        return out
 
     # ---- device-pointer operators (pointers are ints, e.g. torch data_ptr()) -----------------
     def encode_dev(self, d_signal, n, expand_blanks, d_scores):

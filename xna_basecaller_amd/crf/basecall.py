@@ -9,6 +9,7 @@ from threading import Thread
 
 import numpy as np
 
+from .._lib import output_level
 from ..util import chunk, stitch, batchify, unbatchify, mean_qscore_from_qstring
 
 
@@ -65,17 +66,9 @@ def compute_scores(model, batch, beam_width=32, beam_cut=100.0, scale=1.0, offse
     probability byte of every letter alphabet[1 + b], left-packed beside the bases (xb_basecall_chunks_ub; xb_decode_ub with
     reverse); the qualities and moves are the device's with qscores, else the placeholders.
     """
-    if ub_probs:
-        if not model.encoder[-1].expand_blanks:
-            raise ValueError("letter probabilities come from the Viterbi decode; this model takes the beam search")
-        if reverse:
-            scores = model.seqdist.reverse_complement(model(batch))
-            ctx = model.context(np.asarray(batch).shape[-1], scores.shape[1])
-            sequence, _, qstring, moves, probs = ctx.decode_ub(scores, model.alphabet, *model.qscore_params())
-        else:
-            sequence, _, qstring, moves, probs = model.basecall_chunks(batch, ub_probs=True)
-        return _ub_dict(sequence, qstring, moves, probs, qscores)
     if not model.encoder[-1].expand_blanks:
+        if ub_probs:
+            raise ValueError("letter probabilities come from the Viterbi decode; this model takes the beam search")
         own = model.encoder[-1].blank_score
         if own is None or float(own) != float(blank_score):
             raise ValueError("beam search uses the model's fixed blank score (%r); blank_score=%r was asked for"
@@ -86,38 +79,32 @@ def compute_scores(model, batch, beam_width=32, beam_cut=100.0, scale=1.0, offse
         else:
             res = model.basecall_chunks_beam(batch, beam_width, beam_cut, scale, offset)
         return {"qstring": res["qstring"], "sequence": res["sequence"], "moves": res["moves"].astype(bool)}
-    if qscores:
-        if reverse:
-            scores = model.seqdist.reverse_complement(model(batch))
-            ctx = model.context(np.asarray(batch).shape[-1], scores.shape[1])
-            sequence, _, qstring, moves = ctx.decode_q(scores, model.alphabet, *model.qscore_params())
-        else:
-            sequence, _, qstring, moves = model.basecall_chunks(batch, qscores=True)
-        return {"qstring": qstring, "sequence": sequence, "moves": moves.astype(bool)}
+    level = output_level(qscores, ub_probs)
     if reverse:
         scores = model.seqdist.reverse_complement(model(batch))
         ctx = model.context(np.asarray(batch).shape[-1], scores.shape[1])
-        sequence, _ = ctx.decode(scores, model.alphabet)
+        rows = getattr(ctx, _DECODE[level])(scores, model.alphabet, *(model.qscore_params() if level else ()))
     else:
-        sequence, _ = model.basecall_chunks(batch)
-    return _scores_dict(sequence)
+        rows = model.basecall_chunks(batch, **_LEVEL_FLAGS[level])
+    return _result_dict(rows, qscores)
 
 
-def _scores_dict(sequence):
-    """The reference's result layout around the left-packed ASCII rows: dummy quality 'O', no moves."""
-    qstring = np.where(sequence != 0, np.int8(ord("O")), np.int8(0)).astype(np.int8)
-    return {
-        "qstring": qstring,
-        "sequence": sequence,
-        "moves": np.zeros(sequence.shape, dtype=bool),
-    }
+_DECODE = ("decode", "decode_q", "decode_ub")                         # the Context decode of each output level
+_LEVEL_FLAGS = ({}, {"qscores": True}, {"ub_probs": True})            # ... and the Model keywords that ask for it
 
 
-def _ub_dict(sequence, qstring, moves, probs, qscores):
-    """compute_scores' dict of a letter-probability decode: the device qualities and moves with qscores, else the
-    placeholders of _scores_dict (the bytes of a run without qualities)."""
-    out = {"qstring": qstring, "sequence": sequence, "moves": moves.astype(bool)} if qscores else _scores_dict(sequence)
-    out["probs"] = probs
+def _result_dict(rows, qscores):
+    """compute_scores' dict of a decode's rows (seq, lens[, qstring, moves[, probs]]): the device qualities and moves with
+    qscores, else the reference's layout around the left-packed ASCII rows -- dummy quality 'O', no moves (the bytes of a run
+    without qualities, with letter probabilities too) -- and the letter-probability planes where the rows carry them."""
+    sequence = rows[0]
+    if qscores:
+        out = {"qstring": rows[2], "sequence": sequence, "moves": rows[3].astype(bool)}
+    else:
+        out = {"qstring": np.where(sequence != 0, np.int8(ord("O")), np.int8(0)).astype(np.int8), "sequence": sequence,
+               "moves": np.zeros(sequence.shape, dtype=bool)}
+    if len(rows) > 4:
+        out["probs"] = rows[4]
     return out
 
 
@@ -133,25 +120,19 @@ def compute_sequences_pipelined(model, batches, reverse=False, qscores=False, ub
     With qscores every item is instead compute_scores' dict with the device qualities and moves (Viterbi branch), with
     ub_probs compute_scores' dict with the letter-probability planes.
     """
-    as_dict = qscores or ub_probs
+    level = output_level(qscores, ub_probs)
     if reverse or not model.encoder[-1].expand_blanks:
         for key, batch in batches:                       # decode of host-side reverse-complemented scores: synchronous
             res = compute_scores(model, batch, reverse=reverse, qscores=qscores, ub_probs=ub_probs)
-            yield key, res if as_dict else res["sequence"]
+            yield key, res if level else res["sequence"]
         return
 
     def submit(slot, batch):
-        if ub_probs:
-            return model.submit_chunks(slot, batch, ub_probs=True)
-        return model.submit_chunks(slot, batch, qscores=True) if qscores else model.submit_chunks(slot, batch)
+        return model.submit_chunks(slot, batch, **_LEVEL_FLAGS[level])
 
     def collect(handle):
-        out = model.collect_chunks(handle)
-        if ub_probs:
-            return _ub_dict(out[0], out[2], out[3], out[4], qscores)
-        if qscores:
-            return {"qstring": out[2], "sequence": out[0], "moves": out[3].astype(bool)}
-        return out[0]
+        rows = model.collect_chunks(handle)
+        return _result_dict(rows, qscores) if level else rows[0]
 
     pending, slot, depth = deque(), 0, 2
     for key, batch in batches:
@@ -179,7 +160,7 @@ def compute_scores_pipelined(model, batches, reverse=False, qscores=False, ub_pr
             yield key, compute_scores(model, batch, reverse=reverse, ub_probs=ub_probs)
         return
     for key, res in compute_sequences_pipelined(model, batches, reverse=reverse, qscores=qscores, ub_probs=ub_probs):
-        yield key, res if (qscores or ub_probs) else _scores_dict(res)
+        yield key, res if (qscores or ub_probs) else _result_dict((res,), False)
 
 
 def to_str(x, encoding="ascii"):

@@ -407,28 +407,23 @@ class Model(torch.nn.Module):
         included) also probs (N,nb,T) uint8, the letter-probability planes left-packed beside seq (xb_basecall_chunks_ub)."""
         sig = self._as_signal(batch)
         ctx = self.context(sig.shape[1], sig.shape[0])
-        if ub_probs:
-            return ctx.basecall_chunks_ub(sig, self.alphabet, *self.qscore_params())
-        if qscores:
-            return ctx.basecall_chunks_q(sig, self.alphabet, *self.qscore_params())
-        return ctx.basecall_chunks(sig, self.alphabet)
+        return ctx.basecall_chunks(sig, self.alphabet, *self.qscore_params(), level=_lib.output_level(qscores, ub_probs))
 
-    def decode_q(self, scores):
-        """(T,N,C) host scores -> (seq, lens, qstring, moves) of the Viterbi decode with qualities (xb_decode_q)."""
+    def _decode_rows(self, scores, op):
         if hasattr(scores, "detach"):
             scores = scores.detach().to(torch.float32).cpu().numpy()
         scores = np.ascontiguousarray(scores, dtype=np.float32)
         T, N, _ = scores.shape
-        return self.context(T * self.stride, N).decode_q(scores, self.alphabet, *self.qscore_params())
+        return getattr(self.context(T * self.stride, N), op)(scores, self.alphabet, *self.qscore_params())
+
+    def decode_q(self, scores):
+        """(T,N,C) host scores -> (seq, lens, qstring, moves) of the Viterbi decode with qualities (xb_decode_q)."""
+        return self._decode_rows(scores, "decode_q")
 
     def decode_ub(self, scores):
         """(T,N,C) host scores -> (seq, lens, qstring, moves, probs) of the Viterbi decode with qualities and letter
         probabilities (xb_decode_ub)."""
-        if hasattr(scores, "detach"):
-            scores = scores.detach().to(torch.float32).cpu().numpy()
-        scores = np.ascontiguousarray(scores, dtype=np.float32)
-        T, N, _ = scores.shape
-        return self.context(T * self.stride, N).decode_ub(scores, self.alphabet, *self.qscore_params())
+        return self._decode_rows(scores, "decode_ub")
 
     def basecall_chunks_beam(self, batch, beam_width=32, beam_cut=100.0, scale=1.0, offset=0.0):
         """Fused encode + beam search of a (N,1,L) batch -> {'sequence', 'qstring' (N,T) int8, 'moves' (N,T) uint8, 'score'}:
@@ -447,17 +442,13 @@ class Model(torch.nn.Module):
 
     def submit_chunks(self, slot, batch, qscores=False, ub_probs=False):
         """Enqueue the fused encode + decode of a (N,1,L) batch in pipeline slot 0 .. 3 without waiting; returns a handle
-        for collect_chunks.  The caller keeps at most one handle per slot in flight.  qscores: the decode with qualities
-        (xb_submit_chunks_q); collect_chunks then returns (seq, lens, qstring, moves).  ub_probs: with qualities and letter
-        probabilities (xb_submit_chunks_ub); collect_chunks then returns (seq, lens, qstring, moves, probs)."""
+        for collect_chunks, which returns what basecall_chunks returns for the same flags (xb_submit_chunks[_q|_ub]).  The
+        caller keeps at most one handle per slot in flight."""
         sig = self._as_signal(batch)
         ctx = self.context(sig.shape[1], sig.shape[0])
         self.chunks_submitted = getattr(self, "chunks_submitted", 0) + sig.shape[0]
-        if ub_probs:
-            return ctx, slot, ctx.submit_chunks_ub(slot, sig, self.alphabet, *self.qscore_params()), "ub"
-        if qscores:
-            return ctx, slot, ctx.submit_chunks_q(slot, sig, self.alphabet, *self.qscore_params()), True
-        return ctx, slot, ctx.submit_chunks(slot, sig, self.alphabet)
+        level = _lib.output_level(qscores, ub_probs)
+        return ctx, slot, ctx.submit_chunks(slot, sig, self.alphabet, *self.qscore_params(), level=level), level
 
     def pipeline_depth(self, chunk_len, n):
         """Batches the host pipeline keeps in flight on the context for (chunk_len, n): 4 when the context co-schedules two
@@ -476,9 +467,5 @@ class Model(torch.nn.Module):
 
     @staticmethod
     def collect_chunks(handle):
-        ctx, slot, n = handle[:3]
-        if len(handle) > 3 and handle[3] == "ub":       # submitted with letter probabilities
-            return ctx.collect_chunks_ub(slot, n)
-        if len(handle) > 3:                     # submitted with qualities
-            return ctx.collect_chunks_q(slot, n)
-        return ctx.collect_chunks(slot, n)
+        ctx, slot, n, level = handle
+        return ctx.collect_chunks(slot, n, level=level)

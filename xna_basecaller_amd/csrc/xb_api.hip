@@ -31,6 +31,30 @@ struct StageEvent {
     hipEvent_t a, b;
 };
 
+// What a Viterbi decode writes beside the bases (seq, len), by output level: 0 nothing, 1 qualities and moves (the kernel's
+// quality variant), 2 those and the letter probabilities (its UB variant).  Device pointers, except in the bodies of the
+// host-pointer entry points.
+struct DecodeOut {
+    int level = 0;
+    float qscale = 1.0f, qoffset = 0.0f;
+    int8_t *qstr = nullptr;      // (n, T), level >= 1
+    uint8_t *moves = nullptr;    // (n, T) or nullptr, level >= 1
+    uint8_t *probs = nullptr;    // (n, nb, T), level 2
+};
+
+// A decode's outputs as byte planes: seq (T bytes per chunk), len (4), qstring (T), moves (T), probs (nb T).  A level writes
+// the first plane_count(level); len and moves may be null.
+constexpr int PLANES = 5;
+struct Planes {
+    void *p[PLANES];
+};
+
+Planes planes(void *seq, void *len, const DecodeOut &o) { return {{seq, len, o.qstr, o.moves, o.probs}}; }
+int plane_count(int level) { return level == 0 ? 2 : (level == 1 ? 4 : 5); }
+size_t plane_bytes(int T, int nb, int i) { return i == 1 ? sizeof(int32_t) : (i == 4 ? (size_t)nb * T : (size_t)T); }
+// seq, and by level qstring and probs: the planes an entry point requires (xb_decode alone may leave seq out)
+bool has_required(const Planes &o, int level) { return o.p[0] && (level < 1 || o.p[2]) && (level < 2 || o.p[4]); }
+
 }  // namespace
 
 struct xb_ctx {
@@ -47,19 +71,14 @@ struct xb_ctx {
     // host pipeline (xb_submit_chunks / xb_collect_chunks): two slots of pinned staging + device buffers
     struct Slot {
         float *h_signal = nullptr, *d_signal = nullptr;
-        int8_t *h_seq = nullptr, *d_seq = nullptr;
-        int32_t *h_len = nullptr, *d_len = nullptr;
+        // pinned + device outputs of max_batch chunks, plane by plane: those of an output level are allocated by the slot's
+        // first submission at that level
+        Planes h{}, d{};
         unsigned *h_err = nullptr;             // snapshot of the device error word taken on the result stream behind this batch
         hipEvent_t h2d = nullptr, done = nullptr;
         int n = 0;
         bool busy = false;
-        // qualities and moves (xb_submit_chunks_q): pinned + device staging, allocated by the slot's first _q submission
-        int8_t *h_q = nullptr, *d_q = nullptr;
-        uint8_t *h_mv = nullptr, *d_mv = nullptr;
-        bool qs = false;                       // the batch in flight was submitted with qualities
-        // letter probabilities (xb_submit_chunks_ub): pinned + device staging (max_batch, nb, T), allocated by the first _ub submission
-        uint8_t *h_p = nullptr, *d_p = nullptr;
-        bool ub = false;                       // the batch in flight was submitted with letter probabilities
+        int level = 0;                         // output level of the batch in flight
     } slots[XB_PIPELINE_SLOTS];
     bool pipeline_failed = false;          // a collected batch reported a lost rendezvous: every batch in flight fails with it
     hipStream_t stream_copy = nullptr;     // H2D of the next batch beside the compute of the current one
@@ -117,14 +136,13 @@ struct xb_ctx {
     uint8_t *beam_moves = nullptr;
     int8_t *labels = nullptr, *seq = nullptr;
     int32_t *seq_len = nullptr;
-    // Viterbi qualities (xb_decode_q, lazily allocated): device staging of the host-pointer calls (max_batch, T) and the
-    // results of a co-scheduled pair of _q calls before they are split (2 max_batch, T)
+    // the planes of output levels 1 (qstring, moves) and 2 (probs), lazily allocated by ensure_staging: the device staging
+    // of the host-pointer calls (max_batch chunks) and the results of a co-scheduled pair before they are split
+    // (2 max_batch); level 2 also the per-step letter mass workspace (cap, T, nb) fp32
     int8_t *q_seq = nullptr, *q_fseq = nullptr;
     uint8_t *q_moves = nullptr, *q_fmoves = nullptr;
-    // letter probabilities (xb_decode_ub, lazily allocated): the per-step letter mass workspace (cap, T, nb) fp32, the device
-    // staging of the host-pointer calls (max_batch, nb, T) and the planes of a co-scheduled pair before they are split
-    float *u_buf = nullptr;
     uint8_t *u_probs = nullptr, *u_fprobs = nullptr;
+    float *u_buf = nullptr;
     unsigned *sync = nullptr;    // [64 groups * 32] counters + error word at the end
     unsigned *error = nullptr;
     int lstm_mode = 0;
@@ -164,12 +182,7 @@ struct xb_ctx {
         int slot = -1;                          // host pipeline slot whose D2H copies and done event follow the launch
         void (*after)(void *) = nullptr;        // xb_comm: the gather of this call's results, enqueued right behind it
         void *after_arg = nullptr;
-        int qs = 0;                             // 1: the decode's quality variant (xb_basecall_chunks_q / xb_submit_chunks_q)
-        float qscale = 1.0f, qoffset = 0.0f;
-        int8_t *qstr = nullptr;                 // (n, T) device, required with qs
-        uint8_t *moves = nullptr;               // (n, T) device or nullptr
-        int ub = 0;                             // 1 (with qs): the letter-probability variant (xb_basecall_chunks_ub / xb_submit_chunks_ub)
-        uint8_t *probs = nullptr;               // (n, nb, T) device, required with ub
+        DecodeOut out;                          // output level (xb_basecall_chunks_q / _ub, xb_submit_chunks_q / _ub) and its planes
     };
     int fuse_ok = 1;                            // pairing is possible in this context (schedule, batch size, XB_FUSE)
     int fuse = 0;                               // ... and the caller asked for it (xb_reserve_pairing)
@@ -756,17 +769,10 @@ struct ScanOut {
     float *alpha = nullptr, *beta = nullptr, *logz = nullptr, *post = nullptr;   // device; post has row stride ldq
 };
 
-// qualities and moves of the Viterbi decode (xb_decode_q): the kernel's quality variant, beta rows into the beta stash
-struct QualOut {
-    int8_t *qstr = nullptr;      // (n, T) device
-    uint8_t *moves = nullptr;    // (n, T) device or nullptr
-    float qscale = 1.0f, qoffset = 0.0f;
-    uint8_t *probs = nullptr;    // (n, nb, T) device or nullptr: the letter-probability variant (xb_decode_ub)
-};
-
+// out: the outputs of level 1 and 2 (the quality variant writes its beta rows into the beta stash); null for level 0
 int run_decode(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, int ld, const char *alphabet,
                int8_t *d_labels, int8_t *d_seq, int32_t *d_len, hipStream_t st = nullptr, const ScanOut *scan = nullptr,
-               const QualOut *qual = nullptr)
+               const DecodeOut *out = nullptr)
 {
     if (!st) st = ctx->stream;
     const xb_config &c = ctx->cfg;
@@ -785,13 +791,13 @@ int run_decode(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, 
         p.stop_after = (scan->beta || scan->post) ? 2 : 1;
     }
     p.labels = d_labels; p.seq = d_seq; p.seq_len = d_len;
-    if (qual) {
-        if (!qual->qstr || !d_seq) return fail(ctx, XB_ERR_INVALID, "qualities need the seq and qstring outputs");
-        p.qstr = qual->qstr; p.moves = qual->moves; p.qscale = qual->qscale; p.qoffset = qual->qoffset;
+    if (out && out->level >= 1) {
+        if (!out->qstr || !d_seq) return fail(ctx, XB_ERR_INVALID, "qualities need the seq and qstring outputs");
+        p.qstr = out->qstr; p.moves = out->moves; p.qscale = out->qscale; p.qoffset = out->qoffset;
         p.beta_out = ctx->beta;
-        if (qual->probs) {
+        if (out->level == 2) {
             if (!ctx->u_buf) return fail(ctx, XB_ERR_INVALID, "letter probabilities need their workspace");
-            p.probs = qual->probs; p.ubuf = ctx->u_buf;
+            p.probs = out->probs; p.ubuf = ctx->u_buf;
         }
     }
     memset(p.alphabet, 0, sizeof p.alphabet);
@@ -824,28 +830,56 @@ int join_async_decode(xb_ctx *ctx)
     return XB_OK;
 }
 
-// device staging of the quality calls (once per context)
-int ensure_q_staging(xb_ctx *ctx)
+template <typename Tp>
+int dev_alloc_once(xb_ctx *ctx, Tp **out, size_t count) { return *out ? XB_OK : dev_alloc(ctx, out, count); }
+
+// device staging and workspace of an output level (once per context; level 2 includes level 1's).  The pair planes exist
+// only where calls can pair (enqueue_call pairs none of a level while they are missing).
+int ensure_staging(xb_ctx *ctx, int level)
 {
-    const size_t N = (size_t)ctx->cfg.max_batch, T = (size_t)ctx->T;
-    int rc = ctx->q_seq ? XB_OK : dev_alloc(ctx, &ctx->q_seq, N * T);
-    if (!rc && !ctx->q_moves) rc = dev_alloc(ctx, &ctx->q_moves, N * T);
-    if (ctx->fuse_ok) {      // a pair of _q calls (enqueue_call pairs none while these are missing)
-        if (!rc && !ctx->q_fseq) rc = dev_alloc(ctx, &ctx->q_fseq, 2 * N * T);
-        if (!rc && !ctx->q_fmoves) rc = dev_alloc(ctx, &ctx->q_fmoves, 2 * N * T);
+    const size_t NT = (size_t)ctx->cfg.max_batch * ctx->T, NPT = NT * ctx->cfg.n_base;
+    const bool pairs = ctx->fuse_ok != 0;
+    int rc = XB_OK;
+    if (level >= 1) {
+        rc = rc ? rc : dev_alloc_once(ctx, &ctx->q_seq, NT);
+        rc = rc ? rc : dev_alloc_once(ctx, &ctx->q_moves, NT);
+        if (pairs) rc = rc ? rc : dev_alloc_once(ctx, &ctx->q_fseq, 2 * NT);
+        if (pairs) rc = rc ? rc : dev_alloc_once(ctx, &ctx->q_fmoves, 2 * NT);
+    }
+    if (level == 2) {
+        rc = rc ? rc : dev_alloc_once(ctx, &ctx->u_buf, (pairs ? 2 : 1) * NPT);
+        rc = rc ? rc : dev_alloc_once(ctx, &ctx->u_probs, NPT);
+        if (pairs) rc = rc ? rc : dev_alloc_once(ctx, &ctx->u_fprobs, 2 * NPT);
     }
     return rc;
 }
 
-// device workspace and staging of the letter-probability calls (once per context; the quality staging too)
-int ensure_ub_staging(xb_ctx *ctx)
+// the device staging of a host-pointer call with outputs o: the same level and calibration, moves only where o has them
+DecodeOut staging_of(const xb_ctx *ctx, const DecodeOut &o)
 {
-    const size_t N = (size_t)ctx->cfg.max_batch, T = (size_t)ctx->T, nb = (size_t)ctx->cfg.n_base;
-    int rc = ensure_q_staging(ctx);
-    if (!rc && !ctx->u_buf) rc = dev_alloc(ctx, &ctx->u_buf, (ctx->fuse_ok ? 2 : 1) * N * T * nb);
-    if (!rc && !ctx->u_probs) rc = dev_alloc(ctx, &ctx->u_probs, N * nb * T);
-    if (ctx->fuse_ok && !rc && !ctx->u_fprobs) rc = dev_alloc(ctx, &ctx->u_fprobs, 2 * N * nb * T);
-    return rc;
+    DecodeOut d = o;
+    d.qstr = ctx->q_seq; d.moves = o.moves ? ctx->q_moves : nullptr; d.probs = ctx->u_probs;
+    return d;
+}
+
+// chunks [c0, c0 + n) of the planes of a level from src to chunks [0, n) of dst (rows of T steps); planes null on either
+// side are skipped
+int copy_planes(xb_ctx *ctx, int level, const Planes &dst, const Planes &src, int c0, int n, int T, hipMemcpyKind kind,
+                hipStream_t st)
+{
+    for (int i = 0; i < plane_count(level); ++i) {
+        const size_t b = plane_bytes(T, ctx->cfg.n_base, i);
+        if (dst.p[i] && src.p[i])
+            XB_HIP(ctx, hipMemcpyAsync(dst.p[i], static_cast<const char *>(src.p[i]) + (size_t)c0 * b, (size_t)n * b, kind, st));
+    }
+    return XB_OK;
+}
+
+int check_alphabet(xb_ctx *ctx, const char *alphabet)
+{
+    if ((int)strlen(alphabet) < ctx->cfg.n_base + 1 || strlen(alphabet) >= sizeof(xb_ctx::Call{}.alphabet))
+        return fail(ctx, XB_ERR_INVALID, "alphabet needs %d symbols", ctx->cfg.n_base + 1);
+    return XB_OK;
 }
 
 int sync_all(xb_ctx *ctx)
@@ -1020,12 +1054,8 @@ XB_API void xb_ctx_destroy(xb_ctx *ctx)
     for (auto &e : ctx->dec_done) if (e) (void)hipEventDestroy(e);
     for (auto &sl : ctx->slots) {
         if (sl.h_signal) (void)hipHostFree(sl.h_signal);
-        if (sl.h_seq) (void)hipHostFree(sl.h_seq);
-        if (sl.h_len) (void)hipHostFree(sl.h_len);
         if (sl.h_err) (void)hipHostFree(sl.h_err);
-        if (sl.h_q) (void)hipHostFree(sl.h_q);
-        if (sl.h_mv) (void)hipHostFree(sl.h_mv);
-        if (sl.h_p) (void)hipHostFree(sl.h_p);
+        for (void *h : sl.h.p) if (h) (void)hipHostFree(h);
         if (sl.h2d) (void)hipEventDestroy(sl.h2d);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
@@ -1225,118 +1255,86 @@ XB_API int xb_encode(xb_ctx *ctx, const float *signal, int n, int expand_blanks,
     return xb_synchronize(ctx);
 }
 
-XB_API int xb_decode_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const char *alphabet,
-                         int8_t *d_labels, int8_t *d_seq, int32_t *d_seq_len)
+// the device-pointer decodes: labels (level 0 only), the bases and the outputs of o's level, on the main stream
+static int decode_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const char *alphabet, int8_t *d_labels,
+                      int8_t *d_seq, int32_t *d_seq_len, const DecodeOut &o)
 {
     if (!ctx) return XB_ERR_INVALID;
     if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
-    if (!d_scores) return fail(ctx, XB_ERR_INVALID, "null device pointer");
+    if (o.level == 0 && !d_scores) return fail(ctx, XB_ERR_INVALID, "null device pointer");
+    if (o.level >= 1 && (!d_scores || !has_required(planes(d_seq, d_seq_len, o), o.level) || !alphabet))
+        return fail(ctx, XB_ERR_INVALID, "null argument");
     XB_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = join_async_decode(ctx)) return rc;
+    if (o.level == 2)                                 // the letter mass workspace
+        if (int rc = ensure_staging(ctx, 2)) return rc;
     ctx->result_stream = ctx->stream;
     const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
-    return run_decode(ctx, d_scores, T, n, has_blank ? 1 : 0, ld, alphabet, d_labels, d_seq, d_seq_len);
+    return run_decode(ctx, d_scores, T, n, has_blank ? 1 : 0, ld, alphabet, d_labels, d_seq, d_seq_len, nullptr, nullptr, &o);
+}
+
+// the host-pointer decodes: through the context's staging; labels and a null seq at level 0 only
+static int decode_host(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, const char *alphabet, int8_t *labels,
+                       int8_t *seq, int32_t *seq_len, const DecodeOut &o)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
+    const Planes dst = planes(seq, seq_len, o);
+    if (o.level == 0 && !scores) return fail(ctx, XB_ERR_INVALID, "null host pointer");
+    if (o.level >= 1 && (!scores || !has_required(dst, o.level) || !alphabet)) return fail(ctx, XB_ERR_INVALID, "null argument");
+    if (T < 1 || T > ctx->T) return fail(ctx, XB_ERR_INVALID, "T=%d outside [1, %d]", T, ctx->T);
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcj = join_async_decode(ctx)) return rcj;
+    if (o.level)
+        if (int rcs = ensure_staging(ctx, o.level)) return rcs;
+    const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
+    XB_HIP(ctx, hipMemcpyAsync(ctx->scores, scores, sizeof(float) * (size_t)T * n * ld, hipMemcpyHostToDevice, ctx->stream));
+    const DecodeOut d = staging_of(ctx, o);
+    int rc = run_decode(ctx, ctx->scores, T, n, has_blank ? 1 : 0, ld, alphabet, o.level ? nullptr : ctx->labels,
+                        seq ? ctx->seq : nullptr, ctx->seq_len, nullptr, nullptr, &d);
+    if (rc) return rc;
+    if (labels) XB_HIP(ctx, hipMemcpyAsync(labels, ctx->labels, (size_t)n * T, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = copy_planes(ctx, o.level, dst, planes(ctx->seq, ctx->seq_len, d), 0, n, T, hipMemcpyDeviceToHost, ctx->stream)))
+        return rc;
+    return xb_synchronize(ctx);
+}
+
+XB_API int xb_decode_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const char *alphabet,
+                         int8_t *d_labels, int8_t *d_seq, int32_t *d_seq_len)
+{
+    return decode_dev(ctx, d_scores, T, n, has_blank, alphabet, d_labels, d_seq, d_seq_len, {});
 }
 
 XB_API int xb_decode(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, const char *alphabet,
                      int8_t *labels, int8_t *seq, int32_t *seq_len)
 {
-    if (!ctx) return XB_ERR_INVALID;
-    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
-    if (!scores) return fail(ctx, XB_ERR_INVALID, "null host pointer");
-    if (T < 1 || T > ctx->T) return fail(ctx, XB_ERR_INVALID, "T=%d outside [1, %d]", T, ctx->T);
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rcj = join_async_decode(ctx)) return rcj;
-    const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
-    XB_HIP(ctx, hipMemcpyAsync(ctx->scores, scores, sizeof(float) * (size_t)T * n * ld, hipMemcpyHostToDevice, ctx->stream));
-    int rc = run_decode(ctx, ctx->scores, T, n, has_blank ? 1 : 0, ld, alphabet, ctx->labels, seq ? ctx->seq : nullptr,
-                        ctx->seq_len);
-    if (rc) return rc;
-    if (labels) XB_HIP(ctx, hipMemcpyAsync(labels, ctx->labels, (size_t)n * T, hipMemcpyDeviceToHost, ctx->stream));
-    if (seq) XB_HIP(ctx, hipMemcpyAsync(seq, ctx->seq, (size_t)n * T, hipMemcpyDeviceToHost, ctx->stream));
-    if (seq_len) XB_HIP(ctx, hipMemcpyAsync(seq_len, ctx->seq_len, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    return xb_synchronize(ctx);
+    return decode_host(ctx, scores, T, n, has_blank, alphabet, labels, seq, seq_len, {});
 }
 
 XB_API int xb_decode_q_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const char *alphabet, float qscale,
                            float qoffset, int8_t *d_seq, int8_t *d_qstring, uint8_t *d_moves, int32_t *d_seq_len)
 {
-    if (!ctx) return XB_ERR_INVALID;
-    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
-    if (!d_scores || !d_seq || !d_qstring || !alphabet) return fail(ctx, XB_ERR_INVALID, "null argument");
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
-    ctx->result_stream = ctx->stream;
-    const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
-    QualOut q;
-    q.qstr = d_qstring; q.moves = d_moves; q.qscale = qscale; q.qoffset = qoffset;
-    return run_decode(ctx, d_scores, T, n, has_blank ? 1 : 0, ld, alphabet, nullptr, d_seq, d_seq_len, nullptr, nullptr, &q);
+    return decode_dev(ctx, d_scores, T, n, has_blank, alphabet, nullptr, d_seq, d_seq_len, {1, qscale, qoffset, d_qstring, d_moves});
 }
 
 XB_API int xb_decode_q(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, const char *alphabet, float qscale,
                        float qoffset, int8_t *seq, int8_t *qstring, uint8_t *moves, int32_t *seq_len)
 {
-    if (!ctx) return XB_ERR_INVALID;
-    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
-    if (!scores || !seq || !qstring || !alphabet) return fail(ctx, XB_ERR_INVALID, "null argument");
-    if (T < 1 || T > ctx->T) return fail(ctx, XB_ERR_INVALID, "T=%d outside [1, %d]", T, ctx->T);
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rcj = join_async_decode(ctx)) return rcj;
-    if (int rcs = ensure_q_staging(ctx)) return rcs;
-    const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
-    XB_HIP(ctx, hipMemcpyAsync(ctx->scores, scores, sizeof(float) * (size_t)T * n * ld, hipMemcpyHostToDevice, ctx->stream));
-    QualOut q;
-    q.qstr = ctx->q_seq; q.moves = moves ? ctx->q_moves : nullptr; q.qscale = qscale; q.qoffset = qoffset;
-    int rc = run_decode(ctx, ctx->scores, T, n, has_blank ? 1 : 0, ld, alphabet, nullptr, ctx->seq, ctx->seq_len, nullptr, nullptr, &q);
-    if (rc) return rc;
-    const size_t nt = (size_t)n * T;
-    XB_HIP(ctx, hipMemcpyAsync(seq, ctx->seq, nt, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(qstring, ctx->q_seq, nt, hipMemcpyDeviceToHost, ctx->stream));
-    if (moves) XB_HIP(ctx, hipMemcpyAsync(moves, ctx->q_moves, nt, hipMemcpyDeviceToHost, ctx->stream));
-    if (seq_len) XB_HIP(ctx, hipMemcpyAsync(seq_len, ctx->seq_len, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    return xb_synchronize(ctx);
+    return decode_host(ctx, scores, T, n, has_blank, alphabet, nullptr, seq, seq_len, {1, qscale, qoffset, qstring, moves});
 }
 
 XB_API int xb_decode_ub_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const char *alphabet,
                             float qscale, float qoffset, int8_t *d_seq, int8_t *d_qstring, uint8_t *d_moves, uint8_t *d_probs,
                             int32_t *d_seq_len)
 {
-    if (!ctx) return XB_ERR_INVALID;
-    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
-    if (!d_scores || !d_seq || !d_qstring || !d_probs || !alphabet) return fail(ctx, XB_ERR_INVALID, "null argument");
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
-    if (int rc = ensure_ub_staging(ctx)) return rc;
-    ctx->result_stream = ctx->stream;
-    const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
-    QualOut q;
-    q.qstr = d_qstring; q.moves = d_moves; q.qscale = qscale; q.qoffset = qoffset; q.probs = d_probs;
-    return run_decode(ctx, d_scores, T, n, has_blank ? 1 : 0, ld, alphabet, nullptr, d_seq, d_seq_len, nullptr, nullptr, &q);
+    return decode_dev(ctx, d_scores, T, n, has_blank, alphabet, nullptr, d_seq, d_seq_len,
+                      {2, qscale, qoffset, d_qstring, d_moves, d_probs});
 }
 
 XB_API int xb_decode_ub(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, const char *alphabet, float qscale,
                         float qoffset, int8_t *seq, int8_t *qstring, uint8_t *moves, uint8_t *probs, int32_t *seq_len)
 {
-    if (!ctx) return XB_ERR_INVALID;
-    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
-    if (!scores || !seq || !qstring || !probs || !alphabet) return fail(ctx, XB_ERR_INVALID, "null argument");
-    if (T < 1 || T > ctx->T) return fail(ctx, XB_ERR_INVALID, "T=%d outside [1, %d]", T, ctx->T);
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rcj = join_async_decode(ctx)) return rcj;
-    if (int rcs = ensure_ub_staging(ctx)) return rcs;
-    const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
-    XB_HIP(ctx, hipMemcpyAsync(ctx->scores, scores, sizeof(float) * (size_t)T * n * ld, hipMemcpyHostToDevice, ctx->stream));
-    QualOut q;
-    q.qstr = ctx->q_seq; q.moves = moves ? ctx->q_moves : nullptr; q.qscale = qscale; q.qoffset = qoffset; q.probs = ctx->u_probs;
-    int rc = run_decode(ctx, ctx->scores, T, n, has_blank ? 1 : 0, ld, alphabet, nullptr, ctx->seq, ctx->seq_len, nullptr, nullptr, &q);
-    if (rc) return rc;
-    const size_t nt = (size_t)n * T;
-    XB_HIP(ctx, hipMemcpyAsync(seq, ctx->seq, nt, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(qstring, ctx->q_seq, nt, hipMemcpyDeviceToHost, ctx->stream));
-    if (moves) XB_HIP(ctx, hipMemcpyAsync(moves, ctx->q_moves, nt, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(probs, ctx->u_probs, nt * ctx->cfg.n_base, hipMemcpyDeviceToHost, ctx->stream));
-    if (seq_len) XB_HIP(ctx, hipMemcpyAsync(seq_len, ctx->seq_len, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    return xb_synchronize(ctx);
+    return decode_host(ctx, scores, T, n, has_blank, alphabet, nullptr, seq, seq_len, {2, qscale, qoffset, qstring, moves, probs});
 }
 
 XB_API int xb_crf_scans_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, float *d_alpha, float *d_beta,
@@ -1643,17 +1641,10 @@ static int call_post_actions(xb_ctx *ctx, const xb_ctx::Call &c, hipStream_t rs)
 {
     if (c.slot >= 0) {
         xb_ctx::Slot &sl = ctx->slots[c.slot];
-        XB_HIP(ctx, hipMemcpyAsync(sl.h_seq, sl.d_seq, (size_t)c.n * ctx->T, hipMemcpyDeviceToHost, rs));
-        XB_HIP(ctx, hipMemcpyAsync(sl.h_len, sl.d_len, sizeof(int32_t) * (size_t)c.n, hipMemcpyDeviceToHost, rs));
+        if (int rc = copy_planes(ctx, c.out.level, sl.h, sl.d, 0, c.n, ctx->T, hipMemcpyDeviceToHost, rs)) return rc;
         // the error word as THIS batch left it (stream order: behind its recurrences and its decode), not as whatever batch
         // happens to be running when the slot is collected finds it
         XB_HIP(ctx, hipMemcpyAsync(sl.h_err, ctx->error, sizeof(unsigned), hipMemcpyDeviceToHost, rs));
-        if (c.qs) {
-            XB_HIP(ctx, hipMemcpyAsync(sl.h_q, sl.d_q, (size_t)c.n * ctx->T, hipMemcpyDeviceToHost, rs));
-            XB_HIP(ctx, hipMemcpyAsync(sl.h_mv, sl.d_mv, (size_t)c.n * ctx->T, hipMemcpyDeviceToHost, rs));
-        }
-        if (c.ub)
-            XB_HIP(ctx, hipMemcpyAsync(sl.h_p, sl.d_p, (size_t)c.n * ctx->cfg.n_base * ctx->T, hipMemcpyDeviceToHost, rs));
         XB_HIP(ctx, hipEventRecord(sl.done, rs));
     }
     if (c.after) c.after(c.after_arg);
@@ -1664,26 +1655,20 @@ static int call_post_actions(xb_ctx *ctx, const xb_ctx::Call &c, hipStream_t rs)
 static int launch_calls(xb_ctx *ctx, const xb_ctx::Call &a, const xb_ctx::Call *b)
 {
     const int n = a.n + (b ? b->n : 0);
+    const float *sig2 = b ? b->signal : nullptr;
+    // a pair (enqueue_call: the same level and calibration) decodes into the pair planes, which are then split
+    const Planes fused = {{ctx->fseq, ctx->flen, ctx->q_fseq, ctx->q_fmoves, ctx->u_fprobs}};
     int8_t *d_seq = b ? ctx->fseq : a.seq;
     int32_t *d_len = b ? ctx->flen : a.len;
-    const float *sig2 = b ? b->signal : nullptr;
-    // a pair is two plain calls or two _q calls of the same qscale / qoffset (enqueue_call)
-    QualOut qo;
-    const QualOut *qual = nullptr;
-    if (a.qs) {
-        qo.qstr = b ? ctx->q_fseq : a.qstr;
-        qo.moves = b ? ctx->q_fmoves : a.moves;
-        qo.qscale = a.qscale; qo.qoffset = a.qoffset;
-        if (a.ub) qo.probs = b ? ctx->u_fprobs : a.probs;
-        qual = &qo;
-    }
+    DecodeOut out = a.out;
+    if (b) { out.qstr = ctx->q_fseq; out.moves = ctx->q_fmoves; out.probs = ctx->u_fprobs; }
     int rc;
     hipStream_t rs;
     if (!ctx->overlap || !ctx->stream3 || !ctx->scores2 || !ctx->decode_async) {
         rs = ctx->result_stream = ctx->stream;
         rc = run_encoder(ctx, a.signal, n, 0, ctx->scores, ctx->ld_nb, sig2, a.n);
         if (rc) return rc;
-        rc = run_decode(ctx, ctx->scores, ctx->T, n, 0, ctx->ld_nb, a.alphabet, nullptr, d_seq, d_len, nullptr, nullptr, qual);
+        rc = run_decode(ctx, ctx->scores, ctx->T, n, 0, ctx->ld_nb, a.alphabet, nullptr, d_seq, d_len, nullptr, nullptr, &out);
         if (rc) return rc;
     } else {
         // asynchronous decode: the encoder of this batch writes score buffer p while the decode of the previous batch may
@@ -1698,27 +1683,15 @@ static int launch_calls(xb_ctx *ctx, const xb_ctx::Call &a, const xb_ctx::Call *
         if ((rc = next_dep(ctx, &enc))) return rc;
         XB_HIP(ctx, hipEventRecord(enc, ctx->stream));
         XB_HIP(ctx, hipStreamWaitEvent(ctx->stream3, enc, 0));
-        rc = run_decode(ctx, sc, ctx->T, n, 0, ctx->ld_nb, a.alphabet, nullptr, d_seq, d_len, ctx->stream3, nullptr, qual);
+        rc = run_decode(ctx, sc, ctx->T, n, 0, ctx->ld_nb, a.alphabet, nullptr, d_seq, d_len, ctx->stream3, nullptr, &out);
         if (rc) return rc;
     }
     if (b) {        // the pair's rows back to where each caller wants them
-        const size_t T = (size_t)ctx->T;
-        XB_HIP(ctx, hipMemcpyAsync(a.seq, ctx->fseq, (size_t)a.n * T, hipMemcpyDeviceToDevice, rs));
-        XB_HIP(ctx, hipMemcpyAsync(b->seq, ctx->fseq + (size_t)a.n * T, (size_t)b->n * T, hipMemcpyDeviceToDevice, rs));
-        if (a.len) XB_HIP(ctx, hipMemcpyAsync(a.len, ctx->flen, sizeof(int32_t) * (size_t)a.n, hipMemcpyDeviceToDevice, rs));
-        if (b->len) XB_HIP(ctx, hipMemcpyAsync(b->len, ctx->flen + a.n, sizeof(int32_t) * (size_t)b->n, hipMemcpyDeviceToDevice, rs));
-        if (a.qs) {
-            XB_HIP(ctx, hipMemcpyAsync(a.qstr, ctx->q_fseq, (size_t)a.n * T, hipMemcpyDeviceToDevice, rs));
-            XB_HIP(ctx, hipMemcpyAsync(b->qstr, ctx->q_fseq + (size_t)a.n * T, (size_t)b->n * T, hipMemcpyDeviceToDevice, rs));
-            if (a.moves) XB_HIP(ctx, hipMemcpyAsync(a.moves, ctx->q_fmoves, (size_t)a.n * T, hipMemcpyDeviceToDevice, rs));
-            if (b->moves)
-                XB_HIP(ctx, hipMemcpyAsync(b->moves, ctx->q_fmoves + (size_t)a.n * T, (size_t)b->n * T, hipMemcpyDeviceToDevice, rs));
-        }
-        if (a.ub) {      // (n, nb, T) planes: a's chunks first
-            const size_t pt = (size_t)ctx->cfg.n_base * T;
-            XB_HIP(ctx, hipMemcpyAsync(a.probs, ctx->u_fprobs, (size_t)a.n * pt, hipMemcpyDeviceToDevice, rs));
-            XB_HIP(ctx, hipMemcpyAsync(b->probs, ctx->u_fprobs + (size_t)a.n * pt, (size_t)b->n * pt, hipMemcpyDeviceToDevice, rs));
-        }
+        const int level = a.out.level;
+        if ((rc = copy_planes(ctx, level, planes(a.seq, a.len, a.out), fused, 0, a.n, ctx->T, hipMemcpyDeviceToDevice, rs)))
+            return rc;
+        if ((rc = copy_planes(ctx, level, planes(b->seq, b->len, b->out), fused, a.n, b->n, ctx->T, hipMemcpyDeviceToDevice, rs)))
+            return rc;
     }
     if (rs == ctx->stream3) {
         const int pb = (int)((ctx->batch_idx - 1) & 1u);
@@ -1746,6 +1719,19 @@ int flush_held(xb_ctx *ctx)
     return rc;
 }
 
+// Two calls share one pass only where it produces exactly what each produces alone: the same alphabet and output level (and
+// at level >= 1 the same qscale / qoffset), different seq / qstring / probs buffers, at most 2 max_batch chunks, and the
+// level's pair planes in place (enqueue_call then makes room for the pair's workspaces).
+static bool can_pair(const xb_ctx *ctx, const xb_ctx::Call &h, const xb_ctx::Call &c)
+{
+    const DecodeOut &x = h.out, &y = c.out;
+    if (!ctx->fuse || h.n + c.n > 2 * ctx->cfg.max_batch || strcmp(h.alphabet, c.alphabet) != 0 || h.seq == c.seq) return false;
+    if (x.level != y.level) return false;
+    if (x.level >= 1 && (x.qscale != y.qscale || x.qoffset != y.qoffset || x.qstr == y.qstr || !ctx->q_fseq)) return false;
+    if (x.level == 2 && (x.probs == y.probs || !ctx->u_fprobs)) return false;
+    return true;
+}
+
 static int enqueue_call(xb_ctx *ctx, const xb_ctx::Call &c)
 {
     if (ctx->deferred_rc) {
@@ -1756,11 +1742,7 @@ static int enqueue_call(xb_ctx *ctx, const xb_ctx::Call &c)
     if (ctx->holding) {
         const xb_ctx::Call h = ctx->held;
         ctx->holding = false;
-        bool pair = ctx->fuse && h.n + c.n <= 2 * ctx->cfg.max_batch && strcmp(h.alphabet, c.alphabet) == 0 && h.seq != c.seq;
-        // qualities: only with a call of the same mode and the same qscale / qoffset (one decode pass serves both)
-        pair = pair && h.qs == c.qs && (!c.qs || (h.qscale == c.qscale && h.qoffset == c.qoffset && h.qstr != c.qstr && ctx->q_fseq));
-        // letter probabilities: only with another _ub call (of the same qscale / qoffset, above)
-        pair = pair && h.ub == c.ub && (!c.ub || (h.probs != c.probs && ctx->u_fprobs));
+        bool pair = can_pair(ctx, h, c);
         if (pair && h.n + c.n > ctx->cap && reserve_pairing(ctx) != XB_OK) pair = false;     // no room for both: one by one
         if (pair) {
             const int rc = launch_calls(ctx, h, &c);
@@ -1778,145 +1760,99 @@ static int enqueue_call(xb_ctx *ctx, const xb_ctx::Call &c)
     return launch_calls(ctx, c, nullptr);
 }
 
+// an asynchronous basecall of n chunks at d_signal into device outputs (seq, len, out), of pipeline slot `slot` or none
+static int basecall_async(xb_ctx *ctx, const float *d_signal, int n, const char *alphabet, int8_t *seq, int32_t *len,
+                          const DecodeOut &out, int slot = -1)
+{
+    xb_ctx::Call c;
+    c.signal = d_signal; c.n = n; c.seq = seq; c.len = len; c.slot = slot; c.out = out;
+    strcpy(c.alphabet, alphabet);
+    return enqueue_call(ctx, c);
+}
+
 XB_API int xb_basecall_chunks_dev(xb_ctx *ctx, const float *d_signal, int n, const char *alphabet, int8_t *d_seq,
                                   int32_t *d_seq_len)
 {
     int rc = check_ready(ctx, n);
     if (rc) return rc;
     if (!d_signal || !d_seq || !alphabet) return fail(ctx, XB_ERR_INVALID, "null argument");
-    if ((int)strlen(alphabet) < ctx->cfg.n_base + 1 || strlen(alphabet) >= sizeof(xb_ctx::Call{}.alphabet))
-        return fail(ctx, XB_ERR_INVALID, "alphabet needs %d symbols", ctx->cfg.n_base + 1);
+    if ((rc = check_alphabet(ctx, alphabet))) return rc;
     XB_HIP(ctx, hipSetDevice(ctx->device));
-    xb_ctx::Call c;
-    c.signal = d_signal; c.n = n; c.seq = d_seq; c.len = d_seq_len;
-    strcpy(c.alphabet, alphabet);
-    return enqueue_call(ctx, c);
+    return basecall_async(ctx, d_signal, n, alphabet, d_seq, d_seq_len, {});
+}
+
+// the blocking basecalls: through the context's staging, and back to the host
+static int basecall_host(xb_ctx *ctx, const float *signal, int n, const char *alphabet, int8_t *seq, int32_t *seq_len,
+                         const DecodeOut &o)
+{
+    int rc = check_ready(ctx, n);
+    if (rc) return rc;
+    const Planes dst = planes(seq, seq_len, o);
+    if (!signal || !has_required(dst, o.level) || !alphabet) return fail(ctx, XB_ERR_INVALID, "null argument");
+    if ((rc = check_alphabet(ctx, alphabet))) return rc;
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if (o.level && (rc = ensure_staging(ctx, o.level))) return rc;
+    XB_HIP(ctx, hipMemcpyAsync(ctx->d_signal, signal, sizeof(float) * (size_t)n * ctx->cfg.chunk_len,
+                               hipMemcpyHostToDevice, ctx->stream));
+    const DecodeOut d = staging_of(ctx, o);
+    if ((rc = basecall_async(ctx, ctx->d_signal, n, alphabet, ctx->seq, ctx->seq_len, d))) return rc;
+    if ((rc = join_async_decode(ctx))) return rc;
+    if ((rc = copy_planes(ctx, o.level, dst, planes(ctx->seq, ctx->seq_len, d), 0, n, ctx->T, hipMemcpyDeviceToHost, ctx->stream)))
+        return rc;
+    return xb_synchronize(ctx);
 }
 
 XB_API int xb_basecall_chunks(xb_ctx *ctx, const float *signal, int n, const char *alphabet, int8_t *seq,
                               int32_t *seq_len)
 {
-    int rc = check_ready(ctx, n);
-    if (rc) return rc;
-    if (!signal || !seq || !alphabet) return fail(ctx, XB_ERR_INVALID, "null argument");
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    XB_HIP(ctx, hipMemcpyAsync(ctx->d_signal, signal, sizeof(float) * (size_t)n * ctx->cfg.chunk_len,
-                               hipMemcpyHostToDevice, ctx->stream));
-    rc = xb_basecall_chunks_dev(ctx, ctx->d_signal, n, alphabet, ctx->seq, ctx->seq_len);
-    if (rc) return rc;
-    if ((rc = join_async_decode(ctx))) return rc;
-    XB_HIP(ctx, hipMemcpyAsync(seq, ctx->seq, (size_t)n * ctx->T, hipMemcpyDeviceToHost, ctx->stream));
-    if (seq_len) XB_HIP(ctx, hipMemcpyAsync(seq_len, ctx->seq_len, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    return xb_synchronize(ctx);
+    return basecall_host(ctx, signal, n, alphabet, seq, seq_len, {});
 }
 
 XB_API int xb_basecall_chunks_q(xb_ctx *ctx, const float *signal, int n, const char *alphabet, float qscale, float qoffset,
                                 int8_t *seq, int8_t *qstring, uint8_t *moves, int32_t *seq_len)
 {
-    int rc = check_ready(ctx, n);
-    if (rc) return rc;
-    if (!signal || !seq || !qstring || !alphabet) return fail(ctx, XB_ERR_INVALID, "null argument");
-    if ((int)strlen(alphabet) < ctx->cfg.n_base + 1 || strlen(alphabet) >= sizeof(xb_ctx::Call{}.alphabet))
-        return fail(ctx, XB_ERR_INVALID, "alphabet needs %d symbols", ctx->cfg.n_base + 1);
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = ensure_q_staging(ctx))) return rc;
-    XB_HIP(ctx, hipMemcpyAsync(ctx->d_signal, signal, sizeof(float) * (size_t)n * ctx->cfg.chunk_len,
-                               hipMemcpyHostToDevice, ctx->stream));
-    xb_ctx::Call c;
-    c.signal = ctx->d_signal; c.n = n; c.seq = ctx->seq; c.len = ctx->seq_len;
-    c.qs = 1; c.qscale = qscale; c.qoffset = qoffset; c.qstr = ctx->q_seq; c.moves = moves ? ctx->q_moves : nullptr;
-    strcpy(c.alphabet, alphabet);
-    if ((rc = enqueue_call(ctx, c))) return rc;
-    if ((rc = join_async_decode(ctx))) return rc;
-    const size_t nt = (size_t)n * ctx->T;
-    XB_HIP(ctx, hipMemcpyAsync(seq, ctx->seq, nt, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(qstring, ctx->q_seq, nt, hipMemcpyDeviceToHost, ctx->stream));
-    if (moves) XB_HIP(ctx, hipMemcpyAsync(moves, ctx->q_moves, nt, hipMemcpyDeviceToHost, ctx->stream));
-    if (seq_len) XB_HIP(ctx, hipMemcpyAsync(seq_len, ctx->seq_len, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    return xb_synchronize(ctx);
+    return basecall_host(ctx, signal, n, alphabet, seq, seq_len, {1, qscale, qoffset, qstring, moves});
 }
 
 XB_API int xb_basecall_chunks_ub(xb_ctx *ctx, const float *signal, int n, const char *alphabet, float qscale, float qoffset,
                                  int8_t *seq, int8_t *qstring, uint8_t *moves, uint8_t *probs, int32_t *seq_len)
 {
-    int rc = check_ready(ctx, n);
-    if (rc) return rc;
-    if (!signal || !seq || !qstring || !probs || !alphabet) return fail(ctx, XB_ERR_INVALID, "null argument");
-    if ((int)strlen(alphabet) < ctx->cfg.n_base + 1 || strlen(alphabet) >= sizeof(xb_ctx::Call{}.alphabet))
-        return fail(ctx, XB_ERR_INVALID, "alphabet needs %d symbols", ctx->cfg.n_base + 1);
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = ensure_ub_staging(ctx))) return rc;
-    XB_HIP(ctx, hipMemcpyAsync(ctx->d_signal, signal, sizeof(float) * (size_t)n * ctx->cfg.chunk_len,
-                               hipMemcpyHostToDevice, ctx->stream));
-    xb_ctx::Call c;
-    c.signal = ctx->d_signal; c.n = n; c.seq = ctx->seq; c.len = ctx->seq_len;
-    c.qs = 1; c.qscale = qscale; c.qoffset = qoffset; c.qstr = ctx->q_seq; c.moves = moves ? ctx->q_moves : nullptr;
-    c.ub = 1; c.probs = ctx->u_probs;
-    strcpy(c.alphabet, alphabet);
-    if ((rc = enqueue_call(ctx, c))) return rc;
-    if ((rc = join_async_decode(ctx))) return rc;
-    const size_t nt = (size_t)n * ctx->T;
-    XB_HIP(ctx, hipMemcpyAsync(seq, ctx->seq, nt, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(qstring, ctx->q_seq, nt, hipMemcpyDeviceToHost, ctx->stream));
-    if (moves) XB_HIP(ctx, hipMemcpyAsync(moves, ctx->q_moves, nt, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(probs, ctx->u_probs, nt * ctx->cfg.n_base, hipMemcpyDeviceToHost, ctx->stream));
-    if (seq_len) XB_HIP(ctx, hipMemcpyAsync(seq_len, ctx->seq_len, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    return xb_synchronize(ctx);
+    return basecall_host(ctx, signal, n, alphabet, seq, seq_len, {2, qscale, qoffset, qstring, moves, probs});
 }
 
-// lazily created: most contexts (tests, bench) never use the host pipeline
-static int ensure_slot(xb_ctx *ctx, int slot)
+// a slot's staging, lazily (most contexts -- tests, bench -- never use the host pipeline): the signal, and the planes of an
+// output level on the slot's first submission at that level
+static int ensure_slot(xb_ctx *ctx, int slot, int level)
 {
     xb_ctx::Slot &sl = ctx->slots[slot];
-    if (sl.h_signal) return XB_OK;
-    const size_t N = ctx->cfg.max_batch, L = ctx->cfg.chunk_len, T = ctx->T;
-    if (!ctx->stream_copy) XB_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream_copy, hipStreamNonBlocking));
-    XB_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&sl.h_signal), sizeof(float) * N * L, hipHostMallocDefault));
-    XB_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&sl.h_seq), N * T, hipHostMallocDefault));
-    XB_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&sl.h_len), sizeof(int32_t) * N, hipHostMallocDefault));
-    XB_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&sl.h_err), sizeof(unsigned), hipHostMallocDefault));
-    int rc = dev_alloc(ctx, &sl.d_signal, N * L);
-    rc = rc ? rc : dev_alloc(ctx, &sl.d_seq, N * T);
-    rc = rc ? rc : dev_alloc(ctx, &sl.d_len, N);
-    if (rc) return rc;
-    XB_HIP(ctx, hipEventCreateWithFlags(&sl.h2d, hipEventDisableTiming));
-    XB_HIP(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    return XB_OK;
+    const size_t N = ctx->cfg.max_batch, L = ctx->cfg.chunk_len;
+    if (!sl.h_signal) {
+        if (!ctx->stream_copy) XB_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream_copy, hipStreamNonBlocking));
+        XB_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&sl.h_signal), sizeof(float) * N * L, hipHostMallocDefault));
+        XB_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&sl.h_err), sizeof(unsigned), hipHostMallocDefault));
+        if (int rc = dev_alloc(ctx, &sl.d_signal, N * L)) return rc;
+        XB_HIP(ctx, hipEventCreateWithFlags(&sl.h2d, hipEventDisableTiming));
+        XB_HIP(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    }
+    for (int i = 0; i < plane_count(level); ++i) {
+        const size_t bytes = N * plane_bytes(ctx->T, ctx->cfg.n_base, i);
+        if (!sl.h.p[i]) XB_HIP(ctx, hipHostMalloc(&sl.h.p[i], bytes, hipHostMallocDefault));
+        if (!sl.d.p[i]) {
+            uint8_t *p = nullptr;
+            if (int rc = dev_alloc(ctx, &p, bytes)) return rc;
+            sl.d.p[i] = p;
+        }
+    }
+    return level ? ensure_staging(ctx, level) : XB_OK;
 }
 
-// the slot's staging of qualities and moves, on its first _q submission
-static int ensure_slot_q(xb_ctx *ctx, int slot)
-{
-    xb_ctx::Slot &sl = ctx->slots[slot];
-    const size_t NT = (size_t)ctx->cfg.max_batch * ctx->T;
-    if (!sl.h_q) XB_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&sl.h_q), NT, hipHostMallocDefault));
-    if (!sl.h_mv) XB_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&sl.h_mv), NT, hipHostMallocDefault));
-    int rc = sl.d_q ? XB_OK : dev_alloc(ctx, &sl.d_q, NT);
-    if (!rc && !sl.d_mv) rc = dev_alloc(ctx, &sl.d_mv, NT);
-    if (!rc) rc = ensure_q_staging(ctx);
-    return rc;
-}
-
-// the slot's staging of letter probabilities, on its first _ub submission
-static int ensure_slot_ub(xb_ctx *ctx, int slot)
-{
-    xb_ctx::Slot &sl = ctx->slots[slot];
-    const size_t NPT = (size_t)ctx->cfg.max_batch * ctx->cfg.n_base * ctx->T;
-    if (!sl.h_p) XB_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&sl.h_p), NPT, hipHostMallocDefault));
-    int rc = sl.d_p ? XB_OK : dev_alloc(ctx, &sl.d_p, NPT);
-    if (!rc) rc = ensure_ub_staging(ctx);
-    return rc;
-}
-
-static int submit_chunks(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet, const xb_ctx::Call *q)
+static int submit_chunks(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet, const DecodeOut &o)
 {
     int rc = check_ready(ctx, n);
     if (rc) return rc;
     if (slot < 0 || slot >= XB_PIPELINE_SLOTS || !signal || !alphabet) return fail(ctx, XB_ERR_INVALID, "bad slot / null argument");
     XB_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = ensure_slot(ctx, slot))) return rc;
-    if (q && (rc = ensure_slot_q(ctx, slot))) return rc;
-    if (q && q->ub && (rc = ensure_slot_ub(ctx, slot))) return rc;
+    if ((rc = ensure_slot(ctx, slot, o.level))) return rc;
     xb_ctx::Slot &sl = ctx->slots[slot];
     if (sl.busy) return fail(ctx, XB_ERR_STATE, "slot %d was submitted and not collected", slot);
     const size_t bytes = sizeof(float) * (size_t)n * ctx->cfg.chunk_len;
@@ -1924,88 +1860,51 @@ static int submit_chunks(xb_ctx *ctx, int slot, const float *signal, int n, cons
     XB_HIP(ctx, hipMemcpyAsync(sl.d_signal, sl.h_signal, bytes, hipMemcpyHostToDevice, ctx->stream_copy));
     XB_HIP(ctx, hipEventRecord(sl.h2d, ctx->stream_copy));
     XB_HIP(ctx, hipStreamWaitEvent(ctx->stream, sl.h2d, 0));
-    if ((int)strlen(alphabet) < ctx->cfg.n_base + 1 || strlen(alphabet) >= sizeof(xb_ctx::Call{}.alphabet))
-        return fail(ctx, XB_ERR_INVALID, "alphabet needs %d symbols", ctx->cfg.n_base + 1);
+    if ((rc = check_alphabet(ctx, alphabet))) return rc;
     // the D2H copies of the results, the error-word snapshot and the slot's done event follow the launch of this call
     // (call_post_actions) -- which may be held back until the next submit so that the two batches share one pass
-    xb_ctx::Call c;
-    c.signal = sl.d_signal; c.n = n; c.seq = sl.d_seq; c.len = sl.d_len; c.slot = slot;
-    if (q) {
-        c.qs = 1; c.qscale = q->qscale; c.qoffset = q->qoffset; c.qstr = sl.d_q; c.moves = sl.d_mv;
-        if (q->ub) { c.ub = 1; c.probs = sl.d_p; }
-    }
-    strcpy(c.alphabet, alphabet);
-    rc = enqueue_call(ctx, c);
+    DecodeOut d = o;
+    d.qstr = static_cast<int8_t *>(sl.d.p[2]); d.moves = static_cast<uint8_t *>(sl.d.p[3]); d.probs = static_cast<uint8_t *>(sl.d.p[4]);
+    rc = basecall_async(ctx, sl.d_signal, n, alphabet, static_cast<int8_t *>(sl.d.p[0]), static_cast<int32_t *>(sl.d.p[1]), d, slot);
     if (rc) return rc;
     sl.n = n;
     sl.busy = true;
-    sl.qs = q != nullptr;
-    sl.ub = q != nullptr && q->ub;
+    sl.level = o.level;
     return XB_OK;
 }
 
 XB_API int xb_submit_chunks(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet)
 {
-    return submit_chunks(ctx, slot, signal, n, alphabet, nullptr);
+    return submit_chunks(ctx, slot, signal, n, alphabet, {});
 }
 
 XB_API int xb_submit_chunks_q(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet, float qscale,
                               float qoffset)
 {
-    xb_ctx::Call q;
-    q.qscale = qscale; q.qoffset = qoffset;
-    return submit_chunks(ctx, slot, signal, n, alphabet, &q);
+    return submit_chunks(ctx, slot, signal, n, alphabet, {1, qscale, qoffset});
 }
 
 XB_API int xb_submit_chunks_ub(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet, float qscale,
                                float qoffset)
 {
-    xb_ctx::Call q;
-    q.qscale = qscale; q.qoffset = qoffset; q.ub = 1;
-    return submit_chunks(ctx, slot, signal, n, alphabet, &q);
+    return submit_chunks(ctx, slot, signal, n, alphabet, {2, qscale, qoffset});
 }
 
-XB_API int xb_collect_chunks_ub(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len, int8_t *qstring, uint8_t *moves,
-                                uint8_t *probs)
+// collects the planes of an output level: a submission at that level or above (below: XB_ERR_STATE)
+static int collect_chunks(xb_ctx *ctx, int slot, int level, const Planes &dst)
 {
+    static const char *const none_in_flight[3] = {"slot %d has nothing in flight", "slot %d has no submission with qualities in flight",
+                                                  "slot %d has no submission with letter probabilities in flight"};
     if (!ctx) return XB_ERR_INVALID;
-    if (slot < 0 || slot >= XB_PIPELINE_SLOTS || !seq || !qstring || !probs)
-        return fail(ctx, XB_ERR_INVALID, "bad slot / null argument");
+    if (slot < 0 || slot >= XB_PIPELINE_SLOTS || !has_required(dst, level)) return fail(ctx, XB_ERR_INVALID, "bad slot / null argument");
     xb_ctx::Slot &sl = ctx->slots[slot];
-    if (!sl.busy || !sl.ub) return fail(ctx, XB_ERR_STATE, "slot %d has no submission with letter probabilities in flight", slot);
-    const int n = sl.n;
-    const int rc = xb_collect_chunks_q(ctx, slot, seq, seq_len, qstring, moves);
-    if (rc) return rc;
-    memcpy(probs, sl.h_p, (size_t)n * ctx->cfg.n_base * ctx->T);
-    return XB_OK;
-}
-
-XB_API int xb_collect_chunks_q(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len, int8_t *qstring, uint8_t *moves)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    if (slot < 0 || slot >= XB_PIPELINE_SLOTS || !seq || !qstring) return fail(ctx, XB_ERR_INVALID, "bad slot / null argument");
-    xb_ctx::Slot &sl = ctx->slots[slot];
-    if (!sl.busy || !sl.qs) return fail(ctx, XB_ERR_STATE, "slot %d has no submission with qualities in flight", slot);
-    const int n = sl.n;
-    const int rc = xb_collect_chunks(ctx, slot, seq, seq_len);
-    if (rc) return rc;
-    memcpy(qstring, sl.h_q, (size_t)n * ctx->T);
-    if (moves) memcpy(moves, sl.h_mv, (size_t)n * ctx->T);
-    return XB_OK;
-}
-
-XB_API int xb_collect_chunks(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    if (slot < 0 || slot >= XB_PIPELINE_SLOTS || !seq) return fail(ctx, XB_ERR_INVALID, "bad slot / null argument");
-    xb_ctx::Slot &sl = ctx->slots[slot];
-    if (!sl.busy) return fail(ctx, XB_ERR_STATE, "slot %d has nothing in flight", slot);
+    if (!sl.busy || sl.level < level) return fail(ctx, XB_ERR_STATE, none_in_flight[level], slot);
     XB_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->holding && ctx->held.slot == slot) (void)flush_held(ctx);      // a failure shows as pipeline_failed below
     XB_HIP(ctx, hipEventSynchronize(sl.done));
     sl.busy = false;
-    memcpy(seq, sl.h_seq, (size_t)sl.n * ctx->T);
-    if (seq_len) memcpy(seq_len, sl.h_len, sizeof(int32_t) * (size_t)sl.n);
+    for (int i = 0; i < plane_count(level); ++i)
+        if (dst.p[i]) memcpy(dst.p[i], sl.h.p[i], (size_t)sl.n * plane_bytes(ctx->T, ctx->cfg.n_base, i));
     // the persistent recurrence reports a lost rendezvous through the error word (snapshot taken behind this batch):
     // results would be garbage.  The word is not cleared while another batch is in flight -- that batch fails too (it ran
     // on a device in an unknown state) -- and is reset once the pipeline has drained.
@@ -2021,6 +1920,22 @@ XB_API int xb_collect_chunks(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_le
         return fail(ctx, XB_ERR_DEVICE, "LSTM inter-workgroup sync timed out (persistent kernel was not fully resident?)");
     }
     return XB_OK;
+}
+
+XB_API int xb_collect_chunks_ub(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len, int8_t *qstring, uint8_t *moves,
+                                uint8_t *probs)
+{
+    return collect_chunks(ctx, slot, 2, {{seq, seq_len, qstring, moves, probs}});
+}
+
+XB_API int xb_collect_chunks_q(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len, int8_t *qstring, uint8_t *moves)
+{
+    return collect_chunks(ctx, slot, 1, {{seq, seq_len, qstring, moves, nullptr}});
+}
+
+XB_API int xb_collect_chunks(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len)
+{
+    return collect_chunks(ctx, slot, 0, {{seq, seq_len, nullptr, nullptr, nullptr}});
 }
 
 XB_API int xb_set_profiling(xb_ctx *ctx, int on)
