@@ -163,10 +163,6 @@ struct xb_ctx {
     int lstm_wide = 1;           // XB_LSTM_WIDE: 1 (default) batches just above a launch's XCD-local capacity get up to cu_count / members group
                                  // slots with the groups dealt over all XCDs instead of a second round (run_lstm_layer); 0: never
     int lstm_dual = 1;           // XB_LSTM_DUAL: 0 never, 1 when a launch would otherwise need a second chunk slab, 2 always
-    int lstm_quad = 0;           // XB_LSTM_QUAD=1: the two-groups-per-workgroup launches run the software-pipelined kernel of xb_lstm_quad.h
-                                 // where it applies (F = 768, q8 exchange image).  Bit-identical and SLOWER (41.9 vs 31.0 ms per layer of
-                                 // 1024 chunks): an experiment kept for its measurements, never the default
-    int lstm_quad_res = -1;      // its occupancy (queried once)
 
     // Two asynchronous basecalls in flight are co-scheduled once the caller has opted in with xb_reserve_pairing (contexts of at
     // most 512 chunks; XB_FUSE=0 refuses): the first xb_basecall_chunks_dev of a pair is held back until the second arrives, then
@@ -399,7 +395,7 @@ void fragment_major(const std::vector<half_t> &hi, const std::vector<half_t> &lo
     out.assign((size_t)nk * *kstride, 0);
     const unsigned char *hib = reinterpret_cast<const unsigned char *>(hi.data());
     const unsigned char *lob = reinterpret_cast<const unsigned char *>(lo.data());
-    if (nsplit == 3 && XB_GEMM_S16 != 0) {
+    if (nsplit == 3) {
         // the 16x16x32 arithmetic: piece 2 * part + c = rows 16 c .. 16 c + 15 of the block, lane l = row (l & 15), k 8 (l >> 4) .. + 8
         for (int kt = 0; kt < nk; ++kt)
             for (int nt = 0; nt < nt32; ++nt)
@@ -421,10 +417,7 @@ void fragment_major(const std::vector<half_t> &hi, const std::vector<half_t> &lo
                 if (r >= rows) continue;
                 unsigned char *blk = out.data() + (size_t)kt * *kstride + (size_t)nt * npc * 1024 + (size_t)l * 16;
                 const size_t e0 = (size_t)r * ld + (size_t)kt * 32;          // element offset of the row's k-tile
-                for (int ks = 0; ks < 2; ++ks) {
-                    memcpy(blk + ks * 1024, hib + (e0 + ks * 16 + h * 8) * 2, 16);
-                    if (nsplit == 3) memcpy(blk + (2 + ks) * 1024, lob + (e0 + ks * 16 + h * 8) * 2, 16);
-                }
+                for (int ks = 0; ks < 2; ++ks) memcpy(blk + ks * 1024, hib + (e0 + ks * 16 + h * 8) * 2, 16);
                 if (nsplit == 2) {
                     // q8 block of the 32 columns: [h8 x 32 | l8 x 32]; the B role reads l8 in lanes 0-31, h8 in lanes 32-63
                     const unsigned char *q = lob + e0 * 2 + (h == 0 ? 32 : 0);
@@ -561,7 +554,7 @@ int sync_all(xb_ctx *ctx);
 // Recurrence of one layer from `gin` into (xout_hi, xout_lo).  With `next` set, the GEMM that consumes this layer's output
 // is issued as well: either afterwards on the main stream, or -- overlapped mode -- slab by slab on the second stream while
 // the recurrence (192 of the 256 CUs, latency bound) is still running; the main stream then waits for the last slab.
-// group slots of the arrival counters: 64 groups of 64 chunks, or (lstm_quad_kernel) 128 groups of 32
+// the arrival counters: SYNC_SLOTS x 32 words, i.e. the 64 group slots of 64 chunks at 64 words each (lstm_kernel LG_SYNC)
 constexpr int SYNC_SLOTS = 128;
 
 int run_lstm_layer(xb_ctx *ctx, int layer, int n, const float *gin, half_t *xout_hi, half_t *xout_lo, const NextGemm *next)
@@ -596,10 +589,6 @@ int run_lstm_layer(xb_ctx *ctx, int layer, int n, const float *gin, half_t *xout
         p.nsplit = ctx->lstm_i8 == 2 ? 5 : 4; p.wq1 = ctx->whh_q1[layer]; p.wq0 = ctx->whh_q0[layer]; p.wscale = ctx->whh_sc[layer];
     }
     if (const char *e = getenv("XB_LSTM_SPREAD")) p.spread = atoi(e) != 0;
-    // the software-pipelined kernel serves the launches that put two groups of 64 on a workgroup (as four groups of 32)
-    bool quad_ok = ctx->lstm_quad && F == 768 && p.nsplit == 2 && !i8;
-    if (quad_ok && ctx->lstm_quad_res < 0) ctx->lstm_quad_res = xb::lstm_quad_resident_per_cu();
-    quad_ok = quad_ok && ctx->lstm_quad_res >= 1;
     bool overlapped = false;
     if (mode == 2) {
         // a workgroup can serve two groups alternately (lstm_kernel DUAL): a launch then holds 2 * gmax groups, and a
@@ -648,7 +637,6 @@ int run_lstm_layer(xb_ctx *ctx, int layer, int n, const float *gin, half_t *xout
                 StageScope sc(ctx, XB_STAGE_LSTM_REC, 1);
                 p.n0 = 0; p.nslab = n; p.s_begin = 0; p.s_end = T; p.persistent = 1;
                 p.dual = dual_batch && (ctx->lstm_dual == 2 ? n > bn : n > gslab * bn);
-                p.quad = p.dual && quad_ok;
                 p.grp0 = 0; p.slab = 0; p.xcd_local = ctx->lstm_local; p.sync_base = 0;
                 p.sig_flag = ctx->sig_flag; p.sig_done = ctx->sig_done; p.sig_base = ctx->sig_seq; p.sig_nts = nts;
                 XB_HIP(ctx, xb::launch_lstm(p, ctx->stream));
@@ -678,7 +666,6 @@ int run_lstm_layer(xb_ctx *ctx, int layer, int n, const float *gin, half_t *xout
                     p.s_begin = s0; p.s_end = s1; p.persistent = 1;
                     // a tail slab that fits the single-group launch gets one workgroup per group (twice the CUs at work)
                     p.dual = dual_batch && (ctx->lstm_dual == 2 ? p.nslab > bn : p.nslab > gslab * bn);
-                    p.quad = p.dual && quad_ok;
                     // counters are zeroed once per layer (above): consecutive launches follow each other without a memset in
                     // between, so the next launch's workgroups are dispatched the moment the previous one retires
                     p.grp0 = global_groups ? n0 / bn : 0;
@@ -945,7 +932,6 @@ XB_API int xb_ctx_create(xb_ctx **out, int device, const xb_config *cfg)
     if (const char *e = getenv("XB_LSTM_MODE")) ctx->lstm_mode = atoi(e);
     if (const char *e = getenv("XB_LSTM_DUAL")) ctx->lstm_dual = atoi(e);
     if (const char *e = getenv("XB_LSTM_WIDE")) ctx->lstm_wide = atoi(e) != 0;
-    if (const char *e = getenv("XB_LSTM_QUAD")) ctx->lstm_quad = atoi(e) != 0;
     if (const char *e = getenv("XB_LSTM_LOCAL")) ctx->lstm_local = atoi(e) != 0;
     if (const char *e = getenv("XB_DECODE_ASYNC")) ctx->decode_async = atoi(e) != 0;
     if (const char *e = getenv("XB_IN1_LAYERS")) ctx->in1_layers = atoi(e) & 31;

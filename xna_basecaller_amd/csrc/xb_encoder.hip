@@ -199,9 +199,6 @@ __device__ __forceinline__ void gemm_epilogue(const xb::GemmParams &p, const flo
 {
     constexpr int HS = L16 ? 8 : 4;              // rows between the two lane halves
     if (mw >= p.M || nw >= p.Nn) return;         // a wave wholly outside the matrix (edge tiles)
-#if defined(XB_GEMM_ABL_EPI)                     // timing-only builds (WRONG results): no epilogue at all
-    if (p.M > 0) return;
-#endif
     float bj[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -434,7 +431,7 @@ __global__ __launch_bounds__(GTHREADS) void gemm8r_kernel(xb::GemmParams p)
         la[ks] = (unsigned)((lane & 31) * 64 + (((2 * ks + (lane >> 5)) ^ ((lane >> 2) & 3)) * 16));
     // S16 (the three-product arithmetic on v_mfma_f32_16x16x32_f16, see gemm4p_kernel): row (lane & 15) of a 16-row tile, the
     // lane's eight k values are cell (lane >> 4) of the row
-    constexpr bool S16 = NSPLIT == 3 && XB_GEMM_S16 != 0;
+    constexpr bool S16 = NSPLIT == 3;
     const unsigned la16 = (unsigned)((lane & 15) * 64 + (((lane >> 4) ^ ((lane >> 2) & 3)) * 16));
     const unsigned char *const fragA = smem_raw + wr * 2 * HTB;                              // SA_wr
     const unsigned char *const fragB = smem_raw + (2 + (wc >> 1)) * 2 * HTB + (wc & 1) * 4096;   // 64 rows of SB_(wc/2)
@@ -461,7 +458,7 @@ __global__ __launch_bounds__(GTHREADS) void gemm8r_kernel(xb::GemmParams p)
         const unsigned char *t_ = fragA + (d) * HTB + ((mh) * 2 + i2) * 2048;                         \
         _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                \
             ah[i2][ks] = *reinterpret_cast<const half8 *>(t_ + (S16 ? ks * 1024 + la16 : la[ks]));        \
-            if (NSPLIT == 3) al[i2][ks] = *reinterpret_cast<const half8 *>(t_ + PARTB + (S16 ? ks * 1024 + la16 : la[ks])); \
+            if (S16) al[i2][ks] = *reinterpret_cast<const half8 *>(t_ + PARTB + ks * 1024 + la16);       \
         }                                                                                                 \
         if (NSPLIT == 2) {                                                                                \
             const v4i x_ = *reinterpret_cast<const v4i *>(t_ + PARTB + lqa[0]);                           \
@@ -474,7 +471,7 @@ __global__ __launch_bounds__(GTHREADS) void gemm8r_kernel(xb::GemmParams p)
         const unsigned char *t_ = fragB + (d) * HTB + (n) * 2048;                                     \
         _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                \
             bh[ks] = *reinterpret_cast<const half8 *>(t_ + (S16 ? ks * 1024 + la16 : la[ks]));            \
-            if (NSPLIT == 3) bl[ks] = *reinterpret_cast<const half8 *>(t_ + PARTB + (S16 ? ks * 1024 + la16 : la[ks])); \
+            if (S16) bl[ks] = *reinterpret_cast<const half8 *>(t_ + PARTB + ks * 1024 + la16);           \
         }                                                                                                 \
         if (NSPLIT == 2) {                                                                                \
             const v4i x_ = *reinterpret_cast<const v4i *>(t_ + PARTB + lqb[0]);                           \
@@ -505,12 +502,6 @@ __global__ __launch_bounds__(GTHREADS) void gemm8r_kernel(xb::GemmParams p)
             G8_F16(1, 1, n, ah, bh);                                                                      \
         } else {                                                                                          \
             _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                            \
-                if (NSPLIT == 3) {                                                                        \
-                    G8_F16(0, ks, n, al, bh);                                                             \
-                    G8_F16(1, ks, n, al, bh);                                                             \
-                    G8_F16(0, ks, n, ah, bl);                                                             \
-                    G8_F16(1, ks, n, ah, bl);                                                             \
-                }                                                                                         \
                 G8_F16(0, ks, n, ah, bh);                                                                 \
                 G8_F16(1, ks, n, ah, bh);                                                                 \
             }                                                                                             \
@@ -636,24 +627,6 @@ __global__ __launch_bounds__(GTHREADS) void gemm8r_kernel(xb::GemmParams p)
 // 47.9 ms per five GEMMs) and the workgroup shape (one 256 x 256 workgroup per CU, gemm8r: 50 ms) move it by a few percent:
 // the bytes per element are the lever that is left.
 // ======================================================================================
-#ifndef XB_GEMM_LATE_A           // 1: (three- and one-product kernels) a k-tile's LDS-DMA requests behind its first MFMA group (A/B builds)
-#define XB_GEMM_LATE_A 1
-#endif
-#ifndef XB_GEMM_ABL              // timing-only builds (WRONG results unless 0): bit 0 = every weight reload reads k-tile 0 again (L1-resident), bit 1 = every
-#define XB_GEMM_ABL 0            // A-tile request reads k-tile 0 again: what the loop's L2 -> CU traffic costs, instruction stream unchanged
-#endif
-#ifndef XB_GEMM_S16_V            // A/B builds of the 16x16x32 loop: bit 0 = lo weight pieces reloaded behind their last product (the prologue's order
-#define XB_GEMM_S16_V 1          // follows), bit 1 = the second A fragment set requested behind the first product group of phase 0
-#endif
-#ifndef XB_GEMM_TAIL             // 1 (round 5): the requests the branch-free k loop issues past the last k-tile (two tiles' worth per workgroup, so that
-#define XB_GEMM_TAIL 1           // every counted wait keeps its value) fetch one cache line each instead of the last tile again; 0: rounds 3-4 (A/B builds)
-#endif
-#ifndef XB_GEMM_XTILE            // 1 (round 5, the 16x16x32 loop): the k-tile's barrier sits between its third and fourth MFMA phase instead of at its top, and
-#define XB_GEMM_XTILE 1          // the first fragments of tile t + 1 are requested behind it -- their LDS latency runs under the fourth phase's 24 MFMAs; 0: rounds 3-4
-#endif
-#ifndef XB_GEMM_DMA_ASM          // 1: gemm4p_kernel's A-tile LDS-DMA requests as inline asm (see dma_a); 0: the builtin (A/B builds)
-#define XB_GEMM_DMA_ASM 1
-#endif
 constexpr int G4_BM = 128, G4_BN = 256, G4_THREADS = 256;
 #ifdef XB_GEMM_STAMPS
 // diagnostic build only: cycle sums over wave 0 of every gemm4p_kernel<*, 3> workgroup, by phase -- 0 prologue (kernel start to the first
@@ -712,12 +685,12 @@ __global__ __launch_bounds__(G4_THREADS, 2) void gemm4p_kernel(xb::GemmParams p)
     }
     const unsigned char *const tA_hi = reinterpret_cast<const unsigned char *>(p.a_hi + (size_t)m0 * p.lda);
     const unsigned char *const tA_lo = reinterpret_cast<const unsigned char *>(p.a_lo + (size_t)m0 * p.lda);
-    // (XB_GEMM_DMA_ASM: the requests as inline asm -- wave-uniform base in an SGPR pair, 32-bit lane offset -- so that hipcc does not
-    //  book them as LDS events: with the builtin every wait for an A fragment in the k loop is lgkmcnt(0), i.e. all eight fragment
-    //  reads of a k-step are waited for before its first MFMA; hidden from the compiler it counts, and the MFMAs on the first two
-    //  row tiles start while the other two tiles' fragments are still in flight)
-    // `live` false (round 5, XB_GEMM_TAIL): a request past the last k-tile -- issued all the same so that every counted wait keeps
-    // its value, but with every lane on the tile's first 16 bytes: one cache line through the vector-memory path instead of sixteen
+    // (the requests as inline asm -- wave-uniform base in an SGPR pair, 32-bit lane offset -- so that hipcc does not book them as
+    //  LDS events: with the builtin every wait for an A fragment in the k loop is lgkmcnt(0), i.e. all eight fragment reads of a
+    //  k-step are waited for before its first MFMA; hidden from the compiler it counts, and the MFMAs on the first two row tiles
+    //  start while the other two tiles' fragments are still in flight)
+    // `live` false (round 5): a request past the last k-tile -- issued all the same so that every counted wait keeps its value,
+    // but with every lane on the tile's first 16 bytes: one cache line through the vector-memory path instead of sixteen
     auto dma_a = [&](int t, int stage, bool live = true) {
         const size_t kb = (size_t)t * (GBK * 2);
         unsigned char *dst = smem_raw + stage * STB + wid * 1024;
@@ -726,16 +699,10 @@ __global__ __launch_bounds__(G4_THREADS, 2) void gemm4p_kernel(xb::GemmParams p)
         for (int part = 0; part < NPA; ++part)
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-#if XB_GEMM_DMA_ASM
                 const unsigned m0v = __builtin_amdgcn_readfirstlane(
                     (unsigned)(uintptr_t)(__attribute__((address_space(3))) void *)(dst + part * PARTB + h * 4096));
                 asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
                              ::"v"(ol[h]), "s"((part ? tA_lo : tA_hi) + kb), "s"(m0v) : "memory", "m0");
-#else
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) void *)((part ? tA_lo : tA_hi) + kb + ol[h]),
-                    (__attribute__((address_space(3))) void *)(dst + part * PARTB + h * 4096), 16, 0, 0);
-#endif
             }
     };
 
@@ -773,11 +740,12 @@ __global__ __launch_bounds__(G4_THREADS, 2) void gemm4p_kernel(xb::GemmParams p)
     // 16x16; a k-tile is ONE k-step of 32; A fragment of a 16-row tile: row (lane & 15), cell (lane >> 4) of the row (the LDS image
     // and its swizzle are unchanged); the weight image's four pieces of a 32-row block are (hi, lo) x (rows 0-15, 16-31) with lane
     // l = row (l & 15), k 8 (l >> 4) .. + 8 (xb_api.hip: fragment_major).
-    constexpr bool S16 = NSPLIT == 3 && XB_GEMM_S16 != 0;
+    // The k-tile's barrier then sits between its third and fourth MFMA phase instead of at its top, and the first fragments of
+    // tile t + 1 are requested behind it: their LDS latency runs under the fourth phase's 24 MFMAs.
+    constexpr bool S16 = NSPLIT == 3;
     const unsigned la16 = (unsigned)((lane & 15) * 64 + (((lane >> 4) ^ sw) * 16));
 
-    constexpr bool XT = S16 && XB_GEMM_XTILE != 0 && (XB_GEMM_S16_V & 2) == 0;
-    half8 xh[2], xl[2];                         // S16: the A fragments of phase 0 / 2 (XT: requested one tile ahead)
+    half8 xh[2], xl[2];                         // S16: the A fragments of phase 0 / 2 (phase 0's requested one tile ahead)
     floatx16 acc[4][2];
     f32x4 acc16[8][4];
 #pragma unroll
@@ -794,7 +762,6 @@ __global__ __launch_bounds__(G4_THREADS, 2) void gemm4p_kernel(xb::GemmParams p)
             for (int r = 0; r < 4; ++r) acc16[i][j][r] = 0.0f;
 
 #define G4P_SB() __builtin_amdgcn_sched_barrier(0)
-    constexpr bool G4P_LATE_A = XB_GEMM_LATE_A != 0 && NSPLIT != 2;
     // fragments of two 32-row tiles (ih = 0: rows 0..63, ih = 1: rows 64..127) of one part and k-step / of the q8 image
 #define G4P_RD_H(d, sa, part, ih, ks)                                                           \
     _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_)                                            \
@@ -846,22 +813,21 @@ __global__ __launch_bounds__(G4_THREADS, 2) void gemm4p_kernel(xb::GemmParams p)
 #define G4P_TILE(bS, t)                                                                         \
     do {                                                                                        \
         const unsigned char *const sa = smem_raw + cur * STB;                                   \
-        const int t2r_ = (t) + 2 < nk ? (t) + 2 : nk - 1;                                       \
-        const int t2_ = (XB_GEMM_ABL & 2) ? 0 : t2r_;       /* timing-only builds, see XB_GEMM_ABL */ \
-        const unsigned char *const b2 = tB + (size_t)((XB_GEMM_ABL & 1) ? 0 : t2r_) * bks;      \
+        const int t2_ = (t) + 2 < nk ? (t) + 2 : nk - 1;                                        \
+        const unsigned char *const b2 = tB + (size_t)t2_ * bks;                                 \
         /* the last two tiles have no tile t + 2: their requests keep the counts and fetch one line each (see dma_a) */ \
-        const bool live_ = XB_GEMM_TAIL == 0 || (t) + 2 < nk;                                   \
+        const bool live_ = (t) + 2 < nk;                                                        \
         const unsigned vb_ = live_ ? voff0 : 0u;                                                \
         if ((t) == 0) G4P_STAMP(0);                                                             \
-        if constexpr (!XT) {                                                                    \
+        if constexpr (!S16) {                                                                   \
             asm volatile("s_waitcnt vmcnt(%0)" ::"i"(2 * NB + NA) : "memory");                  \
             G4P_SB();                                                                           \
             __builtin_amdgcn_s_barrier();                                                       \
             G4P_SB();                                                                           \
             G4P_STAMP(1);                                                                       \
         }                                                                                       \
-        if constexpr (!G4P_LATE_A) dma_a(t2_, nxt2, live_);                                            \
         if constexpr (NSPLIT == 2) {                                                            \
+            dma_a(t2_, nxt2, live_);          /* (the other arithmetics: behind the first MFMA group) */ \
             /* fragments of the NEXT group are requested ahead of the last four MFMAs of the current one: hipcc forgets its */ \
             /* lgkmcnt bookkeeping at every asm statement and waits lgkmcnt(0) behind it, which is free once they landed */ \
             half8 h0[2], h1[2], g0[2], g1[2];                                                   \
@@ -897,42 +863,22 @@ __global__ __launch_bounds__(G4_THREADS, 2) void gemm4p_kernel(xb::GemmParams p)
             G4P_LDB_GROUP_V(bS, vb_, b2, 1);                                                           \
         } else if constexpr (S16) {                                                             \
             /* four phases of 24 MFMAs; the A fragments of phases q and q + 1 in two register sets (x, y), those of phase q + 2  */ \
-            /* requested right behind the MFMAs of phase q; all eight B pieces are live until the last phase and are reloaded     */ \
-            /* for tile t + 2 behind it -- a whole k-tile (two, with the CU's other workgroup) ahead of their first use.  Issue   */ \
-            /* order per tile, hence the counted waits: A(t + 2) behind phase 0, B(t + 2) at the end.                             */ \
-            /* XT (round 5): the fragments of phase 0 (xh, xl: loop-carried) were requested behind the barrier inside the      */ \
-            /* previous tile (the prologue, for tile 0); that barrier -- every wave has A(t + 1) landed, vmcnt(NB + NA): B(t + 1) */ \
-            /* and A(t + 2) are younger, and has finished reading tile t -- sits between phases 2 and 3.  The order of the     */ \
-            /* vector-memory instructions, hence every other counted wait, is unchanged.                                         */ \
+            /* requested right behind the MFMAs of phase q; all eight B pieces are live until the last phase, the lo pieces are   */ \
+            /* reloaded for tile t + 2 behind their last product, the hi pieces at the end -- a whole k-tile (two, with the CU's  */ \
+            /* other workgroup) ahead of their first use.  Issue order per tile, hence the counted waits: A(t + 2) behind phase 0  */ \
+            /* (NA fewer younger operations at the first wait), B(t + 2) at the end.  The fragments of phase 0 (xh, xl:          */ \
+            /* loop-carried) were requested behind the barrier inside the previous tile (the prologue, for tile 0); that barrier */ \
+            /* -- every wave has A(t + 1) landed, vmcnt(NB + NA): B(t + 1) and A(t + 2) are younger, and has finished reading    */ \
+            /* tile t -- sits between phases 2 and 3.                                                                             */ \
             half8 yh[2], yl[2];                                                                 \
-            constexpr int LA_ = G4P_LATE_A ? NA : 0;                                            \
-            if constexpr (!XT) {                                                                \
-                G4P_RD16(xl, sa, 1, 0);                                                         \
-                G4P_RD16(xh, sa, 0, 0);                                                         \
-            }                                                                                   \
-            if constexpr (!(XB_GEMM_S16_V & 2)) {                                               \
-                G4P_RD16(yl, sa, 1, 1);                                                         \
-                G4P_RD16(yh, sa, 0, 1);                                                         \
-            }                                                                                   \
-            G4P_WAIT8(INFL - 8 - LA_, bS);                                                      \
+            G4P_RD16(yl, sa, 1, 1);                                                             \
+            G4P_RD16(yh, sa, 0, 1);                                                             \
+            G4P_WAIT8(INFL - 8 - NA, bS);                                                       \
             G4P_STAMP(2);                                                                       \
-            if constexpr (XB_GEMM_S16_V & 2) {                                                  \
-                /* the second set's reads behind the first product group of phase 0 */          \
-                G4P_MFMA_BEGIN();                                                               \
-                G4P_M16(xl, 0, bS, 0);                                                          \
-                G4P_MFMA_END();                                                                 \
-                G4P_RD16(yl, sa, 1, 1);                                                         \
-                G4P_RD16(yh, sa, 0, 1);                                                         \
-                G4P_MFMA_BEGIN();                                                               \
-                G4P_M16(xh, 0, bS, 2);                                                          \
-                G4P_M16(xh, 0, bS, 0);                                                          \
-                G4P_MFMA_END();                                                                 \
-            } else {                                                                            \
-                G4P_MFMA_BEGIN();                                                               \
-                G4P_S16(xh, xl, 0, bS);                                                         \
-                G4P_MFMA_END();                                                                 \
-            }                                                                                   \
-            if constexpr (G4P_LATE_A) dma_a(t2_, nxt2, live_);                                         \
+            G4P_MFMA_BEGIN();                                                                   \
+            G4P_S16(xh, xl, 0, bS);                                                             \
+            G4P_MFMA_END();                                                                     \
+            dma_a(t2_, nxt2, live_);                                                            \
             G4P_RD16(xl, sa, 1, 2);                                                             \
             G4P_RD16(xh, sa, 0, 2);                                                             \
             G4P_MFMA_BEGIN();                                                                   \
@@ -943,92 +889,59 @@ __global__ __launch_bounds__(G4_THREADS, 2) void gemm4p_kernel(xb::GemmParams p)
             G4P_MFMA_BEGIN();                                                                   \
             G4P_S16(xh, xl, 2, bS);                                                             \
             G4P_MFMA_END();                                                                     \
-            if constexpr (XT) {                                                                 \
-                G4P_STAMP(3);                                                                   \
-                asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" ::"i"(NB + NA) : "memory"); \
-                G4P_SB();                                                                       \
-                __builtin_amdgcn_s_barrier();                                                   \
-                G4P_SB();                                                                       \
-                G4P_STAMP(1);                                                                   \
-                const unsigned char *const sn = smem_raw + nxt1 * STB;                          \
-                G4P_RD16(xl, sn, 1, 0);                                                         \
-                G4P_RD16(xh, sn, 0, 0);                                                         \
-            }                                                                                   \
-            if constexpr (XB_GEMM_S16_V & 1) {                                                  \
-                /* the lo pieces are reloaded behind their last product, the hi pieces at the end */ \
-                G4P_MFMA_BEGIN();                                                               \
-                G4P_M16(yl, 3, bS, 0);                                                          \
-                G4P_M16(yh, 3, bS, 2);                                                          \
-                G4P_MFMA_END();                                                                 \
-                G4P_LDB_GROUP_V(bS, vb_, b2, 2);                                                       \
-                G4P_LDB_GROUP_V(bS, vb_, b2, 3);                                                       \
-                G4P_MFMA_BEGIN();                                                               \
-                G4P_M16(yh, 3, bS, 0);                                                          \
-                G4P_MFMA_END();                                                                 \
-                G4P_LDB_GROUP_V(bS, vb_, b2, 0);                                                       \
-                G4P_LDB_GROUP_V(bS, vb_, b2, 1);                                                       \
-            } else {                                                                            \
-                G4P_MFMA_BEGIN();                                                               \
-                G4P_S16(yh, yl, 3, bS);                                                         \
-                G4P_MFMA_END();                                                                 \
-                G4P_LDB_GROUP_V(bS, vb_, b2, 0);                                                       \
-                G4P_LDB_GROUP_V(bS, vb_, b2, 1);                                                       \
-                G4P_LDB_GROUP_V(bS, vb_, b2, 2);                                                       \
-                G4P_LDB_GROUP_V(bS, vb_, b2, 3);                                                       \
-            }                                                                                   \
+            G4P_STAMP(3);                                                                       \
+            asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" ::"i"(NB + NA) : "memory"); \
+            G4P_SB();                                                                           \
+            __builtin_amdgcn_s_barrier();                                                       \
+            G4P_SB();                                                                           \
+            G4P_STAMP(1);                                                                       \
+            const unsigned char *const sn = smem_raw + nxt1 * STB;                              \
+            G4P_RD16(xl, sn, 1, 0);                                                             \
+            G4P_RD16(xh, sn, 0, 0);                                                             \
+            G4P_MFMA_BEGIN();                                                                   \
+            G4P_M16(yl, 3, bS, 0);                                                              \
+            G4P_M16(yh, 3, bS, 2);                                                              \
+            G4P_MFMA_END();                                                                     \
+            G4P_LDB_GROUP_V(bS, vb_, b2, 2);                                                    \
+            G4P_LDB_GROUP_V(bS, vb_, b2, 3);                                                    \
+            G4P_MFMA_BEGIN();                                                                   \
+            G4P_M16(yh, 3, bS, 0);                                                              \
+            G4P_MFMA_END();                                                                     \
+            G4P_LDB_GROUP_V(bS, vb_, b2, 0);                                                    \
+            G4P_LDB_GROUP_V(bS, vb_, b2, 1);                                                    \
         } else {                                                                                \
-            /* NSPLIT 3: per k-step lo*hi, hi*lo, hi*hi (pieces: 0, 1 = hi of k-step 0, 1; 2, 3 = lo); NSPLIT 1: hi*hi.         */ \
-            /* The A fragments of the two row-tile pairs (ih = 0: rows 0..63, ih = 1: rows 64..127) are software-pipelined by  */ \
-            /* half k-steps (round 4): the reads for (ks + 1, ih) go out right behind the MFMAs of (ks, ih) and have the other  */ \
-            /* pair's twelve MFMAs to land; only the tile's first reads -- behind the barrier -- are waited for.  The order of */ \
-            /* the vector-memory instructions (hence every counted vmcnt) is unchanged.                                         */ \
-            half8 ah0[2], al0[2], ah1[2], al1[2];                                               \
+            /* NSPLIT 1: hi*hi per k-step (pieces 0, 1 = k-step 0, 1).  The A fragments of the two row-tile pairs (ih = 0: rows  */ \
+            /* 0..63, ih = 1: rows 64..127) are software-pipelined by half k-steps (round 4): the reads for (ks + 1, ih) go out   */ \
+            /* right behind the MFMAs of (ks, ih) and have the other pair's MFMAs to land; only the tile's first reads -- behind  */ \
+            /* the barrier -- are waited for.                                                                                     */ \
+            half8 ah0[2], ah1[2];                                                               \
             G4P_RD_H(ah0, sa, 0, 0, 0);                                                         \
-            if (NSPLIT == 3) G4P_RD_H(al0, sa, 1, 0, 0);                                        \
             G4P_RD_H(ah1, sa, 0, 1, 0);                                                         \
-            if (NSPLIT == 3) G4P_RD_H(al1, sa, 1, 1, 0);                                        \
             _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                  \
-                /* (G4P_LATE_A: the tile's LDS-DMA requests go out behind its first twelve MFMAs instead of in front of them, */ \
-                /*  so the first wait has NA fewer younger operations)                                                        */ \
-                constexpr int LA_ = G4P_LATE_A ? NA : 0;                                        \
-                if (NSPLIT == 3) {                                                              \
-                    if (ks == 0) G4P_WAIT4(INFL - 4 - LA_, bS[0][0], bS[1][0], bS[0][2], bS[1][2]); \
-                    else G4P_WAIT4(INFL - 4, bS[0][1], bS[1][1], bS[0][3], bS[1][3]);           \
-                } else {                                                                        \
-                    if (ks == 0) G4P_WAIT2(INFL - 2 - LA_, bS[0][0], bS[1][0]);                 \
-                    else G4P_WAIT2(INFL - 2, bS[0][1], bS[1][1]);                               \
-                }                                                                               \
+                /* the tile's LDS-DMA requests go out behind its first MFMA group instead of in front of it, so the first */ \
+                /* wait has NA fewer younger operations                                                                   */ \
+                constexpr int LA_ = NA;                                                         \
+                if (ks == 0) G4P_WAIT2(INFL - 2 - LA_, bS[0][0], bS[1][0]);                     \
+                else G4P_WAIT2(INFL - 2, bS[0][1], bS[1][1]);                                   \
                 G4P_MFMA_BEGIN();                                                               \
-                if (NSPLIT == 3) {                                                              \
-                    G4P_F16(al0, 0, bS, ks);                                                    \
-                    G4P_F16(ah0, 0, bS, 2 + ks);                                                \
-                }                                                                               \
                 G4P_F16(ah0, 0, bS, ks);                                                        \
                 G4P_MFMA_END();                                                                 \
                 if (ks == 0) {                                                                  \
-                    if constexpr (G4P_LATE_A) dma_a(t2_, nxt2, live_);                                 \
+                    dma_a(t2_, nxt2, live_);                                                    \
                     G4P_RD_H(ah0, sa, 0, 0, 1);                                                 \
-                    if (NSPLIT == 3) G4P_RD_H(al0, sa, 1, 0, 1);                                \
                 }                                                                               \
                 G4P_MFMA_BEGIN();                                                               \
-                if (NSPLIT == 3) {                                                              \
-                    G4P_F16(al1, 1, bS, ks);                                                    \
-                    G4P_F16(ah1, 1, bS, 2 + ks);                                                \
-                }                                                                               \
                 G4P_F16(ah1, 1, bS, ks);                                                        \
                 G4P_MFMA_END();                                                                 \
                 if (ks == 0) {                                                                  \
                     G4P_RD_H(ah1, sa, 0, 1, 1);                                                 \
-                    if (NSPLIT == 3) G4P_RD_H(al1, sa, 1, 1, 1);                                \
-                    G4P_LDB_GROUP_V(bS, vb_, b2, 0);                                                   \
-                    if (NSPLIT == 3) G4P_LDB_GROUP_V(bS, vb_, b2, 2);                                  \
+                    G4P_LDB_GROUP_V(bS, vb_, b2, 0);                                            \
                 } else {                                                                        \
-                    G4P_LDB_GROUP_V(bS, vb_, b2, 1);                                                   \
-                    if (NSPLIT == 3) G4P_LDB_GROUP_V(bS, vb_, b2, 3);                                  \
+                    G4P_LDB_GROUP_V(bS, vb_, b2, 1);                                            \
                 }                                                                               \
             }                                                                                   \
         }                                                                                       \
-        if constexpr (!XT) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                   \
+        if constexpr (!S16) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                  \
         G4P_STAMP(3);                                                                           \
         { const int c_ = cur; cur = nxt1; nxt1 = nxt2; nxt2 = c_; }                             \
     } while (0)
@@ -1042,11 +955,11 @@ __global__ __launch_bounds__(G4_THREADS, 2) void gemm4p_kernel(xb::GemmParams p)
         dma_a(nk > 1 ? 1 : 0, 1);
         int c0 = 0, c1 = 1, c2 = 2;
 #pragma unroll 1
-        // (XT: barrier k certifies A(k) landed and tile k - 1 read; there are nk + 1 of them, the prologue's and one inside every tile)
-        for (int t = 0; t < nk + (XT ? 1 : 0); ++t) {
+        // (S16: barrier k certifies A(k) landed and tile k - 1 read; there are nk + 1 of them, the prologue's and one inside every tile)
+        for (int t = 0; t < nk + (S16 ? 1 : 0); ++t) {
             asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NA) : "memory");      // A(t) landed; A(t + 1) may be in flight
             __builtin_amdgcn_s_barrier();
-            dma_a(t + 2 < nk ? t + 2 : nk - 1, c2, XB_GEMM_TAIL == 0 || t + 2 < nk);
+            dma_a(t + 2 < nk ? t + 2 : nk - 1, c2, t + 2 < nk);
             const int c_ = c0; c0 = c1; c1 = c2; c2 = c_;
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1066,23 +979,21 @@ __global__ __launch_bounds__(G4_THREADS, 2) void gemm4p_kernel(xb::GemmParams p)
         dma_a(0, 0);
         if constexpr (NSPLIT == 2) {
             G4P_LDB_GROUP(bE, b0, 0); G4P_LDB_GROUP(bE, b0, 2); G4P_LDB_GROUP(bE, b0, 3); G4P_LDB_GROUP(bE, b0, 1);
-        } else if constexpr (S16 && (XB_GEMM_S16_V & 1)) {
+        } else if constexpr (S16) {
             G4P_LDB_GROUP(bE, b0, 2); G4P_LDB_GROUP(bE, b0, 3); G4P_LDB_GROUP(bE, b0, 0); G4P_LDB_GROUP(bE, b0, 1);
         } else {
-            G4P_LDB_GROUP(bE, b0, 0); if (NSPLIT == 3) G4P_LDB_GROUP(bE, b0, 2);
-            G4P_LDB_GROUP(bE, b0, 1); if (NSPLIT == 3) G4P_LDB_GROUP(bE, b0, 3);
+            G4P_LDB_GROUP(bE, b0, 0); G4P_LDB_GROUP(bE, b0, 1);
         }
         dma_a(t1, 1);
         if constexpr (NSPLIT == 2) {
             G4P_LDB_GROUP(bO, b1, 0); G4P_LDB_GROUP(bO, b1, 2); G4P_LDB_GROUP(bO, b1, 3); G4P_LDB_GROUP(bO, b1, 1);
-        } else if constexpr (S16 && (XB_GEMM_S16_V & 1)) {
+        } else if constexpr (S16) {
             G4P_LDB_GROUP(bO, b1, 2); G4P_LDB_GROUP(bO, b1, 3); G4P_LDB_GROUP(bO, b1, 0); G4P_LDB_GROUP(bO, b1, 1);
         } else {
-            G4P_LDB_GROUP(bO, b1, 0); if (NSPLIT == 3) G4P_LDB_GROUP(bO, b1, 2);
-            G4P_LDB_GROUP(bO, b1, 1); if (NSPLIT == 3) G4P_LDB_GROUP(bO, b1, 3);
+            G4P_LDB_GROUP(bO, b1, 0); G4P_LDB_GROUP(bO, b1, 1);
         }
     }
-    if constexpr (XT) {
+    if constexpr (S16) {
         asm volatile("s_waitcnt vmcnt(%0)" ::"i"(2 * NB + NA) : "memory");      // A(0) landed
         G4P_SB();
         __builtin_amdgcn_s_barrier();

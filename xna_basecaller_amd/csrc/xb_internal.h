@@ -136,18 +136,14 @@ struct GemmParams {
     int one_per_cu;              // gemm4p: 1 = at most one workgroup per CU (launches beside the recurrence)
     int sn;                      // gemm4p: N tiles per XCD super-tile (0 = the rule gemm_super_n; XB_GEMM_SN, experiments)
 };
-// XB_GEMM_S16 (compile time, both GEMM kernels and the host's weight images): 1 (default, round 5) = the three-product arithmetic
-// (nsplit 3) runs on v_mfma_f32_16x16x32_f16 -- per accumulator and k-tile of 32: lo*hi, hi*lo, hi*hi --, 0 = on 32x32x16 (per
-// k-step of 16) as in rounds 1-4.  The two sum the same products in different orders (low-bit differences); the chip holds a
-// 13 % higher clock on the 16x16x32 shape (profiles/r05_mfma_shape_ubench.txt).
-#ifndef XB_GEMM_S16
-#define XB_GEMM_S16 1
-#endif
+// The three-product arithmetic (nsplit 3) of both GEMM kernels runs on v_mfma_f32_16x16x32_f16 -- per accumulator and k-tile of 32:
+// lo*hi, hi*lo, hi*hi (round 5; rounds 1-4 ran it on 32x32x16 per k-step of 16, which sums the same products in another order).
+// The chip holds a 13 % higher clock on the 16x16x32 shape (profiles/r05_mfma_shape_ubench.txt).
 // pieces per 32-row block and k-tile of the fragment-major image for a given nsplit (lane l = 32 h + r holds row r):
-//   piece 0, 1: the 8 fp16 `hi` values of columns 32 kt + 16 ks + 8 h .. + 8, ks = 0, 1
-//   nsplit 3: piece 2, 3: the same of `lo`;   nsplit 2: pieces 2, 3 = bytes 0..15 / 16..31 of the q8 half the B role reads
-//   (h = 0: the l8 codes of the 32 columns, h = 1: the h8 codes)
-//   nsplit 3 with XB_GEMM_S16: lane l = 16 g + r; piece 2 part + c (part 0 = hi, 1 = lo; c = 0, 1) holds row 16 c + r's eight
+//   nsplit 1, 2: piece 0, 1: the 8 fp16 `hi` values of columns 32 kt + 16 ks + 8 h .. + 8, ks = 0, 1
+//   nsplit 2: pieces 2, 3 = bytes 0..15 / 16..31 of the q8 half the B role reads (h = 0: the l8 codes of the 32 columns, h = 1:
+//   the h8 codes)
+//   nsplit 3 (16x16x32 fragments): lane l = 16 g + r; piece 2 part + c (part 0 = hi, 1 = lo; c = 0, 1) holds row 16 c + r's eight
 //   values of columns 32 kt + 8 g .. + 8
 inline int gemm4_pieces(int nsplit) { return nsplit == 1 ? 2 : 4; }
 // gin layout (input projection of an LSTM layer, written by the GEMM, read by lstm_kernel): row m = t * n + chunk, column
@@ -191,9 +187,6 @@ struct LstmParams {
                                  // runs in the other arithmetic
     int spread;                  // 1: spread each group's members over all XCDs (placement-independence test)
     int dual;                    // 1: a workgroup serves two groups alternately (a launch then holds twice the groups)
-    int quad;                    // 1 (with dual, F = 768, nsplit 2, persistent): the software-pipelined kernel of xb_lstm_quad.h -- four
-                                 // groups of 32 chunks per workgroup, the gate math of one group-step between the MFMAs of the next; the
-                                 // exchange buffer and the counters are then indexed in 32-chunk groups (slot 2 grp0 + g, 128 slots)
     int slab;                    // index of this launch among the layer's time slabs (selects the byte of the XCD mask below)
     int xcd_local;               // 1: members prove per launch that their group sits on one XCD (words 1..4 of the group's sync
                                  // slot, one byte per time slab, zeroed with the counters) and then exchange h with plain stores
@@ -210,7 +203,6 @@ hipError_t launch_lstm(const LstmParams &p, hipStream_t stream);
 // workgroups of the persistent kernel the occupancy calculator admits per CU for feature size F (0: the kernel cannot be
 // resident at all, e.g. LDS or registers taken by another tenant's limits); the persistent mode needs >= 1
 int lstm_resident_per_cu(int F, int nsplit, int dual);
-int lstm_quad_resident_per_cu();   // the same for the software-pipelined kernel (F = 768, nsplit 2)
 int lstm_members(int F);
 int lstm_group_chunks();
 bool lstm_supported_features(int F);

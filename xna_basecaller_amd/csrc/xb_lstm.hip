@@ -26,14 +26,10 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // (bounded spin), workgroup barrier, then EVERY load of the exchanged bytes is an sc1 load
 // (LDS-DMA with the sc1 bit), so no L1 line can be stale and no fence is needed.
 // ======================================================================================
-#ifndef XB_LSTM_DMA_ASM          // 1: the exchange pieces' LDS-DMA requests as inline asm (see dma16_sc1); 0: the builtin (A/B builds)
-#define XB_LSTM_DMA_ASM 1
-#endif
 constexpr int LG_BN = 64;        // chunks per group (2 MFMA column tiles)
 constexpr int LG_UNITS = 32;     // hidden units per member workgroup
-constexpr int LG_SYNC = 64;      // words between the counter slots of consecutive 64-chunk groups (lstm_quad_kernel's 32-chunk groups: 32)
+constexpr int LG_SYNC = 64;      // words between the counter slots of consecutive 64-chunk groups
 constexpr unsigned long long LG_SPIN_CYCLES = 4000000000ull;   // ~2 s at 2 GHz
-constexpr int CPOL_SC1 = 16;     // gfx940+ cache-policy immediate: sc0 = 1, nt = 2, sc1 = 16
 constexpr int ST_LD = 68;        // dword stride of one unit-pair row of the h staging (64 chunks + 4: 2-way reads)
 
 // (Inline asm, not __builtin_amdgcn_global_load_lds: hipcc books an LDS-DMA as an LDS event of the lgkm counter, and with two
@@ -43,23 +39,14 @@ constexpr int ST_LD = 68;        // dword stride of one unit-pair row of the h s
 // counted waits the software pipeline needs; completion is the explicit s_waitcnt vmcnt(0) + barrier that closes every piece.)
 __device__ __forceinline__ void dma16_sc1(const void *g, void *lds_wave_base)
 {
-#if XB_LSTM_DMA_ASM
     const unsigned m0v = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) void *)lds_wave_base);
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off sc1" ::"v"(g), "s"(m0v) : "memory", "m0");
-#else
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
-                                     (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, CPOL_SC1);
-#endif
 }
 // the same with a wave-uniform base (an SGPR pair) and a 32-bit per-lane byte offset: no 64-bit address arithmetic per request
 __device__ __forceinline__ void dma16_sc1_off(const void *ubase, int byte_off, void *lds_wave_base)
 {
-#if XB_LSTM_DMA_ASM
     const unsigned m0v = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) void *)lds_wave_base);
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 sc1" ::"v"(byte_off), "s"(ubase), "s"(m0v) : "memory", "m0");
-#else
-    dma16_sc1(reinterpret_cast<const unsigned char *>(ubase) + byte_off, lds_wave_base);
-#endif
 }
 
 // Round 5: the LEAN request.  The kernel is bound by its one wave's instruction COUNT (every instruction, scalar ones included,
@@ -116,62 +103,6 @@ __device__ unsigned long long g_lstm_stamps[10];   // 0..7 cycle sums, 8 = early
 // hand-off (stores reaching L2, the other members' arrivals, the poll) then completes while the workgroup runs the other
 // group's step, the first h piece of the coming group-step is requested before the gate math of the current one, and
 // the gin tile is requested a whole group-step ahead: a launch holds twice the chunks at the same residency.
-#ifndef XB_LSTM_DMA_SPREAD       // 1: every LDS-DMA request of the MFMA loop directly behind one MFMA; 0 (default): in pairs behind the k-step's
-                                 // MFMAs -- measured on one box (profiles/r04_lstm_loop_ab.txt): no gain on top of XB_LSTM_DMA_ASM, a loss with one group per workgroup
-#define XB_LSTM_DMA_SPREAD 0
-#endif
-#ifndef XB_LSTM_DEFER_ARRIVE     // 1 (default): two groups per workgroup -- the arrival of a group-step is issued behind the first
-                                 // piece-closing drain + barrier of the OTHER group's step instead of behind a drain of its own (A/B builds: 0)
-#define XB_LSTM_DEFER_ARRIVE 1
-#endif
-#ifndef XB_LSTM_LEAN             // the three-instruction LDS-DMA requests (dma16_lean_sc1): 1 everywhere, 2 only with two groups per workgroup,
-                                 // 0 nowhere (the seven-instruction form of rounds 1-4).  Measured (profiles/r05_lstm_lean_ab.txt): with two groups
-                                 // per workgroup -5 % per launch; with ONE group the launch gets 4-6 % SLOWER -- its critical path is the hand-off
-                                 // chain, and the gin / first-piece requests bunched into a third of the issue time fill the CU's request queue
-#define XB_LSTM_LEAN 2
-#endif
-#ifndef XB_LSTM_PKGATE           // 1: the gate math on PAIRS of cells with the packed fp32 VALU (v_pk_mul / v_pk_add / v_pk_fma_f32: two lanes' worth of
-                                 // work per issue slot) -- the same IEEE operations in the same order per cell, so the results do not change;
-                                 // 0: one cell at a time (rounds 1-4; A/B builds).  Not combined with XB_LSTM_GIN_SPREAD.
-#define XB_LSTM_PKGATE 1
-#endif
-#ifndef XB_LSTM_RING3            // 1: two groups per workgroup, piece count a multiple of three -- the pieces go through a ring of THREE buffers and are
-                                 // requested up to two pieces ahead (see R3 in lstm_kernel); 0 (default): two buffers, one piece ahead.  Measured:
-                                 // bit-identical and NEUTRAL (28.43-28.55 vs 28.51-28.56 ms per paired launch, profiles/r05_lstm_lean_ab.txt 8):
-                                 // what a piece's closing waits for is not its successor's landing
-#define XB_LSTM_RING3 0
-#endif
-#ifndef XB_LSTM_GIN_SPREAD       // 1: two groups per workgroup (no counted drain behind the exchange stores) -- the eight gin requests of the
-                                 // coming step go out ONE PER CELL inside the gate math instead of back to back behind the exchange stores, where each
-                                 // found the CU's request queue still full of its predecessors and held the wave ~50 cycles.  Measured: no gain
-                                 // (29.16-29.35 vs 29.06-29.13 ms per paired launch, profiles/r05_lstm_lean_ab.txt) -> 0 (default)
-#define XB_LSTM_GIN_SPREAD 0
-#endif
-#ifndef XB_LSTM_ONE_WAIT         // 1 (default, round 5): ONE counted LDS wait per k-step in front of its MFMAs; 0: hipcc's own wait in front of every MFMA (A/B builds)
-#define XB_LSTM_ONE_WAIT 1
-#endif
-#ifndef XB_LSTM_CPREFETCH        // 1 (default, round 5): the lane's eight cell states are requested together in front of the gate math; 0: each at its use (A/B builds)
-#define XB_LSTM_CPREFETCH 1
-#endif
-#ifndef XB_LSTM_GIN_DIRECT       // 1 (default, round 5): the input projection goes from global memory STRAIGHT INTO THE ACCUMULATORS (plain
-                                 // loads one group-step ahead, an L2 prefetch two ahead); 0: through a 32 KiB LDS tile per group by LDS-DMA (rounds 1-4)
-#define XB_LSTM_GIN_DIRECT 0
-#endif
-#ifndef XB_GIN_NT
-#define XB_GIN_NT 1
-#endif
-#ifndef XB_GIN_PREFETCH
-#define XB_GIN_PREFETCH 1
-#endif
-#ifndef XB_LSTM_PIPE_PIECES      // 1: the k-step pipeline runs across the piece boundary (see PIPE in lstm_kernel); with two piece buffers it measured
-                                 // 4 % SLOWER (profiles/r05_lstm_lean_ab.txt: the piece is then closed a k-step earlier and waits longer for its successors DMA)
-#define XB_LSTM_PIPE_PIECES 0
-#endif
-#ifdef XB_NO_SIGNAL
-#define XB_SIG(x) false
-#else
-#define XB_SIG(x) (x)
-#endif
 // YALT = true (NSPLIT 2 or 3 only): the layer output y carries the OTHER second part than the exchange image -- the fp16
 // residual when the recurrence itself runs on q8 images (NSPLIT 2), the q8 image when it runs on residuals (NSPLIT 3) -- because
 // the GEMM that consumes y runs in the other arithmetic (mixed-precision encoders: xb_api.hip stage_nsplit).  The extra
@@ -210,25 +141,9 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
     // input-projection tile of the step: [NG][64 chunks][32 cells of 16 B = the four gates of one unit], cell XOR (chunk & 31)
     unsigned char *sG0 = reinterpret_cast<unsigned char *>(sC0 + NG * LG_UNITS * LG_BN);
     constexpr unsigned OFF_G = 2 * NPARTS * PIECE_BYTES + STP * 16 * ST_LD * 4 + NG * LG_UNITS * LG_BN * 4;   // of sG0 in the block
-    constexpr bool GDIR = XB_LSTM_GIN_DIRECT != 0;
-    // GDIR: no tile -- what is left at sG0 is 1 KiB that the L2 prefetch requests write into (never read)
-    constexpr unsigned G_TILE = GDIR ? 0 : LG_BN * LG_UNITS * 16;                                         // one group's gin tile
-    int *sFlag = reinterpret_cast<int *>(sG0 + (GDIR ? 1024 : NG * LG_BN * LG_UNITS * 16));
-    // ---- R3 (round 5): a ring of THREE piece buffers without a byte of extra LDS.  With two groups per workgroup each group has a gin
-    // tile buffer of 32 KiB -- and a group's tile is dead from the moment its accumulators have been read at the top of the
-    // group-step until the next tile is requested at its end.  In between the buffer is the third piece buffer: piece pc sits in
-    // slot pc % 3 (piece buffers 0, 1, the current group's tile buffer) and is requested up to TWO pieces ahead:
-    //     during piece 0: nothing (the tile buffer is still being read by slower waves until this piece's closing barrier)
-    //     during piece 1: piece 2 (first half of the k-steps) and piece 3 (second half);   during piece pc >= 2: piece pc + 2,
-    //     i.e. during the last two pieces the first two pieces of the coming group-step (when the look-ahead poll, one piece
-    //     earlier than before, has seen the other group's members arrive).
-    // A piece then has two piece times to land instead of one (piece 2: one), and what closes a piece is a COUNTED wait that leaves
-    // the requests issued behind its successor's in flight -- the previous group-step's gin tile included, which the first
-    // closing used to wait for.  The alternative y staging (YALT) moves from piece buffer 1 (no longer idle during the gate math)
-    // into the group's tile buffer, and the tile request moves behind the barrier that ends the staging reads.
-    constexpr bool R3 = XB_LSTM_RING3 != 0 && DUAL && !I8 && !GDIR && (XB_LSTM_LEAN == 2 || XB_LSTM_LEAN == 1) &&
-                        (CPR & (CPR - 1)) == 0 && NP >= 3 && NP % 3 == 0 && G_TILE >= (unsigned)(NPARTS * PIECE_BYTES);
-    unsigned *sTy = reinterpret_cast<unsigned *>(smem_raw + NPARTS * PIECE_BYTES);   // YALT: [16][ST_LD] in piece buffer 1 (R3: re-pointed per group, see serve)
+    constexpr unsigned G_TILE = LG_BN * LG_UNITS * 16;                                                     // one group's gin tile
+    int *sFlag = reinterpret_cast<int *>(sG0 + NG * G_TILE);
+    unsigned *sTy = reinterpret_cast<unsigned *>(smem_raw + NPARTS * PIECE_BYTES);   // YALT: [16][ST_LD] in piece buffer 1
     // DUAL: the first W_hh fragment lives in LDS (16 B per thread behind the flags and stamps) and is read back at the top of
     // every group-step: with all 512 registers taken hipcc otherwise parks half of it in scratch, and the reload -- a
     // scratch load with vmcnt(0) behind it -- would wait for the other group's gin tile and y stores still in flight
@@ -247,7 +162,10 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
     // LDS byte addresses as 32-bit integers (a generic pointer cast to the LDS address space costs a null check per use)
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void *)smem_raw;
     const unsigned lds_w = lds0 + (unsigned)wid * 1024u;       // this wave's 1 KiB slot of a request group (wave-uniform: an SGPR)
-    constexpr bool LEAN = XB_LSTM_LEAN == 2 ? DUAL : XB_LSTM_LEAN != 0;
+    // the three-instruction LDS-DMA requests (dma16_lean_sc1) with two groups per workgroup only: there they made the launch 5 %
+    // shorter; with ONE group it got 4-6 % SLOWER (profiles/r05_lstm_lean_ab.txt) -- its critical path is the hand-off chain, and
+    // the gin / first-piece requests bunched into a third of the issue time fill the CU's request queue
+    constexpr bool LEAN = DUAL;
     const int members = F / LG_UNITS;
     const int ngroups = (p.nslab + LG_BN - 1) / LG_BN;
     const int gh = DUAL ? (ngroups + 1) / 2 : ngroups;          // workgroup slots: slot g serves group g (and g + gh)
@@ -311,7 +229,6 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
         sC = sC0 + gi * (LG_UNITS * LG_BN);
         sG = sG0 + gi * G_TILE;
         lds_g = lds_w + OFF_G + (unsigned)gi * G_TILE;
-        if constexpr (R3) sTy = reinterpret_cast<unsigned *>(sG);
     };
 
     // ---- cell state lives in LDS as [unit][chunk] (the register file is full of W_hh): lane owns
@@ -398,56 +315,6 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
         }
     };
 
-    // ---- GDIR (round 5): the tile never touches LDS.  The accumulators START from the input projection, so the lane's 32 values
-    // (chunk row 32 nt + (lane & 31), the four gates of units 8 wid + 2 rg + hsel: 16 bytes each) are loaded straight into the
-    // accumulator registers -- eight dwordx4 loads per lane, issued at
-    // the END of the previous group-step, when the gate math has taken the last value out of them (one accumulator set, one
-    // tile in flight).  What that buys: the eight LDS-DMA requests per wave and group-step (14 % of the bytes through the CU's
-    // 64 B/clk vector-memory -> LDS path), the eight conflicting ds_read_b128 that fetched the tile back, and 64 KiB of LDS.
-    // The tile is streamed from HBM (read once), and a group-step is too short to cover that latency, so the tile of the
-    // group-step AFTER the coming one is pulled into L2 first: one LDS-DMA of one dword per lane and wave, each lane touching
-    // one of the tile's 256 lines (the four bytes land in a scratch area nobody reads -- a load with a register destination
-    // would leave that register unusable until it has landed).  Rows past the slab's last chunk read the slack rows behind
-    // the buffer, as before.
-    auto gin_tile = [&](int g_i, int s_i) {         // wave-uniform address of the tile of (group g_i of this slot, step s_i)
-        const int tn = p.reverse ? T - 1 - s_i : s_i;
-        return reinterpret_cast<const unsigned char *>(p.gin + (((size_t)tn * members + mb) * N + p.n0 + (grp + g_i * gh) * LG_BN) * 128);
-    };
-    auto load_gin_acc = [&](floatx16 (&acc)[2], int g_i, int s_i) {
-        const unsigned char *base = gin_tile(g_i, s_i);
-        int lo = lane;
-        asm volatile("" : "+v"(lo));
-        const unsigned voff = (unsigned)((lo & 31) * 512 + wid * 128 + (lo >> 5) * 16);
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
-#if XB_GIN_NT
-                const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(base + voff + nt * 16384 + rg * 32));
-#else
-                const f32x4 v = *reinterpret_cast<const f32x4 *>(base + voff + nt * 16384 + rg * 32);
-#endif
-                acc[nt][4 * rg + 0] = v[0]; acc[nt][4 * rg + 1] = v[1];
-                acc[nt][4 * rg + 2] = v[2]; acc[nt][4 * rg + 3] = v[3];
-            }
-    };
-    auto prefetch_gin = [&](int g_i, int s_i) {
-        if (!XB_GIN_PREFETCH) return;
-        const unsigned char *base = gin_tile(g_i, s_i);
-        int lo = lane;
-        asm volatile("" : "+v"(lo));
-        const unsigned voff = (unsigned)((wid * 64 + lo) * 128);
-        unsigned t;
-        asm volatile("s_add_i32 m0, %[lb], %[lc]\n\tv_add_u32 %[t], 0, %[vo]\n\tglobal_load_lds_dword %[t], %[sb]"
-                     : [t] "=&v"(t) : [lb] "s"(lds0 + (unsigned)wid * 256u), [lc] "n"((int)OFF_G), [vo] "v"(voff), [sb] "s"(base) : "memory", "m0");
-    };
-    // the group-step after (g_i, s_i) in this slot's order
-    auto next_gs = [&](int g_i, int s_i, int &g_o, int &s_o) {
-        const bool to_second = DUAL && second && g_i == 0;
-        g_o = to_second ? 1 : 0;
-        s_o = to_second ? s_i : s_i + 1;
-    };
-
     // h_{t-1} of a group's chunks comes piece by piece through LDS (every load sc1).
     // A piece is NPARTS * CPR wave-instructions of 1 KiB; wave w issues NDMA = NPARTS * CPR / 4 of
     // them (q = w, w+4, ..), exactly one per MFMA k-step when NSPLIT == 3, so the next piece's
@@ -467,10 +334,10 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
         const int lane_off = lane_off_step;
         const int part = NPARTS == 2 ? (d & 1) : 0;
         const int j = NPARTS == 2 ? (d >> 1) : d;
-        const bool slot2 = R3 && pc % 3 == 2;                     // the current group's tile buffer (LDS base lds_g, a runtime value)
-        const int lconst = (R3 ? (pc % 3 == 1 ? NPARTS * PIECE_BYTES : 0) : (pc & 1) * NPARTS * PIECE_BYTES) + part * PIECE_BYTES + 4 * j * 1024;
+        const int lconst = (pc & 1) * NPARTS * PIECE_BYTES + part * PIECE_BYTES + 4 * j * 1024;
         if constexpr (POW2 && !LEAN) {
-            // rounds 1-4: wave-uniform 64-bit base per request + the lane's byte offset (lane_off_step is the same value in both forms)
+            // one group per workgroup (see LEAN): wave-uniform 64-bit base per request + the lane's byte offset (lane_off_step is
+            // the same value in both forms)
             constexpr int ROWB = I8 ? F : F * 2;
             const unsigned char *base = reinterpret_cast<const unsigned char *>(xprev) + (size_t)part * (XPART * 2) +
                                         (size_t)(4 * j * RPI) * ROWB + pc * KP * ES;
@@ -480,7 +347,7 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
             // (the piece's column offset goes into the literal as well: the load's IMMEDIATE offset is added to the LDS address
             //  too -- measured in round 5: with offset:pc * 256 every piece but the first landed 256 pc bytes off)
             const int vconst = part * (int)(XPART * 2) + 4 * j * RPI * ROWB + pc * KP * ES;
-            dma16_lean_sc1((unsigned)lane_off, vconst, xprev, slot2 ? lds_g : lds_w, lconst, 0);
+            dma16_lean_sc1((unsigned)lane_off, vconst, xprev, lds_w, lconst, 0);
         } else {
             const int q = wid + 4 * j;
             const int cell = 64 * q + lo;
@@ -489,29 +356,21 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
         }
     };
 
-    floatx16 acc[2];            // (GDIR: carried from group-step to group-step -- the coming one's input projection is loaded into it)
-    if constexpr (GDIR) {
-        load_gin_acc(acc, 0, p.s_begin);
-        int g1, s1;
-        next_gs(0, p.s_begin, g1, s1);
-        if (s1 < p.s_end) prefetch_gin(g1, s1);
-    } else {
+    floatx16 acc[2];
 #pragma unroll 1
     for (int gi = 0; gi < NG; ++gi) {
         if (gi == 1 && !second) break;
         serve(gi);
         issue_gin(p.reverse ? T - 1 - p.s_begin : p.s_begin);
     }
-    }
-    bool early = false;     // DUAL: the first piece (R3: the first two pieces) of the coming group-step was requested during the previous one
-    bool gin_prev = false;  // R3: the previous group-step requested a gin tile (eight requests the first closing leaves in flight)
+    bool early = false;     // DUAL: the first piece of the coming group-step was requested during the previous one
     // DUAL with both groups present: the exchange stores of a group-step are not drained at its end; the next full drain +
     // barrier -- the one that closes the first piece of the other group's step, ~2.7 k cycles later -- covers them, and the
     // arrival goes out behind that (the group's hand-off still has most of the other group's step to complete: its members
     // are looked at ~3.8 k cycles after that point).  One group per slot: its next step waits for this very arrival -- not deferred.
-    constexpr bool DEFER = DUAL && XB_LSTM_DEFER_ARRIVE != 0;
+    constexpr bool DEFER = DUAL;
     unsigned *arrive_due = nullptr;
-    int sig_i = 0, sig_next = XB_SIG(p.sig_flag) ? (int)((long long)T / p.sig_nts) : -1;     // slab being worked on, its end step
+    int sig_i = 0, sig_next = p.sig_flag ? (int)((long long)T / p.sig_nts) : -1;     // slab being worked on, its end step
     for (int s = p.s_begin; s < p.s_end; ++s) {
         const int t = p.reverse ? T - 1 - s : s;
 #pragma unroll 1
@@ -532,8 +391,6 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
             const half_t *xnext = p.xh + (size_t)(p.grp0 + grp + ngi * gh) * (2 * 2 * LG_BN * F) + (size_t)((ns - 1) & 1) * XPAR;
             const bool was_early = early;
             early = false;
-            const bool gin_was = gin_prev;
-            gin_prev = false;
             int go = 0;         // EIL: request the coming group-step's first piece during the last piece
 
             if (s > 0) {
@@ -568,7 +425,7 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
                         if (*sFlag == 0) {
                             // timed out (the error word is set, the host fails the batch): release the stream that waits for
                             // this launch's slabs -- a wait on the flag has no timeout of its own
-                            if (tid == 0 && XB_SIG(p.sig_flag))
+                            if (tid == 0 && p.sig_flag)
                                 __hip_atomic_fetch_max(p.sig_flag, p.sig_base + (unsigned)p.sig_nts, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
                             return;
                         }
@@ -576,16 +433,8 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
                     XB_STAMP(1);   // gin loads issued + wait for the group
 #pragma unroll
                     for (int d = 0; d < NDMA; ++d) issue_dma(xprev, 0, d);
-                    if constexpr (R3) {
-#pragma unroll
-                        for (int d = 0; d < NDMA; ++d) issue_dma(xprev, 1, d);
-                        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(NDMA) : "memory");   // all but the second piece's requests
-                        __builtin_amdgcn_s_barrier();
-                        __builtin_amdgcn_sched_barrier(0);
-                    } else {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // first piece and the gin tile (this wave's shares)
                     __syncthreads();
-                    }
                 }
                 // (early: the drain wait and barrier that ended the previous group-step covered the first piece and this
                 //  group's gin tile, both older than the exchange stores drained there)
@@ -603,7 +452,7 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
                     asm volatile("" : "+v"(to));
                     w0 = *reinterpret_cast<const half8 *>(sW0 + to * 16);
                 }
-                if constexpr (!GDIR) acc_from_gin(acc);
+                acc_from_gin(acc);
                 // lane byte offsets of the B-fragment cells inside a piece part (one register per k-step / q8 cell; the
                 // piece buffer, the part and the column tile are immediates)
                 unsigned fa[KSP], qa[KSP / 2 > 0 ? KSP / 2 : 1][2];
@@ -627,40 +476,14 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
                             qa[b][j] = POW2 ? qa0 ^ (unsigned)((4 * b + j) << 4) : (r * CPR + ((4 * b + 2 * (1 - hs) + j) ^ (r & SWZ))) * 16;
                 }
                 // B fragments double-buffered by k-step: the 4 reads of k-step ks+1 are issued before the 6 MFMAs
-                // of ks (sched_barrier keeps hipcc from sinking the reads back to their first use).  Round 5: the k-step
-                // pipeline runs ACROSS the piece boundary (PIPE): a piece that has a successor is closed (DMA drain +
-                // barrier) in front of its LAST k-step's MFMAs, whose fragments are in registers by then, and the
-                // successor's first fragments are requested behind that barrier -- their LDS latency, which used to sit
-                // exposed at the top of every piece with the matrix pipe drained, runs under those MFMAs.
+                // of ks (sched_barrier keeps hipcc from sinking the reads back to their first use).  (Running this pipeline
+                // across the piece boundary -- each piece closed in front of its last k-step's MFMAs -- measured 4 % slower,
+                // profiles/r05_lstm_lean_ab.txt: the piece then waits longer for its successor's DMA.)
                 half8 fh[2][2], fl[2][2];
                 v8i fq[2];
-                constexpr bool PIPE = !I8 && XB_LSTM_PIPE_PIECES != 0 && KSP % 2 == 0;
 #pragma unroll
                 for (int pc = 0; pc < NP; ++pc) {
-                    const unsigned char *buf = R3 ? (pc % 3 == 2 ? sG : sPiece + (pc % 3) * NPARTS * PIECE_BYTES) : sPiece + (pc & 1) * NPARTS * PIECE_BYTES;
-                    const unsigned char *bufn = R3 ? ((pc + 1) % 3 == 2 ? sG : sPiece + ((pc + 1) % 3) * NPARTS * PIECE_BYTES)
-                                                   : sPiece + ((pc + 1) & 1) * NPARTS * PIECE_BYTES;      // the successor's buffer
-                    // what closes this piece.  R3: everything has landed but the requests issued behind the successor's -- this piece's
-                    // (piece 1: its second half), and at the first closing the previous group-step's gin tile; else: everything
-                    auto close_wait = [&]() {
-#define XB_VM(n) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(n) : "memory")
-                        if constexpr (R3) {
-                            if (pc == 0) { if (was_early && gin_was) XB_VM(8); else XB_VM(0); }
-                            else if (pc == 1) { if (NP > 3 || go) XB_VM(NDMA); else XB_VM(0); }
-                            else { if (pc + 2 < NP || go) XB_VM(NDMA); else XB_VM(0); }
-                        } else {
-                            XB_VM(0);
-                        }
-#undef XB_VM
-                    };
-                    auto load_frags_at = [&](const unsigned char *bf, int ks, half8 (&h)[2], half8 (&l)[2]) {
-#pragma unroll
-                        for (int nt = 0; nt < 2; ++nt) {
-                            const unsigned char *a = bf + nt * (32 * CPR * 16) + fa[ks];
-                            h[nt] = *reinterpret_cast<const half8 *>(a);
-                            if (NSPLIT == 3) l[nt] = *reinterpret_cast<const half8 *>(a + PIECE_BYTES);
-                        }
-                    };
+                    const unsigned char *buf = sPiece + (pc & 1) * NPARTS * PIECE_BYTES;
                     auto load_frags = [&](int ks, half8 (&h)[2], half8 (&l)[2]) {
 #pragma unroll
                         for (int nt = 0; nt < 2; ++nt) {
@@ -692,18 +515,13 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
                         }
                     };
                     if constexpr (I8) load_dig(0, bd1[0], bd0[0]);
-                    else if (!PIPE || pc == 0) load_frags(0, fh[0], fl[0]);      // (PIPE, pc > 0: requested behind the previous piece's closing barrier)
+                    else load_frags(0, fh[0], fl[0]);
                     // DUAL: has the group of the coming group-step arrived?  One look at its counter (its members had a whole
                     // group-step for it) at the start of the piece whose closing barrier publishes the answer: the last
                     // piece, or (EIL) the one before it.
-                    constexpr int PCHK = R3 ? NP - 3 : (EIL ? NP - 2 : NP - 1);
-                    if (DUAL && pc == PCHK && nxt_h && nxt_poll && tid == 0) {
-                        // (R3: as inline asm -- hipcc would guard the use of a load it can see with vmcnt(0), and this wave would drain
-                        //  the requests the counted wait of the piece's closing is there to leave in flight)
-                        if constexpr (R3) asm volatile("global_load_dword %0, %1, off sc1" : "=v"(seen) : "v"(ncnt) : "memory");
-                        else seen = __hip_atomic_load(ncnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                    if (R3 ? pc == NP - 2 : (EIL && pc == NP - 1)) go = __builtin_amdgcn_readfirstlane(nxt_h ? sFlag[1] : 0);
+                    constexpr int PCHK = EIL ? NP - 2 : NP - 1;
+                    if (DUAL && pc == PCHK && nxt_h && nxt_poll && tid == 0) seen = __hip_atomic_load(ncnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (EIL && pc == NP - 1) go = __builtin_amdgcn_readfirstlane(nxt_h ? sFlag[1] : 0);
                     if constexpr (I8) {
                         constexpr int KBP = KP / 32;            // 32-column blocks per piece = DMA requests per wave and piece
                         static_assert(NDMA == KBP, "one piece request per block");
@@ -744,7 +562,6 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
 #pragma unroll
                     for (int ks = 0; ks < KSP; ++ks) {
                         const int kg = pc * KSP + ks;
-                        const bool closing = PIPE && ks + 1 == KSP && pc + 1 < NP;     // this piece is closed in front of these MFMAs
                         if (ks + 1 < KSP) load_frags(ks + 1, fh[(ks + 1) & 1], fl[(ks + 1) & 1]);
                         if (NSPLIT == 2 && (ks & 1) == 0) load_q8(ks >> 1);        // used by the odd k-step that follows
                         __builtin_amdgcn_sched_barrier(0);
@@ -752,7 +569,7 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
                         // fragment this k-step's MFMAs take (they were requested a k-step ago).  hipcc otherwise puts a counted
                         // lgkmcnt in front of EVERY MFMA -- 130 s_waitcnt per group-step on a wave whose every instruction costs an
                         // issue slot; with this wait in its scoreboard it emits none.  (the builtin needs a literal: spelled out)
-                        if (XB_LSTM_ONE_WAIT != 0 || closing) {
+                        {
                             constexpr int RD = NSPLIT == 3 ? 4 : 2;                    // ds_reads of one load_frags
                             const bool more = ks + 1 < KSP, q8 = NSPLIT == 2 && (ks & 1) == 0;
 #define XB_LGKM(n) __builtin_amdgcn_s_waitcnt(0xC07F | ((n) << 8))
@@ -760,55 +577,19 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
                             else if (more) XB_LGKM(RD);
                             else if (q8) XB_LGKM(4);
                             else XB_LGKM(0);
+#undef XB_LGKM
                         }
                         __builtin_amdgcn_sched_barrier(0);
-                        if (closing) {
-                            // every fragment of this piece is in registers (lgkmcnt(0) above: nothing was requested in this
-                            // k-step).  Close the piece as its end used to: look-ahead flag, DMA drain, barrier, deferred arrival.
-                            XB_STAMP(3);
-                            if (!R3 && DUAL && pc == PCHK && tid == 0) {
-                                sFlag[1] = (nxt_h && (!nxt_poll || seen >= ntarget)) ? 1 : 0;
-                                XB_LGKM(0);
-                            }
-                            close_wait();                                      // next piece landed (this wave's share)
-                            if (R3 && pc == PCHK) {                            // (the asm poll load is older than this piece's requests: landed)
-                                asm volatile("" : "+v"(seen));
-                                if (tid == 0) sFlag[1] = (nxt_h && (!nxt_poll || seen >= ntarget)) ? 1 : 0;
-                                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                            }
-                            __builtin_amdgcn_s_barrier();
-                            __builtin_amdgcn_sched_barrier(0);
-                            if (DEFER && pc == 0 && arrive_due) {      // the other group's exchange stores are at L2 in every wave
-                                if (tid == 0) __hip_atomic_fetch_add(arrive_due, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                arrive_due = nullptr;
-                            }
-                            XB_STAMP(7);
-                            load_frags_at(bufn, 0, fh[0], fl[0]);      // fh[0] is free: this k-step is odd (KSP is even)
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-#undef XB_LGKM
                         // The next piece's requests, two per k-step so that the last one is issued by mid-piece and has landed at
-                        // the barrier.  (XB_LSTM_DMA_SPREAD: every request directly behind ONE MFMA -- behind the FP8 ones, which
-                        // keep the pipe busy for 64 cycles, where the k-step has them -- instead of in pairs behind the k-step's
-                        // MFMAs: measured, not adopted.)
+                        // the barrier.  (Every request directly behind ONE MFMA -- behind the FP8 ones, which keep the pipe busy for
+                        // 64 cycles, where the k-step has them -- instead of in pairs behind the k-step's MFMAs: measured, no gain,
+                        // profiles/r04_lstm_loop_ab.txt.)
                         auto dma_slot = [&](int j) {
-                            if constexpr (R3) {
-                                // piece 0: nothing; piece 1: pieces 2 and 3 (one half of the k-steps each); piece pc >= 2: piece pc + 2;
-                                // targets beyond this group-step's last piece are the coming group-step's first two (if it is ready)
-                                const int i = 2 * ks + j;
-                                if (pc == 0 || i >= (pc == 1 ? 2 : 1) * NDMA) return;
-                                const int tgt = pc == 1 ? 2 + i / NDMA : pc + 2;
-                                if (tgt < NP) issue_dma(xprev, tgt, i % NDMA);
-                                else if (go) issue_dma(xnext, tgt - NP, i % NDMA);
-                            } else {
                             if (2 * ks + j >= NDMA) return;
                             if (pc + 1 < NP) issue_dma(xprev, pc + 1, 2 * ks + j);
                             else if (EIL && go) issue_dma(xnext, 0, 2 * ks + j);
-                            }
                             __builtin_amdgcn_sched_barrier(0);
                         };
-                        constexpr bool XB_DMA_SPREAD = XB_LSTM_DMA_SPREAD != 0;
-                        const bool q_step = NSPLIT == 2 && (ks & 1) == 1;
 #pragma unroll
                         for (int nt = 0; nt < 2; ++nt) {
                             if (NSPLIT == 3) {
@@ -816,45 +597,26 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
                                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[kg], fl[ks & 1][nt], acc[nt], 0, 0, 0);
                             }
                             acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kg == 0 ? w0 : wh[kg], fh[ks & 1][nt], acc[nt], 0, 0, 0);
-                            if (XB_DMA_SPREAD) __builtin_amdgcn_sched_barrier(0);      // (pins the MFMA order: hipcc otherwise pairs
-                            if (XB_DMA_SPREAD && !q_step) dma_slot(nt);                //  each column tile's dependent fp16 / FP8 MFMAs)
                         }
-                        if (q_step) {
+                        if (NSPLIT == 2 && (ks & 1) == 1) {
 #pragma unroll
-                            for (int nt = 0; nt < 2; ++nt) {
+                            for (int nt = 0; nt < 2; ++nt)
                                 acc[nt] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wq[kg >> 1], fq[nt], acc[nt], 0, 0, 0, sca, 0, scb);
-                                if (XB_DMA_SPREAD) __builtin_amdgcn_sched_barrier(0);
-                                if (XB_DMA_SPREAD) dma_slot(nt);
-                            }
                         }
-                        if (!XB_DMA_SPREAD) {
-                            dma_slot(0);
-                            dma_slot(1);
-                        }
+                        dma_slot(0);
+                        dma_slot(1);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                     }
-                    if (!PIPE || pc + 1 == NP) {
                     XB_STAMP(3);   // piece compute (ds_read + MFMA + next piece's DMA issue)
-                    if (!R3 && DUAL && pc == PCHK && tid == 0) sFlag[1] = (nxt_h && (!nxt_poll || seen >= ntarget)) ? 1 : 0;
-                    close_wait();                                      // next piece landed (this wave's share)
-                    if constexpr (R3) {                                // (raw barrier: __syncthreads() may drain the requests left in flight)
-                        if (pc == PCHK) {                              // the asm poll load is older than this piece's requests: it has landed
-                            asm volatile("" : "+v"(seen));
-                            if (tid == 0) sFlag[1] = (nxt_h && (!nxt_poll || seen >= ntarget)) ? 1 : 0;
-                        }
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                        __builtin_amdgcn_s_barrier();
-                        __builtin_amdgcn_sched_barrier(0);
-                    } else {
+                    if (DUAL && pc == PCHK && tid == 0) sFlag[1] = (nxt_h && (!nxt_poll || seen >= ntarget)) ? 1 : 0;
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // next piece landed (this wave's share)
                     __syncthreads();
-                    }
                     if (DEFER && pc == 0 && arrive_due) {      // the other group's exchange stores are at L2 in every wave
                         if (tid == 0) __hip_atomic_fetch_add(arrive_due, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         arrive_due = nullptr;
                     }
                     XB_STAMP(7);   // piece DMA wait + barrier
-                    }
                 }
                 if constexpr (I8) {
                     // pre-activation = gin + row scale * (2^16 S11 + 2^8 (S10 + S01) + S00): every sum is exact, the fp32
@@ -883,13 +645,13 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
                     if (tid == 0) __hip_atomic_fetch_add(arrive_due, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     arrive_due = nullptr;
                 }
-                if constexpr (!GDIR) acc_from_gin(acc);
+                acc_from_gin(acc);
             }
 
             // DUAL: request the first piece of the coming group-step now -- it lands behind the gate math, and the drain
             // wait below (everything but the eight youngest operations) covers it
-            if (EIL || R3) {
-                early = go != 0;    // requested inside the last piece(s); the closing wait and barrier have landed it
+            if (EIL) {
+                early = go != 0;    // requested inside the last piece; the closing wait and barrier have landed it
             } else if (DUAL && nxt_h && sFlag[1] != 0) {
 #pragma unroll
                 for (int d = 0; d < NDMA; ++d) issue_dma(xnext, 0, d);
@@ -906,19 +668,7 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
             for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
                 for (int rg = 0; rg < 4; ++rg) cprev[nt][rg] = sC[(wid * 8 + 2 * rg + hsel) * LG_BN + nt * 32 + (lane & 31)];
-            if (XB_LSTM_CPREFETCH != 0) __builtin_amdgcn_sched_barrier(0);
-            // (XB_LSTM_GIN_SPREAD) the coming step's gin tile of this group: its buffer has been free since acc_from_gin at the top
-            // of this group-step; one request behind each cell's gate math
-            const bool gin_spread = XB_LSTM_GIN_SPREAD != 0 && !R3 && LEAN && !GDIR && DEFER && second && p.persistent && s + 1 < p.s_end;
-            unsigned gs_lane = 0;
-            const unsigned char *gs_base = nullptr;
-            if (gin_spread) {
-                int lo = lane;
-                asm volatile("" : "+v"(lo));
-                gs_lane = (unsigned)(((2 * wid + (lo >> 5)) * 128 + (((lo & 31) ^ ((2 * wid + (lo >> 5)) & 7)) * 4)) * 4);
-                const int tn = p.reverse ? T - 2 - s : s + 1;
-                gs_base = reinterpret_cast<const unsigned char *>(p.gin + (((size_t)tn * members + mb) * N + cbase) * 128);
-            }
+            __builtin_amdgcn_sched_barrier(0);
             // gates -> cell -> hidden.  A lane owns units 2*rg + hsel of chunk (lane & 31); v_permlane32_swap pairs them
             // with the other half-wave's units so that each lane packs two ADJACENT units into one dword, written to
             // the [pair][chunk] staging (consecutive lanes -> consecutive dwords: conflict-free).
@@ -927,56 +677,36 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
                 unsigned phi[4], plo[4];
                 float hq[4], lq[4];
                 unsigned dg1[4], dg0[4];            // NSPLIT == 4: digit bytes of the four units
-                constexpr bool PKG = XB_LSTM_PKGATE != 0 && XB_LSTM_GIN_SPREAD == 0;
+                // the gate math on PAIRS of cells with the packed fp32 VALU (v_pk_mul / v_pk_add / v_pk_fma_f32: two lanes' worth
+                // of work per issue slot) -- per cell the same IEEE operations in the same order as fast_sigmoid / fast_tanh:
+                // sigmoid(x) = rcp(1 + exp2(-log2e x)), tanh(x) = 1 - 2 rcp(exp2(2 log2e x) + 1)
+                // (x * (2 log2e) is (x + x) * log2e bit for bit: a power-of-two factor commutes with the rounding)
                 float og4[4], th4[4];
-                if constexpr (PKG) {
-                    // sigmoid(x) = rcp(1 + exp2(-log2e x)), tanh(x) = 1 - 2 rcp(exp2(2 log2e x) + 1): fast_sigmoid / fast_tanh spelled out on pairs
-                    // (x * (2 log2e) is (x + x) * log2e bit for bit: a power-of-two factor commutes with the rounding)
-                    constexpr float L2E = 1.44269504088896340736f;
-                    const f32x2 K_IF = {-L2E, -L2E}, K_GO = {2.0f * L2E, -L2E}, K_T = {2.0f * L2E, 2.0f * L2E}, ONE = {1.0f, 1.0f}, M2 = {-2.0f, -2.0f};
-                    auto exp2_2 = [](f32x2 v) { return (f32x2){__builtin_amdgcn_exp2f(v.x), __builtin_amdgcn_exp2f(v.y)}; };
-                    auto rcp_2 = [](f32x2 v) { return (f32x2){__builtin_amdgcn_rcpf(v.x), __builtin_amdgcn_rcpf(v.y)}; };
+                constexpr float L2E = 1.44269504088896340736f;
+                const f32x2 K_IF = {-L2E, -L2E}, K_GO = {2.0f * L2E, -L2E}, K_T = {2.0f * L2E, 2.0f * L2E}, ONE = {1.0f, 1.0f}, M2 = {-2.0f, -2.0f};
+                auto exp2_2 = [](f32x2 v) { return (f32x2){__builtin_amdgcn_exp2f(v.x), __builtin_amdgcn_exp2f(v.y)}; };
+                auto rcp_2 = [](f32x2 v) { return (f32x2){__builtin_amdgcn_rcpf(v.x), __builtin_amdgcn_rcpf(v.y)}; };
 #pragma unroll
-                    for (int rp = 0; rp < 2; ++rp) {
-                        const int r0 = 2 * rp, r1 = r0 + 1;
-                        const f32x2 if0 = rcp_2(exp2_2((f32x2){acc[nt][4 * r0 + 0], acc[nt][4 * r0 + 1]} * K_IF) + ONE);      // i, f of cell r0
-                        const f32x2 go0 = rcp_2(exp2_2((f32x2){acc[nt][4 * r0 + 2], acc[nt][4 * r0 + 3]} * K_GO) + ONE);      // rcp of g's tanh, o
-                        const f32x2 if1 = rcp_2(exp2_2((f32x2){acc[nt][4 * r1 + 0], acc[nt][4 * r1 + 1]} * K_IF) + ONE);
-                        const f32x2 go1 = rcp_2(exp2_2((f32x2){acc[nt][4 * r1 + 2], acc[nt][4 * r1 + 3]} * K_GO) + ONE);
-                        const f32x2 gg = __builtin_elementwise_fma((f32x2){go0.x, go1.x}, M2, ONE);
-                        const f32x2 ig = {if0.x, if1.x}, fg = {if0.y, if1.y}, og = {go0.y, go1.y};
-                        const f32x2 cn = __builtin_elementwise_fma(ig, gg, fg * (f32x2){cprev[nt][r0], cprev[nt][r1]});
-                        sC[(wid * 8 + 2 * r0 + hsel) * LG_BN + nt * 32 + (lane & 31)] = cn.x;
-                        sC[(wid * 8 + 2 * r1 + hsel) * LG_BN + nt * 32 + (lane & 31)] = cn.y;
-                        // (h = o * tanh(c) itself stays a scalar product below: hipcc contracts it into the f16 split -- fma_mix forms that
-                        //  take the residual from the UNROUNDED product -- and a packed multiply in front of that would change the low bits)
-                        const f32x2 th = __builtin_elementwise_fma(rcp_2(exp2_2(cn * K_T) + ONE), M2, ONE);
-                        og4[r0] = og.x; og4[r1] = og.y;
-                        th4[r0] = th.x; th4[r1] = th.y;
-                    }
+                for (int rp = 0; rp < 2; ++rp) {
+                    const int r0 = 2 * rp, r1 = r0 + 1;
+                    const f32x2 if0 = rcp_2(exp2_2((f32x2){acc[nt][4 * r0 + 0], acc[nt][4 * r0 + 1]} * K_IF) + ONE);      // i, f of cell r0
+                    const f32x2 go0 = rcp_2(exp2_2((f32x2){acc[nt][4 * r0 + 2], acc[nt][4 * r0 + 3]} * K_GO) + ONE);      // rcp of g's tanh, o
+                    const f32x2 if1 = rcp_2(exp2_2((f32x2){acc[nt][4 * r1 + 0], acc[nt][4 * r1 + 1]} * K_IF) + ONE);
+                    const f32x2 go1 = rcp_2(exp2_2((f32x2){acc[nt][4 * r1 + 2], acc[nt][4 * r1 + 3]} * K_GO) + ONE);
+                    const f32x2 gg = __builtin_elementwise_fma((f32x2){go0.x, go1.x}, M2, ONE);
+                    const f32x2 ig = {if0.x, if1.x}, fg = {if0.y, if1.y}, og = {go0.y, go1.y};
+                    const f32x2 cn = __builtin_elementwise_fma(ig, gg, fg * (f32x2){cprev[nt][r0], cprev[nt][r1]});
+                    sC[(wid * 8 + 2 * r0 + hsel) * LG_BN + nt * 32 + (lane & 31)] = cn.x;
+                    sC[(wid * 8 + 2 * r1 + hsel) * LG_BN + nt * 32 + (lane & 31)] = cn.y;
+                    // (h = o * tanh(c) itself stays a scalar product below: hipcc contracts it into the f16 split -- fma_mix forms that
+                    //  take the residual from the UNROUNDED product -- and a packed multiply in front of that would change the low bits)
+                    const f32x2 th = __builtin_elementwise_fma(rcp_2(exp2_2(cn * K_T) + ONE), M2, ONE);
+                    og4[r0] = og.x; og4[r1] = og.y;
+                    th4[r0] = th.x; th4[r1] = th.y;
                 }
 #pragma unroll
                 for (int rg = 0; rg < 4; ++rg) {
-                    float hv;
-                    if constexpr (PKG) {
-                        hv = og4[rg] * th4[rg];
-                    } else {
-                    const float ig = fast_sigmoid(acc[nt][4 * rg + 0]);
-                    const float fg = fast_sigmoid(acc[nt][4 * rg + 1]);
-                    const float gg = fast_tanh(acc[nt][4 * rg + 2]);
-                    const float og = fast_sigmoid(acc[nt][4 * rg + 3]);
-                    float *cp = sC + (wid * 8 + 2 * rg + hsel) * LG_BN + nt * 32 + (lane & 31);
-                    const float cn = __builtin_fmaf(ig, gg, fg * cprev[nt][rg]);     // spelled out: lstm_quad_kernel must round the same way
-                    *cp = cn;
-                    if constexpr (LEAN && !GDIR && DEFER) {
-                        if (gin_spread) {
-                            __builtin_amdgcn_sched_barrier(0);
-                            dma16_lean_nt(gs_lane, (nt * 4 + rg) * 4096, gs_base, lds_g, (nt * 4 + rg) * 4096);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                    }
-                    hv = og * fast_tanh(cn);
-                    }
+                    const float hv = og4[rg] * th4[rg];
                     half_t hi, lo;
                     split_f16(hv, hi, lo);
                     phi[rg] = (unsigned)__builtin_bit_cast(unsigned short, hi);
@@ -1077,17 +807,43 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
                 }
                 }
             }
+            XB_STAMP(4);   // pointwise + exchange stores issued
+            if (p.persistent && s + 1 < p.s_end) {
+                // next step's gin tile (eight LDS-DMAs per wave), then every storing wave drains its exchange stores: all but
+                // the eight youngest operations (raw barrier: __syncthreads() would drain the DMAs as well; the LDS reads of
+                // the staging are retired here)
+                __builtin_amdgcn_sched_barrier(0);
+                issue_gin(p.reverse ? T - 2 - s : s + 1);
+                if (DEFER && second) {
+                    // no drain here (see arrive_due); the barrier stays: the staging (and, YALT, piece buffer 1) is free for the
+                    // other group's step once every wave has read it
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                    __builtin_amdgcn_sched_barrier(0);
+                    arrive_due = cnt;
+                    XB_STAMP(5);
+                    XB_STAMP(6);
+                } else {
+                    asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                    __builtin_amdgcn_sched_barrier(0);
+                    XB_STAMP(5);   // stores drained
+                    if (tid == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    XB_STAMP(6);   // arrive
+                }
+            } else {
+                __syncthreads();   // sT is rewritten next step (this also lands an early first piece)
+            }
             // layer output for the next layer: plain stores, nobody in this launch reads them
             // (address recomputed from the thread index here: a value kept across the loop gets spilled, and its reload -- a
             // scratch load with a vmcnt(0) behind it -- would wait for the gin DMAs just issued)
-            bool y_done = false;
-            auto store_y = [&]() {
+            {
                 int to = tid;
                 asm volatile("" : "+v"(to));
                 const int n = cbase + (to >> 2);
                 if (n <= nlast) {
                     const size_t o = ((size_t)t * N + n) * F + mb * LG_UNITS + (to & 3) * 8;
-                    if (XB_SIG(p.sig_flag)) {           // read by another stream's kernel while this launch is still running: write-through
+                    if (p.sig_flag) {           // read by another stream's kernel while this launch is still running: write-through
                         store16_sc1(p.y_hi + o, vhi);
                         store16_sc1(p.y_lo + o, vylo);
                     } else {
@@ -1095,74 +851,11 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
                         *reinterpret_cast<uint4 *>(p.y_lo + o) = vylo;
                     }
                 }
-            };
-            XB_STAMP(4);   // pointwise + exchange stores issued
-            if (p.persistent && s + 1 < p.s_end) {
-                // next step's gin tile (eight LDS-DMAs per wave), then every storing wave drains its exchange stores: all but
-                // the eight youngest operations (raw barrier: __syncthreads() would drain the DMAs as well; the LDS reads of
-                // the staging are retired here)
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (GDIR) {
-                    // one L2 prefetch + eight loads, ALWAYS (the non-deferring drain below counts them): the coming group-step's
-                    // tile into the accumulators, the tile after it -- clamped to the launch's last step -- into L2
-                    int g1, s1, g2, s2;
-                    next_gs(gi, s, g1, s1);
-                    next_gs(g1, s1, g2, s2);
-                    prefetch_gin(g2, s2 < p.s_end ? s2 : p.s_end - 1);
-                    load_gin_acc(acc, g1, s1);              // s1 <= s + 1 < s_end
-                    __builtin_amdgcn_sched_barrier(0);
-                } else {
-                if (!R3 && !gin_spread) issue_gin(p.reverse ? T - 2 - s : s + 1);
-                }
-                if (DEFER && second) {
-                    // no drain here (see arrive_due); the barrier stays: the staging (and, YALT, piece buffer 1) is free for the
-                    // other group's step once every wave has read it
-                    if constexpr (R3) { store_y(); y_done = true; }    // (before the tile requests: the first closing of the coming
-                                                                      //  group-step leaves exactly those eight in flight)
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_s_barrier();
-                    __builtin_amdgcn_sched_barrier(0);
-                    arrive_due = cnt;
-                    if constexpr (R3) {     // the tile buffer held the alternative y staging: requests only behind the barrier
-                        issue_gin(p.reverse ? T - 2 - s : s + 1);
-                        gin_prev = true;
-                    }
-                    XB_STAMP(5);
-                    XB_STAMP(6);
-                } else if constexpr (R3) {
-                    // one group in this slot: its next step waits for this very arrival -- drain everything (nothing is younger than
-                    // the exchange stores), arrive, THEN the tile requests (behind the barrier, as above)
-                    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_s_barrier();
-                    __builtin_amdgcn_sched_barrier(0);
-                    XB_STAMP(5);
-                    if (tid == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    XB_STAMP(6);
-                    issue_gin(p.reverse ? T - 2 - s : s + 1);
-                    gin_prev = true;
-                } else {
-                if constexpr (GDIR && XB_GIN_PREFETCH != 0) asm volatile("s_waitcnt vmcnt(9) lgkmcnt(0)" ::: "memory");      // all but the prefetch and the eight loads
-                else if constexpr (GDIR) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-                XB_STAMP(5);   // stores drained
-                if (tid == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                XB_STAMP(6);   // arrive
-                }
-            } else {
-                if constexpr (GDIR) {       // the launch's last step: the second group's step may still follow
-                    int g1, s1;
-                    next_gs(gi, s, g1, s1);
-                    if (s1 < p.s_end) load_gin_acc(acc, g1, s1);
-                }
-                __syncthreads();   // sT is rewritten next step (this also lands an early first piece)
             }
-            if (!y_done) store_y();
         }
         // time slab complete: every wave's output stores are at the coherence point, then one arrival per workgroup; the last
         // one to arrive publishes the slab to the stream that waits on the flag
-        if (XB_SIG(p.sig_flag) && s + 1 == sig_next) {
+        if (p.sig_flag && s + 1 == sig_next) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             if (tid == 0) {
@@ -1194,10 +887,6 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
     }
 }
 
-#ifdef XB_WITH_QUAD          // the software-pipelined experiment: diagnostic library only (make diag), never libxnacall.so
-#include "../../tools/diag/xb_lstm_quad.h"
-#endif
-
 // dynamic LDS of lstm_kernel<KS, nsplit, dual>
 template <int KS>
 static size_t lstm_lds_bytes(int nsplit, bool dual)
@@ -1207,9 +896,8 @@ static size_t lstm_lds_bytes(int nsplit, bool dual)
     const int nparts = nsplit == 1 ? 1 : 2;
     const int ng = dual ? 2 : 1;
     const int es = nsplit >= 4 ? 1 : 2, stp = nsplit >= 4 ? 3 : nparts;     // lstm_kernel: ES, STP
-    const size_t gin_bytes = XB_LSTM_GIN_DIRECT != 0 ? 1024 : (size_t)ng * LG_BN * LG_UNITS * 16;      // prefetch scratch, or the tiles
     return (size_t)2 * nparts * LG_BN * KP * es + (size_t)stp * 16 * ST_LD * 4 +
-           (size_t)ng * sizeof(float) * LG_UNITS * LG_BN + gin_bytes + 16 + 80 + 256 * 16 + 128 * 4;
+           (size_t)ng * sizeof(float) * LG_UNITS * LG_BN + (size_t)ng * LG_BN * LG_UNITS * 16 + 16 + 80 + 256 * 16 + 128 * 4;
 }
 
 template <int KS, int NSPLIT, bool DUAL, bool YALT = false>
@@ -1225,11 +913,6 @@ template <int KS>
 hipError_t launch_lstm_ks(const xb::LstmParams &p, hipStream_t stream)
 {
     constexpr int F = KS * 16;
-#ifdef XB_WITH_QUAD
-    if constexpr (KS == Q_KS) {
-        if (p.quad) return launch_lstm_quad(p, stream);
-    }
-#endif
     const int ngroups = (p.nslab + LG_BN - 1) / LG_BN;
     const bool dual = p.dual != 0;
     const int gh = dual ? (ngroups + 1) / 2 : ngroups;      // workgroup slots (lstm_kernel)
@@ -1326,11 +1009,6 @@ int lstm_resident_per_cu(int F, int nsplit, int dual)
     }
 }
 
-#ifdef XB_WITH_QUAD
-int lstm_quad_resident_per_cu() { return lstm_quad_occupancy(); }
-#else
-int lstm_quad_resident_per_cu() { return 0; }
-#endif
 int lstm_members(int F) { return F / LG_UNITS; }
 int lstm_group_chunks() { return LG_BN; }
 
@@ -1341,11 +1019,6 @@ hipError_t launch_lstm(const LstmParams &p, hipStream_t stream)
     if (p.n0 < 0 || p.n0 + p.nslab > p.N) return hipErrorInvalidValue;
     if (p.nsplit < 1 || p.nsplit > 5) return hipErrorInvalidValue;
     if (p.nsplit >= 4 && (!p.wq1 || !p.wq0 || !p.wscale)) return hipErrorInvalidValue;
-#ifdef XB_WITH_QUAD
-    if (p.quad && (p.F != Q_F || p.nsplit != 2 || !p.persistent || !p.dual)) return hipErrorInvalidValue;
-#else
-    if (p.quad) return hipErrorInvalidValue;
-#endif
     if (p.sig_flag && (!p.persistent || p.s_begin != 0 || p.s_end != p.T || !p.sig_done || p.sig_nts < 1 || p.sig_nts > p.T))
         return hipErrorInvalidValue;
     switch (p.F / 16) {
