@@ -10,6 +10,7 @@ that is already resident in HBM.  Default workload = BASELINE.json configs[2]: t
 
   python bench.py --gpus 1 --steps 3 --warmup 1
   python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR     (+ what the last timed step returned, as DIR/*.npy)
+  python bench.py --gpus 1 --steps 3 --warmup 1 --full                  (+ the CPU baseline: the oracle timed on the host)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -17,6 +18,10 @@ N > 1: one process per GPU; every rank basecalls its own batch (reads shard, wea
 called sequences are gathered with ONE all-gather per step over RCCL (the path's only exchange: xb_gather_called of the C
 ABI, on the communicator's own stream behind an event), so that N = 1 and N > 1 time the same device pipeline.
 Rank 0 prints ONE JSON line.
+
+A plain run does what its headline figure needs: set up, warm up, time the steps, dump, print.  The stage times and the
+rooflines in its line are read off the timed steps' own HIP events, so they cost no run of their own.  --full adds what does:
+the CPU baseline (cpu_baseline: tens of seconds of host time at the default sample).
 """
 import argparse
 import json
@@ -128,8 +133,10 @@ def main():
     ap.add_argument("--features", type=int, default=768)
     ap.add_argument("--precision", default="mixed", choices=["mixed", "f16x3", "f16", "f16f8", "f16f8i"],
                     help="mixed (the product default): feed-forward projections in f16x3, recurrent ones in f16f8")
-    ap.add_argument("--cpu-chunks", type=int, default=64, help="chunks in the bounded cpu_baseline sample (0 = skip)")
-    ap.add_argument("--cpu-repeats", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (one GPU only)")
+    ap.add_argument("--cpu-chunks", type=int, default=64, help="--full: chunks in the bounded cpu_baseline sample (0 = skip)")
+    ap.add_argument("--cpu-repeats", type=int, default=3, help="--full: timed passes of cpu_baseline (their median is reported)")
     ap.add_argument("--lstm-mode", type=int, default=0)
     ap.add_argument("--weights", default="seeded", choices=["seeded", "peaky"],
                     help="seeded: N(0, 1/sqrt(fan_in)) weights (flat posteriors: every step calls a base); peaky: "
@@ -338,7 +345,7 @@ def main():
                       "beside the previous layer's recurrence, so the stages overlap and do not add up to ms_per_step",
         "called_bases_last_step": called, "called_bases_per_time_step": called / float(N * T),
     }
-    if world == 1 and args.cpu_chunks > 0:
+    if args.full and world == 1 and args.cpu_chunks > 0:
         out["cpu_baseline"] = cpu_baseline(sd, F, nb, L, args.cpu_chunks, alphabet, args.cpu_repeats)
     real_stdout.write(json.dumps(out) + "\n")
     real_stdout.flush()

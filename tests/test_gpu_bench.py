@@ -43,3 +43,22 @@ def test_bench_dump_outputs_are_the_timed_paths_results(tmp_path):
     ctx.close()
     assert np.array_equal(lens, want_len) and np.array_equal(seq, want_seq)
     assert res["called_bases_last_step"] == int(want_len.sum())
+
+
+def _bench_line(*args):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--batch", "64", "--chunksize", "2000"] + list(args), cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 1, r.stdout[-4000:]
+    return json.loads(lines[0])
+
+
+def test_bench_cpu_baseline_only_under_full():
+    """A plain run prints the headline line without the CPU baseline; --full adds it (a small sample here) and nothing else."""
+    plain = _bench_line()
+    assert "cpu_baseline" not in plain
+    full = _bench_line("--full", "--cpu-chunks", "2", "--cpu-repeats", "1")
+    assert set(full) - set(plain) == {"cpu_baseline"} and set(plain) <= set(full)
+    base = full["cpu_baseline"]
+    assert base["value"] > 0 and base["unit"] == "samples/s" and base["kind"] == "port"

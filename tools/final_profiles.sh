@@ -8,7 +8,7 @@ set -e
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04; mkdir -p $O
 cd $R
 if [ "$PART" = "bench" ]; then
-timeout -k 10 300 python bench.py --steps 6 --warmup 2 > $O/bench_nb6.json 2> $O/bench.err
+timeout -k 10 300 python bench.py --steps 6 --warmup 2 --full > $O/bench_nb6.json 2> $O/bench.err
 timeout -k 10 300 python bench.py --steps 6 --warmup 2 --nbase 5 --cpu-chunks 0 > $O/bench_nb5.json 2>> $O/bench.err
 timeout -k 10 300 python bench.py --steps 4 --warmup 2 --batch 1024 --cpu-chunks 0 > $O/bench_n1024.json 2>> $O/bench.err
 timeout -k 10 300 python bench.py --steps 4 --warmup 2 --batch 2048 --cpu-chunks 0 > $O/bench_n2048.json 2>> $O/bench.err
