@@ -435,9 +435,15 @@ __global__ __launch_bounds__(256) void lstm_kernel(xb::LstmParams p)
                     for (int d = 0; d < NDMA; ++d) issue_dma(xprev, 0, d);
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // first piece and the gin tile (this wave's shares)
                     __syncthreads();
+                } else if (!EIL && second) {
+                    // early, odd piece count, two groups: the first piece was requested behind the previous group-step's last
+                    // piece, and that step ended without a drain (DEFER) -- wait for this wave's share, then for every wave's
+                    // (without it the MFMAs read whatever piece buffer 0 still held: the other group's last piece)
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    __syncthreads();
                 }
-                // (early: the drain wait and barrier that ended the previous group-step covered the first piece and this
-                //  group's gin tile, both older than the exchange stores drained there)
+                // (early otherwise: the wait and barrier that closed the previous group-step's last piece (EIL), or its drain
+                //  wait and barrier (one group in the slot), covered the first piece and this group's gin tile)
                 XB_STAMP(2);   // first piece landed
                 // the group's second hand-off is complete (blocking poll or, with two groups per workgroup, the look-ahead one):
                 // every member has arrived at least once, so every member's XCD bit is in the mask
