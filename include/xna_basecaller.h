@@ -373,6 +373,51 @@ XB_API int xb_stream_wait_event(xb_ctx *ctx, void *hip_event);
 XB_API int xb_align_accuracy(const char *ref, int ref_len, const char *seq, int seq_len, double min_coverage, int balanced,
                              double *accuracy, int32_t counts[4]);
 
+/* ---- mapping calls to a template library (an extension: `basecaller --reference`) ----------------------------------
+ * The reference maps its calls with minimap2 through mappy (bonito/aligner.py:12-16), a genome aligner no image here has.
+ * XNA experiments map reads to a small TEMPLATE LIBRARY (tens to a thousand templates of about a hundred letters, reads about
+ * as long), and at that size the device aligns every row against every template on both strands exhaustively: no seeding,
+ * no chaining, optimal under its scoring.  minimap2 is absent, so there is nothing to pin it to: PARITY UNPINNED; the
+ * contract below is this library's own and the kernels are bit-exact against a CPU restatement of it (tests/map_ref.py).
+ *   letters    A C G T in either case are codes 0..3; every other byte (N, X, Y, ..) is code 4, "ambiguous", in the rows and in
+ *              the templates alike (minimap2's own table).  The reverse strand aligns the reverse complement of the row's
+ *              CODES (0 <-> 3, 1 <-> 2, 4 stays 4) to the template as it is.
+ *   score      local (Smith-Waterman) alignment, one affine gap piece, int32 arithmetic: a column of equal codes below 4 scores
+ *              +match, of different codes -mismatch, a column with a code 4 on either side -ambiguous (and counts as a
+ *              mismatch column); a gap of k letters costs gap_open + k * gap_extend (minimap2's convention; xb_align_accuracy
+ *              below follows parasail's open + (k - 1) * extend).  minimap2's map-ont first piece is 2 / 4 / 4 / 2 / 1.  All
+ *              five are >= 0 and <= 1000.
+ *   winner     of a row: the maximum score over (template t, strand, end cell (i, j)); ties go to the lowest t, then + before
+ *              -, then the first cell in row-major order (row position i on the aligned strand, then template column j).  No
+ *              positive score anywhere: unmapped.
+ *   trace      back from the winning cell to the first cell of score 0; among equal predecessors the diagonal, then a deletion
+ *              (a template letter with nothing opposite), then an insertion; a gap that can equally be opened or extended at a
+ *              cell is opened there.
+ *   second     the best score over all OTHER templates (either strand), 0 when there is none.  The callers' mapping quality is
+ *              clamp((int)(60 * (1 - second / score)), 0, 60) -- NOT minimap2's formula, which needs chain scores; libraries whose
+ *              templates share their flanks therefore report low to middling values.
+ * Arguments: seq (n, W) int8 rows, left-packed as xb_decode writes them, seq_len (n) (a length outside [0, W] is clamped);
+ * templates: the library's letters concatenated, offsets (R + 1) into them (offsets[0] = 0), both HOST pointers in both
+ * forms -- the library's device image is kept by the context and rebuilt only when the bytes change.  Outputs, (n) each:
+ * tmpl int32 (-1 unmapped), strand int8 (+1, -1; 0 unmapped), score, second, q_st, q_en (half-open, positions in the row ON THE
+ * ALIGNED STRAND: for strand -1 in its reverse complement -- mappy's original-strand pair is (len - q_en, len - q_st)), r_st,
+ * r_en (half-open, in the template), n_ops, and ops (n, W + Lmax) uint8, Lmax = the longest template: one byte per alignment
+ * column in template order, '=' 'X' 'I' (row letter with nothing opposite) 'D', zero-filled behind n_ops.  Unmapped rows: all
+ * zeros beside tmpl.
+ * Limits: W <= 4096, templates of 1 .. 4096 letters, a library of at most 2^20 letters, and 2 n W sum(L) <= 1.2e11 cells a call
+ * (XB_ERR_INVALID with the figures otherwise; the context stays usable).  Two launches on the main stream: a score pass over
+ * every (row, template, strand) that keeps its anti-diagonals in registers and leaves one 24-byte record per (row, 16 KB of
+ * templates), and a trace pass over the winners.  The _dev form returns without waiting (xb_synchronize).
+ */
+XB_API int xb_map_templates(xb_ctx *ctx, const int8_t *seq, const int32_t *seq_len, int n, int W, const char *templates,
+                            const int32_t *offsets, int R, int match, int mismatch, int gap_open, int gap_extend, int ambiguous,
+                            int32_t *tmpl, int8_t *strand, int32_t *score, int32_t *second, int32_t *q_st, int32_t *q_en,
+                            int32_t *r_st, int32_t *r_en, uint8_t *ops, int32_t *n_ops);
+XB_API int xb_map_templates_dev(xb_ctx *ctx, const int8_t *d_seq, const int32_t *d_seq_len, int n, int W, const char *templates,
+                                const int32_t *offsets, int R, int match, int mismatch, int gap_open, int gap_extend, int ambiguous,
+                                int32_t *d_tmpl, int8_t *d_strand, int32_t *d_score, int32_t *d_second, int32_t *d_q_st,
+                                int32_t *d_q_en, int32_t *d_r_st, int32_t *d_r_en, uint8_t *d_ops, int32_t *d_n_ops);
+
 /* ---- introspection / measurement ---------------------------------------------------------- */
 
 enum { XB_STAGE_CONV = 0, XB_STAGE_LSTM_IN = 1, XB_STAGE_LSTM_REC = 2, XB_STAGE_LINEAR = 3,

@@ -6,6 +6,7 @@ the CPU (the CPU restatement lives in oracle/ and is test infrastructure only).
 import ctypes as C
 import os
 import subprocess
+import threading
 
 import numpy as np
 
@@ -29,6 +30,7 @@ EXPORTS = [
     "xb_beam_search", "xb_beam_search_dev", "xb_basecall_chunks_beam", "xb_reserve_pairing", "xb_pairing_active", "xb_debug_layer_output",
     "xb_decode_q", "xb_decode_q_dev", "xb_basecall_chunks_q", "xb_submit_chunks_q", "xb_collect_chunks_q",
     "xb_decode_ub", "xb_decode_ub_dev", "xb_basecall_chunks_ub", "xb_submit_chunks_ub", "xb_collect_chunks_ub",
+    "xb_map_templates", "xb_map_templates_dev",
 ]
 XB_COMM_ID_BYTES = 128
 # xb_status (include/xna_basecaller.h)
@@ -119,6 +121,8 @@ def load():
     lib.xb_basecall_chunks_ub.argtypes = [vp, vp, ip, C.c_char_p, fl, fl, vp, vp, vp, vp, vp]
     lib.xb_submit_chunks_ub.argtypes = [vp, ip, vp, ip, C.c_char_p, fl, fl]
     lib.xb_collect_chunks_ub.argtypes = [vp, ip, vp, vp, vp, vp, vp]
+    lib.xb_map_templates.argtypes = [vp, vp, vp, ip, ip, C.c_char_p, vp, ip] + [ip] * 5 + [vp] * 10
+    lib.xb_map_templates_dev.argtypes = lib.xb_map_templates.argtypes
     lib.xb_result_stream.argtypes = [vp]
     lib.xb_result_stream.restype = C.c_void_p
     lib.xb_set_profiling.argtypes = [vp, ip]
@@ -188,12 +192,40 @@ def _calib(level, qscale, qoffset):
     return (float(qscale), float(qoffset)) if level else ()
 
 
+class _Locked:
+    """One library function behind a context's lock; argtypes / restype are the function's own."""
+    __slots__ = ("fn", "lock")
+
+    def __init__(self, fn, lock):
+        self.fn, self.lock = fn, lock
+
+    def __call__(self, *args):
+        with self.lock:
+            return self.fn(*args)
+
+    argtypes = property(lambda self: self.fn.argtypes, lambda self, v: setattr(self.fn, "argtypes", v))
+    restype = property(lambda self: self.fn.restype, lambda self, v: setattr(self.fn, "restype", v))
+
+
+class _OneCallAtATime:
+    """The library's functions behind one lock: an xb_ctx is used by one thread at a time (include/xna_basecaller.h), and the
+    basecalling pipeline's device stage and the mapper of `--reference` reach the same context from two threads."""
+
+    def __init__(self, lib):
+        self._lib, self._lock = lib, threading.RLock()
+
+    def __getattr__(self, name):
+        call = _Locked(getattr(self._lib, name), self._lock)
+        setattr(self, name, call)
+        return call
+
+
 class Context:
     """One xb_ctx: a GPU, a stream, the device copies of the weights and all workspaces."""
 
     def __init__(self, device, n_base, state_len, features, winlen, stride, scale, blank_score,
                  chunk_len, max_batch, precision=XB_PREC_F16X3, lstm_mode=0):
-        self.lib = load()
+        self.lib = _OneCallAtATime(load())
         self.cfg = XbConfig(n_base, state_len, features, winlen, stride, scale, blank_score, chunk_len,
                             max_batch, precision, lstm_mode)
         h = C.c_void_p()
@@ -432,6 +464,30 @@ class Context:
         self._check(self.lib.xb_beam_search_dev(self.h, _ptr(d_scores), int(T), int(n), int(bool(has_blank)),
                                                 "".join(alphabet).encode(), int(beam_width), float(beam_cut), float(scale),
                                                 float(offset), _ptr(d_sequence), _ptr(d_qstring), _ptr(d_moves), _ptr(d_score)))
+
+    # ---- template mapper (xb_map_templates): an extension, parity unpinned ----------
+    MAP_OUTPUTS = (("tmpl", np.int32), ("strand", np.int8), ("score", np.int32), ("second", np.int32), ("q_st", np.int32),
+                   ("q_en", np.int32), ("r_st", np.int32), ("r_en", np.int32), ("ops", np.uint8), ("n_ops", np.int32))
+
+    def map_templates(self, seq, seq_len, templates, offsets, scoring=(2, 4, 4, 2, 1)):
+        """xb_map_templates: seq (n, W) int8 left-packed rows and seq_len (n) against the library `templates` (its letters
+        concatenated, bytes) with `offsets` (R + 1) -> dict of the outputs named in MAP_OUTPUTS; ops is (n, W + Lmax)."""
+        seq = np.ascontiguousarray(seq, dtype=np.int8)
+        lens = np.ascontiguousarray(seq_len, dtype=np.int32)
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        n, W = seq.shape
+        lmax = int(np.diff(off).max()) if off.size > 1 else 0
+        out = {k: np.empty((n, W + lmax) if k == "ops" else (n,), dtype=dt) for k, dt in self.MAP_OUTPUTS}
+        self._check(self.lib.xb_map_templates(self.h, seq.ctypes.data, lens.ctypes.data, n, W, bytes(templates), off.ctypes.data,
+                                              off.size - 1, *[int(v) for v in scoring], *[out[k].ctypes.data for k, _ in self.MAP_OUTPUTS]))
+        return out
+
+    def map_templates_dev(self, d_seq, d_seq_len, n, W, templates, offsets, scoring, d_out):
+        """xb_map_templates_dev: device pointers for the rows and for the outputs (d_out: name -> pointer, MAP_OUTPUTS)."""
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        self._check(self.lib.xb_map_templates_dev(self.h, _ptr(d_seq), _ptr(d_seq_len), int(n), int(W), bytes(templates),
+                                                  off.ctypes.data, off.size - 1, *[int(v) for v in scoring],
+                                                  *[_ptr(d_out[k]) for k, _ in self.MAP_OUTPUTS]))
 
     # ---- host pipeline: two batches in flight (xb_submit_chunks / xb_collect_chunks) ----------
     def submit_chunks(self, slot, signal, alphabet, qscale=1.0, qoffset=0.0, level=0):

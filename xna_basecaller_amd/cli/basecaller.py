@@ -4,8 +4,10 @@ arguments, flags, defaults and stderr lines; FASTQ (or, redirected to `*.sam`, u
 `<stdout-stem>_summary.tsv` beside it.
 
 Differences, all outside the hot path: reads come from `*.xsig.npz` signal bundles (no HDF5/VBZ reader in
-this image, see reads.py); --reference / --modified-bases / --save-ctc are rejected (mappy / remora /
-CTCWriter are not on the north-star path); under torchrun (WORLD_SIZE > 1) reads are sharded over the
+this image, see reads.py); --modified-bases / --save-ctc are rejected (remora / CTCWriter are not on the
+north-star path); --reference FASTA maps every call to a TEMPLATE LIBRARY on the device (aligner.py: exhaustive
+alignment, this package's own contract, not minimap2) and, as in the reference, makes SAM the default output;
+--paf PATH (an extension) writes the mappings as PAF beside it; under torchrun (WORLD_SIZE > 1) reads are sharded over the
 ranks and gathered to rank 0 over RCCL before writing.  Extension: --qscores writes the Viterbi decode's device
 qualities (xb_decode_q) in place of the reference's placeholder 'O'; --ub-probs adds per-base probabilities of every
 letter outside A, C, G, T as `u<letter>:B:C` tags (xb_decode_ub); without them the output is unchanged.
@@ -71,7 +73,7 @@ def _gathered_results(results, loader, rank, world, window=256):
                 held = item
                 break
             batch.append((read.index, tuple(getattr(read, k) for k in READ_FIELDS), read.tagdata(), len(read.signal),
-                          res["sequence"], res["qstring"], res.get("mods", [])))
+                          res["sequence"], res["qstring"], res.get("mods", []), res.get("mapping", False)))
         payload = ("error", repr(failure)) if failure is not None else ("ok", batch)
         gathered = [None] * world if rank == 0 else None
         tdist.gather_object(payload, gathered, dst=0)
@@ -82,10 +84,12 @@ def _gathered_results(results, loader, rank, world, window=256):
                 failure = RuntimeError("a rank failed while basecalling: %s" % "; ".join(bad))
                 continue
             merged = sorted((rec for p in gathered for rec in p[1]), key=lambda rec: rec[0])
-            for _, fields, tags, n_samples, seq, qstring, mods in merged:
+            for _, fields, tags, n_samples, seq, qstring, mods, mapping in merged:
                 res = {"sequence": seq, "qstring": qstring}
                 if mods:
                     res["mods"] = mods
+                if mapping is not False:                 # --reference: every rank mapped its own reads
+                    res["mapping"] = mapping
                 yield _CalledRead(fields, tags, n_samples), res
     if failure is not None:
         raise failure
@@ -150,15 +154,30 @@ def main(args):
 
     basecall = load_symbol(args.model_directory, "basecall")
 
-    if args.reference or args.modified_bases or args.modified_base_model or args.save_ctc:
-        sys.stderr.write("> error: --reference/--modified-bases/--save-ctc are not part of the MI355X path\n")
+    if args.modified_bases or args.modified_base_model or args.save_ctc:
+        sys.stderr.write("> error: --modified-bases/--save-ctc are not part of the MI355X path\n")
         exit(1)
+    if args.paf and not args.reference:
+        sys.stderr.write("> error: --paf writes the mappings of --reference\n")
+        exit(1)
+    aligner = None
+    if args.reference:
+        # a template library, mapped exhaustively on the device (aligner.py) -- on the model's own context, so that the
+        # mapper's launches queue on the basecaller's stream instead of competing with its persistent kernels
+        from ..aligner import TemplateAligner
+        sys.stderr.write("> loading reference\n")
+        try:
+            aligner = TemplateAligner.from_config(args.reference, model.config, device=getattr(model, "_device", 0),
+                                                  context=lambda: getattr(model, "_ctx", None))
+        except (OSError, ValueError) as e:
+            sys.stderr.write("> failed to load/build index: %s\n" % e)
+            exit(1)
     if args.ub_probs:
         why = ub_probs_refusal(model)
         if why is not None:
             sys.stderr.write("> error: %s\n" % why)
             exit(1)
-    fmt = biofmt(aligned=False)
+    fmt = biofmt(aligned=aligner is not None)
     sys.stderr.write(f"> outputting {fmt.aligned} {fmt.name}\n")
     if fmt.name not in ("fastq", "sam"):
         sys.stderr.write("> error: FASTQ and SAM text output are implemented (redirect stdout to *.fastq or *.sam); "
@@ -179,6 +198,10 @@ def main(args):
                        chunksize=model.config["basecaller"]["chunksize"],
                        overlap=model.config["basecaller"]["overlap"], **extra)
 
+    if aligner is not None:             # every rank maps its own reads, before the gather
+        from ..aligner import align_map
+        results = align_map(aligner, results)
+
     t0 = perf_counter()
     if world > 1:
         results = _gathered_results(results, reads, rank, world)
@@ -187,9 +210,14 @@ def main(args):
                 pass
             return
 
-    writer = Writer(fmt.mode, results, aligner=None, group_key=args.model_directory, groups=groups)
+    paf = open(args.paf, "w") if args.paf else None
+    writer = Writer(fmt.mode, results, aligner=aligner, group_key=args.model_directory, groups=groups, paf=paf)
     writer.start()
     writer.join()
+    if paf is not None:
+        paf.close()
+    if aligner is not None:
+        aligner.close()
     if writer.error is not None:
         raise writer.error
     duration = perf_counter() - t0
@@ -213,7 +241,9 @@ def argparser():
     parser = ArgumentParser(formatter_class=ArgumentDefaultsHelpFormatter, add_help=False)
     parser.add_argument("model_directory")
     parser.add_argument("reads_directory")
-    parser.add_argument("--reference")
+    parser.add_argument("--reference", help="FASTA of a template library: every call is mapped to it on the device (exhaustive "
+                        "local alignment, both strands; libraries up to 2^20 letters, templates up to 4096)")
+    parser.add_argument("--paf", help="with --reference: also write the mappings as PAF to this file; not in the reference CLI")
     parser.add_argument("--modified-bases", nargs="+")
     parser.add_argument("--modified-base-model")
     parser.add_argument("--read-ids")

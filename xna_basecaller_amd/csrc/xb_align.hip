@@ -1,4 +1,5 @@
-// xb_align.hip -- host-side accuracy of a called sequence against its reference (no device code).
+// xb_align.hip -- alignment of called sequences: the host-side accuracy of a call against its reference (xb_align_accuracy,
+// below), and the device mapper of calls to a template library (xb_map_templates: the two kernels at the end of this file).
 //
 // `bonito evaluate` scores every call with util.accuracy (ub-bonito/bonito/util.py:402-424):
 //     parasail.sw_trace_striped_32(seq, ref, 8, 4, parasail.dnafull) -> CIGAR -> '=' / ('=' + 'I' + 'X' + 'D') * 100,
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "../../include/xna_basecaller.h"
+#include "xb_internal.h"
 
 extern "C" XB_API int xb_align_accuracy(const char *ref, int ref_len, const char *seq, int seq_len, double min_coverage,
                                         int balanced, double *accuracy, int32_t counts[4])
@@ -81,3 +83,329 @@ extern "C" XB_API int xb_align_accuracy(const char *ref, int ref_len, const char
     *accuracy = den > 0 ? 100.0 * num / den : 0.0;
     return XB_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// xb_map_templates: exhaustive local alignment of every called row against every template, both strands (contract: the
+// public header).  Two kernels.
+//
+// Score pass: grid (read, template chunk), a workgroup stages its chunk's template codes and the read's codes in LDS once,
+// its waves take the (template, strand) pairs of the chunk in turn.  One wave runs one pair as a systolic array: the
+// template lies across the lanes, K consecutive columns per lane (a stripe of 64 K columns; longer templates take several
+// stripes, the last column of a stripe handed to the next through a per-wave LDS column of (H, E)), lane l works on query
+// row s - l at step s, and takes H and E of its left neighbour's last column with one __shfl_up per value and step; the
+// diagonal is the value it took one step earlier.  Only the previous row's H and F of a lane's own K columns live in
+// registers.  Per pair the result is (score, first end cell); per workgroup one record of MAP_PARTIAL_INTS ints goes to
+// memory -- nothing per cell, nothing per pair.
+//
+// Trace pass: one wave per read merges the read's records (winner and `second`), runs the winner's pair once more through the
+// same cell update, this time storing a direction byte per cell (LDS when the pair fits, else the context's scratch), and
+// lane 0 walks back from the end cell.
+namespace {
+
+using xb::MapParams;
+
+constexpr int MAP_NEG = -(1 << 28);
+
+struct MapScoring { int match, mis, go, ge, amb; };
+
+struct MapBest { int score, t, s, i, j, sec; };
+
+__device__ inline bool map_better(const MapBest &x, const MapBest &a)
+{
+    if (x.score != a.score) return x.score > a.score;
+    if (x.t != a.t) return x.t < a.t;
+    if (x.s != a.s) return x.s < a.s;
+    if (x.i != a.i) return x.i < a.i;
+    return x.j < a.j;
+}
+
+// a <- the summary of the union of what a and x summarise: the winner by the tie order, and the best score among the
+// templates other than the winner's
+__device__ inline void map_merge(MapBest &a, const MapBest &x)
+{
+    // field by field: selecting whole structs sends them through private memory
+    const bool take = x.score > 0 && (a.score <= 0 || map_better(x, a));      // x wins
+    const bool both = x.score > 0 && a.score > 0;
+    const int l_score = take ? a.score : x.score, l_t = take ? a.t : x.t, l_sec = take ? a.sec : x.sec;   // the loser
+    int sec = take ? x.sec : a.sec;
+    a.score = take ? x.score : a.score;
+    a.t = take ? x.t : a.t;
+    a.s = take ? x.s : a.s;
+    a.i = take ? x.i : a.i;
+    a.j = take ? x.j : a.j;
+    if (both) {
+        sec = sec > l_sec ? sec : l_sec;
+        if (l_t != a.t && l_score > sec) sec = l_score;
+    }
+    a.sec = sec;
+}
+
+__device__ inline int map_code(int8_t c)
+{
+    switch (c) {
+    case 'A': case 'a': return 0;
+    case 'C': case 'c': return 1;
+    case 'G': case 'g': return 2;
+    case 'T': case 't': return 3;
+    default: return 4;
+    }
+}
+
+// One (read, template, strand) pair on one wave.  q: the read's codes (forward), n of them; strand 1 aligns their reverse
+// complement.  t: the template's codes, L of them.  bnd: 2 (n + 1) ints of this wave (needed when L > 64 K).  TRACE: a
+// direction byte per cell to dir[(i - 1) * L + (j - 1)]: bits 0-1 where H came from (0 nowhere: H = 0, 1 diagonal, 2 E, 3 F),
+// bit 2 E was opened from H, bit 3 F was opened from H.  Returns, on every lane, score << 32 | (65535 - i) << 16 | (65535 - j)
+// of the first maximal cell in row-major order (i, j 1-based), or 0.
+template <int K, bool TRACE>
+__device__ inline unsigned long long map_pair(const uint8_t *q, int n, int strand, const uint8_t *t, int L, const MapScoring sc,
+                                              int *bnd, uint8_t *dir, int lane)
+{
+    unsigned long long best = 0;
+    int *bH = bnd, *bE = bnd + (n + 1);
+    const int open = sc.go + sc.ge;
+    for (int j0 = 0; j0 < L; j0 += 64 * K) {
+        const bool more = j0 + 64 * K < L;             // another stripe follows: every column of this one is real
+        const int jc = j0 + lane * K;                  // 0-based first column of this lane
+        int tc[K], Hp[K], Fp[K];
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            tc[c] = jc + c < L ? (int)t[jc + c] : 4;
+            Hp[c] = 0;
+            Fp[c] = MAP_NEG;
+        }
+        int hdiag = 0, last_h = 0, last_e = MAP_NEG;
+        const int steps = n + 63;
+        for (int s = 0; s < steps; ++s) {
+            int in_h = __shfl_up(last_h, 1), in_e = __shfl_up(last_e, 1);
+            const int i = s - lane + 1;                // 1-based query row
+            const bool active = i >= 1 && i <= n;
+            if (lane == 0) {
+                in_h = 0;
+                in_e = MAP_NEG;
+                if (j0 > 0 && active) { in_h = bH[i]; in_e = bE[i]; }
+            }
+            if (active) {
+                int qc = strand ? (int)q[n - i] : (int)q[i - 1];
+                if (strand && qc < 4) qc = 3 - qc;
+                int hl = in_h, el = in_e, hd = hdiag;
+#pragma unroll
+                for (int c = 0; c < K; ++c) {
+                    const int e0 = el - sc.ge, e1 = hl - open;
+                    const int e = e0 > e1 ? e0 : e1;
+                    const int f0 = Fp[c] - sc.ge, f1 = Hp[c] - open;
+                    const int f = f0 > f1 ? f0 : f1;
+                    const int sub = ((qc | tc[c]) & 4) ? -sc.amb : (qc == tc[c] ? sc.match : -sc.mis);
+                    const int d = hd + sub;
+                    int h = d > 0 ? d : 0;
+                    const int g = e > f ? e : f;
+                    h = h > g ? h : g;
+                    const bool real = more || jc + c < L;
+                    if (TRACE) {
+                        if (real) {
+                            const int from = h == 0 ? 0 : (h == d ? 1 : (h == e ? 2 : 3));
+                            dir[(size_t)(i - 1) * L + (jc + c)] = (uint8_t)(from | (e == e1 ? 4 : 0) | (f == f1 ? 8 : 0));
+                        }
+                    }
+                    if (real) {
+                        const unsigned long long key = ((unsigned long long)(unsigned)h << 32) |
+                                                       ((unsigned long long)(65535 - i) << 16) | (unsigned long long)(65535 - (jc + c + 1));
+                        if (h > 0 && key > best) best = key;
+                    }
+                    hd = Hp[c];
+                    Hp[c] = h;
+                    Fp[c] = f;
+                    hl = h;
+                    el = e;
+                }
+                hdiag = in_h;
+                last_h = hl;
+                last_e = el;
+                if (more && lane == 63) { bH[i] = hl; bE[i] = el; }
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned long long o = __shfl_xor(best, off);
+        if (o > best) best = o;
+    }
+    return best;
+}
+
+// waves of a score workgroup: four, fewer when every wave needs a stripe hand-off column in LDS and the rows are wide
+inline int map_score_waves(int W, int Lmax)
+{
+    if (Lmax <= 64 * xb::map_cols_per_lane(Lmax)) return 4;
+    const int fit = 32768 / (8 * (W + 1));
+    return fit < 1 ? 1 : (fit > 4 ? 4 : fit);
+}
+inline size_t map_bnd_ints(int W, int Lmax) { return Lmax <= 64 * xb::map_cols_per_lane(Lmax) ? 0 : 2 * (size_t)(W + 1); }
+inline size_t map_row_bytes(int W) { return ((size_t)W + 15) & ~(size_t)15; }
+
+template <int K>
+__global__ __launch_bounds__(256) void map_score_kernel(const MapParams p, const int bnd_ints)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t map_smem[];
+    uint8_t *tl = map_smem;                                             // MAP_CHUNK_BYTES template codes
+    uint8_t *q = tl + xb::MAP_CHUNK_BYTES;                              // the read's codes
+    int *part = reinterpret_cast<int *>(q + (((size_t)p.W + 15) & ~(size_t)15));   // a record per wave
+    int *bnd = part + 4 * xb::MAP_PARTIAL_INTS;
+    const int r = blockIdx.x, chunk = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = blockDim.x >> 6;
+    const int t0 = p.chunk_first[chunk], t1 = p.chunk_first[chunk + 1];
+    const int base = p.toff[t0], bytes = p.toff[t1] - base;
+    for (int k = tid; k < bytes; k += blockDim.x) tl[k] = p.tcodes[base + k];
+    int n = p.seq_len[r];
+    n = n < 0 ? 0 : (n > p.W ? p.W : n);
+    for (int k = tid; k < n; k += blockDim.x) q[k] = (uint8_t)map_code(p.seq[(size_t)r * p.W + k]);
+    __syncthreads();
+    const MapScoring sc = {p.match, p.mismatch, p.gap_open, p.gap_extend, p.ambiguous};
+    MapBest mine = {0, -1, 0, 0, 0, 0};
+    if (n > 0) {
+        for (int item = wave; item < 2 * (t1 - t0); item += waves) {
+            const int t = t0 + (item >> 1), s = item & 1;
+            const int off = p.toff[t] - base, L = p.toff[t + 1] - p.toff[t];
+            if (L < 1) continue;
+            const unsigned long long key = map_pair<K, false>(q, n, s, tl + off, L, sc, bnd + (size_t)wave * bnd_ints, nullptr, lane);
+            const MapBest x = {(int)(key >> 32), t, s, 65535 - (int)((key >> 16) & 0xffff), 65535 - (int)(key & 0xffff), 0};
+            map_merge(mine, x);
+        }
+    }
+    if (lane == 0) {
+        int *o = part + wave * xb::MAP_PARTIAL_INTS;
+        o[0] = mine.score; o[1] = mine.t; o[2] = mine.s; o[3] = mine.i; o[4] = mine.j; o[5] = mine.sec;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        MapBest all = {0, -1, 0, 0, 0, 0};
+        for (int w = 0; w < waves; ++w) {
+            const int *o = part + w * xb::MAP_PARTIAL_INTS;
+            const MapBest x = {o[0], o[1], o[2], o[3], o[4], o[5]};
+            map_merge(all, x);
+        }
+        int32_t *g = p.partial + ((size_t)r * p.nchunks + chunk) * xb::MAP_PARTIAL_INTS;
+        g[0] = all.score; g[1] = all.t; g[2] = all.s; g[3] = all.i; g[4] = all.j; g[5] = all.sec;
+    }
+}
+
+// LDS of a trace workgroup: the read's codes, the template's codes, the ops written backwards, the stripe hand-off column,
+// and the direction bytes when they fit
+constexpr size_t MAP_TRACE_LDS = 64 * 1024;
+inline size_t map_trace_fixed_bytes(int W, int Lmax)
+{
+    return map_row_bytes(W) + map_row_bytes(Lmax) + map_row_bytes(W + Lmax) + 4 * map_bnd_ints(W, Lmax);
+}
+
+template <int K>
+__global__ __launch_bounds__(64) void map_trace_kernel(const MapParams p, const int dir_in_lds)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t map_smem[];
+    const size_t wq = ((size_t)p.W + 15) & ~(size_t)15, wt = ((size_t)p.Lmax + 15) & ~(size_t)15;
+    const int cap = p.W + p.Lmax;
+    const size_t wo = ((size_t)cap + 15) & ~(size_t)15;
+    uint8_t *q = map_smem, *tl = q + wq, *rev = tl + wt;
+    int *bnd = reinterpret_cast<int *>(rev + wo);
+    const size_t bnd_ints = p.Lmax <= 64 * K ? 0 : 2 * (size_t)(p.W + 1);
+    uint8_t *dir = dir_in_lds ? reinterpret_cast<uint8_t *>(bnd + bnd_ints)
+                              : p.scratch + (size_t)blockIdx.x * (size_t)p.W * (size_t)p.Lmax;
+    const int lane = threadIdx.x;
+    const MapScoring sc = {p.match, p.mismatch, p.gap_open, p.gap_extend, p.ambiguous};
+    for (int r = blockIdx.x; r < p.n; r += gridDim.x) {
+        MapBest win = {0, -1, 0, 0, 0, 0};
+        for (int c = 0; c < p.nchunks; ++c) {
+            const int32_t *g = p.partial + ((size_t)r * p.nchunks + c) * xb::MAP_PARTIAL_INTS;
+            const MapBest x = {g[0], g[1], g[2], g[3], g[4], g[5]};
+            map_merge(win, x);
+        }
+        uint8_t *ops = p.ops + (size_t)r * cap;
+        if (win.score <= 0) {
+            if (lane == 0) {
+                p.tmpl[r] = -1; p.strand[r] = 0; p.score[r] = 0; p.second[r] = 0;
+                p.q_st[r] = 0; p.q_en[r] = 0; p.r_st[r] = 0; p.r_en[r] = 0; p.n_ops[r] = 0;
+            }
+            for (int k = lane; k < cap; k += 64) ops[k] = 0;
+            continue;
+        }
+        int n = p.seq_len[r];
+        n = n > p.W ? p.W : n;
+        const int tb = p.toff[win.t], L = p.toff[win.t + 1] - tb;
+        __syncthreads();                               // the previous read's walk is over
+        for (int k = lane; k < n; k += 64) q[k] = (uint8_t)map_code(p.seq[(size_t)r * p.W + k]);
+        for (int k = lane; k < L; k += 64) tl[k] = p.tcodes[tb + k];
+        __syncthreads();
+        (void)map_pair<K, true>(q, n, win.s, tl, L, sc, bnd, dir, lane);
+        __syncthreads();
+        int n_ops = 0;
+        if (lane == 0) {
+            int i = win.i, j = win.j, state = 0, at = cap;
+            while (i > 0 && j > 0) {
+                const int d = dir[(size_t)(i - 1) * L + (j - 1)];
+                if (state == 0) {
+                    const int from = d & 3;
+                    if (from == 0) break;
+                    if (from == 1) {
+                        int qc = win.s ? (int)q[n - i] : (int)q[i - 1];
+                        if (win.s && qc < 4) qc = 3 - qc;
+                        rev[--at] = (qc < 4 && qc == (int)tl[j - 1]) ? '=' : 'X';
+                        --i;
+                        --j;
+                    } else {
+                        state = from == 2 ? 1 : 2;
+                    }
+                } else if (state == 1) {
+                    rev[--at] = 'D';
+                    state = (d & 4) ? 0 : 1;
+                    --j;
+                } else {
+                    rev[--at] = 'I';
+                    state = (d & 8) ? 0 : 2;
+                    --i;
+                }
+            }
+            n_ops = cap - at;
+            p.tmpl[r] = win.t; p.strand[r] = win.s ? -1 : 1; p.score[r] = win.score; p.second[r] = win.sec;
+            p.q_st[r] = i; p.q_en[r] = win.i; p.r_st[r] = j; p.r_en[r] = win.j; p.n_ops[r] = n_ops;
+        }
+        n_ops = __shfl(n_ops, 0);
+        __syncthreads();
+        for (int k = lane; k < cap; k += 64) ops[k] = k < n_ops ? rev[cap - n_ops + k] : (uint8_t)0;
+    }
+}
+
+}  // namespace
+
+namespace xb {
+
+bool map_trace_in_lds(int W, int Lmax)
+{
+    return map_trace_fixed_bytes(W, Lmax) + (size_t)W * (size_t)Lmax <= MAP_TRACE_LDS;
+}
+
+hipError_t launch_map_score(const MapParams &p, hipStream_t stream)
+{
+    const int waves = map_score_waves(p.W, p.Lmax);
+    const int bnd_ints = (int)map_bnd_ints(p.W, p.Lmax);
+    const size_t lds = MAP_CHUNK_BYTES + map_row_bytes(p.W) + 4 * MAP_PARTIAL_INTS * sizeof(int) + (size_t)waves * bnd_ints * sizeof(int);
+    const dim3 grid(p.n, p.nchunks), block(64 * waves);
+    switch (map_cols_per_lane(p.Lmax)) {
+    case 1: hipLaunchKernelGGL(map_score_kernel<1>, grid, block, lds, stream, p, bnd_ints); break;
+    case 2: hipLaunchKernelGGL(map_score_kernel<2>, grid, block, lds, stream, p, bnd_ints); break;
+    default: hipLaunchKernelGGL(map_score_kernel<4>, grid, block, lds, stream, p, bnd_ints); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_map_trace(const MapParams &p, hipStream_t stream)
+{
+    const int in_lds = map_trace_in_lds(p.W, p.Lmax) ? 1 : 0;
+    const size_t lds = map_trace_fixed_bytes(p.W, p.Lmax) + (in_lds ? (size_t)p.W * (size_t)p.Lmax : 0);
+    const dim3 grid(p.trace_wgs), block(64);
+    switch (map_cols_per_lane(p.Lmax)) {
+    case 1: hipLaunchKernelGGL(map_trace_kernel<1>, grid, block, lds, stream, p, in_lds); break;
+    case 2: hipLaunchKernelGGL(map_trace_kernel<2>, grid, block, lds, stream, p, in_lds); break;
+    default: hipLaunchKernelGGL(map_trace_kernel<4>, grid, block, lds, stream, p, in_lds); break;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace xb

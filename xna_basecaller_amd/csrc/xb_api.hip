@@ -189,6 +189,16 @@ struct xb_ctx {
     int8_t *fseq = nullptr;                     // (cap, T) / (cap) results of a fused pair before they are split
     int32_t *flen = nullptr;
 
+    // template mapper (xb_map_templates): the library last passed in (host copy and its device image: codes, offsets, the
+    // chunks of the score pass) and buffers that grow with the calls -- the score pass's records, the trace pass's direction
+    // scratch, the staging of the host-pointer form.  Owned here, freed by xb_ctx_destroy.
+    struct MapState {
+        std::vector<char> lib;
+        std::vector<int32_t> off;
+        int Lmax = 0, nchunks = 0;
+        DevBuf image, partial, scratch, staging;
+    } map;
+
     bool profiling = false;
     std::vector<StageEvent> events;
     float stage_ms[XB_STAGE_COUNT] = {};
@@ -1050,6 +1060,8 @@ XB_API void xb_ctx_destroy(xb_ctx *ctx)
     for (auto &ev : ctx->events) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto &b : ctx->bufs) (void)hipFree(b.p);
     for (auto &b : ctx->wsbufs) (void)hipFree(b.p);
+    for (DevBuf *b : {&ctx->map.image, &ctx->map.partial, &ctx->map.scratch, &ctx->map.staging})
+        if (b->p) (void)hipFree(b->p);
     for (void *w : ctx->wbufs) (void)hipFree(w);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -1922,6 +1934,182 @@ XB_API int xb_collect_chunks_q(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_
 XB_API int xb_collect_chunks(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len)
 {
     return collect_chunks(ctx, slot, 0, {{seq, seq_len, nullptr, nullptr, nullptr}});
+}
+
+// ---- template mapper (xb_map_templates) -----------------------------------------------------------------------------
+namespace {
+
+// Cells (query row x template column, both strands) one call may ask for, counted with every row as wide as W:
+// 2 n W sum(L).  The score pass runs 6.8e11 cells a second on an MI355X (profiles/map_time.txt: 1024 templates of 89 against
+// 4096 reads in 106 ms), so the bound keeps a call under a fifth of a second of device time.  The library itself is bounded
+// too: beyond a megabyte of templates (the 2.7 MB CPLX full-length library) exhaustive alignment is the wrong tool and a
+// seeding stage would be needed.
+constexpr double MAP_CELL_BUDGET = 1.2e11;
+constexpr size_t MAP_MAX_LIBRARY = (size_t)1 << 20;
+constexpr size_t MAP_MAX_SCRATCH = (size_t)256 << 20;
+
+int map_grow(xb_ctx *ctx, DevBuf *b, size_t bytes)
+{
+    if (bytes <= b->bytes) return XB_OK;
+    XB_HIP(ctx, hipStreamSynchronize(ctx->stream));                     // nothing in flight reads the old buffer
+    if (b->p) (void)hipFree(b->p);
+    b->p = nullptr;
+    b->bytes = 0;
+    bytes = (bytes + 255) & ~(size_t)255;
+    hipError_t e = hipMalloc(&b->p, bytes);
+    if (e != hipSuccess) return fail(ctx, XB_ERR_NOMEM, "hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+    b->bytes = bytes;
+    return XB_OK;
+}
+
+struct MapOut {
+    int32_t *tmpl; int8_t *strand; int32_t *score, *second, *q_st, *q_en, *r_st, *r_en; uint8_t *ops; int32_t *n_ops;
+};
+
+// validation, the library's device image, the two launches: seq, seq_len and o are device pointers
+int map_run(xb_ctx *ctx, const int8_t *d_seq, const int32_t *d_len, int n, int W, const char *templates, const int32_t *offsets,
+            int R, const int sc[5], const MapOut &o)
+{
+    if (n < 1 || W < 1 || W > xb::MAP_MAX_ROW)
+        return fail(ctx, XB_ERR_INVALID, "xb_map_templates: n = %d rows of width %d; need n >= 1 and 1 <= W <= %d", n, W, xb::MAP_MAX_ROW);
+    if (!templates || !offsets || R < 1 || offsets[0] != 0) return fail(ctx, XB_ERR_INVALID, "xb_map_templates: empty template library");
+    for (int k = 0; k < 5; ++k)
+        if (sc[k] < 0 || sc[k] > 1000) return fail(ctx, XB_ERR_INVALID, "xb_map_templates: scoring values must lie in [0, 1000]");
+    int Lmax = 0;
+    for (int t = 0; t < R; ++t) {
+        const int L = offsets[t + 1] - offsets[t];
+        if (L < 1 || L > xb::MAP_MAX_TEMPLATE)
+            return fail(ctx, XB_ERR_INVALID, "xb_map_templates: template %d has %d letters; 1 .. %d are supported", t, L, xb::MAP_MAX_TEMPLATE);
+        Lmax = std::max(Lmax, L);
+    }
+    const size_t total = (size_t)offsets[R];
+    const double cells = 2.0 * n * W * (double)total;
+    if (total > MAP_MAX_LIBRARY || cells > MAP_CELL_BUDGET)
+        return fail(ctx, XB_ERR_INVALID, "xb_map_templates: a library of %d templates, %zu letters, against %d rows of width %d is %.3g "
+                    "cells; one call takes at most %.3g cells and a library of %zu letters (larger libraries need a seeding stage)",
+                    R, total, n, W, cells, MAP_CELL_BUDGET, MAP_MAX_LIBRARY);
+    xb_ctx::MapState &m = ctx->map;
+    const bool same = m.image.p && m.lib.size() == total && (int)m.off.size() == R + 1 &&
+                      !memcmp(m.lib.data(), templates, total) && !memcmp(m.off.data(), offsets, sizeof(int32_t) * (R + 1));
+    if (!same) {
+        std::vector<uint8_t> codes(total);
+        for (size_t k = 0; k < total; ++k) {
+            switch (templates[k]) {
+            case 'A': case 'a': codes[k] = 0; break;
+            case 'C': case 'c': codes[k] = 1; break;
+            case 'G': case 'g': codes[k] = 2; break;
+            case 'T': case 't': codes[k] = 3; break;
+            default: codes[k] = 4;
+            }
+        }
+        std::vector<int32_t> chunks{0};
+        for (int t = 0, used = 0; t < R; ++t) {
+            const int L = offsets[t + 1] - offsets[t];
+            if (used + L > xb::MAP_CHUNK_BYTES) { chunks.push_back(t); used = 0; }
+            used += L;
+        }
+        chunks.push_back(R);
+        const size_t a_off = (total + 15) & ~(size_t)15, a_chunk = a_off + sizeof(int32_t) * (R + 1);
+        m.lib.clear();                                                  // no image while it is being replaced
+        if (int rc = map_grow(ctx, &m.image, a_chunk + sizeof(int32_t) * chunks.size())) return rc;
+        XB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        uint8_t *img = static_cast<uint8_t *>(m.image.p);
+        XB_HIP(ctx, hipMemcpy(img, codes.data(), total, hipMemcpyHostToDevice));
+        XB_HIP(ctx, hipMemcpy(img + a_off, offsets, sizeof(int32_t) * (R + 1), hipMemcpyHostToDevice));
+        XB_HIP(ctx, hipMemcpy(img + a_chunk, chunks.data(), sizeof(int32_t) * chunks.size(), hipMemcpyHostToDevice));
+        m.lib.assign(templates, templates + total);
+        m.off.assign(offsets, offsets + R + 1);
+        m.Lmax = Lmax;
+        m.nchunks = (int)chunks.size() - 1;
+    }
+    xb::MapParams p{};
+    p.seq = d_seq; p.seq_len = d_len; p.n = n; p.W = W;
+    const size_t a_off = (total + 15) & ~(size_t)15;
+    uint8_t *img = static_cast<uint8_t *>(m.image.p);
+    p.tcodes = img;
+    p.toff = reinterpret_cast<const int32_t *>(img + a_off);
+    p.chunk_first = p.toff + (R + 1);
+    p.R = R; p.Lmax = Lmax; p.nchunks = m.nchunks;
+    p.match = sc[0]; p.mismatch = sc[1]; p.gap_open = sc[2]; p.gap_extend = sc[3]; p.ambiguous = sc[4];
+    if (int rc = map_grow(ctx, &m.partial, sizeof(int32_t) * xb::MAP_PARTIAL_INTS * (size_t)n * m.nchunks)) return rc;
+    p.partial = static_cast<int32_t *>(m.partial.p);
+    p.trace_wgs = std::min(n, 2048);
+    if (!xb::map_trace_in_lds(W, Lmax)) {
+        const size_t one = (size_t)W * Lmax;
+        p.trace_wgs = (int)std::max<size_t>(1, std::min<size_t>(p.trace_wgs, MAP_MAX_SCRATCH / one));
+        if (int rc = map_grow(ctx, &m.scratch, one * p.trace_wgs)) return rc;
+        p.scratch = static_cast<uint8_t *>(m.scratch.p);
+    }
+    p.tmpl = o.tmpl; p.strand = o.strand; p.score = o.score; p.second = o.second;
+    p.q_st = o.q_st; p.q_en = o.q_en; p.r_st = o.r_st; p.r_en = o.r_en; p.ops = o.ops; p.n_ops = o.n_ops;
+    XB_HIP(ctx, xb::launch_map_score(p, ctx->stream));
+    XB_HIP(ctx, xb::launch_map_trace(p, ctx->stream));
+    return XB_OK;
+}
+
+bool map_out_complete(const MapOut &o)
+{
+    return o.tmpl && o.strand && o.score && o.second && o.q_st && o.q_en && o.r_st && o.r_en && o.ops && o.n_ops;
+}
+
+}  // namespace
+
+XB_API int xb_map_templates_dev(xb_ctx *ctx, const int8_t *d_seq, const int32_t *d_seq_len, int n, int W, const char *templates,
+                                const int32_t *offsets, int R, int match, int mismatch, int gap_open, int gap_extend, int ambiguous,
+                                int32_t *d_tmpl, int8_t *d_strand, int32_t *d_score, int32_t *d_second, int32_t *d_q_st,
+                                int32_t *d_q_en, int32_t *d_r_st, int32_t *d_r_en, uint8_t *d_ops, int32_t *d_n_ops)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    const MapOut o = {d_tmpl, d_strand, d_score, d_second, d_q_st, d_q_en, d_r_st, d_r_en, d_ops, d_n_ops};
+    if (!d_seq || !d_seq_len || !map_out_complete(o)) return fail(ctx, XB_ERR_INVALID, "xb_map_templates: null device pointer");
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = join_async_decode(ctx)) return rc;
+    ctx->result_stream = ctx->stream;
+    const int sc[5] = {match, mismatch, gap_open, gap_extend, ambiguous};
+    return map_run(ctx, d_seq, d_seq_len, n, W, templates, offsets, R, sc, o);
+}
+
+XB_API int xb_map_templates(xb_ctx *ctx, const int8_t *seq, const int32_t *seq_len, int n, int W, const char *templates,
+                            const int32_t *offsets, int R, int match, int mismatch, int gap_open, int gap_extend, int ambiguous,
+                            int32_t *tmpl, int8_t *strand, int32_t *score, int32_t *second, int32_t *q_st, int32_t *q_en,
+                            int32_t *r_st, int32_t *r_en, uint8_t *ops, int32_t *n_ops)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    const MapOut h = {tmpl, strand, score, second, q_st, q_en, r_st, r_en, ops, n_ops};
+    if (!seq || !seq_len || !map_out_complete(h)) return fail(ctx, XB_ERR_INVALID, "xb_map_templates: null host pointer");
+    if (n < 1 || W < 1 || W > xb::MAP_MAX_ROW || !offsets || R < 1)
+        return fail(ctx, XB_ERR_INVALID, "xb_map_templates: n = %d rows of width %d, %d templates; need n >= 1, 1 <= W <= %d, R >= 1",
+                    n, W, R, xb::MAP_MAX_ROW);
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = join_async_decode(ctx)) return rc;
+    int Lmax = 0;
+    for (int t = 0; t < R; ++t) Lmax = std::max(Lmax, offsets[t + 1] - offsets[t]);
+    if (Lmax < 1 || Lmax > xb::MAP_MAX_TEMPLATE)
+        return fail(ctx, XB_ERR_INVALID, "xb_map_templates: the longest template has %d letters; 1 .. %d are supported", Lmax, xb::MAP_MAX_TEMPLATE);
+    // staging: seq | len | the eight int32 outputs | strand | ops, each 256-byte aligned
+    const size_t N = (size_t)n, cap = (size_t)W + Lmax;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_seq = al(N * W), b_i32 = al(N * 4), b_i8 = al(N), b_ops = al(N * cap);
+    if (b_seq + 9 * b_i32 + b_i8 + b_ops > ((size_t)2 << 30))
+        return fail(ctx, XB_ERR_INVALID, "xb_map_templates: %d rows of width %d in one call; split the batch", n, W);
+    if (int rc = map_grow(ctx, &ctx->map.staging, b_seq + 9 * b_i32 + b_i8 + b_ops)) return rc;
+    uint8_t *base = static_cast<uint8_t *>(ctx->map.staging.p);
+    int8_t *d_seq = reinterpret_cast<int8_t *>(base);
+    int32_t *d_i32[9];
+    for (int k = 0; k < 9; ++k) d_i32[k] = reinterpret_cast<int32_t *>(base + b_seq + k * b_i32);
+    int8_t *d_strand = reinterpret_cast<int8_t *>(base + b_seq + 9 * b_i32);
+    uint8_t *d_ops = reinterpret_cast<uint8_t *>(d_strand) + b_i8;
+    XB_HIP(ctx, hipMemcpyAsync(d_seq, seq, N * W, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(d_i32[0], seq_len, N * 4, hipMemcpyHostToDevice, ctx->stream));
+    const MapOut d = {d_i32[1], d_strand, d_i32[2], d_i32[3], d_i32[4], d_i32[5], d_i32[6], d_i32[7], d_ops, d_i32[8]};
+    const int sc[5] = {match, mismatch, gap_open, gap_extend, ambiguous};
+    if (int rc = map_run(ctx, d_seq, d_i32[0], n, W, templates, offsets, R, sc, d)) return rc;
+    int32_t *const h_i32[8] = {tmpl, score, second, q_st, q_en, r_st, r_en, n_ops};
+    for (int k = 0; k < 8; ++k)
+        XB_HIP(ctx, hipMemcpyAsync(h_i32[k], d_i32[k + 1], N * 4, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(strand, d_strand, N, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(ops, d_ops, N * cap, hipMemcpyDeviceToHost, ctx->stream));
+    return xb_synchronize(ctx);
 }
 
 XB_API int xb_set_profiling(xb_ctx *ctx, int on)

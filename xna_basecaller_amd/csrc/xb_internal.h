@@ -206,6 +206,35 @@ int lstm_resident_per_cu(int F, int nsplit, int dual);
 int lstm_members(int F);
 int lstm_group_chunks();
 bool lstm_supported_features(int F);
+// ---------------------------------------------------------------- template mapper (xb_align.hip)
+// xb_map_templates: every called row against every template of a small library on both strands (the contract is in the
+// public header).  Letters travel as codes: A C G T = 0..3, everything else 4.
+constexpr int MAP_MAX_TEMPLATE = 4096;      // longest template
+constexpr int MAP_MAX_ROW = 4096;           // widest row of called sequences
+constexpr int MAP_CHUNK_BYTES = 16384;      // template codes one score workgroup stages in LDS (whole templates only)
+constexpr int MAP_PARTIAL_INTS = 6;         // score, template, strand (0 +, 1 -), end row i, end column j (1-based), second
+struct MapParams {
+    const int8_t *seq;           // (n, W) ASCII rows, left-packed
+    const int32_t *seq_len;      // (n)
+    int n, W;
+    const uint8_t *tcodes;       // the templates' codes, concatenated
+    const int32_t *toff;         // (R + 1) offsets into tcodes
+    const int32_t *chunk_first;  // (nchunks + 1) first template of every chunk of at most MAP_CHUNK_BYTES codes
+    int R, Lmax, nchunks;
+    int match, mismatch, gap_open, gap_extend, ambiguous;
+    int32_t *partial;            // (n, nchunks, MAP_PARTIAL_INTS): what the score pass leaves, all it writes
+    int32_t *tmpl, *score, *second, *q_st, *q_en, *r_st, *r_en, *n_ops;   // (n)
+    int8_t *strand;              // (n) +1 / -1, 0 unmapped
+    uint8_t *ops;                // (n, W + Lmax)
+    uint8_t *scratch;            // direction bytes of the trace pass when a pair does not fit LDS: trace_wgs x W x Lmax
+    int trace_wgs;               // workgroups of the trace pass (each walks reads blockIdx.x, + trace_wgs, ..)
+};
+// columns per lane of a stripe (1, 2 or 4) for a library whose longest template is Lmax
+inline int map_cols_per_lane(int Lmax) { return Lmax <= 64 ? 1 : (Lmax <= 128 ? 2 : 4); }
+bool map_trace_in_lds(int W, int Lmax);     // the direction bytes of one pair fit the trace workgroup's LDS
+hipError_t launch_map_score(const MapParams &p, hipStream_t stream);
+hipError_t launch_map_trace(const MapParams &p, hipStream_t stream);
+
 #ifdef XB_LSTM_STAMPS
 void lstm_read_stamps(unsigned long long out[10], bool reset);   // diagnostic build only
 void gemm_read_stamps(unsigned long long out[8], bool reset);    // diagnostic build only (XB_GEMM_STAMPS)

@@ -11,7 +11,8 @@ Written from the OUTPUT FORMAT the reference produces (ub-bonito/bonito/io.py), 
     header text as it is and each record as its own line; pysam is in no image, so the text is written directly.  The
     reference's header also carries `@PG ID:aligner PN:minimap2 VN:<mappy version>` whether or not anything is aligned; here
     that line is written only when an aligner version is given (none exists: mappy is in no image), so an unaligned file does
-    not claim an aligner.  `.bam` / `.cram` need htslib and aligned records need mappy: refused;
+    not claim an aligner; with `--reference` the line names this package's own mapper (PN:xnacall-map, aligner.py), never
+    minimap2, and the records are aligned ones.  `.bam` / `.cram` need htslib: refused;
   * a FASTQ record is  "@<read_id> <tag>\\t<tag>...\\n<sequence>\\n+\\n<qstring>\\n"  (io.py:76-84) with the tags
     RG:Z:<run_id>_<model>  qs:i:<rounded mean q>  mx:i  ch:i  st:Z  rn:i  f5:Z  (io.py:412-419, fast5.py:118-128);
   * the summary is `<stdout stem>_summary.tsv` (`summary.tsv` on a tty or a pipe; io.py:148-155), tab separated with the
@@ -34,6 +35,12 @@ Format = namedtuple("Format", "aligned name mode")
 
 SUMMARY_COLUMNS = ("filename", "read_id", "run_id", "channel", "mux", "start_time", "duration", "template_start",
                    "template_duration", "sequence_length_template", "mean_qscore_template")
+# the columns an aligner adds (io.py:170-187)
+ALIGNMENT_COLUMNS = ("alignment_genome", "alignment_genome_start", "alignment_genome_end", "alignment_strand_start",
+                     "alignment_strand_end", "alignment_direction", "alignment_length", "alignment_num_aligned",
+                     "alignment_num_correct", "alignment_num_insertions", "alignment_num_deletions",
+                     "alignment_num_substitutions", "alignment_mapq", "alignment_strand_coverage", "alignment_identity",
+                     "alignment_accuracy")
 _MODES = {"fq": ("fastq", "wfq"), "fastq": ("fastq", "wfq"), "sam": ("sam", "w"), "bam": ("bam", "wb"),
           "cram": ("cram", "wc")}
 
@@ -73,16 +80,19 @@ def write_fasta(header, sequence, fd=sys.stdout):
 SAM_SPEC = "0.0.1"          # the reference's __ont_bam_spec__ (io.py:27)
 
 
-def sam_header(groups, sep="\t", version=None, argv=None, aligner_version=None):
+ALIGNER_NAME = "xnacall-map"    # the @PG PN of this package's template mapper (aligner.py); it is not minimap2
+
+
+def sam_header(groups, sep="\t", version=None, argv=None, aligner_version=None, aligner_name="minimap2", aligner_ds="mappy"):
     """The SAM header text (io.py:87-112): @HD, @PG of the basecaller (PN:bonito -- the drop-in's program name -- with `version`
-    and the command line `argv`), optionally the aligner's @PG, then the read-group lines; lines joined by os.linesep, one
-    trailing newline."""
+    and the command line `argv`), optionally the aligner's @PG (the reference's names by default; the Writer passes this
+    package's mapper), then the read-group lines; lines joined by os.linesep, one trailing newline."""
     from . import __version__
     lines = [sep.join(["@HD", "VN:1.5", "SO:unknown", "ob:%s" % SAM_SPEC]),
              sep.join(["@PG", "ID:basecaller", "PN:bonito", "VN:%s" % (__version__ if version is None else version),
                        "CL:bonito %s" % " ".join(sys.argv[1:] if argv is None else argv)])]
     if aligner_version is not None:
-        lines.append(sep.join(["@PG", "ID:aligner", "PN:minimap2", "VN:%s" % aligner_version, "DS:mappy"]))
+        lines.append(sep.join(["@PG", "ID:aligner", "PN:%s" % aligner_name, "VN:%s" % aligner_version, "DS:%s" % aligner_ds]))
     return "%s\n" % os.linesep.join(lines + list(groups))
 
 
@@ -105,7 +115,7 @@ def sam_record(read_id, sequence, qstring, mapping=None, tags=None, sep="\t"):
     a mappy.Alignment-shaped object (ctg, r_st, q_st, q_en, strand, mapq, cigar_str, NM, MD): flag 0 / 16, 1-based position,
     the CIGAR wrapped in the soft clips of the unaligned query ends (swapped on the reverse strand), the sequence reverse
     complemented on the reverse strand -- and the quality string left as it is, as the reference does.  The formatting is pinned
-    by tests/golden/sam.json; producing a mapping needs mappy (`--reference`), which is in no image."""
+    by tests/golden/sam.json; `--reference` produces the mapping with this package's template mapper (aligner.Mapping)."""
     if mapping:
         tail = len(sequence) - mapping.q_en
         softclip = ["%sS" % mapping.q_st if mapping.q_st else "", mapping.cigar_str, "%sS" % tail if tail else ""]
@@ -165,23 +175,53 @@ class SummaryTable:
         self.close()
 
 
-def summary_row(read, seqlen, qscore):
-    values = (read.filename, read.read_id, read.run_id, read.channel, read.mux, read.start, read.duration,
-              read.template_start, read.template_duration, seqlen, qscore)
-    return dict(zip(SUMMARY_COLUMNS, values))
+def summary_row(read, seqlen, qscore, alignment=False):
+    """One summary row (io.py:190-237).  alignment False: the eleven read columns.  A mapping: the reference's sixteen
+    alignment columns with its arithmetic; None (an aligner ran, nothing aligned): its empty alignment row."""
+    values = [read.filename, read.read_id, read.run_id, read.channel, read.mux, read.start, read.duration,
+              read.template_start, read.template_duration, seqlen, qscore]
+    if alignment:
+        ins = sum(count for count, op in alignment.cigar if op == 1)
+        dels = sum(count for count, op in alignment.cigar if op == 2)
+        subs = alignment.NM - ins - dels
+        length = alignment.blen
+        matches = length - ins - dels
+        correct = alignment.mlen
+        forward = alignment.strand == +1
+        values += [alignment.ctg, alignment.r_st, alignment.r_en,
+                   alignment.q_st if forward else seqlen - alignment.q_en,
+                   alignment.q_en if forward else seqlen - alignment.q_st,
+                   "+" if forward else "-", length, matches, correct, ins, dels, subs, alignment.mapq,
+                   (alignment.q_en - alignment.q_st) / seqlen, correct / matches, correct / length]
+    elif alignment is None:
+        values += ["*", -1, -1, -1, -1, "*", 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0]
+    return dict(zip(SUMMARY_COLUMNS + ALIGNMENT_COLUMNS, values))
+
+
+def write_paf(fd, read_id, seqlen, mapping):
+    """One PAF line of a mapping: the twelve columns (query coordinates on the call as it was made) and the tags tp:A:P,
+    s1:i:<score>, s2:i:<best other template's score>, cs:Z:<short cs>.  Nothing for an unmapped read, as minimap2."""
+    if not mapping:
+        return
+    fields = [read_id, seqlen, mapping.q_st, mapping.q_en, "+" if mapping.strand == +1 else "-", mapping.ctg, mapping.ctg_len,
+              mapping.r_st, mapping.r_en, mapping.mlen, mapping.blen, mapping.mapq, "tp:A:P", "s1:i:%d" % mapping.score,
+              "s2:i:%d" % mapping.second, "cs:Z:%s" % mapping.cs]
+    fd.write("\t".join(map(str, fields)) + "\n")
 
 
 class Writer(Thread):
-    """Drains the (read, result) iterator on its own thread: FASTQ (mode 'wfq') or unaligned SAM text (mode 'w', header first)
-    to `fd`, a summary row and a log entry per read."""
+    """Drains the (read, result) iterator on its own thread: FASTQ (mode 'wfq') or SAM text (mode 'w', header first) to `fd`, a
+    summary row and a log entry per read.  With an `aligner` (aligner.TemplateAligner; the results then carry 'mapping') the
+    SAM records are aligned ones, the header names this package's mapper, the summary gains the alignment columns and `paf`
+    (a text file object) receives a PAF line per mapped read.  Without one nothing changes."""
 
     def __init__(self, mode, iterator, aligner=None, fd=sys.stdout, duplex=False, ref_fn=None, groups=None,
-                 group_key=None, summary=None):
+                 group_key=None, summary=None, paf=None):
         super().__init__()
-        if mode not in ("wfq", "w") or aligner is not None or duplex:
-            raise NotImplementedError("unaligned FASTQ (mode 'wfq') and unaligned SAM text (mode 'w') are on the MI355X path; "
-                                      "BAM / CRAM need htslib, aligned records need mappy")
+        if mode not in ("wfq", "w") or duplex:
+            raise NotImplementedError("FASTQ (mode 'wfq') and SAM text (mode 'w') are on the MI355X path; BAM / CRAM need htslib")
         self.mode, self.fd, self.iterator = mode, fd, iterator
+        self.aligner, self.paf = aligner, paf
         self.group_key = group_key
         self.groups = sorted(groups) if groups else []
         self.summary = summary
@@ -203,14 +243,24 @@ class Writer(Thread):
             write_fastq(read.read_id, seq, qstring, fd=self.fd, tags=tags)
         else:
             self.fd.write(sam_record(read.read_id, seq, qstring, res.get("mapping", False), tags=tags) + "\n")
-        table.append(summary_row(read, len(seq), mean_q))
+        if self.aligner is None:
+            table.append(summary_row(read, len(seq), mean_q))
+        else:
+            table.append(summary_row(read, len(seq), mean_q, alignment=res.get("mapping")))
+            if self.paf is not None:
+                write_paf(self.paf, read.read_id, len(seq), res.get("mapping"))
         self.log.append((read.read_id, len(read.signal)))
 
     def run(self):
         try:
-            with SummaryTable(self.summary or summary_file()) as table:
-                if self.mode == "w":
+            columns = SUMMARY_COLUMNS if self.aligner is None else SUMMARY_COLUMNS + ALIGNMENT_COLUMNS
+            with SummaryTable(self.summary or summary_file(), columns) as table:
+                if self.mode == "w" and self.aligner is None:
                     self.fd.write(sam_header(self.groups))
+                elif self.mode == "w":
+                    from . import __version__
+                    self.fd.write(sam_header(self.groups, aligner_version=__version__, aligner_name=ALIGNER_NAME,
+                                             aligner_ds="exhaustive template alignment on the device"))
                 for read, res in self.iterator:
                     self._emit(table, read, res)
         except BaseException as e:  # surfaced by the CLI after join()
