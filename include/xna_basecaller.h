@@ -418,6 +418,43 @@ XB_API int xb_map_templates_dev(xb_ctx *ctx, const int8_t *d_seq, const int32_t 
                                 int32_t *d_tmpl, int8_t *d_strand, int32_t *d_score, int32_t *d_second, int32_t *d_q_st,
                                 int32_t *d_q_en, int32_t *d_r_st, int32_t *d_r_en, uint8_t *d_ops, int32_t *d_n_ops);
 
+/* ---- DTW signal segmentation of ctc-data (an extension of the device path: `segment`) --------------------------------
+ * The reference's src/tools/dtw_segmentation.py aligns every training chunk to the expected current levels of its reference
+ * sequence with dtw-python (dtw(chunk, reference, step_pattern=my_asymmetric, window_type='slantedband'), :128-202) on the
+ * host.  dtw-python is in no image, so there is nothing to pin it to: PARITY UNPINNED; the contract below is this library's
+ * own restatement of that call and the kernel is bit-exact against a CPU restatement of it (tests/dtw_ref.py).
+ *   problem    per chunk the query q[0..N) (the chunk's samples, converted exactly to float64) and the reference r[0..M),
+ *              M = ref_rep * K: the chunk's K levels, each held for ref_rep consecutive columns (the kernel repeats them).
+ *   cost       d(i, j) = |q[i] - r[j]| in float64.
+ *   steps      every sample matches exactly one column and no column is skipped: g(0, 0) = d(0, 0);
+ *              g(i, j) = d(i, j) + min(g(i-1, j), g(i-1, j-1)) -- ONE float64 addition per cell, in that order, no contraction;
+ *              a cell with no finite predecessor is unreachable (+infinity), and so is g(0, j > 0).
+ *   TIES       go to the stay step (i-1, j): the diagonal (i-1, j-1) replaces it only when it is STRICTLY smaller.  This is
+ *              this library's statement of dtw-python's loop (pattern 1 first); with ref_rep > 1 neighbouring columns carry
+ *              equal levels, so the rule decides real breakpoints.
+ *   band       window[c] >= 0: cell (i, j) is allowed iff |j - i * M / N| <= window[c], evaluated in float64 as written (i * M
+ *              exact, one division, one subtraction); the callers pass (N / K) * window_size (:160-161).  window[c] < 0, or
+ *              window == NULL: every cell is allowed.  A cell that is not allowed is unreachable.
+ *   end        (N-1, M-1).  Unreachable (always when M > N; possible under a narrow band): the chunk FAILS -- ok = 0,
+ *              cost = +infinity, and the breakpoints are the naive ones of :186-191: N / K samples per base, the first N % K
+ *              bases one more.
+ *   trace      back from (N-1, M-1) along the recorded choices to (0, 0); reps[k] = the samples whose column j has
+ *              j / ref_rep == k; breakpoints = cumsum(reps): breakpoints[K-1] == N, every base gets at least ref_rep samples.
+ * Arguments: signal (n, N) fp32; levels: the chunks' float64 levels concatenated, BEFORE repetition; offsets (n + 1) int32 into
+ * them (offsets[0] = 0), a HOST pointer in both forms (the library sizes its launches from it); window (n) float64 or NULL.
+ * Outputs per chunk: breakpoints (n, Kmax) int32, zero-filled behind the chunk's K; ok (n) int8; cost (n) float64 = g(N-1, M-1).
+ * Limits: 1 <= N <= 65535 (breakpoints.npy is uint16), 1 <= K, ref_rep * K <= 65535, Kmax >= every K (XB_ERR_INVALID with the
+ * figures otherwise; the context stays usable).  One wave per chunk; a bit per feasible cell goes to a scratch buffer the
+ * context owns, and a call is split into launches whose scratch stays under XB_DTW_SCRATCH_MB (default 1024) megabytes.
+ * The _dev form returns without waiting (xb_synchronize).  xb_dtw_scratch_bytes: the choice-bit bytes the last call's
+ * launches wrote, summed over its chunks (a measurement aid).
+ */
+XB_API int xb_dtw_segment(xb_ctx *ctx, const float *signal, int n, int N, const double *levels, const int32_t *offsets, int ref_rep,
+                          const double *window, int Kmax, int32_t *breakpoints, int8_t *ok, double *cost);
+XB_API int xb_dtw_segment_dev(xb_ctx *ctx, const float *d_signal, int n, int N, const double *d_levels, const int32_t *offsets,
+                              int ref_rep, const double *d_window, int Kmax, int32_t *d_breakpoints, int8_t *d_ok, double *d_cost);
+XB_API int64_t xb_dtw_scratch_bytes(const xb_ctx *ctx);
+
 /* ---- introspection / measurement ---------------------------------------------------------- */
 
 enum { XB_STAGE_CONV = 0, XB_STAGE_LSTM_IN = 1, XB_STAGE_LSTM_REC = 2, XB_STAGE_LINEAR = 3,

@@ -1,9 +1,10 @@
 """`python -m xna_basecaller_amd basecaller MODEL_DIR READS_DIR ...` == `bonito basecaller ...`, and `... evaluate MODEL_DIR
---directory CTC_DATA` == `bonito evaluate ...` (bonito/__init__.py:10-33)."""
+--directory CTC_DATA` == `bonito evaluate ...` (bonito/__init__.py:10-33); `... segment CTC_DATA` == the reference's
+`src/tools/dtw_segmentation.py CTC_DATA`."""
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 
 from . import __version__
-from .cli import basecaller, evaluate
+from .cli import basecaller, evaluate, segment
 
 
 def main():
@@ -16,6 +17,8 @@ def main():
     p.set_defaults(func=basecaller.main)
     p = sub.add_parser("evaluate", parents=[evaluate.argparser()])
     p.set_defaults(func=evaluate.main)
+    p = sub.add_parser("segment", parents=[segment.argparser()])
+    p.set_defaults(func=segment.main)
     args = parser.parse_args()
     args.func(args)
 

@@ -31,6 +31,7 @@ EXPORTS = [
     "xb_decode_q", "xb_decode_q_dev", "xb_basecall_chunks_q", "xb_submit_chunks_q", "xb_collect_chunks_q",
     "xb_decode_ub", "xb_decode_ub_dev", "xb_basecall_chunks_ub", "xb_submit_chunks_ub", "xb_collect_chunks_ub",
     "xb_map_templates", "xb_map_templates_dev",
+    "xb_dtw_segment", "xb_dtw_segment_dev", "xb_dtw_scratch_bytes",
 ]
 XB_COMM_ID_BYTES = 128
 # xb_status (include/xna_basecaller.h)
@@ -123,6 +124,10 @@ def load():
     lib.xb_collect_chunks_ub.argtypes = [vp, ip, vp, vp, vp, vp, vp]
     lib.xb_map_templates.argtypes = [vp, vp, vp, ip, ip, C.c_char_p, vp, ip] + [ip] * 5 + [vp] * 10
     lib.xb_map_templates_dev.argtypes = lib.xb_map_templates.argtypes
+    lib.xb_dtw_segment.argtypes = [vp, vp, ip, ip, vp, vp, ip, vp, ip, vp, vp, vp]
+    lib.xb_dtw_segment_dev.argtypes = lib.xb_dtw_segment.argtypes
+    lib.xb_dtw_scratch_bytes.argtypes = [vp]
+    lib.xb_dtw_scratch_bytes.restype = C.c_int64
     lib.xb_result_stream.argtypes = [vp]
     lib.xb_result_stream.restype = C.c_void_p
     lib.xb_set_profiling.argtypes = [vp, ip]
@@ -488,6 +493,44 @@ class Context:
         self._check(self.lib.xb_map_templates_dev(self.h, _ptr(d_seq), _ptr(d_seq_len), int(n), int(W), bytes(templates),
                                                   off.ctypes.data, off.size - 1, *[int(v) for v in scoring],
                                                   *[_ptr(d_out[k]) for k, _ in self.MAP_OUTPUTS]))
+
+    # ---- DTW signal segmentation (xb_dtw_segment): an extension, parity unpinned ----------
+    @staticmethod
+    def _dtw_offsets(levels):
+        """A list of per-chunk level arrays -> (their float64 concatenation, int32 offsets (n + 1))."""
+        off = np.zeros(len(levels) + 1, np.int32)
+        off[1:] = np.cumsum([len(v) for v in levels])
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(v, np.float64).ravel() for v in levels]) if len(levels) else [],
+                                    dtype=np.float64)
+        return flat, off
+
+    def dtw_segment(self, signal, levels, ref_rep=3, window=None, kmax=None):
+        """xb_dtw_segment: signal (n, N) fp32 and per chunk its float64 levels (a list of arrays, before repetition) ->
+        (breakpoints (n, kmax) int32 zero-filled behind each chunk's levels, ok (n,) bool, cost (n,) float64).  window: None
+        or (n,) float64 half-widths of the slanted band in columns, negative = none."""
+        signal = np.ascontiguousarray(signal, dtype=np.float32)
+        n, N = signal.shape
+        flat, off = self._dtw_offsets(levels)
+        if len(levels) != n:
+            raise ValueError("dtw_segment: %d chunks, %d level arrays" % (n, len(levels)))
+        kmax = int(kmax if kmax is not None else max(1, int(np.diff(off).max()) if n else 1))
+        win = None if window is None else np.ascontiguousarray(window, dtype=np.float64).reshape(n)
+        bp = np.empty((n, kmax), np.int32)
+        ok = np.empty((n,), np.int8)
+        cost = np.empty((n,), np.float64)
+        self._check(self.lib.xb_dtw_segment(self.h, signal.ctypes.data, n, N, flat.ctypes.data, off.ctypes.data, int(ref_rep),
+                                            _ptr(win), kmax, bp.ctypes.data, ok.ctypes.data, cost.ctypes.data))
+        return bp, ok.astype(bool), cost
+
+    def dtw_segment_dev(self, d_signal, n, N, d_levels, offsets, ref_rep, d_window, kmax, d_breakpoints, d_ok, d_cost):
+        """xb_dtw_segment_dev: device pointers but for `offsets` (host, (n + 1) int32); returns without waiting."""
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        self._check(self.lib.xb_dtw_segment_dev(self.h, _ptr(d_signal), int(n), int(N), _ptr(d_levels), off.ctypes.data, int(ref_rep),
+                                                _ptr(d_window), int(kmax), _ptr(d_breakpoints), _ptr(d_ok), _ptr(d_cost)))
+
+    def dtw_scratch_bytes(self):
+        """Choice-bit bytes the launches of the last dtw_segment call wrote (xb_dtw_scratch_bytes)."""
+        return int(self.lib.xb_dtw_scratch_bytes(self.h))
 
     # ---- host pipeline: two batches in flight (xb_submit_chunks / xb_collect_chunks) ----------
     def submit_chunks(self, slot, signal, alphabet, qscale=1.0, qoffset=0.0, level=0):

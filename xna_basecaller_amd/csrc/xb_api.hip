@@ -199,6 +199,20 @@ struct xb_ctx {
         DevBuf image, partial, scratch, staging;
     } map;
 
+    // DTW segmentation (xb_dtw_segment): the choice-bit scratch of the launches in flight, the staging of the host-pointer
+    // form, and the chunks' level offsets on their way to the device -- two pinned slots in rotation, so that a call returns
+    // without waiting for its own device work.  Owned here, freed by xb_ctx_destroy.
+    struct DtwState {
+        DevBuf scratch, staging;
+        struct Slot {
+            int32_t *h = nullptr, *d = nullptr;
+            size_t count = 0;
+            hipEvent_t copied = nullptr;
+        } off[2];
+        unsigned calls = 0;
+        size_t scratch_written = 0;                 // bytes of choice words the last call's launches were sized for
+    } dtw;
+
     bool profiling = false;
     std::vector<StageEvent> events;
     float stage_ms[XB_STAGE_COUNT] = {};
@@ -1060,8 +1074,13 @@ XB_API void xb_ctx_destroy(xb_ctx *ctx)
     for (auto &ev : ctx->events) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto &b : ctx->bufs) (void)hipFree(b.p);
     for (auto &b : ctx->wsbufs) (void)hipFree(b.p);
-    for (DevBuf *b : {&ctx->map.image, &ctx->map.partial, &ctx->map.scratch, &ctx->map.staging})
+    for (DevBuf *b : {&ctx->map.image, &ctx->map.partial, &ctx->map.scratch, &ctx->map.staging, &ctx->dtw.scratch, &ctx->dtw.staging})
         if (b->p) (void)hipFree(b->p);
+    for (auto &o : ctx->dtw.off) {
+        if (o.h) (void)hipHostFree(o.h);
+        if (o.d) (void)hipFree(o.d);
+        if (o.copied) (void)hipEventDestroy(o.copied);
+    }
     for (void *w : ctx->wbufs) (void)hipFree(w);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -2111,6 +2130,138 @@ XB_API int xb_map_templates(xb_ctx *ctx, const int8_t *seq, const int32_t *seq_l
     XB_HIP(ctx, hipMemcpyAsync(ops, d_ops, N * cap, hipMemcpyDeviceToHost, ctx->stream));
     return xb_synchronize(ctx);
 }
+
+// ---- DTW signal segmentation (xb_dtw_segment) -------------------------------------------------------------------------
+namespace {
+
+// Choice-bit scratch one launch may own (XB_DTW_SCRATCH_MB, default 1024): a call is split into launches of as many chunks
+// as fit, one chunk when a single chunk needs more (at most 136 MB: 65535 samples against 32768 columns).  A full-size chunk
+// (3600 samples, 1200 columns) takes 488 KB, so the default holds 2201 chunks -- two waves on each of the 1024 SIMDs.
+size_t dtw_scratch_bound()
+{
+    long mb = 1024;
+    if (const char *e = getenv("XB_DTW_SCRATCH_MB")) mb = atol(e);
+    if (mb < 1) mb = 1;
+    if (mb > 65536) mb = 65536;
+    return (size_t)mb << 20;
+}
+
+struct DtwOut {
+    int32_t *bp; int8_t *ok; double *cost;
+};
+
+// validation, the offsets' device copy, the launches: signal, levels, window and o are device pointers, offsets is host
+int dtw_run(xb_ctx *ctx, const float *d_signal, int n, int N, const double *d_levels, const int32_t *offsets, int ref_rep,
+            const double *d_window, bool band, int Kmax, const DtwOut &o)
+{
+    if (n < 1 || N < 1 || N > xb::DTW_MAX_SAMPLES || ref_rep < 1 || ref_rep > xb::DTW_MAX_COLUMNS)
+        return fail(ctx, XB_ERR_INVALID, "xb_dtw_segment: n = %d chunks of %d samples, ref_rep = %d; need n >= 1, 1 <= N <= %d, "
+                    "1 <= ref_rep <= %d", n, N, ref_rep, xb::DTW_MAX_SAMPLES, xb::DTW_MAX_COLUMNS);
+    if (!offsets || offsets[0] != 0) return fail(ctx, XB_ERR_INVALID, "xb_dtw_segment: offsets must start at 0");
+    int Kbig = 0;
+    for (int c = 0; c < n; ++c) {
+        const int K = offsets[c + 1] - offsets[c];
+        if (K < 1 || (int64_t)K * ref_rep > xb::DTW_MAX_COLUMNS)
+            return fail(ctx, XB_ERR_INVALID, "xb_dtw_segment: chunk %d has %d levels, %lld columns at ref_rep = %d; 1 level .. %d "
+                        "columns are supported", c, K, (long long)K * ref_rep, ref_rep, xb::DTW_MAX_COLUMNS);
+        Kbig = std::max(Kbig, K);
+    }
+    if (Kmax < Kbig)
+        return fail(ctx, XB_ERR_INVALID, "xb_dtw_segment: breakpoint rows of %d entries, the longest chunk has %d levels", Kmax, Kbig);
+    const int cols = xb::dtw_cols_per_lane(Kbig * ref_rep);
+    size_t choice = 0;
+    for (int c = 0; c < n; ++c) choice = std::max(choice, xb::dtw_choice_words(N, (offsets[c + 1] - offsets[c]) * ref_rep, cols));
+    const size_t slot_words = choice + 2 * (size_t)N;
+    const size_t per_launch = std::max<size_t>(1, std::min<size_t>((size_t)n, dtw_scratch_bound() / (slot_words * 8)));
+    xb_ctx::DtwState &s = ctx->dtw;
+    if (int rc = map_grow(ctx, &s.scratch, per_launch * slot_words * 8)) return rc;
+    // the offsets: pinned slot (calls & 1), free again once the copy of two calls ago has run
+    xb_ctx::DtwState::Slot &slot = s.off[s.calls++ & 1];
+    if (slot.copied) XB_HIP(ctx, hipEventSynchronize(slot.copied));
+    else XB_HIP(ctx, hipEventCreateWithFlags(&slot.copied, hipEventDisableTiming));
+    if (slot.count < (size_t)n + 1) {
+        XB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (slot.h) (void)hipHostFree(slot.h);
+        if (slot.d) (void)hipFree(slot.d);
+        slot.h = slot.d = nullptr;
+        slot.count = 0;
+        const size_t count = ((size_t)n + 1 + 1023) & ~(size_t)1023;
+        XB_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&slot.h), count * sizeof(int32_t), hipHostMallocDefault));
+        XB_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&slot.d), count * sizeof(int32_t)));
+        slot.count = count;
+    }
+    memcpy(slot.h, offsets, sizeof(int32_t) * ((size_t)n + 1));
+    XB_HIP(ctx, hipMemcpyAsync(slot.d, slot.h, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipEventRecord(slot.copied, ctx->stream));
+    xb::DtwParams p{};
+    p.signal = d_signal; p.levels = d_levels; p.off = slot.d; p.window = band ? d_window : nullptr;
+    p.N = N; p.rep = ref_rep; p.Kmax = Kmax;
+    p.scratch = static_cast<unsigned long long *>(s.scratch.p);
+    p.choice_words = choice; p.slot_words = slot_words;
+    p.bp = o.bp; p.ok = o.ok; p.cost = o.cost;
+    s.scratch_written = 0;
+    for (int c = 0; c < n; ++c) s.scratch_written += 8 * xb::dtw_choice_words(N, (offsets[c + 1] - offsets[c]) * ref_rep, cols);
+    for (size_t first = 0; first < (size_t)n; first += per_launch) {
+        p.first = (int)first;
+        p.count = (int)std::min<size_t>(per_launch, (size_t)n - first);
+        XB_HIP(ctx, xb::launch_dtw(p, cols, band, ctx->stream));
+    }
+    return XB_OK;
+}
+
+}  // namespace
+
+XB_API int xb_dtw_segment_dev(xb_ctx *ctx, const float *d_signal, int n, int N, const double *d_levels, const int32_t *offsets,
+                              int ref_rep, const double *d_window, int Kmax, int32_t *d_breakpoints, int8_t *d_ok, double *d_cost)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    if (!d_signal || !d_levels || !d_breakpoints || !d_ok || !d_cost) return fail(ctx, XB_ERR_INVALID, "xb_dtw_segment: null device pointer");
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = join_async_decode(ctx)) return rc;
+    ctx->result_stream = ctx->stream;
+    return dtw_run(ctx, d_signal, n, N, d_levels, offsets, ref_rep, d_window, d_window != nullptr, Kmax, {d_breakpoints, d_ok, d_cost});
+}
+
+XB_API int xb_dtw_segment(xb_ctx *ctx, const float *signal, int n, int N, const double *levels, const int32_t *offsets, int ref_rep,
+                          const double *window, int Kmax, int32_t *breakpoints, int8_t *ok, double *cost)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    if (!signal || !levels || !breakpoints || !ok || !cost) return fail(ctx, XB_ERR_INVALID, "xb_dtw_segment: null host pointer");
+    if (n < 1 || N < 1 || N > xb::DTW_MAX_SAMPLES || !offsets || offsets[0] != 0 || Kmax < 1 || Kmax > xb::DTW_MAX_COLUMNS)
+        return fail(ctx, XB_ERR_INVALID, "xb_dtw_segment: n = %d chunks of %d samples, breakpoint rows of %d entries; need n >= 1, "
+                    "1 <= N <= %d, offsets from 0 with a level or more per chunk, 1 <= Kmax <= %d", n, N, Kmax, xb::DTW_MAX_SAMPLES,
+                    xb::DTW_MAX_COLUMNS);
+    for (int c = 0; c < n; ++c)
+        if (offsets[c + 1] <= offsets[c]) return fail(ctx, XB_ERR_INVALID, "xb_dtw_segment: chunk %d has %d levels; at least one is needed",
+                                                      c, offsets[c + 1] - offsets[c]);
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = join_async_decode(ctx)) return rc;
+    bool band = false;
+    for (int c = 0; window && c < n; ++c) band = band || window[c] >= 0.0;
+    // staging: signal | levels | window | cost | breakpoints | ok, each 256-byte aligned
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t C = (size_t)n, total = (size_t)offsets[n];
+    const size_t b_sig = al(C * N * 4), b_lev = al(total * 8), b_f64 = al(C * 8), b_bp = al(C * Kmax * 4), b_ok = al(C);
+    if (b_sig + b_lev + 2 * b_f64 + b_bp + b_ok > ((size_t)2 << 30))
+        return fail(ctx, XB_ERR_INVALID, "xb_dtw_segment: %d chunks of %d samples in one call; split the batch", n, N);
+    if (int rc = map_grow(ctx, &ctx->dtw.staging, b_sig + b_lev + 2 * b_f64 + b_bp + b_ok)) return rc;
+    uint8_t *base = static_cast<uint8_t *>(ctx->dtw.staging.p);
+    float *d_sig = reinterpret_cast<float *>(base);
+    double *d_lev = reinterpret_cast<double *>(base + b_sig);
+    double *d_win = reinterpret_cast<double *>(base + b_sig + b_lev), *d_cost = d_win + b_f64 / 8;
+    int32_t *d_bp = reinterpret_cast<int32_t *>(base + b_sig + b_lev + 2 * b_f64);
+    int8_t *d_ok = reinterpret_cast<int8_t *>(d_bp) + b_bp;
+    XB_HIP(ctx, hipMemcpyAsync(d_sig, signal, C * N * 4, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(d_lev, levels, total * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (band) XB_HIP(ctx, hipMemcpyAsync(d_win, window, C * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = dtw_run(ctx, d_sig, n, N, d_lev, offsets, ref_rep, d_win, band, Kmax, {d_bp, d_ok, d_cost})) return rc;
+    XB_HIP(ctx, hipMemcpyAsync(breakpoints, d_bp, C * Kmax * 4, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(ok, d_ok, C, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(cost, d_cost, C * 8, hipMemcpyDeviceToHost, ctx->stream));
+    return xb_synchronize(ctx);
+}
+
+XB_API int64_t xb_dtw_scratch_bytes(const xb_ctx *ctx) { return ctx ? (int64_t)ctx->dtw.scratch_written : 0; }
 
 XB_API int xb_set_profiling(xb_ctx *ctx, int on)
 {

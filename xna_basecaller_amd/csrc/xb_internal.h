@@ -235,6 +235,36 @@ bool map_trace_in_lds(int W, int Lmax);     // the direction bytes of one pair f
 hipError_t launch_map_score(const MapParams &p, hipStream_t stream);
 hipError_t launch_map_trace(const MapParams &p, hipStream_t stream);
 
+// ---------------------------------------------------------------- DTW signal segmentation (xb_dtw.hip)
+// xb_dtw_segment: every signal chunk against the expected levels of its reference by dynamic time warping (the contract is
+// in the public header).  One wave per chunk; the columns lie across the lanes, cols consecutive columns per lane, in
+// stripes of 64 * cols columns.
+constexpr int DTW_MAX_SAMPLES = 65535;      // samples per chunk (breakpoints.npy is uint16)
+constexpr int DTW_MAX_COLUMNS = 65535;      // ref_rep * levels of one chunk
+struct DtwParams {
+    const float *signal;         // (n, N) fp32
+    const double *levels;        // the chunks' levels, concatenated, before repetition
+    const int32_t *off;          // (n + 1) offsets into levels
+    const double *window;        // (n) half-width of the slanted band in columns, negative = none
+    int N, rep, Kmax;
+    int first, count;            // this launch serves chunks first .. first + count - 1, workgroup b chunk first + b
+    unsigned long long *scratch; // count slots of slot_words 8-byte words: choice words, then two hand-off columns of N doubles
+    size_t choice_words, slot_words;
+    int32_t *bp;                 // (n, Kmax)
+    int8_t *ok;                  // (n)
+    double *cost;                // (n)
+};
+// columns per lane (1, 2 or 4) for a call whose widest chunk has Mmax columns
+inline int dtw_cols_per_lane(int Mmax) { return Mmax <= 64 ? 1 : (Mmax <= 128 ? 2 : 4); }
+// 8-byte choice words per stripe / per chunk of N samples and M <= N columns at `cols` columns per lane: a bit per cell of
+// the rows a stripe can reach, in batches of 64 rows
+constexpr size_t dtw_stripe_words(int N, int M, int cols) { return (size_t)((N - M + 64 * cols + 63) & ~63) * cols; }
+constexpr size_t dtw_choice_words(int N, int M, int cols)
+{
+    return M > N ? 0 : (size_t)((M + 64 * cols - 1) / (64 * cols)) * dtw_stripe_words(N, M, cols);
+}
+hipError_t launch_dtw(const DtwParams &p, int cols, bool band, hipStream_t stream);
+
 #ifdef XB_LSTM_STAMPS
 void lstm_read_stamps(unsigned long long out[10], bool reset);   // diagnostic build only
 void gemm_read_stamps(unsigned long long out[8], bool reset);    // diagnostic build only (XB_GEMM_STAMPS)
