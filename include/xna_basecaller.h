@@ -418,6 +418,57 @@ XB_API int xb_map_templates_dev(xb_ctx *ctx, const int8_t *d_seq, const int32_t 
                                 int32_t *d_tmpl, int8_t *d_strand, int32_t *d_score, int32_t *d_second, int32_t *d_q_st,
                                 int32_t *d_q_en, int32_t *d_r_st, int32_t *d_r_en, uint8_t *d_ops, int32_t *d_n_ops);
 
+/* ---- ctc-data labels of mapped rows (`basecaller --save-ctc`) -------------------------------------------------------------
+ * The reference's CTCWriter (bonito/io.py:448-585) decides per chunk, on the host and from a minimap2 mapping, whether the chunk
+ * becomes training data, and cuts its label row from the reference.  Here the mapping is xb_map_templates' (above), so there
+ * is nothing to pin the whole to: PARITY UNPINNED; the contract below restates io.py:495-540 over the mapper's outputs and the
+ * kernel is bit-exact against a CPU restatement of it (tests/savectc_ref.py).
+ *   inputs     per row seq_len (clamped to [0, W] as the mapper clamps it) and the mapper's tmpl, strand, q_st, q_en, r_st, r_en,
+ *              ops (n, W + Lmax), n_ops; the library as xb_map_templates takes it (HOST pointers; the context's cached device
+ *              image is reused).  n_ops is clamped to [0, W + Lmax], r_st / r_en to 0 <= r_st <= r_en <= the template's length.
+ *   mlen       the number of '=' bytes among the row's first n_ops columns; blen = n_ops.  Written for every row.
+ *   verdict    one byte, 0 = the chunk is kept:
+ *                bit 0 FAILED_SEQ      seq_len == 0
+ *                bit 1 FAILED_MAP      tmpl < 0 (or not below R); the mapper leaves an empty row unmapped, so such a row carries
+ *                                      bits 0 and 1, as the reference counts both.  With bit 0 or 1 nothing else is looked at.
+ *                bit 2 SKIPPED_NON_UB  ub_only != 0 and template[r_st:r_en] holds no letter outside ACGTacgt; nothing else is
+ *                                      looked at (io.py:508-510 continues before the thresholds)
+ *                bit 3 FAILED_ACC      (double)mlen / (double)blen < min_accuracy (blen == 0, which the mapper never reports for a
+ *                                      mapped row, fails too)
+ *                bit 4 FAILED_COV      (double)(q_en - q_st) / (double)seq_len < min_coverage
+ *              Bits 3 and 4 may be set together.  Both quotients are IEEE float64, one correctly rounded division each, compared
+ *              as Python compares them: 19 / 20 against 0.95 decides on the device as it does in the reference.
+ *   target     for a row of verdict 0: template[r_st:r_en], on strand -1 reversed with A <-> T and C <-> G (any other letter
+ *              stays), then A C G T (either case) -> 1 2 3 4 and EVERY other byte -> ub_plus on strand +1, ub_minus on strand -1
+ *              (the reference maps 'N' alone, to its X = 5 and Y = 6; every non-ACGT byte is treated as it treats 'N' -- the
+ *              mapper's own letter contract).  target is (n, TW) uint8 with TW = Lmax rounded up to a multiple of 16, 16-byte
+ *              aligned, zero-filled behind target_len; target_len = r_en - r_st.  Rows of any other verdict: all zeros, length 0.
+ * ub_plus and ub_minus lie in 1 .. 255; the thresholds must not be NaN.  One launch on the main stream, one wavefront per row;
+ * not a stage of xb_get_stage_times (nor is the mapper).  The _dev form takes device pointers for the rows and the outputs and
+ * returns without waiting (xb_synchronize).
+ * xb_ctc_chunks is the fused form for the Viterbi decode: signal (n, chunk_len) fp32 on the HOST -> the basecall
+ * (xb_basecall_chunks_dev), the mapper over its left-packed device rows (W = the model's time steps T, in as many launches as the
+ * mapper's cell budget asks for) and the labels, on device buffers with one synchronisation at the end; it returns seq (n, T),
+ * seq_len, every output of xb_map_templates and the five above, exactly what the three host-form calls return one after the
+ * other.
+ */
+XB_API int xb_ctc_targets(xb_ctx *ctx, const int32_t *seq_len, int n, int W, const char *templates, const int32_t *offsets, int R,
+                          const int32_t *tmpl, const int8_t *strand, const int32_t *q_st, const int32_t *q_en, const int32_t *r_st,
+                          const int32_t *r_en, const uint8_t *ops, const int32_t *n_ops, double min_accuracy, double min_coverage,
+                          int ub_only, int ub_plus, int ub_minus, int32_t *mlen, int32_t *blen, uint8_t *verdict, uint8_t *target,
+                          int32_t *target_len);
+XB_API int xb_ctc_targets_dev(xb_ctx *ctx, const int32_t *d_seq_len, int n, int W, const char *templates, const int32_t *offsets,
+                              int R, const int32_t *d_tmpl, const int8_t *d_strand, const int32_t *d_q_st, const int32_t *d_q_en,
+                              const int32_t *d_r_st, const int32_t *d_r_en, const uint8_t *d_ops, const int32_t *d_n_ops,
+                              double min_accuracy, double min_coverage, int ub_only, int ub_plus, int ub_minus, int32_t *d_mlen,
+                              int32_t *d_blen, uint8_t *d_verdict, uint8_t *d_target, int32_t *d_target_len);
+XB_API int xb_ctc_chunks(xb_ctx *ctx, const float *signal, int n, const char *alphabet, const char *templates, const int32_t *offsets,
+                         int R, int match, int mismatch, int gap_open, int gap_extend, int ambiguous, double min_accuracy,
+                         double min_coverage, int ub_only, int ub_plus, int ub_minus, int8_t *seq, int32_t *seq_len, int32_t *tmpl,
+                         int8_t *strand, int32_t *score, int32_t *second, int32_t *q_st, int32_t *q_en, int32_t *r_st, int32_t *r_en,
+                         uint8_t *ops, int32_t *n_ops, int32_t *mlen, int32_t *blen, uint8_t *verdict, uint8_t *target,
+                         int32_t *target_len);
+
 /* ---- DTW signal segmentation of ctc-data (an extension of the device path: `segment`) --------------------------------
  * The reference's src/tools/dtw_segmentation.py aligns every training chunk to the expected current levels of its reference
  * sequence with dtw-python (dtw(chunk, reference, step_pattern=my_asymmetric, window_type='slantedband'), :128-202) on the

@@ -30,7 +30,7 @@ EXPORTS = [
     "xb_beam_search", "xb_beam_search_dev", "xb_basecall_chunks_beam", "xb_reserve_pairing", "xb_pairing_active", "xb_debug_layer_output",
     "xb_decode_q", "xb_decode_q_dev", "xb_basecall_chunks_q", "xb_submit_chunks_q", "xb_collect_chunks_q",
     "xb_decode_ub", "xb_decode_ub_dev", "xb_basecall_chunks_ub", "xb_submit_chunks_ub", "xb_collect_chunks_ub",
-    "xb_map_templates", "xb_map_templates_dev",
+    "xb_map_templates", "xb_map_templates_dev", "xb_ctc_targets", "xb_ctc_targets_dev", "xb_ctc_chunks",
     "xb_dtw_segment", "xb_dtw_segment_dev", "xb_dtw_scratch_bytes",
 ]
 XB_COMM_ID_BYTES = 128
@@ -124,6 +124,10 @@ def load():
     lib.xb_collect_chunks_ub.argtypes = [vp, ip, vp, vp, vp, vp, vp]
     lib.xb_map_templates.argtypes = [vp, vp, vp, ip, ip, C.c_char_p, vp, ip] + [ip] * 5 + [vp] * 10
     lib.xb_map_templates_dev.argtypes = lib.xb_map_templates.argtypes
+    db = C.c_double
+    lib.xb_ctc_targets.argtypes = [vp, vp, ip, ip, C.c_char_p, vp, ip] + [vp] * 8 + [db, db, ip, ip, ip] + [vp] * 5
+    lib.xb_ctc_targets_dev.argtypes = lib.xb_ctc_targets.argtypes
+    lib.xb_ctc_chunks.argtypes = [vp, vp, ip, C.c_char_p, C.c_char_p, vp, ip] + [ip] * 5 + [db, db, ip, ip, ip] + [vp] * 17
     lib.xb_dtw_segment.argtypes = [vp, vp, ip, ip, vp, vp, ip, vp, ip, vp, vp, vp]
     lib.xb_dtw_segment_dev.argtypes = lib.xb_dtw_segment.argtypes
     lib.xb_dtw_scratch_bytes.argtypes = [vp]
@@ -493,6 +497,67 @@ class Context:
         self._check(self.lib.xb_map_templates_dev(self.h, _ptr(d_seq), _ptr(d_seq_len), int(n), int(W), bytes(templates),
                                                   off.ctypes.data, off.size - 1, *[int(v) for v in scoring],
                                                   *[_ptr(d_out[k]) for k, _ in self.MAP_OUTPUTS]))
+
+    # ---- ctc-data labels of mapped rows (xb_ctc_targets, xb_ctc_chunks): parity unpinned ----------
+    CTC_INPUTS = ("tmpl", "strand", "q_st", "q_en", "r_st", "r_en", "ops", "n_ops")
+    CTC_OUTPUTS = (("mlen", np.int32), ("blen", np.int32), ("verdict", np.uint8), ("target", np.uint8), ("target_len", np.int32))
+    FAILED_SEQ, FAILED_MAP, SKIPPED_NON_UB, FAILED_ACC, FAILED_COV = 1, 2, 4, 8, 16      # the bits of verdict
+
+    @staticmethod
+    def ctc_target_width(offsets):
+        """Bytes per label row: the longest template rounded up to a multiple of 16."""
+        return -(-int(np.diff(np.asarray(offsets)).max()) // 16) * 16
+
+    def _ctc_out(self, n, offsets):
+        tw = self.ctc_target_width(offsets)
+        return {k: np.empty((n, tw) if k == "target" else (n,), dtype=dt) for k, dt in self.CTC_OUTPUTS}
+
+    def ctc_targets(self, seq_len, width, mapped, templates, offsets, min_accuracy=0.95, min_coverage=0.90, ub_only=False,
+                    ub_plus=5, ub_minus=6):
+        """xb_ctc_targets: seq_len (n) and the mapper's outputs `mapped` (map_templates' dict, rows of `width`) -> dict of mlen,
+        blen, verdict (n), target (n, TW) uint8 zero-filled behind target_len, target_len (CTC_OUTPUTS)."""
+        lens = np.ascontiguousarray(seq_len, dtype=np.int32)
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        n = lens.shape[0]
+        dts = dict(self.MAP_OUTPUTS)
+        ins = [np.ascontiguousarray(mapped[k], dtype=dts[k]) for k in self.CTC_INPUTS]
+        if ins[6].shape != (n, int(width) + int(np.diff(off).max())):
+            raise ValueError("ctc_targets: ops is %s, (n, width + longest template) expected" % (ins[6].shape,))
+        out = self._ctc_out(n, off)
+        self._check(self.lib.xb_ctc_targets(self.h, lens.ctypes.data, n, int(width), bytes(templates), off.ctypes.data, off.size - 1,
+                                            *[a.ctypes.data for a in ins], float(min_accuracy), float(min_coverage),
+                                            int(bool(ub_only)), int(ub_plus), int(ub_minus),
+                                            *[out[k].ctypes.data for k, _ in self.CTC_OUTPUTS]))
+        return out
+
+    def ctc_targets_dev(self, d_seq_len, n, width, d_mapped, templates, offsets, d_out, min_accuracy=0.95, min_coverage=0.90,
+                        ub_only=False, ub_plus=5, ub_minus=6):
+        """xb_ctc_targets_dev: device pointers for seq_len, the mapper's outputs (d_mapped: name -> pointer, CTC_INPUTS) and the
+        outputs (d_out: name -> pointer, CTC_OUTPUTS; target 16-byte aligned); returns without waiting."""
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        self._check(self.lib.xb_ctc_targets_dev(self.h, _ptr(d_seq_len), int(n), int(width), bytes(templates), off.ctypes.data,
+                                                off.size - 1, *[_ptr(d_mapped[k]) for k in self.CTC_INPUTS], float(min_accuracy),
+                                                float(min_coverage), int(bool(ub_only)), int(ub_plus), int(ub_minus),
+                                                *[_ptr(d_out[k]) for k, _ in self.CTC_OUTPUTS]))
+
+    def ctc_chunks(self, signal, alphabet, templates, offsets, scoring=(2, 4, 4, 2, 1), min_accuracy=0.95, min_coverage=0.90,
+                   ub_only=False, ub_plus=5, ub_minus=6):
+        """xb_ctc_chunks: signal (n, chunk_len) -> dict of seq (n, T) int8, seq_len, every MAP_OUTPUTS array (ops (n, T + Lmax))
+        and every CTC_OUTPUTS array: the Viterbi basecall, the mapper and the labels in one device pass."""
+        signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1, self.chunk_len)
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        n = signal.shape[0]
+        lmax = int(np.diff(off).max())
+        out = {"seq": np.empty((n, self.T), np.int8), "seq_len": np.empty((n,), np.int32)}
+        out.update({k: np.empty((n, self.T + lmax) if k == "ops" else (n,), dtype=dt) for k, dt in self.MAP_OUTPUTS})
+        out.update(self._ctc_out(n, off))
+        self._check(self.lib.xb_ctc_chunks(self.h, signal.ctypes.data, n, "".join(alphabet).encode(), bytes(templates),
+                                           off.ctypes.data, off.size - 1, *[int(v) for v in scoring], float(min_accuracy),
+                                           float(min_coverage), int(bool(ub_only)), int(ub_plus), int(ub_minus),
+                                           out["seq"].ctypes.data, out["seq_len"].ctypes.data,
+                                           *[out[k].ctypes.data for k, _ in self.MAP_OUTPUTS],
+                                           *[out[k].ctypes.data for k, _ in self.CTC_OUTPUTS]))
+        return out
 
     # ---- DTW signal segmentation (xb_dtw_segment): an extension, parity unpinned ----------
     @staticmethod

@@ -169,6 +169,40 @@ class TemplateAligner:
             self._own.close()
             self._own = None
 
+    def seq(self, name, start=0, end=None):
+        """mappy's Aligner.seq: letters [start, end) of the template called `name`."""
+        return self.templates[self.names.index(name)][start:end]
+
+    def mapping(self, got, k, sequence):
+        """Row k of map_templates' outputs `got` as a Mapping of `sequence`, None when the row is unmapped."""
+        t = int(got["tmpl"][k])
+        if t < 0:
+            return None
+        return Mapping(self.names[t], self.templates[t], sequence, int(got["strand"][k]), int(got["r_st"][k]), int(got["q_st"][k]),
+                       got["ops"][k, :int(got["n_ops"][k])].tobytes(), got["score"][k], got["second"][k])
+
+    def ctc_rows(self, sequences, **rule):
+        """Host-form mapping and labelling of called strings (the beam branch of `--save-ctc`): per device call of the mapper
+        (its cell budget) a call of xb_ctc_targets over the same rows; yields (index, mapper outputs, label outputs, row) for
+        every sequence, in order.  rule: ctc_targets' thresholds and labels."""
+        sequences = list(sequences)
+        if any(len(s) > MAX_ROW for s in sequences):
+            raise ValueError("a call longer than the mapper's %d letters" % MAX_ROW)
+        at = 0
+        while at < len(sequences):
+            take = sequences[at:at + self.batch]
+            width = max(16, -(-max(len(s) for s in take) // 16) * 16)
+            fit = int(CELL_BUDGET // (2.0 * width * len(self.library)))
+            if 0 < fit < len(take):
+                take = take[:fit]
+            got = self._call(take)
+            lens = np.array([len(s) for s in take], np.int32)
+            lab = self.context().ctc_targets(lens, got["ops"].shape[1] - int(np.diff(self.offsets).max()), got, self.library,
+                                             self.offsets, **rule)
+            for k in range(len(take)):
+                yield at + k, got, lab, k
+            at += len(take)
+
     def _call(self, seqs):
         width = max(16, -(-max(len(s) for s in seqs) // 16) * 16)
         rows = np.zeros((len(seqs), width), np.int8)
@@ -194,12 +228,7 @@ class TemplateAligner:
                 take = take[:fit]
             got = self._call([sequences[i] for i in take])
             for k, i in enumerate(take):
-                t = int(got["tmpl"][k])
-                if t < 0:
-                    continue
-                out[i] = Mapping(self.names[t], self.templates[t], sequences[i], int(got["strand"][k]), int(got["r_st"][k]),
-                                 int(got["q_st"][k]), got["ops"][k, :int(got["n_ops"][k])].tobytes(), got["score"][k],
-                                 got["second"][k])
+                out[i] = self.mapping(got, k, sequences[i])
             at += len(take)
         return out
 

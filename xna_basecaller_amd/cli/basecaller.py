@@ -4,9 +4,12 @@ arguments, flags, defaults and stderr lines; FASTQ (or, redirected to `*.sam`, u
 `<stdout-stem>_summary.tsv` beside it.
 
 Differences, all outside the hot path: reads come from `*.xsig.npz` signal bundles (no HDF5/VBZ reader in
-this image, see reads.py); --modified-bases / --save-ctc are rejected (remora / CTCWriter are not on the
-north-star path); --reference FASTA maps every call to a TEMPLATE LIBRARY on the device (aligner.py: exhaustive
-alignment, this package's own contract, not minimap2) and, as in the reference, makes SAM the default output;
+this image, see reads.py); --modified-bases is rejected (remora is not on the north-star path); --save-ctc (with
+--reference) cuts every read into chunks, basecalls, maps and labels them on the device (xb_ctc_chunks) and writes a
+ctc-data directory beside stdout (io.CTCWriter) -- it refuses --revcomp, --qscores, --ub-probs, --paf, more than one rank,
+and a library with unnatural positions under a model that cannot call them; --reference FASTA maps every call to a
+TEMPLATE LIBRARY on the device (aligner.py: exhaustive alignment, this package's own contract, not minimap2) and, as in
+the reference, makes SAM the default output;
 --paf PATH (an extension) writes the mappings as PAF beside it; under torchrun (WORLD_SIZE > 1) reads are sharded over the
 ranks and gathered to rank 0 over RCCL before writing.  Extension: --qscores writes the Viterbi decode's device
 qualities (xb_decode_q) in place of the reference's placeholder 'O'; --ub-probs adds per-base probabilities of every
@@ -106,6 +109,45 @@ def ub_probs_refusal(model):
     return None
 
 
+UB_PLUS, UB_MINUS = 5, 6        # the labels `--save-ctc` gives a template's unnatural position: the reference's X and Y
+
+
+def save_ctc_refusal(args, world=1, labels=None, library=None):
+    """Why `--save-ctc` cannot run with these arguments (the message, without the "> " prefix), or None.  labels: the
+    model's alphabet when it could be read; library: the template letters (bytes) when the FASTA could be read."""
+    if not args.reference:
+        return "a reference is needed to output ctc training data"
+    for flag, name in ((args.revcomp, "--revcomp"), (args.qscores, "--qscores"), (args.ub_probs, "--ub-probs"),
+                       (args.paf, "--paf")):
+        if flag:
+            return "error: --save-ctc writes training chunks as they were called; %s does not apply to it" % name
+    if world > 1:
+        return "error: --save-ctc runs on one GPU (WORLD_SIZE is %d): the chunks' signals are not gathered across ranks" % world
+    if labels is not None and library is not None and len(labels) <= UB_MINUS and \
+            any(c not in b"ACGTacgt" for c in library):
+        return ("error: %s has letters outside A, C, G, T, which --save-ctc labels %d and %d; the model's alphabet %s has "
+                "only %d symbols" % (args.reference, UB_PLUS, UB_MINUS, "".join(labels), len(labels)))
+    return None
+
+
+def _save_ctc_early_refusal(args, world):
+    """save_ctc_refusal before anything touches the GPU, with whatever of the model's config and the FASTA can be read
+    (a missing model or reference is reported further down, where it always was)."""
+    labels = library = None
+    try:
+        from .. import toml_lite
+        from ..util import _model_dir
+        labels = toml_lite.load(os.path.join(_model_dir(args.model_directory), "config.toml"))["labels"]["labels"]
+    except (OSError, KeyError, ValueError):
+        pass
+    try:
+        from ..aligner import read_fasta
+        library = "".join(s for _, s in read_fasta(args.reference)).encode("ascii", "replace") if args.reference else None
+    except OSError:
+        pass
+    return save_ctc_refusal(args, world, labels, library)
+
+
 def reader_procs(world=1):
     """Reader workers of this rank: the reference's 8 (cli/basecaller.py:107-111) when the host has them to give -- the cores
     this process may run on, divided by the ranks that share the node (LOCAL_WORLD_SIZE under torchrun, else the world size),
@@ -127,6 +169,11 @@ def main(args):
     # initialises HIP and starts runtime threads) is only joined once the pool exists.  Under torchrun every rank only
     # ever loads its own shard of the reads.
     rank, world = xdist.env_rank_world()
+    if args.save_ctc:
+        why = _save_ctc_early_refusal(args, world)
+        if why is not None:
+            sys.stderr.write("> %s\n" % why)
+            exit(1)
     n_proc = reader_procs(world)
     reads = get_reads(args.reads_directory, n_proc=n_proc, recursive=args.recursive,
                       read_ids=column_to_set(args.read_ids), skip=args.skip, limit=args.max_reads,
@@ -154,8 +201,8 @@ def main(args):
 
     basecall = load_symbol(args.model_directory, "basecall")
 
-    if args.modified_bases or args.modified_base_model or args.save_ctc:
-        sys.stderr.write("> error: --modified-bases/--save-ctc are not part of the MI355X path\n")
+    if args.modified_bases or args.modified_base_model:
+        sys.stderr.write("> error: --modified-bases is not part of the MI355X path\n")
         exit(1)
     if args.paf and not args.reference:
         sys.stderr.write("> error: --paf writes the mappings of --reference\n")
@@ -188,6 +235,9 @@ def main(args):
     if fmt.name != "fastq" and rank == 0:
         groups = get_read_groups(args.reads_directory, args.model_directory, recursive=args.recursive,
                                  read_ids=column_to_set(args.read_ids), skip=args.skip, n_proc=n_proc)
+
+    if args.save_ctc:
+        return _save_ctc(args, model, aligner, reads, fmt, groups, n_proc)
 
     # --qscores (an extension): the Viterbi decode's device qualities instead of the reference's 'O' placeholders
     extra = {"qscores": True} if args.qscores else {}
@@ -234,6 +284,37 @@ def main(args):
         sys.stderr.write("> reads per second: %.0f (reader workers: %d)\n" % (len(writer.log) / duration, n_proc))
         sys.stderr.write("> chunks basecalled: %d x %d samples = %.3E chunk samples per second\n"
                          % (chunks, model.config["basecaller"]["chunksize"], chunks * model.config["basecaller"]["chunksize"] / duration))
+    sys.stderr.write("> done\n")
+
+
+def _save_ctc(args, model, aligner, reads, fmt, groups, n_proc):
+    """`--save-ctc` (cli/basecaller.py:116-129): every read cut into chunks of the model's chunksize, each chunk basecalled,
+    mapped and labelled on the device (crf.basecall.basecall_ctc), the kept ones written as ctc-data (io.CTCWriter)."""
+    from ..crf.basecall import basecall_ctc
+    from ..io import CTCWriter
+    from ..reads import read_chunks
+    why = save_ctc_refusal(args, 1, model.alphabet, aligner.library)
+    if why is not None:
+        sys.stderr.write("> %s\n" % why)
+        exit(1)
+    run = model.config["basecaller"]
+    chunks = (c for read in reads for c in read_chunks(read, chunksize=run["chunksize"], overlap=run["overlap"]))
+    writer_kwargs = dict(min_coverage=args.min_coverage, min_accuracy=args.min_accuracy, ub_only=args.ub_only)
+    sys.stderr.write(f"> writer_kwargs: {writer_kwargs}\n")
+    results = basecall_ctc(model, aligner, chunks, batchsize=run["batchsize"], ub_plus=UB_PLUS, ub_minus=UB_MINUS, **writer_kwargs)
+    t0 = perf_counter()
+    writer = CTCWriter(fmt.mode, results, aligner=aligner, group_key=args.model_directory, ref_fn=args.reference, groups=groups,
+                       ub_plus=UB_PLUS, ub_minus=UB_MINUS, **writer_kwargs)
+    writer.start()
+    writer.join()
+    aligner.close()
+    if writer.error is not None:
+        raise writer.error
+    duration = perf_counter() - t0
+    num_samples = sum(num_samples for read_id, num_samples in writer.log)
+    sys.stderr.write(f"> completed reads: {len(writer.log):0,d}\n")
+    sys.stderr.write("> duration: %s\n" % timedelta(seconds=np.round(duration)))
+    sys.stderr.write("> samples per second %.1E\n" % (num_samples / duration))
     sys.stderr.write("> done\n")
 
 

@@ -267,3 +267,55 @@ def basecall(model, reads, chunksize=4000, overlap=100, batchsize=32, reverse=Fa
         (read, _called(model, stitched))
         for read, stitched in results
     )
+
+
+def _chunk_batches(chunks, batchsize):
+    held = []
+    for c in chunks:
+        held.append(c)
+        if len(held) == batchsize:
+            yield held
+            held = []
+    if held:
+        yield held
+
+
+def basecall_ctc(model, aligner, chunks, batchsize=32, min_accuracy=0.95, min_coverage=0.90, ub_only=False, ub_plus=5,
+                 ub_minus=6):
+    """The device stage of `basecaller --save-ctc`: `chunks` are ReadChunks, each one whole chunk of the model's chunksize, so
+    chunking and stitching have nothing to do (util.py:172-173) and a batch is just `batchsize` signals.  Viterbi models take
+    one fused device call per batch (xb_ctc_chunks: basecall, template mapper, verdict and label row, one synchronisation);
+    beam-search models take the host-form beam call, then the host forms of the mapper and of xb_ctc_targets -- the same
+    kernel.  Batches run one at a time (the fused call is synchronous); the next batch's signals are stacked on a
+    background thread meanwhile.  Yields (chunk, {'sequence', 'qstring', 'mean_qscore', 'mapping', 'target', 'verdict'}) in
+    input order; a Mapping is built only where verdict == 0 (None elsewhere), 'target' is the label row cut to its length."""
+    rule = dict(min_accuracy=min_accuracy, min_coverage=min_coverage, ub_only=ub_only, ub_plus=ub_plus, ub_minus=ub_minus)
+    viterbi = bool(model.encoder[-1].expand_blanks)
+
+    def stacked():
+        for held in _chunk_batches(chunks, batchsize):
+            yield held, np.stack([np.asarray(c.signal, dtype=np.float32) for c in held])
+
+    for held, sig in thread_iter(stacked()):
+        if viterbi:
+            ctx = model.context(sig.shape[1], sig.shape[0])
+            model.chunks_submitted = getattr(model, "chunks_submitted", 0) + sig.shape[0]
+            out = ctx.ctc_chunks(sig, model.alphabet, aligner.library, aligner.offsets, aligner.scoring, **rule)
+            seqs = [out["seq"][k, :out["seq_len"][k]].tobytes().decode("ascii") for k in range(len(held))]
+            quals = [None] * len(held)
+            rows = ((k, out, out, k) for k in range(len(held)))
+        else:
+            res = compute_scores(model, sig[:, None, :])
+            seqs = [to_str(r) for r in res["sequence"]]
+            quals = [to_str(r) for r in res["qstring"]]
+            rows = aligner.ctc_rows(seqs, **rule)
+        for k, got, lab, j in rows:
+            seq, verdict = seqs[k], int(lab["verdict"][j])
+            qstring = "O" * len(seq) if quals[k] is None else quals[k]
+            item = {"sequence": seq, "qstring": qstring, "verdict": verdict, "mapping": None, "target": None,
+                    "mean_qscore": (40.0 if seq else 0.0) if quals[k] is None else
+                    (mean_qscore_from_qstring(qstring) if qstring else 0.0)}
+            if verdict == 0:
+                item["mapping"] = aligner.mapping(got, j, seq)
+                item["target"] = lab["target"][j, :int(lab["target_len"][j])].copy()
+            yield held[k], item

@@ -86,7 +86,7 @@ extern "C" XB_API int xb_align_accuracy(const char *ref, int ref_len, const char
 
 // ---------------------------------------------------------------------------------------------------------------------
 // xb_map_templates: exhaustive local alignment of every called row against every template, both strands (contract: the
-// public header).  Two kernels.
+// public header).  Two kernels.  xb_ctc_targets, the ctc-data verdict and label row of a mapped row, follows them.
 //
 // Score pass: grid (read, template chunk), a workgroup stages its chunk's template codes and the read's codes in LDS once,
 // its waves take the (template, strand) pairs of the chunk in turn.  One wave runs one pair as a systolic array: the
@@ -372,6 +372,115 @@ __global__ __launch_bounds__(64) void map_trace_kernel(const MapParams p, const 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// xb_ctc_targets: what `basecaller --save-ctc` decides per chunk (the reference's CTCWriter.run, io.py:495-540) from the
+// mapper's outputs: mlen, blen, the verdict byte and, for a kept row, the label row cut from the library image.  One
+// workgroup of one wave per row; every branch below depends on the row's scalars alone, so the wave never diverges.
+//   mlen      the '=' bytes among the row's n_ops alignment columns: 16 bytes per lane and load, a masked popcount per lane, one wave sum
+//   slice     template codes [r_st, r_en) staged in LDS through aligned 16-byte loads (the image is padded to 16 bytes, and an
+//             aligned block that holds one byte of a buffer lies in that byte's page), a code 4 anywhere in it noted on the way
+//   labels    16 per lane from the staged codes, reversed and complemented on strand -1, one 16-byte store each; the same loop
+//             zero-fills the row behind target_len (the whole row when the verdict is not 0)
+constexpr int CTC_LDS_BYTES = xb::MAP_MAX_TEMPLATE + 32;
+
+__device__ inline unsigned ctc_byte(const uint4 &v, int j)
+{
+    const unsigned w = j < 4 ? v.x : (j < 8 ? v.y : (j < 12 ? v.z : v.w));
+    return (w >> (8 * (j & 3))) & 0xffu;
+}
+
+// bit 7 of every byte of `w` that is '=' and whose bit in the low four of `in` is set
+__device__ inline unsigned ctc_eq_mask(unsigned w, unsigned in)
+{
+    const unsigned x = w ^ 0x3d3d3d3du;                                                  // '=' bytes become 0
+    const unsigned zero = ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u;        // exact per byte: no carry crosses
+    return zero & (((in & 1u) << 7) | ((in & 2u) << 14) | ((in & 4u) << 21) | ((in & 8u) << 28));
+}
+
+__global__ __launch_bounds__(64) void ctc_targets_kernel(const xb::CtcTargetParams p)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t codes[CTC_LDS_BYTES];
+    const int r = blockIdx.x, lane = threadIdx.x;
+    int sl = p.seq_len[r];
+    sl = sl < 0 ? 0 : (sl > p.W ? p.W : sl);
+    int nops = p.n_ops[r];
+    nops = nops < 0 ? 0 : (nops > p.cap ? p.cap : nops);
+    const int t = p.tmpl[r];
+
+    // mlen: bytes [mis, end) of the row's aligned 16-byte blocks are its columns; a count per lane, then one wave sum
+    int mlen = 0;
+    {
+        const uint8_t *rowp = p.ops + (size_t)r * p.cap;
+        const int mis = (int)(reinterpret_cast<uintptr_t>(rowp) & 15), end = mis + nops;
+        const uint4 *blk = reinterpret_cast<const uint4 *>(rowp - mis);
+        for (int k = lane * 16; k < end; k += 1024) {
+            const uint4 v = blk[k >> 4];
+            const int lo = mis > k ? mis - k : 0, hi = end - k < 16 ? end - k : 16;      // the block's bytes [lo, hi) count
+            const unsigned in = lo < hi ? ((1u << hi) - 1u) & ~((1u << lo) - 1u) : 0u;
+            mlen += __popc(ctc_eq_mask(v.x, in) | ctc_eq_mask(v.y, in >> 4) >> 1 | ctc_eq_mask(v.z, in >> 8) >> 2 |
+                           ctc_eq_mask(v.w, in >> 12) >> 3);
+        }
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) mlen += __shfl_xor(mlen, d);
+    }
+
+    int verdict = (sl == 0 ? xb::CTC_FAILED_SEQ : 0) | ((t < 0 || t >= p.R) ? xb::CTC_FAILED_MAP : 0);
+    int tl = 0, shift = 0, st = 0;
+    if (verdict == 0) {
+        const int tb = p.toff[t], L = p.toff[t + 1] - tb;
+        int r0 = p.r_st[r], r1 = p.r_en[r];
+        r0 = r0 < 0 ? 0 : (r0 > L ? L : r0);
+        r1 = r1 < r0 ? r0 : (r1 > L ? L : r1);
+        tl = r1 - r0;
+        st = p.strand[r];
+        const uint8_t *g0 = p.tcodes + tb + r0;
+        shift = (int)(reinterpret_cast<uintptr_t>(g0) & 15);
+        const uint4 *gblk = reinterpret_cast<const uint4 *>(g0 - shift);
+        bool ub = false;
+        for (int k = lane * 16; k < shift + tl; k += 1024) {
+            const uint4 v = gblk[k >> 4];
+            *reinterpret_cast<uint4 *>(codes + k) = v;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) ub = ub || (k + j >= shift && k + j < shift + tl && ctc_byte(v, j) >= 4u);
+        }
+        const bool has_ub = __ballot(ub) != 0ull;
+        if (p.ub_only && !has_ub) {
+            verdict = xb::CTC_SKIPPED_NON_UB;
+        } else {
+            // one correctly rounded float64 division each (this translation unit is built without contraction or fast-math)
+            const double acc = (double)mlen / (double)nops;
+            const double cov = (double)(p.q_en[r] - p.q_st[r]) / (double)sl;
+            if (nops == 0 || acc < p.min_accuracy) verdict |= xb::CTC_FAILED_ACC;
+            if (cov < p.min_coverage) verdict |= xb::CTC_FAILED_COV;
+        }
+    }
+    __syncthreads();                                   // the staged codes are visible to every lane
+    if (verdict != 0) tl = 0;
+    const unsigned ubl = (unsigned)(st < 0 ? p.ub_minus : p.ub_plus) & 0xffu;
+    uint8_t *row = p.target + (size_t)r * p.TW;
+    for (int k0 = lane * 16; k0 < p.TW; k0 += 1024) {
+        unsigned w[4] = {0u, 0u, 0u, 0u};
+        if (k0 < tl) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int k = k0 + j;
+                if (k < tl) {
+                    unsigned c = codes[shift + (st < 0 ? tl - 1 - k : k)];
+                    if (st < 0 && c < 4u) c = 3u - c;
+                    w[j >> 2] |= (c < 4u ? c + 1u : ubl) << (8 * (j & 3));
+                }
+            }
+        }
+        *reinterpret_cast<uint4 *>(row + k0) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    if (lane == 0) {
+        p.mlen[r] = mlen;
+        p.blen[r] = nops;
+        p.verdict[r] = (uint8_t)verdict;
+        p.target_len[r] = tl;
+    }
+}
+
 }  // namespace
 
 namespace xb {
@@ -405,6 +514,12 @@ hipError_t launch_map_trace(const MapParams &p, hipStream_t stream)
     case 2: hipLaunchKernelGGL(map_trace_kernel<2>, grid, block, lds, stream, p, in_lds); break;
     default: hipLaunchKernelGGL(map_trace_kernel<4>, grid, block, lds, stream, p, in_lds); break;
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_ctc_targets(const CtcTargetParams &p, hipStream_t stream)
+{
+    hipLaunchKernelGGL(ctc_targets_kernel, dim3(p.n), dim3(64), 0, stream, p);
     return hipGetLastError();
 }
 

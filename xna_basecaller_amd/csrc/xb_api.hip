@@ -197,6 +197,7 @@ struct xb_ctx {
         std::vector<int32_t> off;
         int Lmax = 0, nchunks = 0;
         DevBuf image, partial, scratch, staging;
+        DevBuf ctc_staging;                         // xb_ctc_targets (host form) and xb_ctc_chunks
     } map;
 
     // DTW segmentation (xb_dtw_segment): the choice-bit scratch of the launches in flight, the staging of the host-pointer
@@ -1074,7 +1075,8 @@ XB_API void xb_ctx_destroy(xb_ctx *ctx)
     for (auto &ev : ctx->events) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto &b : ctx->bufs) (void)hipFree(b.p);
     for (auto &b : ctx->wsbufs) (void)hipFree(b.p);
-    for (DevBuf *b : {&ctx->map.image, &ctx->map.partial, &ctx->map.scratch, &ctx->map.staging, &ctx->dtw.scratch, &ctx->dtw.staging})
+    for (DevBuf *b : {&ctx->map.image, &ctx->map.partial, &ctx->map.scratch, &ctx->map.staging, &ctx->map.ctc_staging, &ctx->dtw.scratch,
+                      &ctx->dtw.staging})
         if (b->p) (void)hipFree(b->p);
     for (auto &o : ctx->dtw.off) {
         if (o.h) (void)hipHostFree(o.h);
@@ -1985,14 +1987,14 @@ struct MapOut {
     int32_t *tmpl; int8_t *strand; int32_t *score, *second, *q_st, *q_en, *r_st, *r_en; uint8_t *ops; int32_t *n_ops;
 };
 
-// validation, the library's device image, the two launches: seq, seq_len and o are device pointers
-int map_run(xb_ctx *ctx, const int8_t *d_seq, const int32_t *d_len, int n, int W, const char *templates, const int32_t *offsets,
-            int R, const int sc[5], const MapOut &o)
+// the library's device image (rebuilt only when the bytes change) for n rows of width W: validation, *lmax = the longest template
+// (sc: the mapper's scoring, checked where it always was; null for a caller that aligns nothing and is not held to the cell budget)
+int map_library(xb_ctx *ctx, int n, int W, const char *templates, const int32_t *offsets, int R, const int *sc, int *lmax)
 {
     if (n < 1 || W < 1 || W > xb::MAP_MAX_ROW)
         return fail(ctx, XB_ERR_INVALID, "xb_map_templates: n = %d rows of width %d; need n >= 1 and 1 <= W <= %d", n, W, xb::MAP_MAX_ROW);
     if (!templates || !offsets || R < 1 || offsets[0] != 0) return fail(ctx, XB_ERR_INVALID, "xb_map_templates: empty template library");
-    for (int k = 0; k < 5; ++k)
+    for (int k = 0; sc && k < 5; ++k)
         if (sc[k] < 0 || sc[k] > 1000) return fail(ctx, XB_ERR_INVALID, "xb_map_templates: scoring values must lie in [0, 1000]");
     int Lmax = 0;
     for (int t = 0; t < R; ++t) {
@@ -2003,7 +2005,7 @@ int map_run(xb_ctx *ctx, const int8_t *d_seq, const int32_t *d_len, int n, int W
     }
     const size_t total = (size_t)offsets[R];
     const double cells = 2.0 * n * W * (double)total;
-    if (total > MAP_MAX_LIBRARY || cells > MAP_CELL_BUDGET)
+    if (total > MAP_MAX_LIBRARY || (sc && cells > MAP_CELL_BUDGET))
         return fail(ctx, XB_ERR_INVALID, "xb_map_templates: a library of %d templates, %zu letters, against %d rows of width %d is %.3g "
                     "cells; one call takes at most %.3g cells and a library of %zu letters (larger libraries need a seeding stage)",
                     R, total, n, W, cells, MAP_CELL_BUDGET, MAP_MAX_LIBRARY);
@@ -2041,6 +2043,18 @@ int map_run(xb_ctx *ctx, const int8_t *d_seq, const int32_t *d_len, int n, int W
         m.Lmax = Lmax;
         m.nchunks = (int)chunks.size() - 1;
     }
+    *lmax = Lmax;
+    return XB_OK;
+}
+
+// validation, the library's device image, the two launches: seq, seq_len and o are device pointers
+int map_run(xb_ctx *ctx, const int8_t *d_seq, const int32_t *d_len, int n, int W, const char *templates, const int32_t *offsets,
+            int R, const int sc[5], const MapOut &o)
+{
+    int Lmax = 0;
+    if (int rc = map_library(ctx, n, W, templates, offsets, R, sc, &Lmax)) return rc;
+    xb_ctx::MapState &m = ctx->map;
+    const size_t total = (size_t)offsets[R];
     xb::MapParams p{};
     p.seq = d_seq; p.seq_len = d_len; p.n = n; p.W = W;
     const size_t a_off = (total + 15) & ~(size_t)15;
@@ -2128,6 +2142,182 @@ XB_API int xb_map_templates(xb_ctx *ctx, const int8_t *seq, const int32_t *seq_l
         XB_HIP(ctx, hipMemcpyAsync(h_i32[k], d_i32[k + 1], N * 4, hipMemcpyDeviceToHost, ctx->stream));
     XB_HIP(ctx, hipMemcpyAsync(strand, d_strand, N, hipMemcpyDeviceToHost, ctx->stream));
     XB_HIP(ctx, hipMemcpyAsync(ops, d_ops, N * cap, hipMemcpyDeviceToHost, ctx->stream));
+    return xb_synchronize(ctx);
+}
+
+// ---- ctc-data labels of mapped rows (xb_ctc_targets, xb_ctc_chunks) ---------------------------------------------------
+namespace {
+
+struct CtcIn {
+    const int32_t *seq_len, *tmpl; const int8_t *strand; const int32_t *q_st, *q_en, *r_st, *r_en; const uint8_t *ops; const int32_t *n_ops;
+};
+struct CtcOut {
+    int32_t *mlen, *blen; uint8_t *verdict, *target; int32_t *target_len;
+};
+struct CtcRule {
+    double min_accuracy, min_coverage; int ub_only, ub_plus, ub_minus;
+};
+
+bool ctc_complete(const CtcIn &i, const CtcOut &o)
+{
+    return i.seq_len && i.tmpl && i.strand && i.q_st && i.q_en && i.r_st && i.r_en && i.ops && i.n_ops && o.mlen && o.blen && o.verdict &&
+           o.target && o.target_len;
+}
+
+// validation, the library's device image, the launch: i and o are device pointers
+int ctc_run(xb_ctx *ctx, const CtcIn &i, int n, int W, const char *templates, const int32_t *offsets, int R, const CtcRule &rule,
+            const CtcOut &o)
+{
+    if (rule.ub_plus < 1 || rule.ub_plus > 255 || rule.ub_minus < 1 || rule.ub_minus > 255)
+        return fail(ctx, XB_ERR_INVALID, "xb_ctc_targets: ub_plus = %d, ub_minus = %d; labels are 1 .. 255", rule.ub_plus, rule.ub_minus);
+    if (!(rule.min_accuracy == rule.min_accuracy) || !(rule.min_coverage == rule.min_coverage))
+        return fail(ctx, XB_ERR_INVALID, "xb_ctc_targets: a threshold is not a number");
+    if (reinterpret_cast<uintptr_t>(o.target) & 15) return fail(ctx, XB_ERR_INVALID, "xb_ctc_targets: target must be 16-byte aligned");
+    int Lmax = 0;
+    if (int rc = map_library(ctx, n, W, templates, offsets, R, nullptr, &Lmax)) return rc;
+    const size_t total = (size_t)offsets[R];
+    const uint8_t *img = static_cast<const uint8_t *>(ctx->map.image.p);
+    xb::CtcTargetParams p{};
+    p.seq_len = i.seq_len; p.n = n; p.W = W; p.cap = W + Lmax;
+    p.tmpl = i.tmpl; p.strand = i.strand; p.q_st = i.q_st; p.q_en = i.q_en; p.r_st = i.r_st; p.r_en = i.r_en; p.ops = i.ops; p.n_ops = i.n_ops;
+    p.tcodes = img;
+    p.toff = reinterpret_cast<const int32_t *>(img + ((total + 15) & ~(size_t)15));
+    p.R = R; p.TW = xb::ctc_target_width(Lmax);
+    p.min_accuracy = rule.min_accuracy; p.min_coverage = rule.min_coverage;
+    p.ub_only = rule.ub_only != 0; p.ub_plus = rule.ub_plus; p.ub_minus = rule.ub_minus;
+    p.mlen = o.mlen; p.blen = o.blen; p.verdict = o.verdict; p.target = o.target; p.target_len = o.target_len;
+    XB_HIP(ctx, xb::launch_ctc_targets(p, ctx->stream));
+    return XB_OK;
+}
+
+// 256-byte aligned pieces of one staging buffer, in the order they are asked for
+struct Carve {
+    size_t used = 0;
+    size_t take(size_t bytes) { const size_t at = used; used += (bytes + 255) & ~(size_t)255; return at; }
+};
+
+int longest_template(xb_ctx *ctx, const int32_t *offsets, int R, int *lmax)
+{
+    int Lmax = 0;
+    for (int t = 0; offsets && t < R; ++t) Lmax = std::max(Lmax, offsets[t + 1] - offsets[t]);
+    if (Lmax < 1 || Lmax > xb::MAP_MAX_TEMPLATE)
+        return fail(ctx, XB_ERR_INVALID, "xb_ctc_targets: the longest template has %d letters; 1 .. %d are supported", Lmax, xb::MAP_MAX_TEMPLATE);
+    *lmax = Lmax;
+    return XB_OK;
+}
+
+}  // namespace
+
+XB_API int xb_ctc_targets_dev(xb_ctx *ctx, const int32_t *d_seq_len, int n, int W, const char *templates, const int32_t *offsets,
+                              int R, const int32_t *d_tmpl, const int8_t *d_strand, const int32_t *d_q_st, const int32_t *d_q_en,
+                              const int32_t *d_r_st, const int32_t *d_r_en, const uint8_t *d_ops, const int32_t *d_n_ops,
+                              double min_accuracy, double min_coverage, int ub_only, int ub_plus, int ub_minus, int32_t *d_mlen,
+                              int32_t *d_blen, uint8_t *d_verdict, uint8_t *d_target, int32_t *d_target_len)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    const CtcIn i = {d_seq_len, d_tmpl, d_strand, d_q_st, d_q_en, d_r_st, d_r_en, d_ops, d_n_ops};
+    const CtcOut o = {d_mlen, d_blen, d_verdict, d_target, d_target_len};
+    if (!ctc_complete(i, o)) return fail(ctx, XB_ERR_INVALID, "xb_ctc_targets: null device pointer");
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = join_async_decode(ctx)) return rc;
+    ctx->result_stream = ctx->stream;
+    return ctc_run(ctx, i, n, W, templates, offsets, R, {min_accuracy, min_coverage, ub_only, ub_plus, ub_minus}, o);
+}
+
+XB_API int xb_ctc_targets(xb_ctx *ctx, const int32_t *seq_len, int n, int W, const char *templates, const int32_t *offsets, int R,
+                          const int32_t *tmpl, const int8_t *strand, const int32_t *q_st, const int32_t *q_en, const int32_t *r_st,
+                          const int32_t *r_en, const uint8_t *ops, const int32_t *n_ops, double min_accuracy, double min_coverage,
+                          int ub_only, int ub_plus, int ub_minus, int32_t *mlen, int32_t *blen, uint8_t *verdict, uint8_t *target,
+                          int32_t *target_len)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    const CtcIn h = {seq_len, tmpl, strand, q_st, q_en, r_st, r_en, ops, n_ops};
+    const CtcOut ho = {mlen, blen, verdict, target, target_len};
+    if (!ctc_complete(h, ho)) return fail(ctx, XB_ERR_INVALID, "xb_ctc_targets: null host pointer");
+    if (n < 1 || W < 1 || W > xb::MAP_MAX_ROW || R < 1)
+        return fail(ctx, XB_ERR_INVALID, "xb_ctc_targets: n = %d rows of width %d, %d templates; need n >= 1, 1 <= W <= %d, R >= 1", n, W, R,
+                    xb::MAP_MAX_ROW);
+    int Lmax = 0;
+    if (int rc = longest_template(ctx, offsets, R, &Lmax)) return rc;
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = join_async_decode(ctx)) return rc;
+    const size_t N = (size_t)n, cap = (size_t)W + Lmax, TW = (size_t)xb::ctc_target_width(Lmax);
+    if (N * (cap + TW) > ((size_t)2 << 30)) return fail(ctx, XB_ERR_INVALID, "xb_ctc_targets: %d rows of width %d in one call; split the batch", n, W);
+    Carve c;
+    size_t a_i32[10];
+    for (size_t &a : a_i32) a = c.take(N * 4);          // seq_len, tmpl, q_st, q_en, r_st, r_en, n_ops | mlen, blen, target_len
+    const size_t a_strand = c.take(N), a_verdict = c.take(N), a_ops = c.take(N * cap), a_target = c.take(N * TW);
+    if (int rc = map_grow(ctx, &ctx->map.ctc_staging, c.used)) return rc;
+    uint8_t *base = static_cast<uint8_t *>(ctx->map.ctc_staging.p);
+    auto i32 = [&](int k) { return reinterpret_cast<int32_t *>(base + a_i32[k]); };
+    const int32_t *const src[7] = {seq_len, tmpl, q_st, q_en, r_st, r_en, n_ops};
+    for (int k = 0; k < 7; ++k) XB_HIP(ctx, hipMemcpyAsync(i32(k), src[k], N * 4, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(base + a_strand, strand, N, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(base + a_ops, ops, N * cap, hipMemcpyHostToDevice, ctx->stream));
+    const CtcIn d = {i32(0), i32(1), reinterpret_cast<int8_t *>(base + a_strand), i32(2), i32(3), i32(4), i32(5), base + a_ops, i32(6)};
+    const CtcOut o = {i32(7), i32(8), base + a_verdict, base + a_target, i32(9)};
+    if (int rc = ctc_run(ctx, d, n, W, templates, offsets, R, {min_accuracy, min_coverage, ub_only, ub_plus, ub_minus}, o)) return rc;
+    XB_HIP(ctx, hipMemcpyAsync(mlen, o.mlen, N * 4, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(blen, o.blen, N * 4, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(target_len, o.target_len, N * 4, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(verdict, o.verdict, N, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(target, o.target, N * TW, hipMemcpyDeviceToHost, ctx->stream));
+    return xb_synchronize(ctx);
+}
+
+XB_API int xb_ctc_chunks(xb_ctx *ctx, const float *signal, int n, const char *alphabet, const char *templates, const int32_t *offsets,
+                         int R, int match, int mismatch, int gap_open, int gap_extend, int ambiguous, double min_accuracy,
+                         double min_coverage, int ub_only, int ub_plus, int ub_minus, int8_t *seq, int32_t *seq_len, int32_t *tmpl,
+                         int8_t *strand, int32_t *score, int32_t *second, int32_t *q_st, int32_t *q_en, int32_t *r_st, int32_t *r_en,
+                         uint8_t *ops, int32_t *n_ops, int32_t *mlen, int32_t *blen, uint8_t *verdict, uint8_t *target,
+                         int32_t *target_len)
+{
+    int rc = check_ready(ctx, n);
+    if (rc) return rc;
+    const MapOut hm = {tmpl, strand, score, second, q_st, q_en, r_st, r_en, ops, n_ops};
+    if (!signal || !alphabet || !seq || !seq_len || !map_out_complete(hm) || !mlen || !blen || !verdict || !target || !target_len)
+        return fail(ctx, XB_ERR_INVALID, "xb_ctc_chunks: null argument");
+    if ((rc = check_alphabet(ctx, alphabet))) return rc;
+    const int W = ctx->T;
+    if (W > xb::MAP_MAX_ROW) return fail(ctx, XB_ERR_INVALID, "xb_ctc_chunks: rows of %d steps; the mapper takes %d", W, xb::MAP_MAX_ROW);
+    int Lmax = 0;
+    if (R < 1 || (rc = longest_template(ctx, offsets, R, &Lmax))) return rc ? rc : fail(ctx, XB_ERR_INVALID, "xb_ctc_chunks: empty template library");
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    // rows per mapper launch: what its cell budget (2 n W sum(L)) admits
+    const double per_row = 2.0 * W * (double)offsets[R];
+    const int fit = (int)std::min<double>((double)n, std::floor(MAP_CELL_BUDGET / per_row));
+    if (fit < 1) return fail(ctx, XB_ERR_INVALID, "xb_ctc_chunks: one row of %d steps against %d letters is over the mapper's cell budget", W, offsets[R]);
+    const size_t N = (size_t)n, cap = (size_t)W + Lmax, TW = (size_t)xb::ctc_target_width(Lmax);
+    Carve c;
+    size_t a_i32[11];
+    for (size_t &a : a_i32) a = c.take(N * 4);          // tmpl, score, second, q_st, q_en, r_st, r_en, n_ops | mlen, blen, target_len
+    const size_t a_strand = c.take(N), a_verdict = c.take(N), a_ops = c.take(N * cap), a_target = c.take(N * TW);
+    if ((rc = map_grow(ctx, &ctx->map.ctc_staging, c.used))) return rc;
+    uint8_t *base = static_cast<uint8_t *>(ctx->map.ctc_staging.p);
+    auto i32 = [&](int k) { return reinterpret_cast<int32_t *>(base + a_i32[k]); };
+    int8_t *d_strand = reinterpret_cast<int8_t *>(base + a_strand);
+    uint8_t *d_ops = base + a_ops;
+    XB_HIP(ctx, hipMemcpyAsync(ctx->d_signal, signal, sizeof(float) * N * ctx->cfg.chunk_len, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = basecall_async(ctx, ctx->d_signal, n, alphabet, ctx->seq, ctx->seq_len, {}))) return rc;
+    if ((rc = join_async_decode(ctx))) return rc;
+    const int sc[5] = {match, mismatch, gap_open, gap_extend, ambiguous};
+    for (int a = 0; a < n; a += fit) {
+        const int cnt = std::min(fit, n - a);
+        const MapOut d = {i32(0) + a, d_strand + a, i32(1) + a, i32(2) + a, i32(3) + a, i32(4) + a, i32(5) + a, i32(6) + a,
+                          d_ops + (size_t)a * cap, i32(7) + a};
+        if ((rc = map_run(ctx, ctx->seq + (size_t)a * W, ctx->seq_len + a, cnt, W, templates, offsets, R, sc, d))) return rc;
+    }
+    const CtcIn ci = {ctx->seq_len, i32(0), d_strand, i32(3), i32(4), i32(5), i32(6), d_ops, i32(7)};
+    const CtcOut co = {i32(8), i32(9), base + a_verdict, base + a_target, i32(10)};
+    if ((rc = ctc_run(ctx, ci, n, W, templates, offsets, R, {min_accuracy, min_coverage, ub_only, ub_plus, ub_minus}, co))) return rc;
+    XB_HIP(ctx, hipMemcpyAsync(seq, ctx->seq, N * W, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(seq_len, ctx->seq_len, N * 4, hipMemcpyDeviceToHost, ctx->stream));
+    int32_t *const h_i32[11] = {tmpl, score, second, q_st, q_en, r_st, r_en, n_ops, mlen, blen, target_len};
+    for (int k = 0; k < 11; ++k) XB_HIP(ctx, hipMemcpyAsync(h_i32[k], i32(k), N * 4, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(strand, d_strand, N, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(verdict, base + a_verdict, N, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(ops, d_ops, N * cap, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(target, base + a_target, N * TW, hipMemcpyDeviceToHost, ctx->stream));
     return xb_synchronize(ctx);
 }
 

@@ -235,6 +235,26 @@ bool map_trace_in_lds(int W, int Lmax);     // the direction bytes of one pair f
 hipError_t launch_map_score(const MapParams &p, hipStream_t stream);
 hipError_t launch_map_trace(const MapParams &p, hipStream_t stream);
 
+// xb_ctc_targets: per mapped row the ctc-data verdict and label row (the contract is in the public header).  One wave per row.
+constexpr int CTC_FAILED_SEQ = 1, CTC_FAILED_MAP = 2, CTC_SKIPPED_NON_UB = 4, CTC_FAILED_ACC = 8, CTC_FAILED_COV = 16;
+inline int ctc_target_width(int Lmax) { return (Lmax + 15) & ~15; }   // bytes per label row
+struct CtcTargetParams {
+    const int32_t *seq_len;      // (n) as the mapper read it: clamped to [0, W]
+    int n, W, cap;               // cap = W + Lmax: bytes per row of ops
+    const int32_t *tmpl, *q_st, *q_en, *r_st, *r_en, *n_ops;   // (n) the mapper's outputs
+    const int8_t *strand;        // (n)
+    const uint8_t *ops;          // (n, cap)
+    const uint8_t *tcodes;       // the library image: codes and offsets
+    const int32_t *toff;
+    int R, TW;                   // TW = ctc_target_width(Lmax)
+    double min_accuracy, min_coverage;
+    int ub_only, ub_plus, ub_minus;
+    int32_t *mlen, *blen, *target_len;   // (n)
+    uint8_t *verdict;            // (n)
+    uint8_t *target;             // (n, TW), 16-byte aligned
+};
+hipError_t launch_ctc_targets(const CtcTargetParams &p, hipStream_t stream);
+
 // ---------------------------------------------------------------- DTW signal segmentation (xb_dtw.hip)
 // xb_dtw_segment: every signal chunk against the expected levels of its reference by dynamic time warping (the contract is
 // in the public header).  One wave per chunk; the columns lie across the lanes, cols consecutive columns per lane, in

@@ -28,6 +28,8 @@ from collections import namedtuple
 from logging import getLogger
 from threading import Thread
 
+import numpy as np
+
 from .util import mean_qscore_from_qstring
 
 logger = getLogger("bonito")
@@ -266,3 +268,158 @@ class Writer(Thread):
         except BaseException as e:  # surfaced by the CLI after join()
             self.error = e
             raise
+
+
+# ---- `--save-ctc`: ctc-data from filtered, labelled chunks (io.py:448-585) ---------------------------------------------
+FAILED_SEQ, FAILED_MAP, SKIPPED_NON_UB, FAILED_ACC, FAILED_COV = 1, 2, 4, 8, 16      # the verdict bits of xb_ctc_targets
+FILTER_COUNTERS = ("count_failed_seq", "count_failed_map", "count_failed_acc", "count_failed_cov", "count_failed_both",
+                   "non_ubs_skipped")
+_STRAND_COMP = str.maketrans("ACGTacgt", "TGCAtgca")
+
+
+def ctc_verdict(sequence, mapping, refseq, min_accuracy=0.95, min_coverage=0.90, ub_only=False, ub_plus=5, ub_minus=6):
+    """The reference's per-chunk decision (io.py:495-540) on the host, for results that carry no device verdict: ->
+    (verdict byte as xb_ctc_targets writes it, label list or None).  refseq(ctg, r_st, r_en) returns the template letters;
+    every letter outside A, C, G, T counts as the reference's 'N'."""
+    verdict = (FAILED_SEQ if len(sequence) == 0 else 0) | (FAILED_MAP if mapping is None else 0)
+    if verdict:
+        return verdict, None
+    cov = (mapping.q_en - mapping.q_st) / len(sequence)
+    acc = mapping.mlen / mapping.blen
+    letters = refseq(mapping.ctg, mapping.r_st, mapping.r_en)
+    if ub_only and all(c in "ACGTacgt" for c in letters):
+        return SKIPPED_NON_UB, None
+    verdict = (FAILED_ACC if acc < min_accuracy else 0) | (FAILED_COV if cov < min_coverage else 0)
+    if verdict:
+        return verdict, None
+    if mapping.strand == -1:
+        letters = letters[::-1].translate(_STRAND_COMP)
+    ub = ub_minus if mapping.strand == -1 else ub_plus
+    return 0, ["ACGT".find(c.upper()) + 1 or ub for c in letters]
+
+
+def typical_indices(x, n=2.5):
+    """cli/convert.py:80-83: the indices whose value lies STRICTLY inside mean +- n standard deviations.  Quirk kept: when all
+    values are equal the deviation is 0, both bounds are the mean itself, and nothing is kept."""
+    x = np.asarray(x)
+    mu, sd = np.mean(x), np.std(x)
+    idx, = np.where((mu - n * sd < x) & (x < mu + n * sd))
+    return idx
+
+
+def filter_stats_text(counts):
+    """`pandas.Series(counts).to_csv()` without pandas: the header `,0`, then one `name,value` line per counter."""
+    return ",0\n" + "".join("%s,%d\n" % (k, counts[k]) for k in FILTER_COUNTERS)
+
+
+class CTCWriter(Thread):
+    """`basecaller --save-ctc` (io.py:448-585): drains (chunk, result) on its own thread, keeps the chunks that pass, and
+    writes ctc-data beside the stdout target -- chunks.npy float16 (k, chunksize), references.npy uint8 (k, longest label
+    row), reference_lengths.npy uint16 -- plus filter_stats.csv, one SAM record on `fd` and one summary row per kept chunk.
+    A result carries 'sequence', 'qstring', 'mapping' and, from the device stage (crf.basecall.basecall_ctc), 'verdict' and
+    'target' (xb_ctc_targets' byte and label row); without them the decision is made here (ctc_verdict) from the mapping and
+    aligner.seq.  Every chunk is logged.  Kept chunks go through typical_indices on their label lengths -- with its quirk:
+    equal lengths keep NOTHING -- and through np.random.permutation from numpy's global state (util.init seeds it); the
+    summary file is then rewritten with this run's rows in that order (the rows as first written, CRLF: the reference's
+    pandas round trip is not reproduced).  Records are SAM text (mode 'w': header first; 'wfq': no header, as the
+    reference opens pysam then); BAM / CRAM need htslib."""
+
+    def __init__(self, mode, iterator, aligner, fd=sys.stdout, min_coverage=0.90, min_accuracy=0.95, ref_fn=None, groups=None,
+                 group_key=None, ub_only=False, summary=None, directory=None, ub_plus=5, ub_minus=6):
+        super().__init__()
+        if mode not in ("wfq", "w"):
+            raise NotImplementedError("SAM text is on the MI355X path; BAM / CRAM need htslib")
+        self.mode, self.fd, self.iterator, self.aligner = mode, fd, iterator, aligner
+        self.group_key = group_key
+        self.groups = sorted(groups) if groups else []
+        self.min_coverage, self.min_accuracy, self.ub_only = min_coverage, min_accuracy, ub_only
+        self.ub_plus, self.ub_minus = ub_plus, ub_minus
+        self.summary, self.directory = summary, directory
+        self.log = []
+        self.counts = dict.fromkeys(FILTER_COUNTERS, 0)
+        self.error = None
+
+    def _verdict(self, res):
+        if "verdict" in res:
+            return int(res["verdict"]), res.get("target")
+        return ctc_verdict(res["sequence"], res.get("mapping"), self.aligner.seq, self.min_accuracy, self.min_coverage,
+                           self.ub_only, self.ub_plus, self.ub_minus)
+
+    def _count(self, verdict):
+        c = self.counts
+        c["count_failed_seq"] += bool(verdict & FAILED_SEQ)
+        c["count_failed_map"] += bool(verdict & FAILED_MAP)
+        c["non_ubs_skipped"] += bool(verdict & SKIPPED_NON_UB)
+        c["count_failed_acc"] += bool(verdict & FAILED_ACC)
+        c["count_failed_cov"] += bool(verdict & FAILED_COV)
+        c["count_failed_both"] += verdict & (FAILED_ACC | FAILED_COV) == FAILED_ACC | FAILED_COV
+
+    def run(self):
+        try:
+            self._run()
+        except BaseException as e:  # surfaced by the CLI after join()
+            self.error = e
+            raise
+
+    def _run(self):
+        chunks, targets, rows = [], [], []
+        path = self.summary or summary_file()
+        columns = SUMMARY_COLUMNS + ALIGNMENT_COLUMNS
+        with SummaryTable(path, columns) as table:
+            if self.mode == "w":
+                from . import __version__
+                self.fd.write(sam_header(self.groups, aligner_version=__version__, aligner_name=ALIGNER_NAME,
+                                         aligner_ds="exhaustive template alignment on the device"))
+            for read, res in self.iterator:
+                self.log.append((read.read_id, len(read.signal)))
+                verdict, target = self._verdict(res)
+                self._count(verdict)
+                if verdict:
+                    continue
+                seq, qstring, mapping = res["sequence"], res["qstring"], res["mapping"]
+                mean_q = res.get("mean_qscore")
+                if mean_q is None:
+                    mean_q = mean_qscore_from_qstring(qstring)
+                self.fd.write(sam_record(read.read_id, seq, qstring, mapping) + "\n")
+                row = summary_row(read, len(seq), mean_q, alignment=mapping)
+                table.append(row)
+                rows.append(row)
+                targets.append(np.asarray(target, dtype=np.uint8))
+                chunks.append(read.signal)
+            columns = table.columns
+        if self.ub_only:
+            sys.stderr.write("Non-UB chunks skipped: {:0,d}\n".format(self.counts["non_ubs_skipped"]))
+        sys.stderr.write("Filtered reads (failed): {:0,d} seq, {:0,d} map\n".format(
+            self.counts["count_failed_seq"], self.counts["count_failed_map"]))
+        sys.stderr.write("Filtered reads (failed): {:0,d} acc, {:0,d} cov, {:0,d} both\n".format(
+            self.counts["count_failed_acc"], self.counts["count_failed_cov"], self.counts["count_failed_both"]))
+        if len(chunks) == 0:
+            sys.stderr.write("> no suitable ctc data to write\n")
+            return
+        chunks = np.array(chunks, dtype=np.float16)
+        lengths = np.array([len(t) for t in targets], dtype=np.uint16)
+        references = np.zeros((chunks.shape[0], int(lengths.max())), dtype=np.uint8)
+        for idx, target in enumerate(targets):
+            references[idx, :len(target)] = target
+        indices = np.random.permutation(typical_indices(lengths))
+        chunks, references, lengths = chunks[indices], references[indices], lengths[indices]
+        with open(path, "w", newline="") as fh:
+            for fields in [columns] + [[rows[i].get(c, "-") for c in columns] for i in indices]:
+                fh.write("\t".join(_tsv_field(f) for f in fields) + "\r\n")
+        directory = self.directory
+        if directory is None:
+            target = _stdout_target()
+            directory = "." if target is None else os.path.dirname(target)
+        with open(os.path.join(directory, "filter_stats.csv"), "w", newline="") as fh:
+            fh.write(filter_stats_text(self.counts))
+        np.save(os.path.join(directory, "chunks.npy"), chunks)
+        np.save(os.path.join(directory, "references.npy"), references)
+        np.save(os.path.join(directory, "reference_lengths.npy"), lengths)
+        sys.stderr.write("> written ctc training data\n")
+        sys.stderr.write("  - output_directory: {}\n".format(directory))
+        sys.stderr.write("  - chunks.npy with shape (%s)\n" % ",".join(map(str, chunks.shape)))
+        sys.stderr.write("  - references.npy with shape (%s)\n" % ",".join(map(str, references.shape)))
+        sys.stderr.write("  - reference_lengths.npy shape (%s)\n" % ",".join(map(str, lengths.shape)))
+
+    def stop(self):
+        self.join()

@@ -224,6 +224,40 @@ class SyntheticRead:
         return _read_tags(self)
 
 
+class ReadChunk:
+    """One fixed-size piece of a read, as `--save-ctc` basecalls it (fast5.py:131-146): the read's metadata, the id
+    `<read_id>:<i>:<n>` (i from 1) and the template start / duration set to the read's own start / duration."""
+
+    def __init__(self, read, chunk, i, n):
+        self.read_id = "%s:%i:%i" % (read.read_id, i, n)
+        self.run_id = read.run_id
+        self.filename = read.filename
+        self.mux = read.mux
+        self.channel = read.channel
+        self.start = read.start
+        self.duration = read.duration
+        self.template_start = self.start
+        self.template_duration = self.duration
+        self.signal = chunk
+
+    def __repr__(self):
+        return "ReadChunk('%s')" % self.read_id
+
+
+def read_chunks(read, chunksize=4000, overlap=400):
+    """Split a read into ReadChunks of exactly `chunksize` samples, `chunksize - overlap` apart (fast5.py:207-219): a read
+    shorter than chunksize yields nothing, and the first (len - chunksize) % (chunksize - overlap) samples are dropped so that
+    the last chunk ends with the read.  The chunks are strided views of the read's signal, not copies."""
+    signal = np.asarray(read.signal)
+    if len(signal) < chunksize:
+        return
+    step = chunksize - overlap
+    offset = (len(signal) - chunksize) % step
+    blocks = np.lib.stride_tricks.sliding_window_view(signal[offset:], chunksize)[::step]
+    for i, block in enumerate(blocks):
+        yield ReadChunk(read, block, i + 1, len(blocks))
+
+
 def write_bundle(path, reads):
     """reads: iterable of (raw int16 array, attrs dict with at least read_id/range/digitisation/offset/sampling_rate)."""
     arrays, metas = {}, []
