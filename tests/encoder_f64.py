@@ -17,7 +17,9 @@ fixed point, and so on.  Defect names (`run(defects=...)`):
   "conv16:<c>"     conv c (0 or 1) in fp16: its input, weights, bias and output rounded to fp16
   "shift:<l>"      layer l reads its input one time step late (x[t - 1], zeros at t = 0)
   "flip:<l>"       layer l runs in the other direction
-  "pad:<c>"        conv c (0 or 2) pads with the neighbouring chunks' samples instead of zeros
+  "pad:<c>"        conv c (0 or 2) pads with the neighbouring chunks' samples instead of zeros (nothing at padding 0)
+  "win:late"       conv 2 pads pad - 1 samples on the left and pad + 1 on the right: every window starts one sample late
+                   (an off-by-one in the tile origin; needs winlen >= 3)
   "bhh:ignore"     bias_hh left out of every layer's gate bias
   "bhh:order"      bias_hh added with the gate order i, f, o, g instead of i, f, g, o
 """
@@ -94,9 +96,14 @@ def _r16(x):
     return x.to(torch.float16).to(torch.float64)
 
 
-def _conv(x, w, b, stride, pad, neighbour):
-    """x (N, C, L); zero padding, or with `neighbour` the last / first `pad` samples of the previous / next chunk."""
-    if neighbour:
+def _conv(x, w, b, stride, pad, neighbour, late=False):
+    """x (N, C, L); zero padding, or with `neighbour` the last / first `pad` samples of the previous / next chunk; with
+    `late` the zero padding is pad - 1 on the left and pad + 1 on the right."""
+    if late:
+        x = torch.nn.functional.pad(x, (pad - 1, pad + 1))
+    elif neighbour and pad == 0:
+        pass                                              # [..., -0:] would take the whole neighbour
+    elif neighbour:
         short = max(pad - x.shape[2], 0)                  # chunks shorter than the padding: zeros beyond the neighbour
         left = torch.nn.functional.pad(torch.roll(x, 1, dims=0), (short, 0))[..., -pad:]
         right = torch.nn.functional.pad(torch.roll(x, -1, dims=0), (0, short))[..., :pad]
@@ -167,7 +174,7 @@ class Reference:
         first = 6
         for d in defects:
             kind, arg = d.split(":", 1)
-            if kind in ("conv16", "pad"):
+            if kind in ("conv16", "pad", "win"):
                 first = 0
             elif kind in ("shift", "flip"):
                 first = min(first, 1 + int(arg))
@@ -202,7 +209,8 @@ class Reference:
             kind, arg = d.split(":", 1)
             ok = {"w16": lambda a: a in self.w, "w8": lambda a: a in self.w, "wi8": lambda a: a in self.w,
                   "a16": lambda a: a in STAGES, "conv16": lambda a: a in ("0", "1"), "pad": lambda a: a in ("0", "2"),
-                  "shift": lambda a: a in "01234", "flip": lambda a: a in "01234", "bhh": lambda a: a in ("ignore", "order")}
+                  "shift": lambda a: a in "01234", "flip": lambda a: a in "01234", "bhh": lambda a: a in ("ignore", "order"),
+                  "win": lambda a: a == "late" and self.winlen >= 3}
             if kind not in ok or not ok[kind](arg):
                 raise ValueError("unknown defect %r" % d)
         first = self._first_stage(defects) if defects else 0
@@ -222,7 +230,7 @@ class Reference:
                         h, wc, bc = _r16(h), _r16(wc), _r16(bc)
                     if c == 2 and "conv3" in a16:
                         h = _r16(h)
-                    h = _conv(h, wc, bc, stride, pad, "pad:%d" % c in defects)
+                    h = _conv(h, wc, bc, stride, pad, "pad:%d" % c in defects, c == 2 and "win:late" in defects)
                     if half:
                         h = _r16(h)
                 out["conv"] = h.permute(2, 0, 1).contiguous()
@@ -262,8 +270,8 @@ def encode(signal, state_dict, n_base, expand_blanks=True, defects=(), **kw):
 
 # ---- weight sets ---------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
-def _sensitive(features, nb, seed, outlier):
-    sd = peaky_weights(features, nb, seed, blank_bias=3.0)
+def _sensitive(features, nb, seed, outlier, state_len=3, winlen=19):
+    sd = peaky_weights(features, nb, seed, blank_bias=3.0, state_len=state_len, winlen=winlen)
     rng = np.random.default_rng(1000 + seed)
     F = features
     for l in range(5):
@@ -283,19 +291,19 @@ def _sensitive(features, nb, seed, outlier):
     return sd
 
 
-def sensitive_weights(features, nb, seed=25):
+def sensitive_weights(features, nb, seed=25, state_len=3, winlen=19):
     """peaky_weights (signal-dependent, peaky scores: synthetic.peaky_weights) with the CRF blank bias at 3 and non-zero
     LSTM gate biases: b_ih and b_hh ~ N(0, 0.1) differ gate by gate, and b_hh carries a forget-gate offset of +0.2.  A lost
     bias_hh, a bias folded in the wrong gate order or a lost correction product moves the scores visibly; at features 768
     0.55-0.7 bases are called per time step (tests/test_encoder_f64.py checks the regime)."""
-    return {k: v.copy() for k, v in _sensitive(features, nb, seed, False).items()}
+    return {k: v.copy() for k, v in _sensitive(features, nb, seed, False, state_len, winlen).items()}
 
 
-def outlier_weights(features, nb, seed=25):
+def outlier_weights(features, nb, seed=25, state_len=3, winlen=19):
     """sensitive_weights with 3 per mille of the entries of every tensor (at least one) scaled x 8 against the bulk (the
     tensor then rescaled to its former norm): the largest |w| of a tensor, which sets the tensor-wide e4m3 exponent of
     split_rows and the per-row int8 scale, sits far above the bulk, so the bulk keeps fewer significant bits there."""
-    return {k: v.copy() for k, v in _sensitive(features, nb, seed, True).items()}
+    return {k: v.copy() for k, v in _sensitive(features, nb, seed, True, state_len, winlen).items()}
 
 
 WEIGHTS = {"sensitive": sensitive_weights, "outlier": outlier_weights}

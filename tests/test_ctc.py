@@ -11,6 +11,7 @@ import torch
 
 import oracle
 from conftest import make_config, random_scores
+from pairs import PAIR_IDS, PAIRS
 
 
 def _targets(rng, N, Lt, nb, sl, lens=None):
@@ -44,17 +45,19 @@ def _ctc_logz_f64(x, stay_idx, move_idx, npos, semiring="log"):
     return torch.stack(out)
 
 
-@pytest.mark.parametrize("nb", [4, 5, 6])
-def test_oracle_ctc_against_float64_autograd(nb):
-    sl, T, N, Lt = 3, 48, 4, 14
+@pytest.mark.parametrize("nb,sl", PAIRS, ids=PAIR_IDS)
+def test_oracle_ctc_against_float64_autograd(nb, sl):
+    T, Lt = 48, 14
+    N = 4 if sl == 3 else 3                                # state_len 3 as before; the new pairs stay at N <= 3
     rng = np.random.default_rng(nb)
-    sc = random_scores(T, N, nb, seed=nb)
+    sc = random_scores(T, N, nb, sl=sl, seed=nb)
     targets, lens = _targets(rng, N, Lt, nb, sl)
     stay_idx, move_idx = oracle.ctc_indices(targets, nb, sl)
     # the gather indices are the reference's expression (crf/model.py:108-114) written out in numpy
     t0 = np.clip(targets.astype(np.int64) - 1, 0, None)
     n = Lt - (sl - 1)
     ref_stay = sum(t0[:, i:n + i] * nb ** (sl - i - 1) for i in range(sl)) * (nb + 1)
+    assert stay_idx.shape == (N, Lt - sl + 1) and move_idx.shape == (N, Lt - sl)
     assert np.array_equal(stay_idx, ref_stay) and np.array_equal(move_idx, ref_stay[:, 1:] + t0[:, :n - 1] + 1)
     o = oracle.ctc_logz(sc, targets, lens, nb, sl, want_grads=True)
     x = torch.tensor(sc, dtype=torch.float64, requires_grad=True)
@@ -97,14 +100,20 @@ def test_oracle_ctc_rejects_bad_lengths():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+GPU_CASES = [(4, 37, 3, 9, 3), (5, 120, 5, 40, 3), (6, 200, 7, 130, 3), (6, 64, 2, 3, 3), (5, 90, 4, 300, 3),
+             (4, 64, 3, 12, 5), (5, 65, 3, 11, 4), (6, 63, 3, 9, 2), (4, 40, 3, 7, 2)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("nb,T,N,Lt", [(4, 37, 3, 9), (5, 120, 5, 40), (6, 200, 7, 130), (6, 64, 2, 3), (5, 90, 4, 300)])
-def test_gpu_ctc_scans_are_the_oracles_bit_for_bit(nb, T, N, Lt):
+@pytest.mark.parametrize("nb,T,N,Lt,sl", GPU_CASES,
+                         ids=["%d-%d-%d-%d" % c[:4] + ("" if c[4] == 3 else "-sl%d" % c[4]) for c in GPU_CASES])
+def test_gpu_ctc_scans_are_the_oracles_bit_for_bit(nb, T, N, Lt, sl):
+    """At the state lengths other than 3 the ragged target lengths are Lt, state_len + 1 and state_len (a single
+    position)."""
     from xna_basecaller_amd import _lib
-    sl = 3
     rng = np.random.default_rng(Lt + nb)
-    sc = random_scores(T, N, nb, seed=T)
-    targets, lens = _targets(rng, N, Lt, nb, sl)
+    sc = random_scores(T, N, nb, sl=sl, seed=T)
+    targets, lens = _targets(rng, N, Lt, nb, sl, lens=None if sl == 3 else [Lt, sl + 1, sl])
     ctx = _lib.Context(0, nb, sl, 32, 19, 5, 5.0, 2.0, T * 5, N)
     got = ctx.ctc_logz(sc, targets, lens, want_grads=True)
     ref = oracle.ctc_logz(sc, targets, lens, nb, sl, want_grads=True)

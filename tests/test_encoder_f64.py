@@ -8,13 +8,15 @@ import os
 
 import numpy as np
 import pytest
+import torch
 
 import encoder_cases as EC
+import geometry_cases as GC
 import oracle
 from conftest import GOLDEN
 from encoder_f64 import (WEIGHTS, Reference, encode, outlier_weights, rnn, sensitive_weights, split_rows_exp, to_e4m3,
                          to_e4m3_tensor, to_f16, to_i8_rows)
-from xna_basecaller_amd.synthetic import seeded_weights
+from xna_basecaller_amd.synthetic import encoder_shapes, peaky_weights, seeded_state_dict, seeded_weights
 
 
 @pytest.mark.parametrize("name", ["f32_nb6", "f32_nb4_long", "f48_nb5", "f16_nb4"])
@@ -163,5 +165,157 @@ def test_discriminating_power(name):
             if (name, prec, d) in EC.EXCLUDED:
                 continue
             if ratio < EC.DISCRIMINATION:
+                weak.append((prec, d, round(ratio, 2)))
+    assert not weak, weak
+
+
+# ---- geometry: state lengths, windows and strides other than (3, 19, 5) -----------------------------------------------------
+def _seeded_weights_before(features, n_base, seed=25):
+    """seeded_weights as it was before it took state_len and winlen."""
+    keys, shapes = encoder_shapes(features, n_base)
+    return seeded_state_dict(keys, shapes, seed)
+
+
+def _peaky_weights_before(features, n_base, seed=25, input_gain=2.0, linear_gain=10.0, blank_bias=2.0):
+    """peaky_weights as it was before it took state_len and winlen."""
+    sd = _seeded_weights_before(features, n_base, seed)
+    for l in range(4, 9):
+        k = "encoder.%d.rnn.weight_ih_l0" % l
+        sd[k] = (sd[k] * np.float32(input_gain)).astype(np.float32)
+        sd["encoder.%d.rnn.bias_ih_l0" % l] = np.zeros_like(sd["encoder.%d.rnn.bias_ih_l0" % l])
+    sd["encoder.9.linear.weight"] = (sd["encoder.9.linear.weight"] * np.float32(linear_gain)).astype(np.float32)
+    sd["encoder.9.linear.bias"] = np.full_like(sd["encoder.9.linear.bias"], -np.float32(blank_bias))
+    return sd
+
+
+def _sensitive_before(features, nb, seed, outlier):
+    """encoder_f64._sensitive as it was before it took state_len and winlen."""
+    sd = _peaky_weights_before(features, nb, seed, blank_bias=3.0)
+    rng = np.random.default_rng(1000 + seed)
+    F = features
+    for l in range(5):
+        sd[rnn(l, "bias_ih_l0")] = (0.1 * rng.standard_normal(4 * F)).astype(np.float32)
+        sd[rnn(l, "bias_hh_l0")] = (0.1 * rng.standard_normal(4 * F) + np.repeat([0.0, 0.2, 0.0, 0.0], F)).astype(np.float32)
+    if outlier:
+        for k in sorted(sd):
+            a = sd[k].astype(np.float64).reshape(-1)
+            norm = np.sqrt((a ** 2).sum())
+            hit = rng.random(a.size) < 0.003
+            hit[rng.integers(a.size)] = True
+            a[hit] *= 8.0
+            if norm > 0:
+                a *= norm / np.sqrt((a ** 2).sum())
+            sd[k] = a.reshape(sd[k].shape).astype(np.float32)
+    return sd
+
+
+def _same_bytes(a, b):
+    return list(a) == list(b) and all(a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes()
+                                      for k in a)
+
+
+@pytest.mark.parametrize("features,nb", [(32, 4), (96, 6)])
+def test_default_geometry_weights_are_unchanged(features, nb):
+    """The full-size golden fixtures regenerate their weights from these helpers: with the default state_len and winlen
+    every tensor has the bytes it had before the helpers took them."""
+    seed = features + nb
+    assert _same_bytes(seeded_weights(features, nb, seed), _seeded_weights_before(features, nb, seed))
+    assert _same_bytes(seeded_weights(features, nb), _seeded_weights_before(features, nb))
+    assert _same_bytes(peaky_weights(features, nb, seed), _peaky_weights_before(features, nb, seed))
+    assert _same_bytes(peaky_weights(features, nb, seed, blank_bias=3.0, state_len=3, winlen=19),
+                       _peaky_weights_before(features, nb, seed, blank_bias=3.0))
+    assert _same_bytes(sensitive_weights(features, nb, seed), _sensitive_before(features, nb, seed, False))
+    assert _same_bytes(outlier_weights(features, nb, seed), _sensitive_before(features, nb, seed, True))
+    # and the geometry reaches the shapes
+    sd = outlier_weights(features, nb, seed, state_len=2, winlen=5)
+    assert sd["encoder.2.conv.weight"].shape == (features, 16, 5) and sd["encoder.9.linear.weight"].shape == (nb ** 3, features)
+
+
+def test_pad_defect_at_window_one_and_late_window():
+    F, nb = 32, 4
+    x = np.random.default_rng(2).standard_normal((3, 60))
+    r = Reference(x, sensitive_weights(F, nb, 3, state_len=2, winlen=1), nb, winlen=1, stride=2)
+    clean = r.run()
+    assert clean["scores"].shape == (30, 3, 64)
+    got = r.run(["pad:2"])                                   # no padding: nothing to take from the neighbours
+    assert got["scores"].shape == clean["scores"].shape and np.array_equal(got["conv"], clean["conv"])
+    with pytest.raises(ValueError):
+        r.run(["win:late"])
+    # win:late: the model on the signal advanced by one sample, except where the window meets the chunk's ends
+    r = Reference(x, sensitive_weights(F, nb, 3, state_len=2, winlen=5), nb, winlen=5, stride=3)
+    w = {k: torch.from_numpy(np.asarray(v, np.float64)) for k, v in r.w.items()}
+    late = r.run(["win:late"])["conv"]
+    clean = r.run()["conv"]
+    assert late.shape == clean.shape == (20, 3, F) and not np.array_equal(late, clean)
+    h = torch.from_numpy(x)[:, None, :]
+    for c in (0, 1):
+        h = torch.nn.functional.silu(torch.nn.functional.conv1d(h, w["encoder.%d.conv.weight" % c], w["encoder.%d.conv.bias" % c], padding=2))
+    h = torch.nn.functional.pad(h, (1, 3))                   # pad - 1 on the left, pad + 1 on the right
+    want = torch.nn.functional.silu(torch.nn.functional.conv1d(h, w["encoder.2.conv.weight"], w["encoder.2.conv.bias"], stride=3))
+    assert np.allclose(late, want.permute(2, 0, 1).numpy(), rtol=0, atol=1e-12)
+
+
+def test_geometry_table_is_complete():
+    need = {"windows": {1, 3, 5, 9, 31}, "strides": {1, 2, 3, 6, 8}, "T": {1, 32, 33, 64}, "O": {64, 125, 216, 1024, 3125, 4096}}
+    seen = {k: set() for k in need}
+    ragged_stride, ragged_batch, corner, short = set(), False, False, False
+    for name, (F, nb, sl, W, ST, L, N, weights) in GC.GEOMETRY_CASES.items():
+        assert F <= 96 and N <= 70 and L <= 1300 and W % 2 == 1 and 1 <= W <= 31 and 1 <= ST <= 8 and nb ** sl <= 1024
+        assert weights in WEIGHTS
+        seen["windows"].add(W), seen["strides"].add(ST), seen["T"].add(GC.steps(L, W, ST)), seen["O"].add(nb ** (sl + 1))
+        if L % ST:
+            ragged_stride.add(ST)
+        ragged_batch |= N in (65, 70) and nb ** (sl + 1) >= 1024
+        corner |= (W, ST) == (31, 8)
+        short |= W == 31 and L == ST
+    for k in need:
+        assert need[k] <= seen[k], (k, need[k] - seen[k])
+    assert {3, 6, 8} <= ragged_stride and ragged_batch and corner and short
+    assert set(GC.BOUNDS) == set(GC.MEASURED) == set(GC.GEOMETRY_CASES)
+    for name in GC.GEOMETRY_CASES:
+        assert set(GC.BOUNDS[name]) == set(GC.PRECISIONS)
+        for p in GC.PRECISIONS:                                # 2-3 x the measured error
+            assert all(2.0 * m <= b <= 3.0 * m for m, b in zip(GC.MEASURED[name][p], GC.BOUNDS[name][p]))
+    for (name, prec, d), (reason, ratio) in GC.EXCLUDED.items():
+        assert d in GC.catalogue(prec, GC.GEOMETRY_CASES[name][3]) and reason in EC.REASONS and ratio <= GC.DISCRIMINATION
+
+
+def _excluded_share(excluded, triples):
+    return len(excluded) / float(triples)
+
+
+def test_geometry_exclusions_stay_within_the_existing_share():
+    """The share of (row, precision, defect) triples left out of the discrimination check among the geometry rows may not
+    exceed the share among the cases of tests/encoder_cases.py."""
+    before = sum(len(EC.catalogue(p, EC.CASES[n][0])) for n in EC.CASES for p in EC.PRECISIONS)
+    geo = sum(len(GC.catalogue(p, GC.GEOMETRY_CASES[n][3])) for n in GC.GEOMETRY_CASES for p in GC.PRECISIONS)
+    assert _excluded_share(GC.EXCLUDED, geo) <= _excluded_share(EC.EXCLUDED, before), (len(GC.EXCLUDED), geo, len(EC.EXCLUDED), before)
+
+
+@functools.lru_cache(maxsize=None)
+def _geometry_deltas(name):
+    F, nb, sl, W, ST, L, N, weights = GC.GEOMETRY_CASES[name]
+    sd = WEIGHTS[weights](F, nb, GC.seed_of(name), state_len=sl, winlen=W)
+    x = np.random.default_rng(L + N + W).standard_normal((N, L)).astype(np.float32)
+    r = Reference(x[EC.picks(N)[:2]], sd, nb, winlen=W, stride=ST)
+    clean = r.run()["scores"]
+    out = {}
+    for d in sorted(set(sum((GC.catalogue(p, W) for p in GC.PRECISIONS), []))):
+        e = r.run([d])["scores"] - clean
+        out[d] = (float(np.abs(e).max()), float(np.sqrt((e ** 2).mean())))
+    return out
+
+
+@pytest.mark.parametrize("name", list(GC.GEOMETRY_CASES))
+def test_geometry_discriminating_power(name):
+    W = GC.GEOMETRY_CASES[name][3]
+    deltas = _geometry_deltas(name)
+    weak = []
+    for prec in GC.PRECISIONS:
+        bmax, brms = GC.BOUNDS[name][prec]
+        for d in GC.catalogue(prec, W):
+            dmax, drms = deltas[d]
+            ratio = max(dmax / bmax, drms / brms)
+            if (name, prec, d) not in GC.EXCLUDED and ratio < GC.DISCRIMINATION:
                 weak.append((prec, d, round(ratio, 2)))
     assert not weak, weak

@@ -8,6 +8,7 @@ import pytest
 
 import oracle
 from conftest import GOLDEN, random_scores, seeded_state_dict
+from pairs import PAIR_IDS, PAIRS
 
 
 def test_spec_math_accuracy():
@@ -68,9 +69,9 @@ def _backpointer_viterbi(Q, idx):
     return lab
 
 
-@pytest.mark.parametrize("nb", [4, 5, 6])
-def test_decode_against_float64_restatement(nb):
-    sl, T, N = 3, 64, 3
+@pytest.mark.parametrize("nb,sl", PAIRS, ids=PAIR_IDS)
+def test_decode_against_float64_restatement(nb, sl):
+    T, N = 64, 3
     sc = random_scores(T, N, nb, sl, seed=nb)
     out = oracle.decode(sc, nb, sl, want=("logz", "post", "alpha", "beta", "qlog"))
     P, logZ = _fp64_posteriors(sc, nb, sl)

@@ -6,6 +6,7 @@ import pytest
 import oracle
 from conftest import make_config, random_scores
 import qscore_ref
+from pairs import NEW_PAIRS
 
 F32 = np.float32
 
@@ -29,6 +30,26 @@ def test_restated_sequences_are_the_oracles():
     assert np.array_equal(got["seq"], seq) and np.array_equal(got["seq_len"], lens)
     assert np.array_equal(got["moves"], (got["labels"] != 0).astype(np.uint8))
     # qstring is packed in parallel with seq: the same count of non-zero bytes, all printable phred+33 characters
+    assert np.array_equal((got["qstring"] != 0).sum(axis=1), lens)
+    q = got["qstring"][got["qstring"] != 0]
+    assert q.min() >= 34 and q.max() <= 83
+
+
+@pytest.mark.parametrize("with_blank", [True, False])
+@pytest.mark.parametrize("nb,sl", NEW_PAIRS)
+def test_restatement_at_every_state_length(nb, sl, with_blank):
+    """The two checks above at the other state lengths: the rebuilt path is the oracle's, the packed rows are its pack."""
+    T, N, alphabet = 61, 3, "NACGTXY"[:nb + 1]
+    blank = None if with_blank else 2.0
+    sc = random_scores(T, N, nb, sl=sl, seed=40 + nb + sl, with_blank=with_blank)
+    f, ref = qscore_ref.path_edges(sc, nb, sl, blank_score=blank)
+    assert np.array_equal((f % (nb + 1)).astype(np.int8), ref["labels"])
+    assert f.min() >= 0 and f.max() < nb ** sl * (nb + 1)
+    got = qscore_ref.decode_q(sc, nb, alphabet, sl=sl, blank_score=blank)
+    assert np.array_equal(got["labels"], ref["labels"])
+    seq, _, lens = oracle.pack(got["labels"], alphabet)
+    assert np.array_equal(got["seq"], seq) and np.array_equal(got["seq_len"], lens)
+    assert np.array_equal(got["moves"], (got["labels"] != 0).astype(np.uint8))
     assert np.array_equal((got["qstring"] != 0).sum(axis=1), lens)
     q = got["qstring"][got["qstring"] != 0]
     assert q.min() >= 34 and q.max() <= 83

@@ -14,6 +14,7 @@ import pytest
 import oracle
 from conftest import ROOT, random_scores
 import ubprob_ref
+from pairs import NEW_PAIRS
 from test_qscores import _StubModel, _Read
 
 F32 = np.float32
@@ -131,6 +132,40 @@ def test_probabilities_sum_to_one(with_blank):
     # the bases, qualities and moves are those of the quality decode
     import qscore_ref
     q = qscore_ref.decode_q(sc, nb, "NACGTXY", blank_score=None if with_blank else 2.0)
+    for k in ("seq", "qstring", "moves", "seq_len"):
+        assert np.array_equal(got[k], q[k])
+
+
+@pytest.mark.parametrize("with_blank", [True, False])
+@pytest.mark.parametrize("nb,sl", NEW_PAIRS)
+def test_restatement_at_every_state_length(nb, sl, with_blank):
+    """The state lengths other than 3 (nb^(sl - 1) = 4 .. 256 sources per letter: fewer than the 16 summing lanes, and
+    many rounds of them): the posteriors and the letter mass against float64 (autograd posteriors and their float64
+    sums), probabilities that sum to one, and the quality decode's bases, qualities and moves.  Tolerance 1e-4, the one
+    tests/test_oracle.py holds the oracle's posteriors to on these scores: in the fp32 log domain the exponent
+    alpha + M + beta - logZ carries the rounding of numbers of size |logZ| ~ 6 T = 240, i.e. 240 x 2^-24 = 1.4e-5 relative
+    on a posterior of up to 1, and a letter's mass is a sum of posteriors that total at most 1."""
+    import qscore_ref
+    from test_oracle import _fp64_posteriors
+    T, N, alphabet = 40, 2, "NACGTXY"[:nb + 1]
+    S, E = nb ** sl, nb + 1
+    blank = None if with_blank else 2.0
+    sc = random_scores(T, N, nb, sl=sl, seed=9 + nb + sl, with_blank=with_blank)
+    got = ubprob_ref.decode_ub(sc, nb, alphabet, sl=sl, blank_score=blank)
+    # the float64 posteriors take the layout with the blank column; the blank-less run above adds the same constant 2.0
+    # (random_scores' blank and blank_score), so one float64 result serves both layouts
+    post64, _ = _fp64_posteriors(random_scores(T, N, nb, sl=sl, seed=9 + nb + sl), nb, sl)
+    assert np.abs(got["post"] - post64).max() < 1e-4
+    e64 = post64.reshape(T, N, S, E)[..., 1:].sum(axis=2)
+    assert np.abs(got["e"] - e64).max() < 1e-4
+    for n in range(N):
+        L = got["seq_len"][n]
+        assert L > 0
+        assert np.abs(got["prob"][n, :, :L].astype(np.float64).sum(axis=0) - 1.0).max() < 1e-6
+        tot = got["probs"][n, :, :L].astype(int).sum(axis=0)
+        assert np.all(tot <= 256) and np.all(tot > 256 - nb)
+        assert not got["probs"][n, :, L:].any()
+    q = qscore_ref.decode_q(sc, nb, alphabet, sl=sl, blank_score=blank)
     for k in ("seq", "qstring", "moves", "seq_len"):
         assert np.array_equal(got[k], q[k])
 

@@ -49,12 +49,12 @@ def seeded_state_dict(keys, shapes, seed):
     return out
 
 
-def seeded_weights(features, n_base, seed=25):
-    keys, shapes = encoder_shapes(features, n_base)
+def seeded_weights(features, n_base, seed=25, state_len=3, winlen=19):
+    keys, shapes = encoder_shapes(features, n_base, state_len, winlen)
     return seeded_state_dict(keys, shapes, seed)
 
 
-def peaky_weights(features, n_base, seed=25, input_gain=2.0, linear_gain=10.0, blank_bias=2.0):
+def peaky_weights(features, n_base, seed=25, input_gain=2.0, linear_gain=10.0, blank_bias=2.0, state_len=3, winlen=19):
     """Seeded weights whose scores DEPEND on the signal and whose posteriors are peaky -- the regime of a trained
     basecaller, where end-to-end label identity can be asserted (tests/test_gpu_fullsize.py, tools/peaky_parity.py).
     With the plain seeded weights the five random LSTM layers damp the time-varying part of the signal to ~1e-3 of a
@@ -66,7 +66,7 @@ def peaky_weights(features, n_base, seed=25, input_gain=2.0, linear_gain=10.0, b
     per 2000 steps) and the scores move by ~0.5 from step to step.  The model is ~10x more sensitive to
     rounding than the plain seeded one (a 1e-6 relative change of the signal moves a score by up to 4e-5); measured with the
     oracle, tools/peaky_parity.py prints the numbers."""
-    sd = seeded_weights(features, n_base, seed)
+    sd = seeded_weights(features, n_base, seed, state_len, winlen)
     for l in range(4, 9):
         k = "encoder.%d.rnn.weight_ih_l0" % l
         sd[k] = (sd[k] * np.float32(input_gain)).astype(np.float32)
