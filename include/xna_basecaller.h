@@ -469,6 +469,60 @@ XB_API int xb_ctc_chunks(xb_ctx *ctx, const float *signal, int n, const char *al
                          uint8_t *ops, int32_t *n_ops, int32_t *mlen, int32_t *blen, uint8_t *verdict, uint8_t *target,
                          int32_t *target_len);
 
+/* ---- per-position UB accuracy of mapped rows (`basecaller --ub-report`, `analyze`) ----------------------------------------
+ * The third stage of the reference's evaluation (eval_model.sh:91-177) is src/tools/analyze_paf.py -p over minimap2's PAF:
+ * Python loops per read (utils.py:112-191 compute_read_matches, :661-725 polish_target_matches, :727-924 the errors and the
+ * UB-area metrics, analyze_paf.py:520-536 the confusion matrix).  Here the mapping is xb_map_templates', so there is nothing to
+ * pin the whole to: PARITY UNPINNED; the contract below restates those loops over the mapper's outputs and the kernel is
+ * equal, integer for integer, to a CPU restatement of it (tests/ubtally_ref.py).
+ *   inputs     the rows the mapper saw: seq (n, W) int8 ASCII, left-packed, and seq_len (clamped to [0, W]); the mapper's tmpl,
+ *              strand, q_st, r_st, r_en, ops (n, W + Lmax), n_ops; the library as xb_map_templates takes it (HOST pointers; the
+ *              context's cached device image is reused).  n_ops is clamped to [0, W + Lmax], r_st / r_en to 0 <= r_st <= r_en <=
+ *              L (L = the template's length), q_st to [0, seq_len].  A row whose tmpl lies outside [0, R) is unmapped: its counts
+ *              are zero and it adds nothing to the accumulators.  strand < 0 is the reverse strand, anything else the forward.
+ *   target     T[j], j in [0, L): the template letter in upper case when it is one of A C G T, 'X' otherwise -- every non-ACGT
+ *              byte is a UB site (the mapper's letter contract; the reference replaces 'N' alone).
+ *   query      Q[i] on the aligned strand: strand +1 the row with a-z in upper case; strand -1 that row reversed, with A <-> T,
+ *              C <-> G and X <-> Y (utils.py:26-31), every other byte unchanged.  NOT the mapper's own reverse strand, which
+ *              complements codes and leaves X and Y what they are: there both are "ambiguous" either way, here a called X on
+ *              the reverse strand is a Y of the template's strand.
+ *   called     C[0 .. L), all '-' to start with; the columns ops[0 .. n_ops) are walked from ri = r_st, qi = q_st: '=' or 'X':
+ *              C[ri] = Q[qi], both advance; 'I': qi advances; 'D': ri advances.  A column that needs a row letter when qi has
+ *              reached seq_len, or a template position when ri has reached r_en, or that holds any other byte, ends the walk.
+ *   polish     P = a copy of C, then for every UB site u (T[u] == 'X') in ascending order -- the conditions read C, the letter
+ *              that moves is read from P, as the reference does:
+ *                (a) C[u] == 'X': nothing;
+ *                (b) C[u] == '-': with lo .. hi the run of '-' in C that contains u: if lo > 0 and C[lo-1] == 'X', P[lo-1] = '-'
+ *                    and P[u] = 'X'; else if hi < L-1 and C[hi+1] == 'X', P[hi+1] = '-' and P[u] = 'X';
+ *                (c) else if 1 <= u < L-1, C[u-1] == '-' and C[u+1] == 'X': P[u-1] = P[u], P[u] = 'X', P[u+1] = '-';
+ *                (d) else if 1 <= u < L-1, C[u+1] == '-' and C[u-1] == 'X': P[u+1] = P[u], P[u] = 'X', P[u-1] = '-'.
+ *              Where the reference's indices run off an end (Python wraps around or raises) the branch does not apply.
+ *   errors     e[j] = (P[j] != T[j]) for every j in [0, L); positions outside [r_st, r_en) are '-' and count as errors.
+ *   masks      ub[j] = (T[j] == 'X'); area[j] = not ub[j] and some UB site u has |j - u| <= 5 (clipped to [0, L)).
+ *   counts     (n, 8) int32 per row: n_match = L - sum(e), ub_matches, ub_len, ub_area_matches, ub_area_len, non_ub_area_matches,
+ *              non_ub_area_len (neither ub nor area), ubs_detected = the number of j with P[j] in {X, Y}.
+ * Accumulators -- the call ADDS to them, the caller zeroes them:
+ *   reads      (R, 2) int32: rows per (template, strand); strand index 0 is +, 1 is -.
+ *   err        (2, sum(L)) int32: err[s][offsets[t] + p] += e[j] with p = j on +, p = L-1-j on - (errors[::-1], utils.py:764-765).
+ *   cm         (6, 7) int64: rows = the target letter in the order A T C G X Y, columns = the called letter A T C G X Y '-', over
+ *              every j: on + the pair (T[j], P[j]), on - the pair after complementing both with the X <-> Y table (a UB site is
+ *              row Y there); a called byte outside the seven is not counted.
+ * Everything is an integer, so the result does not depend on the order of the additions.  Limits: the mapper's -- W <= 4096,
+ * templates of 1 .. 4096 letters, a library of at most 2^20 letters (XB_ERR_INVALID with the figures otherwise; the context
+ * stays usable).  One launch on the main stream, one wavefront per row, T, C and P in LDS; not a stage of xb_get_stage_times.
+ * The _dev form takes device pointers for the rows, the mapper's outputs, counts and the accumulators and returns without
+ * waiting (xb_synchronize); the host form uploads, runs, waits and copies back -- the accumulators come back as they went in
+ * plus this call's additions.
+ */
+XB_API int xb_ub_tally(xb_ctx *ctx, const int8_t *seq, const int32_t *seq_len, int n, int W, const char *templates,
+                       const int32_t *offsets, int R, const int32_t *tmpl, const int8_t *strand, const int32_t *q_st,
+                       const int32_t *r_st, const int32_t *r_en, const uint8_t *ops, const int32_t *n_ops, int32_t *counts,
+                       int32_t *reads, int32_t *err, int64_t *cm);
+XB_API int xb_ub_tally_dev(xb_ctx *ctx, const int8_t *d_seq, const int32_t *d_seq_len, int n, int W, const char *templates,
+                           const int32_t *offsets, int R, const int32_t *d_tmpl, const int8_t *d_strand, const int32_t *d_q_st,
+                           const int32_t *d_r_st, const int32_t *d_r_en, const uint8_t *d_ops, const int32_t *d_n_ops,
+                           int32_t *d_counts, int32_t *d_reads, int32_t *d_err, int64_t *d_cm);
+
 /* ---- DTW signal segmentation of ctc-data (an extension of the device path: `segment`) --------------------------------
  * The reference's src/tools/dtw_segmentation.py aligns every training chunk to the expected current levels of its reference
  * sequence with dtw-python (dtw(chunk, reference, step_pattern=my_asymmetric, window_type='slantedband'), :128-202) on the

@@ -1,10 +1,11 @@
 """`python -m xna_basecaller_amd basecaller MODEL_DIR READS_DIR ...` == `bonito basecaller ...`, and `... evaluate MODEL_DIR
 --directory CTC_DATA` == `bonito evaluate ...` (bonito/__init__.py:10-33); `... segment CTC_DATA` == the reference's
-`src/tools/dtw_segmentation.py CTC_DATA`."""
+`src/tools/dtw_segmentation.py CTC_DATA`; `... analyze LIB.fasta CALLS.paf -R CALLS.fastq` == the reference's
+`src/tools/analyze_paf.py -p`."""
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 
 from . import __version__
-from .cli import basecaller, evaluate, segment
+from .cli import analyze, basecaller, evaluate, segment
 
 
 def main():
@@ -19,6 +20,8 @@ def main():
     p.set_defaults(func=evaluate.main)
     p = sub.add_parser("segment", parents=[segment.argparser()])
     p.set_defaults(func=segment.main)
+    p = sub.add_parser("analyze", parents=[analyze.argparser()])
+    p.set_defaults(func=analyze.main)
     args = parser.parse_args()
     args.func(args)
 

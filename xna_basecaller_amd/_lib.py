@@ -31,7 +31,7 @@ EXPORTS = [
     "xb_decode_q", "xb_decode_q_dev", "xb_basecall_chunks_q", "xb_submit_chunks_q", "xb_collect_chunks_q",
     "xb_decode_ub", "xb_decode_ub_dev", "xb_basecall_chunks_ub", "xb_submit_chunks_ub", "xb_collect_chunks_ub",
     "xb_map_templates", "xb_map_templates_dev", "xb_ctc_targets", "xb_ctc_targets_dev", "xb_ctc_chunks",
-    "xb_dtw_segment", "xb_dtw_segment_dev", "xb_dtw_scratch_bytes",
+    "xb_ub_tally", "xb_ub_tally_dev", "xb_dtw_segment", "xb_dtw_segment_dev", "xb_dtw_scratch_bytes",
 ]
 XB_COMM_ID_BYTES = 128
 # xb_status (include/xna_basecaller.h)
@@ -128,6 +128,8 @@ def load():
     lib.xb_ctc_targets.argtypes = [vp, vp, ip, ip, C.c_char_p, vp, ip] + [vp] * 8 + [db, db, ip, ip, ip] + [vp] * 5
     lib.xb_ctc_targets_dev.argtypes = lib.xb_ctc_targets.argtypes
     lib.xb_ctc_chunks.argtypes = [vp, vp, ip, C.c_char_p, C.c_char_p, vp, ip] + [ip] * 5 + [db, db, ip, ip, ip] + [vp] * 17
+    lib.xb_ub_tally.argtypes = [vp, vp, vp, ip, ip, C.c_char_p, vp, ip] + [vp] * 11
+    lib.xb_ub_tally_dev.argtypes = lib.xb_ub_tally.argtypes
     lib.xb_dtw_segment.argtypes = [vp, vp, ip, ip, vp, vp, ip, vp, ip, vp, vp, vp]
     lib.xb_dtw_segment_dev.argtypes = lib.xb_dtw_segment.argtypes
     lib.xb_dtw_scratch_bytes.argtypes = [vp]
@@ -227,6 +229,18 @@ class _OneCallAtATime:
         call = _Locked(getattr(self._lib, name), self._lock)
         setattr(self, name, call)
         return call
+
+
+class UbAccumulators:
+    """The accumulators of xb_ub_tally for a library with `offsets` (R + 1): reads (R, 2) int32 rows per (template, strand),
+    err (2, sum(L)) int32 errors per (strand, template position), cm (6, 7) int64 confusion matrix; zero to start with."""
+    __slots__ = ("reads", "err", "cm")
+
+    def __init__(self, offsets):
+        offsets = np.asarray(offsets)
+        self.reads = np.zeros((offsets.size - 1, 2), np.int32)
+        self.err = np.zeros((2, int(offsets[-1])), np.int32)
+        self.cm = np.zeros((6, 7), np.int64)
 
 
 class Context:
@@ -559,6 +573,40 @@ class Context:
                                            *[out[k].ctypes.data for k, _ in self.CTC_OUTPUTS]))
         return out
 
+    # ---- per-position UB accuracy of mapped rows (xb_ub_tally): parity unpinned ----------
+    UB_INPUTS = ("tmpl", "strand", "q_st", "r_st", "r_en", "ops", "n_ops")
+    UB_COUNTS = ("n_match", "ub_matches", "ub_len", "ub_area_matches", "ub_area_len", "non_ub_area_matches", "non_ub_area_len",
+                 "ubs_detected")
+
+    def ub_tally(self, rows, lens, got, library, offsets, acc=None):
+        """xb_ub_tally: the rows the mapper saw (rows (n, W) int8, lens (n)) and its outputs `got` (map_templates' dict) ->
+        (counts (n, 8) int32 in the order UB_COUNTS, acc): acc is a UbAccumulators (a fresh one when None) that this call has
+        added to, to be passed on from call to call."""
+        rows = np.ascontiguousarray(rows, dtype=np.int8)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        n, W = rows.shape
+        acc = UbAccumulators(off) if acc is None else acc
+        if acc.err.shape != (2, int(off[-1])) or acc.reads.shape != (off.size - 1, 2):
+            raise ValueError("ub_tally: the accumulators belong to another library")
+        dts = dict(self.MAP_OUTPUTS)
+        ins = [np.ascontiguousarray(got[k], dtype=dts[k]) for k in self.UB_INPUTS]
+        if lens.shape != (n,) or ins[5].shape != (n, W + int(np.diff(off).max())):
+            raise ValueError("ub_tally: ops is %s, (n, width + longest template) expected" % (ins[5].shape,))
+        counts = np.empty((n, len(self.UB_COUNTS)), np.int32)
+        self._check(self.lib.xb_ub_tally(self.h, rows.ctypes.data, lens.ctypes.data, n, W, bytes(library), off.ctypes.data, off.size - 1,
+                                         *[a.ctypes.data for a in ins], counts.ctypes.data, acc.reads.ctypes.data,
+                                         acc.err.ctypes.data, acc.cm.ctypes.data))
+        return counts, acc
+
+    def ub_tally_dev(self, d_rows, d_lens, n, width, d_got, library, offsets, d_counts, d_reads, d_err, d_cm):
+        """xb_ub_tally_dev: device pointers for the rows, the mapper's outputs (d_got: name -> pointer, UB_INPUTS), counts and
+        the three accumulators; returns without waiting."""
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        self._check(self.lib.xb_ub_tally_dev(self.h, _ptr(d_rows), _ptr(d_lens), int(n), int(width), bytes(library), off.ctypes.data,
+                                             off.size - 1, *[_ptr(d_got[k]) for k in self.UB_INPUTS], _ptr(d_counts), _ptr(d_reads),
+                                             _ptr(d_err), _ptr(d_cm)))
+
     # ---- DTW signal segmentation (xb_dtw_segment): an extension, parity unpinned ----------
     @staticmethod
     def _dtw_offsets(levels):
@@ -653,6 +701,13 @@ class Context:
         ln = (C.c_int64 * 5)()
         self._check(self.lib.xb_get_stage_times(self.h, ms, ln))
         return {k: (float(ms[i]), int(ln[i])) for i, k in enumerate(XB_STAGE_NAMES)}
+
+
+def mapper_context(device=0):
+    """A Context for the entry points that need no model (xb_map_templates, xb_ctc_targets, xb_ub_tally): xb_ctx_create
+    wants a model geometry, so this is the smallest one it accepts -- 4 bases, 32 features, one chunk of 200 samples --
+    and no weights are ever loaded into it."""
+    return Context(device, 4, 3, 32, 19, 5, 5.0, 2.0, 200, 1)
 
 
 class Comm:

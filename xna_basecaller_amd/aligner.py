@@ -147,6 +147,7 @@ class TemplateAligner:
         self.offsets[1:] = np.cumsum([len(t) for t in self.templates])
         self.batch = int(batch)
         self._device, self._context, self._own = device, context, None
+        self.ub_report = None                      # `--ub-report`: a ubreport.Report that map() feeds after every mapper call
 
     @classmethod
     def from_config(cls, path, config, **kwargs):
@@ -161,7 +162,7 @@ class TemplateAligner:
             return ctx
         if self._own is None:
             _lib.require_gpu()
-            self._own = _lib.Context(self._device, 4, 3, 32, 19, 5, 5.0, 2.0, 200, 1)     # the mapper needs no model
+            self._own = _lib.mapper_context(self._device)
         return self._own
 
     def close(self):
@@ -203,15 +204,22 @@ class TemplateAligner:
                 yield at + k, got, lab, k
             at += len(take)
 
-    def _call(self, seqs):
+    @staticmethod
+    def _pack(seqs):
+        """Called strings as the mapper's rows: (n, W) int8 left-packed, W a multiple of 16, and their lengths."""
         width = max(16, -(-max(len(s) for s in seqs) // 16) * 16)
         rows = np.zeros((len(seqs), width), np.int8)
         for r, s in enumerate(seqs):
             rows[r, :len(s)] = np.frombuffer(s.encode("ascii"), np.int8)
-        lens = np.array([len(s) for s in seqs], np.int32)
+        return rows, np.array([len(s) for s in seqs], np.int32)
+
+    def _call(self, seqs):
+        rows, lens = self._pack(seqs)
         return self.context().map_templates(rows, lens, self.library, self.offsets, self.scoring)
 
-    def map(self, sequences):
+    def map(self, sequences, read_ids=None):
+        """[Mapping | None] per sequence.  With a ub_report set, the rows of every mapper call also go through xb_ub_tally
+        (read_ids name them in the report)."""
         sequences = list(sequences)
         out = [None] * len(sequences)
         todo = [i for i, s in enumerate(sequences) if 0 < len(s) <= MAX_ROW]
@@ -226,7 +234,10 @@ class TemplateAligner:
             fit = int(CELL_BUDGET // (2.0 * max(16, width) * len(self.library)))
             if 0 < fit < len(take):                 # fit == 0: one row is over the budget -- the library's refusal says so
                 take = take[:fit]
-            got = self._call([sequences[i] for i in take])
+            rows, lens = self._pack([sequences[i] for i in take])
+            got = self.context().map_templates(rows, lens, self.library, self.offsets, self.scoring)
+            if self.ub_report is not None:
+                self.ub_report.add(self.context(), rows, lens, got, [read_ids[i] if read_ids is not None else str(i) for i in take])
             for k, i in enumerate(take):
                 out[i] = self.mapping(got, k, sequences[i])
             at += len(take)
@@ -239,7 +250,9 @@ def align_map(aligner, results, batch=256):
     held = []
 
     def flush():
-        for (read, res), m in zip(held, aligner.map([res["sequence"] for _, res in held])):
+        ids = [read.read_id for read, _ in held] if getattr(aligner, "ub_report", None) is not None else None
+        seqs = [res["sequence"] for _, res in held]
+        for (read, res), m in zip(held, aligner.map(seqs) if ids is None else aligner.map(seqs, ids)):
             yield read, dict(res, mapping=m)
         held.clear()
 

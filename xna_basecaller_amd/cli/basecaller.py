@@ -10,7 +10,8 @@ ctc-data directory beside stdout (io.CTCWriter) -- it refuses --revcomp, --qscor
 and a library with unnatural positions under a model that cannot call them; --reference FASTA maps every call to a
 TEMPLATE LIBRARY on the device (aligner.py: exhaustive alignment, this package's own contract, not minimap2) and, as in
 the reference, makes SAM the default output;
---paf PATH (an extension) writes the mappings as PAF beside it; under torchrun (WORLD_SIZE > 1) reads are sharded over the
+--paf PATH (an extension) writes the mappings as PAF beside it; --ub-report PREFIX (an extension) tallies the mapped calls'
+per-position UB accuracy on the device (xb_ub_tally) and writes the reference's analyze_paf.py figures; under torchrun (WORLD_SIZE > 1) reads are sharded over the
 ranks and gathered to rank 0 over RCCL before writing.  Extension: --qscores writes the Viterbi decode's device
 qualities (xb_decode_q) in place of the reference's placeholder 'O'; --ub-probs adds per-base probabilities of every
 letter outside A, C, G, T as `u<letter>:B:C` tags (xb_decode_ub); without them the output is unchanged.
@@ -148,6 +149,19 @@ def _save_ctc_early_refusal(args, world):
     return save_ctc_refusal(args, world, labels, library)
 
 
+def ub_report_refusal(args, world=1):
+    """Why `--ub-report` cannot run with these arguments (the message, without the "> " prefix), or None."""
+    if not args.ub_report:
+        return None
+    if not args.reference:
+        return "error: --ub-report tallies the mappings of --reference"
+    if world > 1:
+        return "error: --ub-report runs on one GPU (WORLD_SIZE is %d): the tallies are not gathered across ranks" % world
+    if args.save_ctc:
+        return "error: --ub-report reports on whole reads; --save-ctc maps chunks"
+    return None
+
+
 def reader_procs(world=1):
     """Reader workers of this rank: the reference's 8 (cli/basecaller.py:107-111) when the host has them to give -- the cores
     this process may run on, divided by the ranks that share the node (LOCAL_WORLD_SIZE under torchrun, else the world size),
@@ -169,6 +183,10 @@ def main(args):
     # initialises HIP and starts runtime threads) is only joined once the pool exists.  Under torchrun every rank only
     # ever loads its own shard of the reads.
     rank, world = xdist.env_rank_world()
+    why = ub_report_refusal(args, world)
+    if why is not None:
+        sys.stderr.write("> %s\n" % why)
+        exit(1)
     if args.save_ctc:
         why = _save_ctc_early_refusal(args, world)
         if why is not None:
@@ -248,6 +266,9 @@ def main(args):
                        chunksize=model.config["basecaller"]["chunksize"],
                        overlap=model.config["basecaller"]["overlap"], **extra)
 
+    if args.ub_report:                  # --ub-report (an extension): every mapper call's rows also go through xb_ub_tally
+        from ..ubreport import Report
+        aligner.ub_report = Report(aligner.names, aligner.templates)
     if aligner is not None:             # every rank maps its own reads, before the gather
         from ..aligner import align_map
         results = align_map(aligner, results)
@@ -270,6 +291,9 @@ def main(args):
         aligner.close()
     if writer.error is not None:
         raise writer.error
+    if args.ub_report:
+        for path in aligner.ub_report.write(args.ub_report):
+            sys.stderr.write("> ub report: %s\n" % path)
     duration = perf_counter() - t0
     num_samples = sum(num_samples for read_id, num_samples in writer.log)
 
@@ -325,6 +349,10 @@ def argparser():
     parser.add_argument("--reference", help="FASTA of a template library: every call is mapped to it on the device (exhaustive "
                         "local alignment, both strands; libraries up to 2^20 letters, templates up to 4096)")
     parser.add_argument("--paf", help="with --reference: also write the mappings as PAF to this file; not in the reference CLI")
+    parser.add_argument("--ub-report", metavar="PREFIX",
+                        help="with --reference: per-position UB accuracy of the mapped calls, tallied on the device, as "
+                             "PREFIX.csv, PREFIX-by_tar.csv, PREFIX-by_read.csv.gz and PREFIX-confusion_matrix.npy (the figures of "
+                             "the reference's analyze_paf.py -p); not in the reference CLI")
     parser.add_argument("--modified-bases", nargs="+")
     parser.add_argument("--modified-base-model")
     parser.add_argument("--read-ids")

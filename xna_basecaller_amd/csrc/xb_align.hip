@@ -86,7 +86,8 @@ extern "C" XB_API int xb_align_accuracy(const char *ref, int ref_len, const char
 
 // ---------------------------------------------------------------------------------------------------------------------
 // xb_map_templates: exhaustive local alignment of every called row against every template, both strands (contract: the
-// public header).  Two kernels.  xb_ctc_targets, the ctc-data verdict and label row of a mapped row, follows them.
+// public header).  Two kernels.  xb_ctc_targets, the ctc-data verdict and label row of a mapped row, follows them, and
+// xb_ub_tally, the per-position UB accuracy tallies of a mapped row, follows that.
 //
 // Score pass: grid (read, template chunk), a workgroup stages its chunk's template codes and the read's codes in LDS once,
 // its waves take the (template, strand) pairs of the chunk in turn.  One wave runs one pair as a systolic array: the
@@ -481,6 +482,214 @@ __global__ __launch_bounds__(64) void ctc_targets_kernel(const xb::CtcTargetPara
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// xb_ub_tally: the per-read half of the reference's analyze_paf.py -p (compute_read_matches, polish_target_matches,
+// compute_errors_paf and the UB-area metrics of utils.py, the confusion matrix of analyze_paf.py:520-536) over the mapper's
+// outputs.  One workgroup of one wave per row; the template's letters T, the called letters C and their polished copy P
+// live in LDS, a byte per template position each.
+//   walk      64 alignment columns per step, one per lane: the row and template positions of a column are the counts of
+//             row-consuming / template-consuming columns before it (two ballots and a masked popcount), so every '=' / 'X'
+//             column stores its called letter at once; the first column that leaves a range ends the walk for the lanes
+//             behind it
+//   polish    the UB sites in ascending order, found by a ballot per 64 positions; the conditions read C, which no longer
+//             changes, so every lane evaluates them (the '-' run around a deleted site is scanned 64 positions a step);
+//             lane 0 alone reads and writes P, in order
+//   tallies   per lane over its positions, one wave sum per count; an atomic per wrong position into err, the confusion
+//             cells summed in LDS first, then one atomic per non-zero cell
+constexpr int UB_LDS_BYTES = xb::MAP_MAX_TEMPLATE;
+constexpr int UB_CM_CELLS = xb::UB_CM_ROWS * xb::UB_CM_COLS;
+
+// index of a called byte in the confusion matrix's column order A T C G X Y '-', -1 for any other byte; the complement on
+// the reverse strand (A <-> T, C <-> G, X <-> Y, '-' stays) is index ^ 1 below 6
+__device__ inline int ub_letter_index(unsigned c)
+{
+    switch (c) {
+    case 'A': return 0;
+    case 'T': return 1;
+    case 'C': return 2;
+    case 'G': return 3;
+    case 'X': return 4;
+    case 'Y': return 5;
+    case '-': return 6;
+    default: return -1;
+    }
+}
+
+// the row's letter at position i of the aligned strand: upper case, on strand -1 read from the far end and complemented
+// with the X <-> Y table
+__device__ inline unsigned ub_query_letter(const int8_t *row, int sl, int i, bool minus)
+{
+    unsigned c = (unsigned)(uint8_t)row[minus ? sl - 1 - i : i];
+    if (c >= 'a' && c <= 'z') c -= 32u;
+    if (minus) {
+        switch (c) {
+        case 'A': c = 'T'; break;
+        case 'T': c = 'A'; break;
+        case 'C': c = 'G'; break;
+        case 'G': c = 'C'; break;
+        case 'X': c = 'Y'; break;
+        case 'Y': c = 'X'; break;
+        default: break;
+        }
+    }
+    return c;
+}
+
+// ones of m from bit 0 up to the first zero
+__device__ inline int ub_low_ones(unsigned long long m) { return ~m == 0ull ? 64 : __ffsll((unsigned long long)~m) - 1; }
+
+// the run of '-' in c[0, L) that contains u (c[u] == '-'): every lane calls, every lane gets [*lo, *hi]
+__device__ inline void ub_gap_run(const uint8_t *c, int u, int L, int lane, int *lo, int *hi)
+{
+    int l = u, h = u;
+    for (int b = u - 1; b >= 0; b -= 64) {
+        const int j = b - lane;
+        const int ones = ub_low_ones(__ballot(j >= 0 && c[j >= 0 ? j : 0] == '-'));
+        l = b - ones + 1;
+        if (ones < 64) break;
+    }
+    for (int b = u + 1; b < L; b += 64) {
+        const int j = b + lane;
+        const int ones = ub_low_ones(__ballot(j < L && c[j < L ? j : L - 1] == '-'));
+        h = b + ones - 1;
+        if (ones < 64) break;
+    }
+    *lo = l;
+    *hi = h;
+}
+
+__global__ __launch_bounds__(64) void ub_tally_kernel(const xb::UbTallyParams p)
+{
+    __shared__ uint8_t T[UB_LDS_BYTES], Cc[UB_LDS_BYTES], P[UB_LDS_BYTES];
+    __shared__ unsigned cells[UB_CM_CELLS];
+    const int r = blockIdx.x, lane = threadIdx.x;
+    int32_t *cnt = p.counts + (size_t)r * xb::UB_COUNTS;
+    const int t = p.tmpl[r];
+    if (t < 0 || t >= p.R) {                           // unmapped: zeros, nothing accumulated (the whole wave leaves)
+        if (lane < xb::UB_COUNTS) cnt[lane] = 0;
+        return;
+    }
+    int sl = p.seq_len[r];
+    sl = sl < 0 ? 0 : (sl > p.W ? p.W : sl);
+    int nops = p.n_ops[r];
+    nops = nops < 0 ? 0 : (nops > p.cap ? p.cap : nops);
+    const int tb = p.toff[t], L = p.toff[t + 1] - tb;
+    int r0 = p.r_st[r], r1 = p.r_en[r], q0 = p.q_st[r];
+    r0 = r0 < 0 ? 0 : (r0 > L ? L : r0);
+    r1 = r1 < r0 ? r0 : (r1 > L ? L : r1);
+    q0 = q0 < 0 ? 0 : (q0 > sl ? sl : q0);
+    const bool minus = p.strand[r] < 0;
+
+    for (int j = lane; j < L; j += 64) {
+        const unsigned c = p.tcodes[tb + j];
+        T[j] = c < 4u ? (uint8_t)"ACGT"[c] : (uint8_t)'X';
+        Cc[j] = '-';
+    }
+    if (lane < UB_CM_CELLS) cells[lane] = 0u;
+    __syncthreads();
+
+    // the walk
+    {
+        const uint8_t *ops = p.ops + (size_t)r * p.cap;
+        const int8_t *row = p.seq + (size_t)r * p.W;
+        const unsigned long long below = (1ull << lane) - 1ull;
+        int qb = q0, rb = r0;
+        for (int k0 = 0; k0 < nops; k0 += 64) {
+            const int k = k0 + lane;
+            const bool in = k < nops;
+            const unsigned op = in ? ops[k] : 0u;
+            const bool both = op == '=' || op == 'X';
+            const bool isq = both || op == 'I', isr = both || op == 'D';
+            const unsigned long long mq = __ballot(isq), mr = __ballot(isr);
+            const int qi = qb + __popcll(mq & below), ri = rb + __popcll(mr & below);
+            const bool stop = in && ((!isq && !isr) || (isq && qi >= sl) || (isr && ri >= r1));
+            const unsigned long long ms = __ballot(stop);
+            const int first = ms ? __ffsll(ms) - 1 : 64;
+            if (both && lane < first) Cc[ri] = (uint8_t)ub_query_letter(row, sl, qi, minus);
+            if (ms) break;
+            qb += __popcll(mq);
+            rb += __popcll(mr);
+        }
+    }
+    __syncthreads();
+    for (int j = lane; j < L; j += 64) P[j] = Cc[j];
+    __syncthreads();
+
+    // the polish
+    for (int j0 = 0; j0 < L; j0 += 64) {
+        const int j = j0 + lane;
+        unsigned long long sites = __ballot(j < L && T[j < L ? j : 0] == 'X');
+        while (sites) {
+            const int u = j0 + __ffsll(sites) - 1;
+            sites &= sites - 1ull;
+            const unsigned cu = Cc[u];
+            if (cu == 'X') continue;
+            if (cu == '-') {
+                int lo, hi;
+                ub_gap_run(Cc, u, L, lane, &lo, &hi);
+                if (lane == 0) {
+                    if (lo > 0 && Cc[lo - 1] == 'X') { P[lo - 1] = '-'; P[u] = 'X'; }
+                    else if (hi < L - 1 && Cc[hi + 1] == 'X') { P[hi + 1] = '-'; P[u] = 'X'; }
+                }
+            } else if (u >= 1 && u < L - 1 && lane == 0) {
+                if (Cc[u - 1] == '-' && Cc[u + 1] == 'X') { P[u - 1] = P[u]; P[u] = 'X'; P[u + 1] = '-'; }
+                else if (Cc[u + 1] == '-' && Cc[u - 1] == 'X') { P[u + 1] = P[u]; P[u] = 'X'; P[u - 1] = '-'; }
+            }
+        }
+    }
+    __syncthreads();
+
+    // the tallies
+    int n_err = 0, ub_len = 0, ub_match = 0, area_len = 0, area_match = 0, detected = 0;
+    int32_t *err = p.err + (size_t)(minus ? p.total : 0) + tb;
+    for (int j = lane; j < L; j += 64) {
+        const unsigned tj = T[j], pj = P[j];
+        const bool e = pj != tj, ub = tj == 'X';
+        bool area = false;
+        if (!ub) {
+#pragma unroll
+            for (int d = 1; d <= xb::UB_AREA; ++d)
+                area = area || (j - d >= 0 && T[j - d >= 0 ? j - d : 0] == 'X') || (j + d < L && T[j + d < L ? j + d : 0] == 'X');
+        }
+        n_err += e;
+        ub_len += ub;
+        ub_match += ub && !e;
+        area_len += area;
+        area_match += area && !e;
+        detected += pj == 'X' || pj == 'Y';
+        if (e) atomicAdd(err + (minus ? L - 1 - j : j), 1);
+        int row = tj == 'A' ? 0 : (tj == 'T' ? 1 : (tj == 'C' ? 2 : (tj == 'G' ? 3 : 4)));
+        int col = ub_letter_index(pj);
+        if (col >= 0) {
+            if (minus) { row ^= 1; col = col < 6 ? col ^ 1 : col; }
+            atomicAdd(&cells[row * xb::UB_CM_COLS + col], 1u);
+        }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        n_err += __shfl_xor(n_err, d);
+        ub_len += __shfl_xor(ub_len, d);
+        ub_match += __shfl_xor(ub_match, d);
+        area_len += __shfl_xor(area_len, d);
+        area_match += __shfl_xor(area_match, d);
+        detected += __shfl_xor(detected, d);
+    }
+    __syncthreads();                                   // the cells are complete
+    if (lane < UB_CM_CELLS && cells[lane]) atomicAdd(p.cm + lane, (unsigned long long)cells[lane]);
+    if (lane == 0) {
+        const int n_match = L - n_err;
+        cnt[0] = n_match;
+        cnt[1] = ub_match;
+        cnt[2] = ub_len;
+        cnt[3] = area_match;
+        cnt[4] = area_len;
+        cnt[5] = n_match - ub_match - area_match;
+        cnt[6] = L - ub_len - area_len;
+        cnt[7] = detected;
+        atomicAdd(p.reads + 2 * t + (minus ? 1 : 0), 1);
+    }
+}
+
 }  // namespace
 
 namespace xb {
@@ -520,6 +729,12 @@ hipError_t launch_map_trace(const MapParams &p, hipStream_t stream)
 hipError_t launch_ctc_targets(const CtcTargetParams &p, hipStream_t stream)
 {
     hipLaunchKernelGGL(ctc_targets_kernel, dim3(p.n), dim3(64), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_ub_tally(const UbTallyParams &p, hipStream_t stream)
+{
+    hipLaunchKernelGGL(ub_tally_kernel, dim3(p.n), dim3(64), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -198,6 +198,7 @@ struct xb_ctx {
         int Lmax = 0, nchunks = 0;
         DevBuf image, partial, scratch, staging;
         DevBuf ctc_staging;                         // xb_ctc_targets (host form) and xb_ctc_chunks
+        DevBuf ub_staging;                          // xb_ub_tally (host form)
     } map;
 
     // DTW segmentation (xb_dtw_segment): the choice-bit scratch of the launches in flight, the staging of the host-pointer
@@ -1075,8 +1076,8 @@ XB_API void xb_ctx_destroy(xb_ctx *ctx)
     for (auto &ev : ctx->events) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto &b : ctx->bufs) (void)hipFree(b.p);
     for (auto &b : ctx->wsbufs) (void)hipFree(b.p);
-    for (DevBuf *b : {&ctx->map.image, &ctx->map.partial, &ctx->map.scratch, &ctx->map.staging, &ctx->map.ctc_staging, &ctx->dtw.scratch,
-                      &ctx->dtw.staging})
+    for (DevBuf *b : {&ctx->map.image, &ctx->map.partial, &ctx->map.scratch, &ctx->map.staging, &ctx->map.ctc_staging, &ctx->map.ub_staging,
+                      &ctx->dtw.scratch, &ctx->dtw.staging})
         if (b->p) (void)hipFree(b->p);
     for (auto &o : ctx->dtw.off) {
         if (o.h) (void)hipHostFree(o.h);
@@ -1988,26 +1989,28 @@ struct MapOut {
 };
 
 // the library's device image (rebuilt only when the bytes change) for n rows of width W: validation, *lmax = the longest template
-// (sc: the mapper's scoring, checked where it always was; null for a caller that aligns nothing and is not held to the cell budget)
-int map_library(xb_ctx *ctx, int n, int W, const char *templates, const int32_t *offsets, int R, const int *sc, int *lmax)
+// (sc: the mapper's scoring, checked where it always was; null for a caller that aligns nothing and is not held to the cell budget;
+// who: the entry point a refusal names)
+int map_library(xb_ctx *ctx, int n, int W, const char *templates, const int32_t *offsets, int R, const int *sc, int *lmax,
+                const char *who = "xb_map_templates")
 {
     if (n < 1 || W < 1 || W > xb::MAP_MAX_ROW)
-        return fail(ctx, XB_ERR_INVALID, "xb_map_templates: n = %d rows of width %d; need n >= 1 and 1 <= W <= %d", n, W, xb::MAP_MAX_ROW);
-    if (!templates || !offsets || R < 1 || offsets[0] != 0) return fail(ctx, XB_ERR_INVALID, "xb_map_templates: empty template library");
+        return fail(ctx, XB_ERR_INVALID, "%s: n = %d rows of width %d; need n >= 1 and 1 <= W <= %d", who, n, W, xb::MAP_MAX_ROW);
+    if (!templates || !offsets || R < 1 || offsets[0] != 0) return fail(ctx, XB_ERR_INVALID, "%s: empty template library", who);
     for (int k = 0; sc && k < 5; ++k)
-        if (sc[k] < 0 || sc[k] > 1000) return fail(ctx, XB_ERR_INVALID, "xb_map_templates: scoring values must lie in [0, 1000]");
+        if (sc[k] < 0 || sc[k] > 1000) return fail(ctx, XB_ERR_INVALID, "%s: scoring values must lie in [0, 1000]", who);
     int Lmax = 0;
     for (int t = 0; t < R; ++t) {
         const int L = offsets[t + 1] - offsets[t];
         if (L < 1 || L > xb::MAP_MAX_TEMPLATE)
-            return fail(ctx, XB_ERR_INVALID, "xb_map_templates: template %d has %d letters; 1 .. %d are supported", t, L, xb::MAP_MAX_TEMPLATE);
+            return fail(ctx, XB_ERR_INVALID, "%s: template %d has %d letters; 1 .. %d are supported", who, t, L, xb::MAP_MAX_TEMPLATE);
         Lmax = std::max(Lmax, L);
     }
     const size_t total = (size_t)offsets[R];
     const double cells = 2.0 * n * W * (double)total;
     if (total > MAP_MAX_LIBRARY || (sc && cells > MAP_CELL_BUDGET))
-        return fail(ctx, XB_ERR_INVALID, "xb_map_templates: a library of %d templates, %zu letters, against %d rows of width %d is %.3g "
-                    "cells; one call takes at most %.3g cells and a library of %zu letters (larger libraries need a seeding stage)",
+        return fail(ctx, XB_ERR_INVALID, "%s: a library of %d templates, %zu letters, against %d rows of width %d is %.3g "
+                    "cells; one call takes at most %.3g cells and a library of %zu letters (larger libraries need a seeding stage)", who,
                     R, total, n, W, cells, MAP_CELL_BUDGET, MAP_MAX_LIBRARY);
     xb_ctx::MapState &m = ctx->map;
     const bool same = m.image.p && m.lib.size() == total && (int)m.off.size() == R + 1 &&
@@ -2318,6 +2321,109 @@ XB_API int xb_ctc_chunks(xb_ctx *ctx, const float *signal, int n, const char *al
     XB_HIP(ctx, hipMemcpyAsync(verdict, base + a_verdict, N, hipMemcpyDeviceToHost, ctx->stream));
     XB_HIP(ctx, hipMemcpyAsync(ops, d_ops, N * cap, hipMemcpyDeviceToHost, ctx->stream));
     XB_HIP(ctx, hipMemcpyAsync(target, base + a_target, N * TW, hipMemcpyDeviceToHost, ctx->stream));
+    return xb_synchronize(ctx);
+}
+
+// ---- per-position UB accuracy of mapped rows (xb_ub_tally) --------------------------------------------------------------
+namespace {
+
+struct UbIn {
+    const int8_t *seq; const int32_t *seq_len, *tmpl; const int8_t *strand; const int32_t *q_st, *r_st, *r_en; const uint8_t *ops;
+    const int32_t *n_ops;
+};
+struct UbOut {
+    int32_t *counts, *reads, *err; int64_t *cm;
+};
+
+bool ub_complete(const UbIn &i, const UbOut &o)
+{
+    return i.seq && i.seq_len && i.tmpl && i.strand && i.q_st && i.r_st && i.r_en && i.ops && i.n_ops && o.counts && o.reads && o.err && o.cm;
+}
+
+// validation, the library's device image, the launch: i and o are device pointers
+int ub_run(xb_ctx *ctx, const UbIn &i, int n, int W, const char *templates, const int32_t *offsets, int R, const UbOut &o)
+{
+    int Lmax = 0;
+    if (int rc = map_library(ctx, n, W, templates, offsets, R, nullptr, &Lmax, "xb_ub_tally")) return rc;
+    const size_t total = (size_t)offsets[R];
+    const uint8_t *img = static_cast<const uint8_t *>(ctx->map.image.p);
+    xb::UbTallyParams p{};
+    p.seq = i.seq; p.seq_len = i.seq_len; p.n = n; p.W = W; p.cap = W + Lmax;
+    p.tmpl = i.tmpl; p.strand = i.strand; p.q_st = i.q_st; p.r_st = i.r_st; p.r_en = i.r_en; p.ops = i.ops; p.n_ops = i.n_ops;
+    p.tcodes = img;
+    p.toff = reinterpret_cast<const int32_t *>(img + ((total + 15) & ~(size_t)15));
+    p.R = R; p.total = (int)total;
+    p.counts = o.counts; p.reads = o.reads; p.err = o.err;
+    p.cm = reinterpret_cast<unsigned long long *>(o.cm);
+    XB_HIP(ctx, xb::launch_ub_tally(p, ctx->stream));
+    return XB_OK;
+}
+
+}  // namespace
+
+XB_API int xb_ub_tally_dev(xb_ctx *ctx, const int8_t *d_seq, const int32_t *d_seq_len, int n, int W, const char *templates,
+                           const int32_t *offsets, int R, const int32_t *d_tmpl, const int8_t *d_strand, const int32_t *d_q_st,
+                           const int32_t *d_r_st, const int32_t *d_r_en, const uint8_t *d_ops, const int32_t *d_n_ops,
+                           int32_t *d_counts, int32_t *d_reads, int32_t *d_err, int64_t *d_cm)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    const UbIn i = {d_seq, d_seq_len, d_tmpl, d_strand, d_q_st, d_r_st, d_r_en, d_ops, d_n_ops};
+    const UbOut o = {d_counts, d_reads, d_err, d_cm};
+    if (!ub_complete(i, o)) return fail(ctx, XB_ERR_INVALID, "xb_ub_tally: null device pointer");
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = join_async_decode(ctx)) return rc;
+    ctx->result_stream = ctx->stream;
+    return ub_run(ctx, i, n, W, templates, offsets, R, o);
+}
+
+XB_API int xb_ub_tally(xb_ctx *ctx, const int8_t *seq, const int32_t *seq_len, int n, int W, const char *templates,
+                       const int32_t *offsets, int R, const int32_t *tmpl, const int8_t *strand, const int32_t *q_st,
+                       const int32_t *r_st, const int32_t *r_en, const uint8_t *ops, const int32_t *n_ops, int32_t *counts,
+                       int32_t *reads, int32_t *err, int64_t *cm)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    const UbIn h = {seq, seq_len, tmpl, strand, q_st, r_st, r_en, ops, n_ops};
+    const UbOut ho = {counts, reads, err, cm};
+    if (!ub_complete(h, ho)) return fail(ctx, XB_ERR_INVALID, "xb_ub_tally: null host pointer");
+    if (n < 1 || W < 1 || W > xb::MAP_MAX_ROW || !offsets || R < 1 || offsets[0] != 0)
+        return fail(ctx, XB_ERR_INVALID, "xb_ub_tally: n = %d rows of width %d, %d templates; need n >= 1, 1 <= W <= %d, R >= 1", n, W, R,
+                    xb::MAP_MAX_ROW);
+    int Lmax = 0;
+    for (int t = 0; t < R; ++t) {
+        const int L = offsets[t + 1] - offsets[t];
+        if (L < 1 || L > xb::MAP_MAX_TEMPLATE)
+            return fail(ctx, XB_ERR_INVALID, "xb_ub_tally: template %d has %d letters; 1 .. %d are supported", t, L, xb::MAP_MAX_TEMPLATE);
+        Lmax = std::max(Lmax, L);
+    }
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = join_async_decode(ctx)) return rc;
+    const size_t N = (size_t)n, cap = (size_t)W + Lmax, total = (size_t)offsets[R];
+    if (N * (cap + W) > ((size_t)2 << 30)) return fail(ctx, XB_ERR_INVALID, "xb_ub_tally: %d rows of width %d in one call; split the batch", n, W);
+    Carve c;
+    size_t a_i32[6];
+    for (size_t &a : a_i32) a = c.take(N * 4);          // seq_len, tmpl, q_st, r_st, r_en, n_ops
+    const size_t a_strand = c.take(N), a_seq = c.take(N * W), a_ops = c.take(N * cap), a_counts = c.take(N * xb::UB_COUNTS * 4);
+    const size_t b_reads = (size_t)R * 2 * 4, b_err = 2 * total * 4, b_cm = (size_t)xb::UB_CM_ROWS * xb::UB_CM_COLS * 8;
+    const size_t a_reads = c.take(b_reads), a_err = c.take(b_err), a_cm = c.take(b_cm);
+    if (int rc = map_grow(ctx, &ctx->map.ub_staging, c.used)) return rc;
+    uint8_t *base = static_cast<uint8_t *>(ctx->map.ub_staging.p);
+    auto i32 = [&](size_t at) { return reinterpret_cast<int32_t *>(base + at); };
+    const int32_t *const src[6] = {seq_len, tmpl, q_st, r_st, r_en, n_ops};
+    for (int k = 0; k < 6; ++k) XB_HIP(ctx, hipMemcpyAsync(base + a_i32[k], src[k], N * 4, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(base + a_strand, strand, N, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(base + a_seq, seq, N * W, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(base + a_ops, ops, N * cap, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(base + a_reads, reads, b_reads, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(base + a_err, err, b_err, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(base + a_cm, cm, b_cm, hipMemcpyHostToDevice, ctx->stream));
+    const UbIn d = {reinterpret_cast<int8_t *>(base + a_seq), i32(a_i32[0]), i32(a_i32[1]), reinterpret_cast<int8_t *>(base + a_strand),
+                    i32(a_i32[2]), i32(a_i32[3]), i32(a_i32[4]), base + a_ops, i32(a_i32[5])};
+    const UbOut o = {i32(a_counts), i32(a_reads), i32(a_err), reinterpret_cast<int64_t *>(base + a_cm)};
+    if (int rc = ub_run(ctx, d, n, W, templates, offsets, R, o)) return rc;
+    XB_HIP(ctx, hipMemcpyAsync(counts, o.counts, N * xb::UB_COUNTS * 4, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(reads, o.reads, b_reads, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(err, o.err, b_err, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(cm, o.cm, b_cm, hipMemcpyDeviceToHost, ctx->stream));
     return xb_synchronize(ctx);
 }
 

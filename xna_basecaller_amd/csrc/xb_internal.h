@@ -255,6 +255,29 @@ struct CtcTargetParams {
 };
 hipError_t launch_ctc_targets(const CtcTargetParams &p, hipStream_t stream);
 
+// xb_ub_tally: per mapped row the called letter of every template position, the UB polish and the integer tallies of the
+// UB report (the contract is in the public header).  One wave per row.
+constexpr int UB_COUNTS = 8;                // int32 per row of counts
+constexpr int UB_AREA = 5;                  // a position within this many letters of a UB site lies in the UB area
+constexpr int UB_CM_ROWS = 6, UB_CM_COLS = 7;
+struct UbTallyParams {
+    const int8_t *seq;           // (n, W) ASCII rows, left-packed
+    const int32_t *seq_len;      // (n)
+    int n, W, cap;               // cap = W + Lmax: bytes per row of ops
+    const int32_t *tmpl, *q_st, *r_st, *r_en, *n_ops;   // (n) the mapper's outputs
+    const int8_t *strand;        // (n)
+    const uint8_t *ops;          // (n, cap)
+    const uint8_t *tcodes;       // the library image: codes and offsets
+    const int32_t *toff;
+    int R;
+    int32_t *counts;             // (n, UB_COUNTS)
+    int32_t *reads;              // (R, 2) accumulator
+    int32_t *err;                // (2, total) accumulator
+    int total;                   // letters of the library
+    unsigned long long *cm;      // (UB_CM_ROWS, UB_CM_COLS) accumulator (int64 on the host)
+};
+hipError_t launch_ub_tally(const UbTallyParams &p, hipStream_t stream);
+
 // ---------------------------------------------------------------- DTW signal segmentation (xb_dtw.hip)
 // xb_dtw_segment: every signal chunk against the expected levels of its reference by dynamic time warping (the contract is
 // in the public header).  One wave per chunk; the columns lie across the lanes, cols consecutive columns per lane, in
