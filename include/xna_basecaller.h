@@ -560,6 +560,67 @@ XB_API int xb_dtw_segment_dev(xb_ctx *ctx, const float *d_signal, int n, int N, 
                               int ref_rep, const double *d_window, int Kmax, int32_t *d_breakpoints, int8_t *d_ok, double *d_cost);
 XB_API int64_t xb_dtw_scratch_bytes(const xb_ctx *ctx);
 
+/* ---- XNA spliced augmentation of ctc-data (an extension of the device path: `splice`) ----------------------------------
+ * The reference's ub-bonito/bonito/stitch_chunks.py (`bonito train -m per_kmer`) cuts the signal of the six k-mers around an
+ * unnatural base out of XNA chunks and pastes it into DNA chunks, per read, in the data loader.  Here one wave per chunk does
+ * it.  Everything but the random stream is pinned to the reference (tests/golden/splice.json); the DRAWS are this library's
+ * own: parity unpinned.  The kernel is bit-exact against a CPU restatement of the contract (tests/splice_ref.py).
+ *
+ * xb_splice_library keeps the candidates of slice_xna(.., 'per_kmer') (:127-239) on the device until the next call or until
+ * the context is destroyed (host pointers; the call waits):
+ *   pool       pool_len float16 samples (their bit patterns): the kept windows of the XNA chunks, back to back.
+ *   rows       (n_rows, 2) int32: pool offset and length (1 .. 100 samples) of every row, in the reference's order
+ *              (ub, template, kmer_ub_pos, kmer, read_idx).
+ *   table      (table_len, 2) int32, table_len = 2 * 7^5 * 6: first row and count of the group (ub, template, kmer_ub_pos) at
+ *              index ((ub - 5) * 7^5 + t) * 6 + kmer_ub_pos, t = the template's five labels as base-7 digits, the first the
+ *              most significant.  Grouped WITHOUT the k-mer, as the reference looks candidates up (:377): a group may hold
+ *              rows of different k-mers.  count 0: no such group.
+ *
+ * xb_splice_chunks: signal (n, N) fp32, targets (n, Lt) labels 0 .. 6, lengths (n) int32, breakpoints (n, Lt) uint16 (the
+ * sample where each base's signal ends; non-decreasing and at most N within a chunk's length).  A chunk's result depends only
+ * on its data, the library, the parameters, `seed` and its GLOBAL index c = first_index + row -- never on the batch.
+ *   draws      draw k of chunk c: z = mix(mix(seed + G (c + 1)) + G (k + 1)) in uint64, G = 0x9E3779B97F4A7C15, mix =
+ *              splitmix64's finaliser (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB,
+ *              z ^= z >> 31).  bounded(m) = ((z >> 32) * m) >> 32; unit = (z >> 11) * 2^-53.  k counts from 0 in the order
+ *              below; a draw is spent exactly where the reference calls its generator (rng.choice(ubs) with one UB included).
+ *   proportion var_prop > 0: prop = lo + (hi - lo) * unit with lo = prop - var_prop, hi = prop + var_prop, in float64 as
+ *              written.  n_pos = max(rint(length * prop) - #existing UBs, 1), rint to even (Python's round of a float64).
+ *   positions  choose_positions (:104-125): a base is valid unless it is among the first or last 10 or within 2 * pad of a
+ *              label above 4.  Up to n_pos rounds; a round without a valid base ends them all; otherwise it takes
+ *              valid[bounded(#valid)] and invalidates pos - pad .. pos + pad.  The positions are then handled in ascending order.
+ *   per position (stitch_read_per_kmer, :349-446)  ub = ubs[bounded(#ubs)], ubs = the set bits of ubs_mask (1: X = 5, 2: Y = 6)
+ *              in that order.  The six k-mers come from the ORIGINAL labels pos - 5 .. pos + 5 with the UB in the middle; k-mer
+ *              i = 0 .. 5 looks up the group (ub, its five labels behind the UB followed by those in front of it, 5 - i).  A
+ *              missing group abandons the position; the draws already spent stay spent.  cand_sample_size > 1: m =
+ *              min(count, cand_sample_size) rows are sampled without replacement by a partial Fisher-Yates shuffle over the
+ *              virtual identity permutation (draw j picks slot j + bounded(count - j)), and the first sampled row with the
+ *              smallest |length - kmer_rep| is kept.  cand_sample_size = 1: the row bounded(count).
+ *   resample   prepare_slice_chunk (:241-271), numpy's float64 arithmetic, no contraction.  The six rows have slice_len samples
+ *              together, the signal they replace ins_len = breakpoints[pos] - breakpoints[pos - 6].  Stretch (slice_len <
+ *              ins_len): xp as the reference builds it -- linspace (i * step + start, the last value the stop), .round() to
+ *              even, astype(int) -- then numpy.interp: j = the largest with xp[j] <= x; xp[j] == x or j last: fp[j]; else
+ *              slope = (fp[j+1] - fp[j]) / (xp[j+1] - xp[j]), y = slope * (x - xp[j]) + fp[j].  Shrink: the samples at
+ *              linspace(0, slice_len - 1, slice_len - ins_len, dtype=int) are dropped.  Equal: a copy.
+ *   outputs    the pasted values are the float16 pool values or the float64 interpolation, rounded ONCE to float32; the label
+ *              at the position becomes ub; out_signal / out_targets are copies of the inputs elsewhere.  success (n) int8: at
+ *              least one paste; inserted (n) int32: how many.
+ * Limits: 1 <= N <= 65535, 1 <= Lt <= 65535, 1 <= cand_sample_size <= 32, pad >= 0, 0 <= prop, var_prop, prop + var_prop <= 1,
+ * ubs_mask 1 .. 3, pool < 2^31 samples (XB_ERR_INVALID with the figures otherwise, before any launch; the context stays
+ * usable); XB_ERR_STATE without a library.  Outputs must not alias inputs.  The host form checks lengths and breakpoints and
+ * names the chunk; the _dev form (device pointers, returns without waiting: xb_synchronize) clamps them instead, so that no
+ * access leaves the rows.
+ */
+XB_API int xb_splice_library(xb_ctx *ctx, const uint16_t *pool, int64_t pool_len, const int32_t *rows, int n_rows,
+                             const int32_t *table, int table_len);
+XB_API int xb_splice_chunks(xb_ctx *ctx, const float *signal, const uint8_t *targets, const int32_t *lengths,
+                            const uint16_t *breakpoints, int n, int N, int Lt, int64_t first_index, uint64_t seed, int ubs_mask,
+                            double prop, double var_prop, int cand_sample_size, int pad, float *out_signal, uint8_t *out_targets,
+                            int8_t *success, int32_t *inserted);
+XB_API int xb_splice_chunks_dev(xb_ctx *ctx, const float *d_signal, const uint8_t *d_targets, const int32_t *d_lengths,
+                                const uint16_t *d_breakpoints, int n, int N, int Lt, int64_t first_index, uint64_t seed, int ubs_mask,
+                                double prop, double var_prop, int cand_sample_size, int pad, float *d_out_signal,
+                                uint8_t *d_out_targets, int8_t *d_success, int32_t *d_inserted);
+
 /* ---- introspection / measurement ---------------------------------------------------------- */
 
 enum { XB_STAGE_CONV = 0, XB_STAGE_LSTM_IN = 1, XB_STAGE_LSTM_REC = 2, XB_STAGE_LINEAR = 3,

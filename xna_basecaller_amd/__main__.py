@@ -1,11 +1,12 @@
 """`python -m xna_basecaller_amd basecaller MODEL_DIR READS_DIR ...` == `bonito basecaller ...`, and `... evaluate MODEL_DIR
 --directory CTC_DATA` == `bonito evaluate ...` (bonito/__init__.py:10-33); `... segment CTC_DATA` == the reference's
 `src/tools/dtw_segmentation.py CTC_DATA`; `... analyze LIB.fasta CALLS.paf -R CALLS.fastq` == the reference's
-`src/tools/analyze_paf.py -p`."""
+`src/tools/analyze_paf.py -p`; `... splice DNA_CTC XNA_CTC OUT --ubs XY --prop-ubs P` == the XNA spliced augmentation of
+`bonito train -m per_kmer` (bonito/stitch_chunks.py) written out as ctc-data."""
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 
 from . import __version__
-from .cli import analyze, basecaller, evaluate, segment
+from .cli import analyze, basecaller, evaluate, segment, splice
 
 
 def main():
@@ -22,6 +23,8 @@ def main():
     p.set_defaults(func=segment.main)
     p = sub.add_parser("analyze", parents=[analyze.argparser()])
     p.set_defaults(func=analyze.main)
+    p = sub.add_parser("splice", parents=[splice.argparser()])
+    p.set_defaults(func=splice.main)
     args = parser.parse_args()
     args.func(args)
 

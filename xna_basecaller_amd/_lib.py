@@ -32,6 +32,7 @@ EXPORTS = [
     "xb_decode_ub", "xb_decode_ub_dev", "xb_basecall_chunks_ub", "xb_submit_chunks_ub", "xb_collect_chunks_ub",
     "xb_map_templates", "xb_map_templates_dev", "xb_ctc_targets", "xb_ctc_targets_dev", "xb_ctc_chunks",
     "xb_ub_tally", "xb_ub_tally_dev", "xb_dtw_segment", "xb_dtw_segment_dev", "xb_dtw_scratch_bytes",
+    "xb_splice_library", "xb_splice_chunks", "xb_splice_chunks_dev",
 ]
 XB_COMM_ID_BYTES = 128
 # xb_status (include/xna_basecaller.h)
@@ -134,6 +135,9 @@ def load():
     lib.xb_dtw_segment_dev.argtypes = lib.xb_dtw_segment.argtypes
     lib.xb_dtw_scratch_bytes.argtypes = [vp]
     lib.xb_dtw_scratch_bytes.restype = C.c_int64
+    lib.xb_splice_library.argtypes = [vp, vp, C.c_int64, vp, ip, vp, ip]
+    lib.xb_splice_chunks.argtypes = [vp] * 5 + [ip, ip, ip, C.c_int64, C.c_uint64, ip, db, db, ip, ip] + [vp] * 4
+    lib.xb_splice_chunks_dev.argtypes = lib.xb_splice_chunks.argtypes
     lib.xb_result_stream.argtypes = [vp]
     lib.xb_result_stream.restype = C.c_void_p
     lib.xb_set_profiling.argtypes = [vp, ip]
@@ -644,6 +648,43 @@ class Context:
     def dtw_scratch_bytes(self):
         """Choice-bit bytes the launches of the last dtw_segment call wrote (xb_dtw_scratch_bytes)."""
         return int(self.lib.xb_dtw_scratch_bytes(self.h))
+
+    # ---- XNA spliced augmentation (xb_splice_library, xb_splice_chunks): draws parity unpinned ----------
+    def splice_library(self, pool, rows, table):
+        """xb_splice_library: pool float16, rows (n_rows, 2) int32 pool offset and length, table (2 * 7^5 * 6, 2) int32 first row
+        and count (splice.Library's arrays); replaces the library of an earlier call."""
+        pool = np.ascontiguousarray(pool, dtype=np.float16)
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 2)
+        table = np.ascontiguousarray(table, dtype=np.int32).reshape(-1, 2)
+        self._check(self.lib.xb_splice_library(self.h, pool.ctypes.data, pool.size, rows.ctypes.data, rows.shape[0],
+                                               table.ctypes.data, table.shape[0]))
+
+    def splice_chunks(self, signal, targets, lengths, breakpoints, first_index, seed, ubs_mask, prop, var_prop=0.0,
+                      cand_sample_size=10, pad=5):
+        """xb_splice_chunks: signal (n, N) fp32, targets (n, Lt) uint8, lengths (n), breakpoints (n, Lt) uint16 ->
+        (signal (n, N) float32, targets (n, Lt) uint8, success (n,) int8, inserted (n,) int32)."""
+        signal = np.ascontiguousarray(signal, dtype=np.float32)
+        targets = np.ascontiguousarray(targets, dtype=np.uint8)
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32)
+        bk = np.ascontiguousarray(breakpoints, dtype=np.uint16)
+        n, N = signal.shape
+        if targets.ndim != 2 or targets.shape[0] != n or bk.shape != targets.shape or lengths.shape != (n,):
+            raise ValueError("splice_chunks: signal (n, N), targets (n, Lt), lengths (n), breakpoints (n, Lt) expected")
+        out, out_t = np.empty_like(signal), np.empty_like(targets)
+        ok, ins = np.empty((n,), np.int8), np.empty((n,), np.int32)
+        self._check(self.lib.xb_splice_chunks(self.h, signal.ctypes.data, targets.ctypes.data, lengths.ctypes.data, bk.ctypes.data,
+                                              n, N, targets.shape[1], int(first_index), int(seed) & (2 ** 64 - 1), int(ubs_mask),
+                                              float(prop), float(var_prop or 0.0), int(cand_sample_size), int(pad), out.ctypes.data,
+                                              out_t.ctypes.data, ok.ctypes.data, ins.ctypes.data))
+        return out, out_t, ok, ins
+
+    def splice_chunks_dev(self, d_signal, d_targets, d_lengths, d_breakpoints, n, N, Lt, first_index, seed, ubs_mask, prop, var_prop,
+                          cand_sample_size, pad, d_out_signal, d_out_targets, d_success, d_inserted):
+        """xb_splice_chunks_dev: device pointers; returns without waiting."""
+        self._check(self.lib.xb_splice_chunks_dev(self.h, _ptr(d_signal), _ptr(d_targets), _ptr(d_lengths), _ptr(d_breakpoints),
+                                                  int(n), int(N), int(Lt), int(first_index), int(seed) & (2 ** 64 - 1), int(ubs_mask),
+                                                  float(prop), float(var_prop or 0.0), int(cand_sample_size), int(pad),
+                                                  _ptr(d_out_signal), _ptr(d_out_targets), _ptr(d_success), _ptr(d_inserted)))
 
     # ---- host pipeline: two batches in flight (xb_submit_chunks / xb_collect_chunks) ----------
     def submit_chunks(self, slot, signal, alphabet, qscale=1.0, qoffset=0.0, level=0):

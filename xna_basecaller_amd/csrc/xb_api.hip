@@ -215,6 +215,13 @@ struct xb_ctx {
         size_t scratch_written = 0;                 // bytes of choice words the last call's launches were sized for
     } dtw;
 
+    // XNA spliced augmentation (xb_splice_library / xb_splice_chunks): the library's device image, kept until the next
+    // xb_splice_library, and the staging of the host-pointer form.  Owned here, freed by xb_ctx_destroy.
+    struct SpliceState {
+        DevBuf pool, rows, table, staging;
+        bool loaded = false;
+    } splice;
+
     bool profiling = false;
     std::vector<StageEvent> events;
     float stage_ms[XB_STAGE_COUNT] = {};
@@ -1077,7 +1084,8 @@ XB_API void xb_ctx_destroy(xb_ctx *ctx)
     for (auto &b : ctx->bufs) (void)hipFree(b.p);
     for (auto &b : ctx->wsbufs) (void)hipFree(b.p);
     for (DevBuf *b : {&ctx->map.image, &ctx->map.partial, &ctx->map.scratch, &ctx->map.staging, &ctx->map.ctc_staging, &ctx->map.ub_staging,
-                      &ctx->dtw.scratch, &ctx->dtw.staging})
+                      &ctx->dtw.scratch, &ctx->dtw.staging, &ctx->splice.pool, &ctx->splice.rows, &ctx->splice.table,
+                      &ctx->splice.staging})
         if (b->p) (void)hipFree(b->p);
     for (auto &o : ctx->dtw.off) {
         if (o.h) (void)hipHostFree(o.h);
@@ -2558,6 +2566,154 @@ XB_API int xb_dtw_segment(xb_ctx *ctx, const float *signal, int n, int N, const 
 }
 
 XB_API int64_t xb_dtw_scratch_bytes(const xb_ctx *ctx) { return ctx ? (int64_t)ctx->dtw.scratch_written : 0; }
+
+// ---- XNA spliced augmentation (xb_splice_library, xb_splice_chunks) ---------------------------------------------------
+XB_API int xb_splice_library(xb_ctx *ctx, const uint16_t *pool, int64_t pool_len, const int32_t *rows, int n_rows,
+                             const int32_t *table, int table_len)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    if (!pool || !rows || !table) return fail(ctx, XB_ERR_INVALID, "xb_splice_library: null host pointer");
+    if (pool_len < 1 || pool_len > 0x7fffffffLL || n_rows < 1 || table_len != xb::SPLICE_TABLE_LEN)
+        return fail(ctx, XB_ERR_INVALID, "xb_splice_library: a pool of %lld samples, %d rows, a table of %d groups; need 1 <= pool < 2^31, "
+                    "n_rows >= 1 and %d groups", (long long)pool_len, n_rows, table_len, xb::SPLICE_TABLE_LEN);
+    for (int r = 0; r < n_rows; ++r) {
+        const int64_t off = rows[2 * r], len = rows[2 * r + 1];
+        if (off < 0 || len < 1 || len > xb::SPLICE_MAX_KMER || off + len > pool_len)
+            return fail(ctx, XB_ERR_INVALID, "xb_splice_library: row %d has %lld samples at offset %lld of a pool of %lld; 1 .. %d samples "
+                        "inside the pool are supported", r, (long long)len, (long long)off, (long long)pool_len, xb::SPLICE_MAX_KMER);
+    }
+    for (int g = 0; g < table_len; ++g) {
+        const int64_t first = table[2 * g], count = table[2 * g + 1];
+        if (count < 0 || (count > 0 && (first < 0 || first + count > n_rows)))
+            return fail(ctx, XB_ERR_INVALID, "xb_splice_library: group %d holds rows %lld .. %lld of %d", g, (long long)first,
+                        (long long)(first + count), n_rows);
+    }
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = join_async_decode(ctx)) return rc;
+    xb_ctx::SpliceState &s = ctx->splice;
+    s.loaded = false;
+    XB_HIP(ctx, hipStreamSynchronize(ctx->stream));                     // nothing in flight reads the library it replaces
+    if (int rc = map_grow(ctx, &s.pool, (size_t)pool_len * 2)) return rc;
+    if (int rc = map_grow(ctx, &s.rows, (size_t)n_rows * 8)) return rc;
+    if (int rc = map_grow(ctx, &s.table, (size_t)table_len * 8)) return rc;
+    XB_HIP(ctx, hipMemcpyAsync(s.pool.p, pool, (size_t)pool_len * 2, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(s.rows.p, rows, (size_t)n_rows * 8, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(s.table.p, table, (size_t)table_len * 8, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s.loaded = true;
+    return XB_OK;
+}
+
+namespace {
+
+struct SpliceArgs {
+    int n, N, Lt;
+    int64_t first_index;
+    uint64_t seed;
+    int ubs_mask;
+    double prop, var_prop;
+    int cand, pad;
+};
+
+// the limits of the contract, before any launch
+int splice_check(xb_ctx *ctx, const SpliceArgs &a)
+{
+    if (!ctx->splice.loaded) return fail(ctx, XB_ERR_STATE, "xb_splice_chunks: no library: call xb_splice_library first");
+    if (a.n < 1 || a.N < 1 || a.N > xb::SPLICE_MAX_SAMPLES || a.Lt < 1 || a.Lt > xb::SPLICE_MAX_LABELS)
+        return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: n = %d chunks of %d samples, label rows of %d entries; need n >= 1, "
+                    "1 <= N <= %d, 1 <= Lt <= %d", a.n, a.N, a.Lt, xb::SPLICE_MAX_SAMPLES, xb::SPLICE_MAX_LABELS);
+    if (a.cand < 1 || a.cand > xb::SPLICE_MAX_CAND)
+        return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: cand_sample_size = %d; 1 .. %d are supported", a.cand, xb::SPLICE_MAX_CAND);
+    if (a.pad < 0) return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: pad = %d is negative", a.pad);
+    if (a.ubs_mask < 1 || a.ubs_mask > 3) return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: ubs_mask = %d; 1 (X), 2 (Y) or 3 (both)", a.ubs_mask);
+    if (!(a.prop >= 0.0) || !(a.var_prop >= 0.0) || !(a.prop + a.var_prop <= 1.0))
+        return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: prop = %g, var_prop = %g; both at least 0, their sum at most 1", a.prop, a.var_prop);
+    if (a.first_index < 0) return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: first_index = %lld is negative", (long long)a.first_index);
+    return XB_OK;
+}
+
+int splice_run(xb_ctx *ctx, const SpliceArgs &a, const float *d_signal, const uint8_t *d_targets, const int32_t *d_lengths,
+               const uint16_t *d_bkps, float *d_out_signal, uint8_t *d_out_targets, int8_t *d_success, int32_t *d_inserted)
+{
+    xb::SpliceParams p{};
+    p.signal = d_signal; p.targets = d_targets; p.lengths = d_lengths; p.bkps = d_bkps;
+    p.n = a.n; p.N = a.N; p.Lt = a.Lt;
+    p.first_index = (unsigned long long)a.first_index; p.seed = a.seed;
+    p.n_ubs = 0;
+    if (a.ubs_mask & 1) p.ubs[p.n_ubs++] = 5;
+    if (a.ubs_mask & 2) p.ubs[p.n_ubs++] = 6;
+    p.prop = a.prop; p.var_prop = a.var_prop; p.cand = a.cand; p.pad = a.pad;
+    p.pool = static_cast<const xb::half_t *>(ctx->splice.pool.p);
+    p.rows = static_cast<const int32_t *>(ctx->splice.rows.p);
+    p.table = static_cast<const int32_t *>(ctx->splice.table.p);
+    p.out_signal = d_out_signal; p.out_targets = d_out_targets; p.success = d_success; p.inserted = d_inserted;
+    XB_HIP(ctx, xb::launch_splice(p, ctx->stream));
+    return XB_OK;
+}
+
+}  // namespace
+
+XB_API int xb_splice_chunks_dev(xb_ctx *ctx, const float *d_signal, const uint8_t *d_targets, const int32_t *d_lengths,
+                                const uint16_t *d_breakpoints, int n, int N, int Lt, int64_t first_index, uint64_t seed, int ubs_mask,
+                                double prop, double var_prop, int cand_sample_size, int pad, float *d_out_signal,
+                                uint8_t *d_out_targets, int8_t *d_success, int32_t *d_inserted)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    if (!d_signal || !d_targets || !d_lengths || !d_breakpoints || !d_out_signal || !d_out_targets || !d_success || !d_inserted)
+        return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: null device pointer");
+    if (d_signal == d_out_signal || d_targets == d_out_targets) return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: outputs alias inputs");
+    const SpliceArgs a{n, N, Lt, first_index, seed, ubs_mask, prop, var_prop, cand_sample_size, pad};
+    if (int rc = splice_check(ctx, a)) return rc;
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = join_async_decode(ctx)) return rc;
+    ctx->result_stream = ctx->stream;
+    return splice_run(ctx, a, d_signal, d_targets, d_lengths, d_breakpoints, d_out_signal, d_out_targets, d_success, d_inserted);
+}
+
+XB_API int xb_splice_chunks(xb_ctx *ctx, const float *signal, const uint8_t *targets, const int32_t *lengths,
+                            const uint16_t *breakpoints, int n, int N, int Lt, int64_t first_index, uint64_t seed, int ubs_mask,
+                            double prop, double var_prop, int cand_sample_size, int pad, float *out_signal, uint8_t *out_targets,
+                            int8_t *success, int32_t *inserted)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    if (!signal || !targets || !lengths || !breakpoints || !out_signal || !out_targets || !success || !inserted)
+        return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: null host pointer");
+    const SpliceArgs a{n, N, Lt, first_index, seed, ubs_mask, prop, var_prop, cand_sample_size, pad};
+    if (int rc = splice_check(ctx, a)) return rc;
+    for (int c = 0; c < n; ++c) {                                       // what the kernel would otherwise clamp
+        const int len = lengths[c];
+        if (len < 0 || len > Lt) return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: chunk %d has %d labels in a row of %d", c, len, Lt);
+        const uint16_t *b = breakpoints + (size_t)c * Lt;
+        for (int l = 0; l < len; ++l)
+            if (b[l] > N || (l && b[l] < b[l - 1]))
+                return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: chunk %d: breakpoint %d of base %d (the one before: %d, samples: %d)", c,
+                            (int)b[l], l, l ? (int)b[l - 1] : 0, N);
+    }
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = join_async_decode(ctx)) return rc;
+    // staging: signal | out_signal | inserted | lengths | breakpoints | targets | out_targets | success, each 256-byte aligned
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t C = (size_t)n, b_sig = al(C * N * 4), b_i32 = al(C * 4), b_bk = al(C * Lt * 2), b_t = al(C * Lt), b_ok = al(C);
+    const size_t total = 2 * b_sig + 2 * b_i32 + b_bk + 2 * b_t + b_ok;
+    if (total > ((size_t)2 << 30)) return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: %d chunks of %d samples in one call; split the batch", n, N);
+    if (int rc = map_grow(ctx, &ctx->splice.staging, total)) return rc;
+    uint8_t *base = static_cast<uint8_t *>(ctx->splice.staging.p);
+    float *d_sig = reinterpret_cast<float *>(base), *d_out = reinterpret_cast<float *>(base + b_sig);
+    int32_t *d_ins = reinterpret_cast<int32_t *>(base + 2 * b_sig), *d_len = reinterpret_cast<int32_t *>(base + 2 * b_sig + b_i32);
+    uint16_t *d_bk = reinterpret_cast<uint16_t *>(base + 2 * b_sig + 2 * b_i32);
+    uint8_t *d_t = base + 2 * b_sig + 2 * b_i32 + b_bk, *d_ot = d_t + b_t;
+    int8_t *d_ok = reinterpret_cast<int8_t *>(d_ot + b_t);
+    XB_HIP(ctx, hipMemcpyAsync(d_sig, signal, C * N * 4, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(d_len, lengths, C * 4, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(d_bk, breakpoints, C * Lt * 2, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(d_t, targets, C * Lt, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = splice_run(ctx, a, d_sig, d_t, d_len, d_bk, d_out, d_ot, d_ok, d_ins)) return rc;
+    XB_HIP(ctx, hipMemcpyAsync(out_signal, d_out, C * N * 4, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(out_targets, d_ot, C * Lt, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(success, d_ok, C, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(inserted, d_ins, C * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return xb_synchronize(ctx);
+}
 
 XB_API int xb_set_profiling(xb_ctx *ctx, int on)
 {

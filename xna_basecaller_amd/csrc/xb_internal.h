@@ -308,6 +308,36 @@ constexpr size_t dtw_choice_words(int N, int M, int cols)
 }
 hipError_t launch_dtw(const DtwParams &p, int cols, bool band, hipStream_t stream);
 
+// ---------------------------------------------------------------- XNA spliced augmentation (xb_splice.hip)
+// xb_splice_chunks: per DNA chunk the positions, the candidate k-mers of the XNA library, their resampled signal pasted over
+// the chunk's own (the contract is in the public header).  One wave per chunk.
+constexpr int SPLICE_MAX_SAMPLES = 65535;   // samples per chunk (breakpoints.npy is uint16)
+constexpr int SPLICE_MAX_LABELS = 65535;    // entries per label row
+constexpr int SPLICE_MAX_CAND = 32;         // cand_sample_size
+constexpr int SPLICE_MAX_KMER = 100;        // samples of one library row (the reference's max_kmer_cnt)
+constexpr int SPLICE_KMERS = 6;
+constexpr int SPLICE_TEMPLATES = 16807;     // 7^5
+constexpr int SPLICE_TABLE_LEN = 2 * SPLICE_TEMPLATES * SPLICE_KMERS;
+struct SpliceParams {
+    const float *signal;         // (n, N) fp32
+    const uint8_t *targets;      // (n, Lt) labels 0 .. 6
+    const int32_t *lengths;      // (n)
+    const uint16_t *bkps;        // (n, Lt): the sample where every base's signal ends
+    int n, N, Lt;
+    unsigned long long first_index, seed;
+    int n_ubs, ubs[2];           // the labels (5, 6) the choice runs over, in its order
+    double prop, var_prop;
+    int cand, pad;
+    const half_t *pool;          // the library: signal pool, rows (n_rows, 2) pool offset and length, table (first row, count)
+    const int32_t *rows;
+    const int32_t *table;
+    float *out_signal;           // (n, N)
+    uint8_t *out_targets;        // (n, Lt)
+    int8_t *success;             // (n)
+    int32_t *inserted;           // (n)
+};
+hipError_t launch_splice(const SpliceParams &p, hipStream_t stream);
+
 #ifdef XB_LSTM_STAMPS
 void lstm_read_stamps(unsigned long long out[10], bool reset);   // diagnostic build only
 void gemm_read_stamps(unsigned long long out[8], bool reset);    // diagnostic build only (XB_GEMM_STAMPS)

@@ -1,7 +1,7 @@
 """
 DTW signal segmentation of ctc-data (the reference's src/tools/dtw_segmentation.py): for every chunk the sample index where
-each reference base's signal ends -- `breakpoints.npy`, which the reference's XNA augmentation cannot load a data set
-without.  The alignment itself runs on the device (xb_dtw_segment, include/xna_basecaller.h: parity unpinned); this module
+each reference base's signal ends -- `breakpoints.npy`, which the reference's XNA augmentation (here: splice.py) cannot load
+a data set without.  The alignment itself runs on the device (xb_dtw_segment, include/xna_basecaller.h: parity unpinned); this module
 is the host side: the k-mer pore model, the expected levels of a reference sequence, batching.
 
 Departures from the reference, all stated in INTEGRATION.md: the noise of the level normalisation comes from an explicit
