@@ -1,236 +1,8 @@
 // xb_api.hip -- C ABI of libxnacall.so (see include/xna_basecaller.h for the contract and the
 // reference call sites each entry point replaces).
-#include <hip/hip_runtime.h>
+#include "xb_ctx.h"
 
-#include <algorithm>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <string>
-#include <vector>
-
-#include "../../include/xna_basecaller.h"
-#include "xb_internal.h"
-
-using xb::half_t;
-
-namespace {
-
-thread_local std::string g_create_error;
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-};
-
-struct StageEvent {
-    int stage;
-    hipEvent_t a, b;
-};
-
-// What a Viterbi decode writes beside the bases (seq, len), by output level: 0 nothing, 1 qualities and moves (the kernel's
-// quality variant), 2 those and the letter probabilities (its UB variant).  Device pointers, except in the bodies of the
-// host-pointer entry points.
-struct DecodeOut {
-    int level = 0;
-    float qscale = 1.0f, qoffset = 0.0f;
-    int8_t *qstr = nullptr;      // (n, T), level >= 1
-    uint8_t *moves = nullptr;    // (n, T) or nullptr, level >= 1
-    uint8_t *probs = nullptr;    // (n, nb, T), level 2
-};
-
-// A decode's outputs as byte planes: seq (T bytes per chunk), len (4), qstring (T), moves (T), probs (nb T).  A level writes
-// the first plane_count(level); len and moves may be null.
-constexpr int PLANES = 5;
-struct Planes {
-    void *p[PLANES];
-};
-
-Planes planes(void *seq, void *len, const DecodeOut &o) { return {{seq, len, o.qstr, o.moves, o.probs}}; }
-int plane_count(int level) { return level == 0 ? 2 : (level == 1 ? 4 : 5); }
-size_t plane_bytes(int T, int nb, int i) { return i == 1 ? sizeof(int32_t) : (i == 4 ? (size_t)nb * T : (size_t)T); }
-// seq, and by level qstring and probs: the planes an entry point requires (xb_decode alone may leave seq out)
-bool has_required(const Planes &o, int level) { return o.p[0] && (level < 1 || o.p[2]) && (level < 2 || o.p[4]); }
-
-}  // namespace
-
-struct xb_ctx {
-    xb_config cfg{};
-    int device = 0;
-    int cu_count = 256;
-    hipStream_t stream = nullptr;    // main stream (highest priority): everything except the overlapped GEMM slabs
-    hipStream_t stream2 = nullptr;   // low-priority stream: the next layer's input GEMM, slab by slab, beside the recurrence
-    hipStream_t stream3 = nullptr;   // low-priority stream: CRF decode of batch k beside the encoder of batch k+1
-    hipEvent_t dec_done[2] = {};     // decode that last read scores buffer p has finished
-    bool dec_pending[2] = {};
-    unsigned batch_idx = 0;
-    hipStream_t result_stream = nullptr;   // stream that produces the outputs of the most recent *_dev call
-    // host pipeline (xb_submit_chunks / xb_collect_chunks): two slots of pinned staging + device buffers
-    struct Slot {
-        float *h_signal = nullptr, *d_signal = nullptr;
-        // pinned + device outputs of max_batch chunks, plane by plane: those of an output level are allocated by the slot's
-        // first submission at that level
-        Planes h{}, d{};
-        unsigned *h_err = nullptr;             // snapshot of the device error word taken on the result stream behind this batch
-        hipEvent_t h2d = nullptr, done = nullptr;
-        int n = 0;
-        bool busy = false;
-        int level = 0;                         // output level of the batch in flight
-    } slots[XB_PIPELINE_SLOTS];
-    bool pipeline_failed = false;          // a collected batch reported a lost rendezvous: every batch in flight fails with it
-    hipStream_t stream_copy = nullptr;     // H2D of the next batch beside the compute of the current one
-    std::vector<hipEvent_t> deps;    // timing-less events for the cross-stream dependencies (reused every call)
-    size_t dep_next = 0;
-    int overlap = 1, time_slabs = 16;   // XB_OVERLAP / XB_TIME_SLABS (upper bound; a slab is at least 125 steps)
-    int slab_steps = 0;                 // XB_SLAB_STEPS: minimum steps per time slab (default 125)
-    // one recurrence launch per layer that reports its time slabs to the GEMM stream (XB_LSTM_SIGNAL, default on where
-    // hipStreamWaitValue32 is supported): flag word, the value the last slab of the previous layer published, slab counters
-    int lstm_signal = 2;                // 0 off, 1 whenever one launch holds the batch, 2 (default) only above 512 chunks (two groups per workgroup)
-    unsigned *sig_flag = nullptr, *sig_done = nullptr;
-    unsigned sig_seq = 0;
-    mutable std::string err;
-    int T = 0, S = 0, hi = 0, O = 0, kp = 0, ld_nb = 0;
-    bool weights_ready = false;
-    std::map<std::string, std::vector<float>> host_w;
-    std::vector<DevBuf> bufs;
-    std::vector<DevBuf> wsbufs;                // the batch-sized workspaces (alloc_workspaces)
-    bool alloc_ws = false;
-
-    // weights on device
-    float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *b3 = nullptr;
-    half_t *w3_hi = nullptr, *w3_lo = nullptr;
-    half_t *wih_hi[5] = {}, *wih_lo[5] = {}, *whh_hi[5] = {}, *whh_lo[5] = {};
-    float *lbias[5] = {};
-    half_t *wl_hi = nullptr, *wl_lo = nullptr;
-    float *bl = nullptr;
-    int w3_exp = 0, wih_exp[5] = {}, whh_exp[5] = {}, wl_exp = 0;   // q8 exponents (XB_PREC_F16F8)
-    // fragment-major images of the GEMM B operands (gemm4p_kernel, xb_internal.h) and their k-tile strides; the input
-    // projections also as hi-only images for XB_PREC_F16F8_IN1
-    unsigned char *w3_f4 = nullptr, *wih_f4[5] = {}, *wih_f4h[5] = {}, *wl_f4 = nullptr;
-    size_t w3_ks = 0, wih_ks = 0, wih_ksh = 0, wl_ks = 0;
-    int gemm_sn = 0;                           // XB_GEMM_SN: N tiles per XCD super-tile of gemm4p_kernel (0 = gemm_super_n's rule; experiments)
-    int gemm_shadow_kernel = 0;                // XB_GEMM_SHADOW: 0 auto (by batch size), 4 gemm4p_kernel, 8 gemm8r_kernel for the slabs beside the recurrence
-    int gemm_shadow_wgs = 2;                   // XB_GEMM_SHADOW_WGS=1: GEMM slabs beside the recurrence run one workgroup per CU
-    int gemm4 = 1;                             // XB_GEMM4=0: gemm8r_kernel (one workgroup per CU) instead of gemm4p_kernel (A/B comparisons)
-    std::vector<void *> wbufs;                 // weight allocations of the current xb_weights_ready (freed by the next one)
-    int8_t *whh_q1[5] = {}, *whh_q0[5] = {};   // int8-limb recurrence (lstm_i8): balanced digits of W_hh, gate-interleaved rows
-    float *whh_sc[5] = {};                     // ... and the factor that turns the integer sum into the recurrent term
-    int lstm_i8 = 0;                           // XB_LSTM_I8 (with precision f16f8 / f16f8i): recurrence on int8 digits; 1 = all
-                                               // four digit products, 2 = without d0 x d0
-
-    // activations / workspaces
-    float *d_signal = nullptr;
-    half_t *im_hi = nullptr, *im_lo = nullptr;
-    half_t *x_hi[2] = {}, *x_lo[2] = {};
-    float *gin = nullptr, *gin2 = nullptr, *c_state = nullptr, *scores = nullptr, *scores2 = nullptr;
-    half_t *xh = nullptr;        // LSTM exchange buffer: 64 groups x 2 parity x 2 parts x 64 chunks x F
-    float *alpha = nullptr, *beta = nullptr, *bmax = nullptr, *qbuf = nullptr, *logz = nullptr;
-    // beam search workspaces and staging (lazily allocated: most contexts never use them)
-    uint32_t *beam_hist = nullptr;
-    int32_t *beam_path = nullptr;
-    float *beam_prob = nullptr, *beam_score = nullptr;
-    int8_t *beam_seq = nullptr, *beam_q = nullptr;
-    uint8_t *beam_moves = nullptr;
-    int8_t *labels = nullptr, *seq = nullptr;
-    int32_t *seq_len = nullptr;
-    // the planes of output levels 1 (qstring, moves) and 2 (probs), lazily allocated by ensure_staging: the device staging
-    // of the host-pointer calls (max_batch chunks) and the results of a co-scheduled pair before they are split
-    // (2 max_batch); level 2 also the per-step letter mass workspace (cap, T, nb) fp32
-    int8_t *q_seq = nullptr, *q_fseq = nullptr;
-    uint8_t *q_moves = nullptr, *q_fmoves = nullptr;
-    uint8_t *u_probs = nullptr, *u_fprobs = nullptr;
-    float *u_buf = nullptr;
-    unsigned *sync = nullptr;    // [64 groups * 32] counters + error word at the end
-    unsigned *error = nullptr;
-    int lstm_mode = 0;
-    // workgroups of the persistent kernel admitted per CU, by recurrence arithmetic (nsplit 1..5) and one / two groups per
-    // workgroup (occupancy query, lazily; -1 = not asked yet)
-    int lstm_resident[6][2] = {{-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}};
-    // Arithmetic of every contraction stage (GemmParams::nsplit: 1 fp16 product, 2 + FP8 corrections, 3 three fp16 products):
-    // conv3, the five input projections, the five recurrences, the CRF linear layer.  One value everywhere for the plain
-    // precisions; XB_PREC_MIXED (and the diagnostic XB_X3_STAGES mask) mix 2 and 3.  An activation tensor's second part
-    // (q8 image or fp16 residual) follows the stage that CONSUMES it.
-    int ns_conv = 3, ns_in[5] = {3, 3, 3, 3, 3}, ns_rec[5] = {3, 3, 3, 3, 3}, ns_lin = 3;
-    int in1_layers = 31;         // XB_IN1_LAYERS (diagnostic): layers whose input projection XB_PREC_F16F8_IN1 reduces
-    int decode_async = 0;        // XB_DECODE_ASYNC=1: the decode of a batch runs on the third stream beside the next batch's conv + first
-                                 // GEMM (rounds 2-3) instead of on the main stream with the chip to itself (round 4 default: the same step
-                                 // time at every batch size -- the step is bound by the kernels' summed CU-time -- and the decode at 0.49-0.52
-                                 // of the HBM roofline instead of 0.35-0.42: profiles/r04_decode_placement.txt)
-    int lstm_local = 1;          // XB_LSTM_LOCAL=0: always exchange h with write-through stores (A/B)
-    int lstm_wide = 1;           // XB_LSTM_WIDE: 1 (default) batches just above a launch's XCD-local capacity get up to cu_count / members group
-                                 // slots with the groups dealt over all XCDs instead of a second round (run_lstm_layer); 0: never
-    int lstm_dual = 1;           // XB_LSTM_DUAL: 0 never, 1 when a launch would otherwise need a second chunk slab, 2 always
-
-    // Two asynchronous basecalls in flight are co-scheduled once the caller has opted in with xb_reserve_pairing (contexts of at
-    // most 512 chunks; XB_FUSE=0 refuses): the first xb_basecall_chunks_dev of a pair is held back until the second arrives, then
-    // both batches go through the encoder and the decode as ONE batch (the recurrence then runs two chunk groups per workgroup,
-    // DESIGN.md 4.1 / 4.5).  Every other entry point, xb_synchronize and xb_result_stream first launch a held-back call on its own.
-    // Without the opt-in every asynchronous call is enqueued before it returns.
-    struct Call {
-        const float *signal = nullptr;
-        int n = 0;
-        char alphabet[16] = {};
-        int8_t *seq = nullptr;
-        int32_t *len = nullptr;
-        int slot = -1;                          // host pipeline slot whose D2H copies and done event follow the launch
-        void (*after)(void *) = nullptr;        // xb_comm: the gather of this call's results, enqueued right behind it
-        void *after_arg = nullptr;
-        DecodeOut out;                          // output level (xb_basecall_chunks_q / _ub, xb_submit_chunks_q / _ub) and its planes
-    };
-    int fuse_ok = 1;                            // pairing is possible in this context (schedule, batch size, XB_FUSE)
-    int fuse = 0;                               // ... and the caller asked for it (xb_reserve_pairing)
-    int cap = 0;                                // chunks the workspaces hold (2 * max_batch when fusing is possible)
-    Call held;
-    bool holding = false, flushing = false;
-    int deferred_rc = 0;                        // failure of a held-back call that was launched where no status could be returned
-    int8_t *fseq = nullptr;                     // (cap, T) / (cap) results of a fused pair before they are split
-    int32_t *flen = nullptr;
-
-    // template mapper (xb_map_templates): the library last passed in (host copy and its device image: codes, offsets, the
-    // chunks of the score pass) and buffers that grow with the calls -- the score pass's records, the trace pass's direction
-    // scratch, the staging of the host-pointer form.  Owned here, freed by xb_ctx_destroy.
-    struct MapState {
-        std::vector<char> lib;
-        std::vector<int32_t> off;
-        int Lmax = 0, nchunks = 0;
-        DevBuf image, partial, scratch, staging;
-        DevBuf ctc_staging;                         // xb_ctc_targets (host form) and xb_ctc_chunks
-        DevBuf ub_staging;                          // xb_ub_tally (host form)
-    } map;
-
-    // DTW segmentation (xb_dtw_segment): the choice-bit scratch of the launches in flight, the staging of the host-pointer
-    // form, and the chunks' level offsets on their way to the device -- two pinned slots in rotation, so that a call returns
-    // without waiting for its own device work.  Owned here, freed by xb_ctx_destroy.
-    struct DtwState {
-        DevBuf scratch, staging;
-        struct Slot {
-            int32_t *h = nullptr, *d = nullptr;
-            size_t count = 0;
-            hipEvent_t copied = nullptr;
-        } off[2];
-        unsigned calls = 0;
-        size_t scratch_written = 0;                 // bytes of choice words the last call's launches were sized for
-    } dtw;
-
-    // XNA spliced augmentation (xb_splice_library / xb_splice_chunks): the library's device image, kept until the next
-    // xb_splice_library, and the staging of the host-pointer form.  Owned here, freed by xb_ctx_destroy.
-    struct SpliceState {
-        DevBuf pool, rows, table, staging;
-        bool loaded = false;
-    } splice;
-
-    bool profiling = false;
-    std::vector<StageEvent> events;
-    float stage_ms[XB_STAGE_COUNT] = {};
-    int64_t stage_launches[XB_STAGE_COUNT] = {};
-};
-
-extern "C" int flush_held(xb_ctx *ctx);      // launches a held-back asynchronous basecall (defined with it below)
-
-namespace {
+namespace { thread_local std::string g_create_error; }
 
 int fail(const xb_ctx *ctx, int code, const char *fmt, ...)
 {
@@ -243,13 +15,42 @@ int fail(const xb_ctx *ctx, int code, const char *fmt, ...)
     return code;
 }
 
-#define XB_HIP(ctx, call)                                                                     \
-    do {                                                                                      \
-        hipError_t e_ = (call);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(ctx, e_ == hipErrorOutOfMemory ? XB_ERR_NOMEM : XB_ERR_HIP,           \
-                        "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+int check_ready(xb_ctx *ctx, int n)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    if (!ctx->weights_ready) return fail(ctx, XB_ERR_STATE, "weights not loaded: call xb_load_weights for all 28 tensors, then xb_weights_ready");
+    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
+    if (ctx->cap < ctx->cfg.max_batch) return fail(ctx, XB_ERR_NOMEM, "the context lost its workspaces (a reallocation failed)");
+    return XB_OK;
+}
+
+// every entry point except the asynchronous basecall first orders the main stream behind decodes still in flight on the
+// third stream (they share the decode workspaces and the score buffers)
+int join_async_decode(xb_ctx *ctx)
+{
+    if (int rc = flush_held(ctx)) return rc;
+    for (int p = 0; p < 2; ++p)
+        if (ctx->dec_pending[p]) {
+            XB_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->dec_done[p], 0));
+            ctx->dec_pending[p] = false;
+        }
+    return XB_OK;
+}
+
+int check_alphabet(xb_ctx *ctx, const char *alphabet)
+{
+    if ((int)strlen(alphabet) < ctx->cfg.n_base + 1 || strlen(alphabet) >= sizeof(xb_ctx::Call{}.alphabet))
+        return fail(ctx, XB_ERR_INVALID, "alphabet needs %d symbols", ctx->cfg.n_base + 1);
+    return XB_OK;
+}
+
+namespace {
+
+Planes planes(void *seq, void *len, const DecodeOut &o) { return {{seq, len, o.qstr, o.moves, o.probs}}; }
+int plane_count(int level) { return level == 0 ? 2 : (level == 1 ? 4 : 5); }
+size_t plane_bytes(int T, int nb, int i) { return i == 1 ? sizeof(int32_t) : (i == 4 ? (size_t)nb * T : (size_t)T); }
+// seq, and by level qstring and probs: the planes an entry point requires (xb_decode alone may leave seq out)
+bool has_required(const Planes &o, int level) { return o.p[0] && (level < 1 || o.p[2]) && (level < 2 || o.p[4]); }
 
 int64_t ipow(int64_t b, int e) { int64_t r = 1; while (e-- > 0) r *= b; return r; }
 
@@ -472,15 +273,6 @@ int upload(xb_ctx *ctx, Tp **dst, const std::vector<Tp> &src)
     ctx->wbufs.push_back(p);
     *dst = reinterpret_cast<Tp *>(p);
     XB_HIP(ctx, hipMemcpy(*dst, src.data(), src.size() * sizeof(Tp), hipMemcpyHostToDevice));
-    return XB_OK;
-}
-
-int check_ready(xb_ctx *ctx, int n)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    if (!ctx->weights_ready) return fail(ctx, XB_ERR_STATE, "weights not loaded: call xb_load_weights for all 28 tensors, then xb_weights_ready");
-    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
-    if (ctx->cap < ctx->cfg.max_batch) return fail(ctx, XB_ERR_NOMEM, "the context lost its workspaces (a reallocation failed)");
     return XB_OK;
 }
 
@@ -837,19 +629,6 @@ int run_decode(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, 
     return XB_OK;
 }
 
-// every entry point except the asynchronous basecall first orders the main stream behind decodes still in flight on the
-// third stream (they share the decode workspaces and the score buffers)
-int join_async_decode(xb_ctx *ctx)
-{
-    if (int rc = flush_held(ctx)) return rc;
-    for (int p = 0; p < 2; ++p)
-        if (ctx->dec_pending[p]) {
-            XB_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->dec_done[p], 0));
-            ctx->dec_pending[p] = false;
-        }
-    return XB_OK;
-}
-
 template <typename Tp>
 int dev_alloc_once(xb_ctx *ctx, Tp **out, size_t count) { return *out ? XB_OK : dev_alloc(ctx, out, count); }
 
@@ -892,13 +671,6 @@ int copy_planes(xb_ctx *ctx, int level, const Planes &dst, const Planes &src, in
         if (dst.p[i] && src.p[i])
             XB_HIP(ctx, hipMemcpyAsync(dst.p[i], static_cast<const char *>(src.p[i]) + (size_t)c0 * b, (size_t)n * b, kind, st));
     }
-    return XB_OK;
-}
-
-int check_alphabet(xb_ctx *ctx, const char *alphabet)
-{
-    if ((int)strlen(alphabet) < ctx->cfg.n_base + 1 || strlen(alphabet) >= sizeof(xb_ctx::Call{}.alphabet))
-        return fail(ctx, XB_ERR_INVALID, "alphabet needs %d symbols", ctx->cfg.n_base + 1);
     return XB_OK;
 }
 
@@ -1083,9 +855,8 @@ XB_API void xb_ctx_destroy(xb_ctx *ctx)
     for (auto &ev : ctx->events) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto &b : ctx->bufs) (void)hipFree(b.p);
     for (auto &b : ctx->wsbufs) (void)hipFree(b.p);
-    for (DevBuf *b : {&ctx->map.image, &ctx->map.partial, &ctx->map.scratch, &ctx->map.staging, &ctx->map.ctc_staging, &ctx->map.ub_staging,
-                      &ctx->dtw.scratch, &ctx->dtw.staging, &ctx->splice.pool, &ctx->splice.rows, &ctx->splice.table,
-                      &ctx->splice.staging})
+    for (DevBuf *b : {&ctx->staging, &ctx->map.image, &ctx->map.partial, &ctx->map.scratch, &ctx->dtw.scratch, &ctx->splice.pool,
+                      &ctx->splice.rows, &ctx->splice.table})
         if (b->p) (void)hipFree(b->p);
     for (auto &o : ctx->dtw.off) {
         if (o.h) (void)hipHostFree(o.h);
@@ -1788,9 +1559,8 @@ static int enqueue_call(xb_ctx *ctx, const xb_ctx::Call &c)
     return launch_calls(ctx, c, nullptr);
 }
 
-// an asynchronous basecall of n chunks at d_signal into device outputs (seq, len, out), of pipeline slot `slot` or none
-static int basecall_async(xb_ctx *ctx, const float *d_signal, int n, const char *alphabet, int8_t *seq, int32_t *len,
-                          const DecodeOut &out, int slot = -1)
+int basecall_async(xb_ctx *ctx, const float *d_signal, int n, const char *alphabet, int8_t *seq, int32_t *len, const DecodeOut &out,
+                   int slot)
 {
     xb_ctx::Call c;
     c.signal = d_signal; c.n = n; c.seq = seq; c.len = len; c.slot = slot; c.out = out;
@@ -1964,755 +1734,6 @@ XB_API int xb_collect_chunks_q(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_
 XB_API int xb_collect_chunks(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len)
 {
     return collect_chunks(ctx, slot, 0, {{seq, seq_len, nullptr, nullptr, nullptr}});
-}
-
-// ---- template mapper (xb_map_templates) -----------------------------------------------------------------------------
-namespace {
-
-// Cells (query row x template column, both strands) one call may ask for, counted with every row as wide as W:
-// 2 n W sum(L).  The score pass runs 6.8e11 cells a second on an MI355X (profiles/map_time.txt: 1024 templates of 89 against
-// 4096 reads in 106 ms), so the bound keeps a call under a fifth of a second of device time.  The library itself is bounded
-// too: beyond a megabyte of templates (the 2.7 MB CPLX full-length library) exhaustive alignment is the wrong tool and a
-// seeding stage would be needed.
-constexpr double MAP_CELL_BUDGET = 1.2e11;
-constexpr size_t MAP_MAX_LIBRARY = (size_t)1 << 20;
-constexpr size_t MAP_MAX_SCRATCH = (size_t)256 << 20;
-
-int map_grow(xb_ctx *ctx, DevBuf *b, size_t bytes)
-{
-    if (bytes <= b->bytes) return XB_OK;
-    XB_HIP(ctx, hipStreamSynchronize(ctx->stream));                     // nothing in flight reads the old buffer
-    if (b->p) (void)hipFree(b->p);
-    b->p = nullptr;
-    b->bytes = 0;
-    bytes = (bytes + 255) & ~(size_t)255;
-    hipError_t e = hipMalloc(&b->p, bytes);
-    if (e != hipSuccess) return fail(ctx, XB_ERR_NOMEM, "hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
-    b->bytes = bytes;
-    return XB_OK;
-}
-
-struct MapOut {
-    int32_t *tmpl; int8_t *strand; int32_t *score, *second, *q_st, *q_en, *r_st, *r_en; uint8_t *ops; int32_t *n_ops;
-};
-
-// the library's device image (rebuilt only when the bytes change) for n rows of width W: validation, *lmax = the longest template
-// (sc: the mapper's scoring, checked where it always was; null for a caller that aligns nothing and is not held to the cell budget;
-// who: the entry point a refusal names)
-int map_library(xb_ctx *ctx, int n, int W, const char *templates, const int32_t *offsets, int R, const int *sc, int *lmax,
-                const char *who = "xb_map_templates")
-{
-    if (n < 1 || W < 1 || W > xb::MAP_MAX_ROW)
-        return fail(ctx, XB_ERR_INVALID, "%s: n = %d rows of width %d; need n >= 1 and 1 <= W <= %d", who, n, W, xb::MAP_MAX_ROW);
-    if (!templates || !offsets || R < 1 || offsets[0] != 0) return fail(ctx, XB_ERR_INVALID, "%s: empty template library", who);
-    for (int k = 0; sc && k < 5; ++k)
-        if (sc[k] < 0 || sc[k] > 1000) return fail(ctx, XB_ERR_INVALID, "%s: scoring values must lie in [0, 1000]", who);
-    int Lmax = 0;
-    for (int t = 0; t < R; ++t) {
-        const int L = offsets[t + 1] - offsets[t];
-        if (L < 1 || L > xb::MAP_MAX_TEMPLATE)
-            return fail(ctx, XB_ERR_INVALID, "%s: template %d has %d letters; 1 .. %d are supported", who, t, L, xb::MAP_MAX_TEMPLATE);
-        Lmax = std::max(Lmax, L);
-    }
-    const size_t total = (size_t)offsets[R];
-    const double cells = 2.0 * n * W * (double)total;
-    if (total > MAP_MAX_LIBRARY || (sc && cells > MAP_CELL_BUDGET))
-        return fail(ctx, XB_ERR_INVALID, "%s: a library of %d templates, %zu letters, against %d rows of width %d is %.3g "
-                    "cells; one call takes at most %.3g cells and a library of %zu letters (larger libraries need a seeding stage)", who,
-                    R, total, n, W, cells, MAP_CELL_BUDGET, MAP_MAX_LIBRARY);
-    xb_ctx::MapState &m = ctx->map;
-    const bool same = m.image.p && m.lib.size() == total && (int)m.off.size() == R + 1 &&
-                      !memcmp(m.lib.data(), templates, total) && !memcmp(m.off.data(), offsets, sizeof(int32_t) * (R + 1));
-    if (!same) {
-        std::vector<uint8_t> codes(total);
-        for (size_t k = 0; k < total; ++k) {
-            switch (templates[k]) {
-            case 'A': case 'a': codes[k] = 0; break;
-            case 'C': case 'c': codes[k] = 1; break;
-            case 'G': case 'g': codes[k] = 2; break;
-            case 'T': case 't': codes[k] = 3; break;
-            default: codes[k] = 4;
-            }
-        }
-        std::vector<int32_t> chunks{0};
-        for (int t = 0, used = 0; t < R; ++t) {
-            const int L = offsets[t + 1] - offsets[t];
-            if (used + L > xb::MAP_CHUNK_BYTES) { chunks.push_back(t); used = 0; }
-            used += L;
-        }
-        chunks.push_back(R);
-        const size_t a_off = (total + 15) & ~(size_t)15, a_chunk = a_off + sizeof(int32_t) * (R + 1);
-        m.lib.clear();                                                  // no image while it is being replaced
-        if (int rc = map_grow(ctx, &m.image, a_chunk + sizeof(int32_t) * chunks.size())) return rc;
-        XB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        uint8_t *img = static_cast<uint8_t *>(m.image.p);
-        XB_HIP(ctx, hipMemcpy(img, codes.data(), total, hipMemcpyHostToDevice));
-        XB_HIP(ctx, hipMemcpy(img + a_off, offsets, sizeof(int32_t) * (R + 1), hipMemcpyHostToDevice));
-        XB_HIP(ctx, hipMemcpy(img + a_chunk, chunks.data(), sizeof(int32_t) * chunks.size(), hipMemcpyHostToDevice));
-        m.lib.assign(templates, templates + total);
-        m.off.assign(offsets, offsets + R + 1);
-        m.Lmax = Lmax;
-        m.nchunks = (int)chunks.size() - 1;
-    }
-    *lmax = Lmax;
-    return XB_OK;
-}
-
-// validation, the library's device image, the two launches: seq, seq_len and o are device pointers
-int map_run(xb_ctx *ctx, const int8_t *d_seq, const int32_t *d_len, int n, int W, const char *templates, const int32_t *offsets,
-            int R, const int sc[5], const MapOut &o)
-{
-    int Lmax = 0;
-    if (int rc = map_library(ctx, n, W, templates, offsets, R, sc, &Lmax)) return rc;
-    xb_ctx::MapState &m = ctx->map;
-    const size_t total = (size_t)offsets[R];
-    xb::MapParams p{};
-    p.seq = d_seq; p.seq_len = d_len; p.n = n; p.W = W;
-    const size_t a_off = (total + 15) & ~(size_t)15;
-    uint8_t *img = static_cast<uint8_t *>(m.image.p);
-    p.tcodes = img;
-    p.toff = reinterpret_cast<const int32_t *>(img + a_off);
-    p.chunk_first = p.toff + (R + 1);
-    p.R = R; p.Lmax = Lmax; p.nchunks = m.nchunks;
-    p.match = sc[0]; p.mismatch = sc[1]; p.gap_open = sc[2]; p.gap_extend = sc[3]; p.ambiguous = sc[4];
-    if (int rc = map_grow(ctx, &m.partial, sizeof(int32_t) * xb::MAP_PARTIAL_INTS * (size_t)n * m.nchunks)) return rc;
-    p.partial = static_cast<int32_t *>(m.partial.p);
-    p.trace_wgs = std::min(n, 2048);
-    if (!xb::map_trace_in_lds(W, Lmax)) {
-        const size_t one = (size_t)W * Lmax;
-        p.trace_wgs = (int)std::max<size_t>(1, std::min<size_t>(p.trace_wgs, MAP_MAX_SCRATCH / one));
-        if (int rc = map_grow(ctx, &m.scratch, one * p.trace_wgs)) return rc;
-        p.scratch = static_cast<uint8_t *>(m.scratch.p);
-    }
-    p.tmpl = o.tmpl; p.strand = o.strand; p.score = o.score; p.second = o.second;
-    p.q_st = o.q_st; p.q_en = o.q_en; p.r_st = o.r_st; p.r_en = o.r_en; p.ops = o.ops; p.n_ops = o.n_ops;
-    XB_HIP(ctx, xb::launch_map_score(p, ctx->stream));
-    XB_HIP(ctx, xb::launch_map_trace(p, ctx->stream));
-    return XB_OK;
-}
-
-bool map_out_complete(const MapOut &o)
-{
-    return o.tmpl && o.strand && o.score && o.second && o.q_st && o.q_en && o.r_st && o.r_en && o.ops && o.n_ops;
-}
-
-}  // namespace
-
-XB_API int xb_map_templates_dev(xb_ctx *ctx, const int8_t *d_seq, const int32_t *d_seq_len, int n, int W, const char *templates,
-                                const int32_t *offsets, int R, int match, int mismatch, int gap_open, int gap_extend, int ambiguous,
-                                int32_t *d_tmpl, int8_t *d_strand, int32_t *d_score, int32_t *d_second, int32_t *d_q_st,
-                                int32_t *d_q_en, int32_t *d_r_st, int32_t *d_r_en, uint8_t *d_ops, int32_t *d_n_ops)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    const MapOut o = {d_tmpl, d_strand, d_score, d_second, d_q_st, d_q_en, d_r_st, d_r_en, d_ops, d_n_ops};
-    if (!d_seq || !d_seq_len || !map_out_complete(o)) return fail(ctx, XB_ERR_INVALID, "xb_map_templates: null device pointer");
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
-    ctx->result_stream = ctx->stream;
-    const int sc[5] = {match, mismatch, gap_open, gap_extend, ambiguous};
-    return map_run(ctx, d_seq, d_seq_len, n, W, templates, offsets, R, sc, o);
-}
-
-XB_API int xb_map_templates(xb_ctx *ctx, const int8_t *seq, const int32_t *seq_len, int n, int W, const char *templates,
-                            const int32_t *offsets, int R, int match, int mismatch, int gap_open, int gap_extend, int ambiguous,
-                            int32_t *tmpl, int8_t *strand, int32_t *score, int32_t *second, int32_t *q_st, int32_t *q_en,
-                            int32_t *r_st, int32_t *r_en, uint8_t *ops, int32_t *n_ops)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    const MapOut h = {tmpl, strand, score, second, q_st, q_en, r_st, r_en, ops, n_ops};
-    if (!seq || !seq_len || !map_out_complete(h)) return fail(ctx, XB_ERR_INVALID, "xb_map_templates: null host pointer");
-    if (n < 1 || W < 1 || W > xb::MAP_MAX_ROW || !offsets || R < 1)
-        return fail(ctx, XB_ERR_INVALID, "xb_map_templates: n = %d rows of width %d, %d templates; need n >= 1, 1 <= W <= %d, R >= 1",
-                    n, W, R, xb::MAP_MAX_ROW);
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
-    int Lmax = 0;
-    for (int t = 0; t < R; ++t) Lmax = std::max(Lmax, offsets[t + 1] - offsets[t]);
-    if (Lmax < 1 || Lmax > xb::MAP_MAX_TEMPLATE)
-        return fail(ctx, XB_ERR_INVALID, "xb_map_templates: the longest template has %d letters; 1 .. %d are supported", Lmax, xb::MAP_MAX_TEMPLATE);
-    // staging: seq | len | the eight int32 outputs | strand | ops, each 256-byte aligned
-    const size_t N = (size_t)n, cap = (size_t)W + Lmax;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_seq = al(N * W), b_i32 = al(N * 4), b_i8 = al(N), b_ops = al(N * cap);
-    if (b_seq + 9 * b_i32 + b_i8 + b_ops > ((size_t)2 << 30))
-        return fail(ctx, XB_ERR_INVALID, "xb_map_templates: %d rows of width %d in one call; split the batch", n, W);
-    if (int rc = map_grow(ctx, &ctx->map.staging, b_seq + 9 * b_i32 + b_i8 + b_ops)) return rc;
-    uint8_t *base = static_cast<uint8_t *>(ctx->map.staging.p);
-    int8_t *d_seq = reinterpret_cast<int8_t *>(base);
-    int32_t *d_i32[9];
-    for (int k = 0; k < 9; ++k) d_i32[k] = reinterpret_cast<int32_t *>(base + b_seq + k * b_i32);
-    int8_t *d_strand = reinterpret_cast<int8_t *>(base + b_seq + 9 * b_i32);
-    uint8_t *d_ops = reinterpret_cast<uint8_t *>(d_strand) + b_i8;
-    XB_HIP(ctx, hipMemcpyAsync(d_seq, seq, N * W, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(d_i32[0], seq_len, N * 4, hipMemcpyHostToDevice, ctx->stream));
-    const MapOut d = {d_i32[1], d_strand, d_i32[2], d_i32[3], d_i32[4], d_i32[5], d_i32[6], d_i32[7], d_ops, d_i32[8]};
-    const int sc[5] = {match, mismatch, gap_open, gap_extend, ambiguous};
-    if (int rc = map_run(ctx, d_seq, d_i32[0], n, W, templates, offsets, R, sc, d)) return rc;
-    int32_t *const h_i32[8] = {tmpl, score, second, q_st, q_en, r_st, r_en, n_ops};
-    for (int k = 0; k < 8; ++k)
-        XB_HIP(ctx, hipMemcpyAsync(h_i32[k], d_i32[k + 1], N * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(strand, d_strand, N, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(ops, d_ops, N * cap, hipMemcpyDeviceToHost, ctx->stream));
-    return xb_synchronize(ctx);
-}
-
-// ---- ctc-data labels of mapped rows (xb_ctc_targets, xb_ctc_chunks) ---------------------------------------------------
-namespace {
-
-struct CtcIn {
-    const int32_t *seq_len, *tmpl; const int8_t *strand; const int32_t *q_st, *q_en, *r_st, *r_en; const uint8_t *ops; const int32_t *n_ops;
-};
-struct CtcOut {
-    int32_t *mlen, *blen; uint8_t *verdict, *target; int32_t *target_len;
-};
-struct CtcRule {
-    double min_accuracy, min_coverage; int ub_only, ub_plus, ub_minus;
-};
-
-bool ctc_complete(const CtcIn &i, const CtcOut &o)
-{
-    return i.seq_len && i.tmpl && i.strand && i.q_st && i.q_en && i.r_st && i.r_en && i.ops && i.n_ops && o.mlen && o.blen && o.verdict &&
-           o.target && o.target_len;
-}
-
-// validation, the library's device image, the launch: i and o are device pointers
-int ctc_run(xb_ctx *ctx, const CtcIn &i, int n, int W, const char *templates, const int32_t *offsets, int R, const CtcRule &rule,
-            const CtcOut &o)
-{
-    if (rule.ub_plus < 1 || rule.ub_plus > 255 || rule.ub_minus < 1 || rule.ub_minus > 255)
-        return fail(ctx, XB_ERR_INVALID, "xb_ctc_targets: ub_plus = %d, ub_minus = %d; labels are 1 .. 255", rule.ub_plus, rule.ub_minus);
-    if (!(rule.min_accuracy == rule.min_accuracy) || !(rule.min_coverage == rule.min_coverage))
-        return fail(ctx, XB_ERR_INVALID, "xb_ctc_targets: a threshold is not a number");
-    if (reinterpret_cast<uintptr_t>(o.target) & 15) return fail(ctx, XB_ERR_INVALID, "xb_ctc_targets: target must be 16-byte aligned");
-    int Lmax = 0;
-    if (int rc = map_library(ctx, n, W, templates, offsets, R, nullptr, &Lmax)) return rc;
-    const size_t total = (size_t)offsets[R];
-    const uint8_t *img = static_cast<const uint8_t *>(ctx->map.image.p);
-    xb::CtcTargetParams p{};
-    p.seq_len = i.seq_len; p.n = n; p.W = W; p.cap = W + Lmax;
-    p.tmpl = i.tmpl; p.strand = i.strand; p.q_st = i.q_st; p.q_en = i.q_en; p.r_st = i.r_st; p.r_en = i.r_en; p.ops = i.ops; p.n_ops = i.n_ops;
-    p.tcodes = img;
-    p.toff = reinterpret_cast<const int32_t *>(img + ((total + 15) & ~(size_t)15));
-    p.R = R; p.TW = xb::ctc_target_width(Lmax);
-    p.min_accuracy = rule.min_accuracy; p.min_coverage = rule.min_coverage;
-    p.ub_only = rule.ub_only != 0; p.ub_plus = rule.ub_plus; p.ub_minus = rule.ub_minus;
-    p.mlen = o.mlen; p.blen = o.blen; p.verdict = o.verdict; p.target = o.target; p.target_len = o.target_len;
-    XB_HIP(ctx, xb::launch_ctc_targets(p, ctx->stream));
-    return XB_OK;
-}
-
-// 256-byte aligned pieces of one staging buffer, in the order they are asked for
-struct Carve {
-    size_t used = 0;
-    size_t take(size_t bytes) { const size_t at = used; used += (bytes + 255) & ~(size_t)255; return at; }
-};
-
-int longest_template(xb_ctx *ctx, const int32_t *offsets, int R, int *lmax)
-{
-    int Lmax = 0;
-    for (int t = 0; offsets && t < R; ++t) Lmax = std::max(Lmax, offsets[t + 1] - offsets[t]);
-    if (Lmax < 1 || Lmax > xb::MAP_MAX_TEMPLATE)
-        return fail(ctx, XB_ERR_INVALID, "xb_ctc_targets: the longest template has %d letters; 1 .. %d are supported", Lmax, xb::MAP_MAX_TEMPLATE);
-    *lmax = Lmax;
-    return XB_OK;
-}
-
-}  // namespace
-
-XB_API int xb_ctc_targets_dev(xb_ctx *ctx, const int32_t *d_seq_len, int n, int W, const char *templates, const int32_t *offsets,
-                              int R, const int32_t *d_tmpl, const int8_t *d_strand, const int32_t *d_q_st, const int32_t *d_q_en,
-                              const int32_t *d_r_st, const int32_t *d_r_en, const uint8_t *d_ops, const int32_t *d_n_ops,
-                              double min_accuracy, double min_coverage, int ub_only, int ub_plus, int ub_minus, int32_t *d_mlen,
-                              int32_t *d_blen, uint8_t *d_verdict, uint8_t *d_target, int32_t *d_target_len)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    const CtcIn i = {d_seq_len, d_tmpl, d_strand, d_q_st, d_q_en, d_r_st, d_r_en, d_ops, d_n_ops};
-    const CtcOut o = {d_mlen, d_blen, d_verdict, d_target, d_target_len};
-    if (!ctc_complete(i, o)) return fail(ctx, XB_ERR_INVALID, "xb_ctc_targets: null device pointer");
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
-    ctx->result_stream = ctx->stream;
-    return ctc_run(ctx, i, n, W, templates, offsets, R, {min_accuracy, min_coverage, ub_only, ub_plus, ub_minus}, o);
-}
-
-XB_API int xb_ctc_targets(xb_ctx *ctx, const int32_t *seq_len, int n, int W, const char *templates, const int32_t *offsets, int R,
-                          const int32_t *tmpl, const int8_t *strand, const int32_t *q_st, const int32_t *q_en, const int32_t *r_st,
-                          const int32_t *r_en, const uint8_t *ops, const int32_t *n_ops, double min_accuracy, double min_coverage,
-                          int ub_only, int ub_plus, int ub_minus, int32_t *mlen, int32_t *blen, uint8_t *verdict, uint8_t *target,
-                          int32_t *target_len)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    const CtcIn h = {seq_len, tmpl, strand, q_st, q_en, r_st, r_en, ops, n_ops};
-    const CtcOut ho = {mlen, blen, verdict, target, target_len};
-    if (!ctc_complete(h, ho)) return fail(ctx, XB_ERR_INVALID, "xb_ctc_targets: null host pointer");
-    if (n < 1 || W < 1 || W > xb::MAP_MAX_ROW || R < 1)
-        return fail(ctx, XB_ERR_INVALID, "xb_ctc_targets: n = %d rows of width %d, %d templates; need n >= 1, 1 <= W <= %d, R >= 1", n, W, R,
-                    xb::MAP_MAX_ROW);
-    int Lmax = 0;
-    if (int rc = longest_template(ctx, offsets, R, &Lmax)) return rc;
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
-    const size_t N = (size_t)n, cap = (size_t)W + Lmax, TW = (size_t)xb::ctc_target_width(Lmax);
-    if (N * (cap + TW) > ((size_t)2 << 30)) return fail(ctx, XB_ERR_INVALID, "xb_ctc_targets: %d rows of width %d in one call; split the batch", n, W);
-    Carve c;
-    size_t a_i32[10];
-    for (size_t &a : a_i32) a = c.take(N * 4);          // seq_len, tmpl, q_st, q_en, r_st, r_en, n_ops | mlen, blen, target_len
-    const size_t a_strand = c.take(N), a_verdict = c.take(N), a_ops = c.take(N * cap), a_target = c.take(N * TW);
-    if (int rc = map_grow(ctx, &ctx->map.ctc_staging, c.used)) return rc;
-    uint8_t *base = static_cast<uint8_t *>(ctx->map.ctc_staging.p);
-    auto i32 = [&](int k) { return reinterpret_cast<int32_t *>(base + a_i32[k]); };
-    const int32_t *const src[7] = {seq_len, tmpl, q_st, q_en, r_st, r_en, n_ops};
-    for (int k = 0; k < 7; ++k) XB_HIP(ctx, hipMemcpyAsync(i32(k), src[k], N * 4, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(base + a_strand, strand, N, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(base + a_ops, ops, N * cap, hipMemcpyHostToDevice, ctx->stream));
-    const CtcIn d = {i32(0), i32(1), reinterpret_cast<int8_t *>(base + a_strand), i32(2), i32(3), i32(4), i32(5), base + a_ops, i32(6)};
-    const CtcOut o = {i32(7), i32(8), base + a_verdict, base + a_target, i32(9)};
-    if (int rc = ctc_run(ctx, d, n, W, templates, offsets, R, {min_accuracy, min_coverage, ub_only, ub_plus, ub_minus}, o)) return rc;
-    XB_HIP(ctx, hipMemcpyAsync(mlen, o.mlen, N * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(blen, o.blen, N * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(target_len, o.target_len, N * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(verdict, o.verdict, N, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(target, o.target, N * TW, hipMemcpyDeviceToHost, ctx->stream));
-    return xb_synchronize(ctx);
-}
-
-XB_API int xb_ctc_chunks(xb_ctx *ctx, const float *signal, int n, const char *alphabet, const char *templates, const int32_t *offsets,
-                         int R, int match, int mismatch, int gap_open, int gap_extend, int ambiguous, double min_accuracy,
-                         double min_coverage, int ub_only, int ub_plus, int ub_minus, int8_t *seq, int32_t *seq_len, int32_t *tmpl,
-                         int8_t *strand, int32_t *score, int32_t *second, int32_t *q_st, int32_t *q_en, int32_t *r_st, int32_t *r_en,
-                         uint8_t *ops, int32_t *n_ops, int32_t *mlen, int32_t *blen, uint8_t *verdict, uint8_t *target,
-                         int32_t *target_len)
-{
-    int rc = check_ready(ctx, n);
-    if (rc) return rc;
-    const MapOut hm = {tmpl, strand, score, second, q_st, q_en, r_st, r_en, ops, n_ops};
-    if (!signal || !alphabet || !seq || !seq_len || !map_out_complete(hm) || !mlen || !blen || !verdict || !target || !target_len)
-        return fail(ctx, XB_ERR_INVALID, "xb_ctc_chunks: null argument");
-    if ((rc = check_alphabet(ctx, alphabet))) return rc;
-    const int W = ctx->T;
-    if (W > xb::MAP_MAX_ROW) return fail(ctx, XB_ERR_INVALID, "xb_ctc_chunks: rows of %d steps; the mapper takes %d", W, xb::MAP_MAX_ROW);
-    int Lmax = 0;
-    if (R < 1 || (rc = longest_template(ctx, offsets, R, &Lmax))) return rc ? rc : fail(ctx, XB_ERR_INVALID, "xb_ctc_chunks: empty template library");
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    // rows per mapper launch: what its cell budget (2 n W sum(L)) admits
-    const double per_row = 2.0 * W * (double)offsets[R];
-    const int fit = (int)std::min<double>((double)n, std::floor(MAP_CELL_BUDGET / per_row));
-    if (fit < 1) return fail(ctx, XB_ERR_INVALID, "xb_ctc_chunks: one row of %d steps against %d letters is over the mapper's cell budget", W, offsets[R]);
-    const size_t N = (size_t)n, cap = (size_t)W + Lmax, TW = (size_t)xb::ctc_target_width(Lmax);
-    Carve c;
-    size_t a_i32[11];
-    for (size_t &a : a_i32) a = c.take(N * 4);          // tmpl, score, second, q_st, q_en, r_st, r_en, n_ops | mlen, blen, target_len
-    const size_t a_strand = c.take(N), a_verdict = c.take(N), a_ops = c.take(N * cap), a_target = c.take(N * TW);
-    if ((rc = map_grow(ctx, &ctx->map.ctc_staging, c.used))) return rc;
-    uint8_t *base = static_cast<uint8_t *>(ctx->map.ctc_staging.p);
-    auto i32 = [&](int k) { return reinterpret_cast<int32_t *>(base + a_i32[k]); };
-    int8_t *d_strand = reinterpret_cast<int8_t *>(base + a_strand);
-    uint8_t *d_ops = base + a_ops;
-    XB_HIP(ctx, hipMemcpyAsync(ctx->d_signal, signal, sizeof(float) * N * ctx->cfg.chunk_len, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = basecall_async(ctx, ctx->d_signal, n, alphabet, ctx->seq, ctx->seq_len, {}))) return rc;
-    if ((rc = join_async_decode(ctx))) return rc;
-    const int sc[5] = {match, mismatch, gap_open, gap_extend, ambiguous};
-    for (int a = 0; a < n; a += fit) {
-        const int cnt = std::min(fit, n - a);
-        const MapOut d = {i32(0) + a, d_strand + a, i32(1) + a, i32(2) + a, i32(3) + a, i32(4) + a, i32(5) + a, i32(6) + a,
-                          d_ops + (size_t)a * cap, i32(7) + a};
-        if ((rc = map_run(ctx, ctx->seq + (size_t)a * W, ctx->seq_len + a, cnt, W, templates, offsets, R, sc, d))) return rc;
-    }
-    const CtcIn ci = {ctx->seq_len, i32(0), d_strand, i32(3), i32(4), i32(5), i32(6), d_ops, i32(7)};
-    const CtcOut co = {i32(8), i32(9), base + a_verdict, base + a_target, i32(10)};
-    if ((rc = ctc_run(ctx, ci, n, W, templates, offsets, R, {min_accuracy, min_coverage, ub_only, ub_plus, ub_minus}, co))) return rc;
-    XB_HIP(ctx, hipMemcpyAsync(seq, ctx->seq, N * W, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(seq_len, ctx->seq_len, N * 4, hipMemcpyDeviceToHost, ctx->stream));
-    int32_t *const h_i32[11] = {tmpl, score, second, q_st, q_en, r_st, r_en, n_ops, mlen, blen, target_len};
-    for (int k = 0; k < 11; ++k) XB_HIP(ctx, hipMemcpyAsync(h_i32[k], i32(k), N * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(strand, d_strand, N, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(verdict, base + a_verdict, N, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(ops, d_ops, N * cap, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(target, base + a_target, N * TW, hipMemcpyDeviceToHost, ctx->stream));
-    return xb_synchronize(ctx);
-}
-
-// ---- per-position UB accuracy of mapped rows (xb_ub_tally) --------------------------------------------------------------
-namespace {
-
-struct UbIn {
-    const int8_t *seq; const int32_t *seq_len, *tmpl; const int8_t *strand; const int32_t *q_st, *r_st, *r_en; const uint8_t *ops;
-    const int32_t *n_ops;
-};
-struct UbOut {
-    int32_t *counts, *reads, *err; int64_t *cm;
-};
-
-bool ub_complete(const UbIn &i, const UbOut &o)
-{
-    return i.seq && i.seq_len && i.tmpl && i.strand && i.q_st && i.r_st && i.r_en && i.ops && i.n_ops && o.counts && o.reads && o.err && o.cm;
-}
-
-// validation, the library's device image, the launch: i and o are device pointers
-int ub_run(xb_ctx *ctx, const UbIn &i, int n, int W, const char *templates, const int32_t *offsets, int R, const UbOut &o)
-{
-    int Lmax = 0;
-    if (int rc = map_library(ctx, n, W, templates, offsets, R, nullptr, &Lmax, "xb_ub_tally")) return rc;
-    const size_t total = (size_t)offsets[R];
-    const uint8_t *img = static_cast<const uint8_t *>(ctx->map.image.p);
-    xb::UbTallyParams p{};
-    p.seq = i.seq; p.seq_len = i.seq_len; p.n = n; p.W = W; p.cap = W + Lmax;
-    p.tmpl = i.tmpl; p.strand = i.strand; p.q_st = i.q_st; p.r_st = i.r_st; p.r_en = i.r_en; p.ops = i.ops; p.n_ops = i.n_ops;
-    p.tcodes = img;
-    p.toff = reinterpret_cast<const int32_t *>(img + ((total + 15) & ~(size_t)15));
-    p.R = R; p.total = (int)total;
-    p.counts = o.counts; p.reads = o.reads; p.err = o.err;
-    p.cm = reinterpret_cast<unsigned long long *>(o.cm);
-    XB_HIP(ctx, xb::launch_ub_tally(p, ctx->stream));
-    return XB_OK;
-}
-
-}  // namespace
-
-XB_API int xb_ub_tally_dev(xb_ctx *ctx, const int8_t *d_seq, const int32_t *d_seq_len, int n, int W, const char *templates,
-                           const int32_t *offsets, int R, const int32_t *d_tmpl, const int8_t *d_strand, const int32_t *d_q_st,
-                           const int32_t *d_r_st, const int32_t *d_r_en, const uint8_t *d_ops, const int32_t *d_n_ops,
-                           int32_t *d_counts, int32_t *d_reads, int32_t *d_err, int64_t *d_cm)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    const UbIn i = {d_seq, d_seq_len, d_tmpl, d_strand, d_q_st, d_r_st, d_r_en, d_ops, d_n_ops};
-    const UbOut o = {d_counts, d_reads, d_err, d_cm};
-    if (!ub_complete(i, o)) return fail(ctx, XB_ERR_INVALID, "xb_ub_tally: null device pointer");
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
-    ctx->result_stream = ctx->stream;
-    return ub_run(ctx, i, n, W, templates, offsets, R, o);
-}
-
-XB_API int xb_ub_tally(xb_ctx *ctx, const int8_t *seq, const int32_t *seq_len, int n, int W, const char *templates,
-                       const int32_t *offsets, int R, const int32_t *tmpl, const int8_t *strand, const int32_t *q_st,
-                       const int32_t *r_st, const int32_t *r_en, const uint8_t *ops, const int32_t *n_ops, int32_t *counts,
-                       int32_t *reads, int32_t *err, int64_t *cm)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    const UbIn h = {seq, seq_len, tmpl, strand, q_st, r_st, r_en, ops, n_ops};
-    const UbOut ho = {counts, reads, err, cm};
-    if (!ub_complete(h, ho)) return fail(ctx, XB_ERR_INVALID, "xb_ub_tally: null host pointer");
-    if (n < 1 || W < 1 || W > xb::MAP_MAX_ROW || !offsets || R < 1 || offsets[0] != 0)
-        return fail(ctx, XB_ERR_INVALID, "xb_ub_tally: n = %d rows of width %d, %d templates; need n >= 1, 1 <= W <= %d, R >= 1", n, W, R,
-                    xb::MAP_MAX_ROW);
-    int Lmax = 0;
-    for (int t = 0; t < R; ++t) {
-        const int L = offsets[t + 1] - offsets[t];
-        if (L < 1 || L > xb::MAP_MAX_TEMPLATE)
-            return fail(ctx, XB_ERR_INVALID, "xb_ub_tally: template %d has %d letters; 1 .. %d are supported", t, L, xb::MAP_MAX_TEMPLATE);
-        Lmax = std::max(Lmax, L);
-    }
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
-    const size_t N = (size_t)n, cap = (size_t)W + Lmax, total = (size_t)offsets[R];
-    if (N * (cap + W) > ((size_t)2 << 30)) return fail(ctx, XB_ERR_INVALID, "xb_ub_tally: %d rows of width %d in one call; split the batch", n, W);
-    Carve c;
-    size_t a_i32[6];
-    for (size_t &a : a_i32) a = c.take(N * 4);          // seq_len, tmpl, q_st, r_st, r_en, n_ops
-    const size_t a_strand = c.take(N), a_seq = c.take(N * W), a_ops = c.take(N * cap), a_counts = c.take(N * xb::UB_COUNTS * 4);
-    const size_t b_reads = (size_t)R * 2 * 4, b_err = 2 * total * 4, b_cm = (size_t)xb::UB_CM_ROWS * xb::UB_CM_COLS * 8;
-    const size_t a_reads = c.take(b_reads), a_err = c.take(b_err), a_cm = c.take(b_cm);
-    if (int rc = map_grow(ctx, &ctx->map.ub_staging, c.used)) return rc;
-    uint8_t *base = static_cast<uint8_t *>(ctx->map.ub_staging.p);
-    auto i32 = [&](size_t at) { return reinterpret_cast<int32_t *>(base + at); };
-    const int32_t *const src[6] = {seq_len, tmpl, q_st, r_st, r_en, n_ops};
-    for (int k = 0; k < 6; ++k) XB_HIP(ctx, hipMemcpyAsync(base + a_i32[k], src[k], N * 4, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(base + a_strand, strand, N, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(base + a_seq, seq, N * W, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(base + a_ops, ops, N * cap, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(base + a_reads, reads, b_reads, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(base + a_err, err, b_err, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(base + a_cm, cm, b_cm, hipMemcpyHostToDevice, ctx->stream));
-    const UbIn d = {reinterpret_cast<int8_t *>(base + a_seq), i32(a_i32[0]), i32(a_i32[1]), reinterpret_cast<int8_t *>(base + a_strand),
-                    i32(a_i32[2]), i32(a_i32[3]), i32(a_i32[4]), base + a_ops, i32(a_i32[5])};
-    const UbOut o = {i32(a_counts), i32(a_reads), i32(a_err), reinterpret_cast<int64_t *>(base + a_cm)};
-    if (int rc = ub_run(ctx, d, n, W, templates, offsets, R, o)) return rc;
-    XB_HIP(ctx, hipMemcpyAsync(counts, o.counts, N * xb::UB_COUNTS * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(reads, o.reads, b_reads, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(err, o.err, b_err, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(cm, o.cm, b_cm, hipMemcpyDeviceToHost, ctx->stream));
-    return xb_synchronize(ctx);
-}
-
-// ---- DTW signal segmentation (xb_dtw_segment) -------------------------------------------------------------------------
-namespace {
-
-// Choice-bit scratch one launch may own (XB_DTW_SCRATCH_MB, default 1024): a call is split into launches of as many chunks
-// as fit, one chunk when a single chunk needs more (at most 136 MB: 65535 samples against 32768 columns).  A full-size chunk
-// (3600 samples, 1200 columns) takes 488 KB, so the default holds 2201 chunks -- two waves on each of the 1024 SIMDs.
-size_t dtw_scratch_bound()
-{
-    long mb = 1024;
-    if (const char *e = getenv("XB_DTW_SCRATCH_MB")) mb = atol(e);
-    if (mb < 1) mb = 1;
-    if (mb > 65536) mb = 65536;
-    return (size_t)mb << 20;
-}
-
-struct DtwOut {
-    int32_t *bp; int8_t *ok; double *cost;
-};
-
-// validation, the offsets' device copy, the launches: signal, levels, window and o are device pointers, offsets is host
-int dtw_run(xb_ctx *ctx, const float *d_signal, int n, int N, const double *d_levels, const int32_t *offsets, int ref_rep,
-            const double *d_window, bool band, int Kmax, const DtwOut &o)
-{
-    if (n < 1 || N < 1 || N > xb::DTW_MAX_SAMPLES || ref_rep < 1 || ref_rep > xb::DTW_MAX_COLUMNS)
-        return fail(ctx, XB_ERR_INVALID, "xb_dtw_segment: n = %d chunks of %d samples, ref_rep = %d; need n >= 1, 1 <= N <= %d, "
-                    "1 <= ref_rep <= %d", n, N, ref_rep, xb::DTW_MAX_SAMPLES, xb::DTW_MAX_COLUMNS);
-    if (!offsets || offsets[0] != 0) return fail(ctx, XB_ERR_INVALID, "xb_dtw_segment: offsets must start at 0");
-    int Kbig = 0;
-    for (int c = 0; c < n; ++c) {
-        const int K = offsets[c + 1] - offsets[c];
-        if (K < 1 || (int64_t)K * ref_rep > xb::DTW_MAX_COLUMNS)
-            return fail(ctx, XB_ERR_INVALID, "xb_dtw_segment: chunk %d has %d levels, %lld columns at ref_rep = %d; 1 level .. %d "
-                        "columns are supported", c, K, (long long)K * ref_rep, ref_rep, xb::DTW_MAX_COLUMNS);
-        Kbig = std::max(Kbig, K);
-    }
-    if (Kmax < Kbig)
-        return fail(ctx, XB_ERR_INVALID, "xb_dtw_segment: breakpoint rows of %d entries, the longest chunk has %d levels", Kmax, Kbig);
-    const int cols = xb::dtw_cols_per_lane(Kbig * ref_rep);
-    size_t choice = 0;
-    for (int c = 0; c < n; ++c) choice = std::max(choice, xb::dtw_choice_words(N, (offsets[c + 1] - offsets[c]) * ref_rep, cols));
-    const size_t slot_words = choice + 2 * (size_t)N;
-    const size_t per_launch = std::max<size_t>(1, std::min<size_t>((size_t)n, dtw_scratch_bound() / (slot_words * 8)));
-    xb_ctx::DtwState &s = ctx->dtw;
-    if (int rc = map_grow(ctx, &s.scratch, per_launch * slot_words * 8)) return rc;
-    // the offsets: pinned slot (calls & 1), free again once the copy of two calls ago has run
-    xb_ctx::DtwState::Slot &slot = s.off[s.calls++ & 1];
-    if (slot.copied) XB_HIP(ctx, hipEventSynchronize(slot.copied));
-    else XB_HIP(ctx, hipEventCreateWithFlags(&slot.copied, hipEventDisableTiming));
-    if (slot.count < (size_t)n + 1) {
-        XB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (slot.h) (void)hipHostFree(slot.h);
-        if (slot.d) (void)hipFree(slot.d);
-        slot.h = slot.d = nullptr;
-        slot.count = 0;
-        const size_t count = ((size_t)n + 1 + 1023) & ~(size_t)1023;
-        XB_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&slot.h), count * sizeof(int32_t), hipHostMallocDefault));
-        XB_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&slot.d), count * sizeof(int32_t)));
-        slot.count = count;
-    }
-    memcpy(slot.h, offsets, sizeof(int32_t) * ((size_t)n + 1));
-    XB_HIP(ctx, hipMemcpyAsync(slot.d, slot.h, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipEventRecord(slot.copied, ctx->stream));
-    xb::DtwParams p{};
-    p.signal = d_signal; p.levels = d_levels; p.off = slot.d; p.window = band ? d_window : nullptr;
-    p.N = N; p.rep = ref_rep; p.Kmax = Kmax;
-    p.scratch = static_cast<unsigned long long *>(s.scratch.p);
-    p.choice_words = choice; p.slot_words = slot_words;
-    p.bp = o.bp; p.ok = o.ok; p.cost = o.cost;
-    s.scratch_written = 0;
-    for (int c = 0; c < n; ++c) s.scratch_written += 8 * xb::dtw_choice_words(N, (offsets[c + 1] - offsets[c]) * ref_rep, cols);
-    for (size_t first = 0; first < (size_t)n; first += per_launch) {
-        p.first = (int)first;
-        p.count = (int)std::min<size_t>(per_launch, (size_t)n - first);
-        XB_HIP(ctx, xb::launch_dtw(p, cols, band, ctx->stream));
-    }
-    return XB_OK;
-}
-
-}  // namespace
-
-XB_API int xb_dtw_segment_dev(xb_ctx *ctx, const float *d_signal, int n, int N, const double *d_levels, const int32_t *offsets,
-                              int ref_rep, const double *d_window, int Kmax, int32_t *d_breakpoints, int8_t *d_ok, double *d_cost)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    if (!d_signal || !d_levels || !d_breakpoints || !d_ok || !d_cost) return fail(ctx, XB_ERR_INVALID, "xb_dtw_segment: null device pointer");
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
-    ctx->result_stream = ctx->stream;
-    return dtw_run(ctx, d_signal, n, N, d_levels, offsets, ref_rep, d_window, d_window != nullptr, Kmax, {d_breakpoints, d_ok, d_cost});
-}
-
-XB_API int xb_dtw_segment(xb_ctx *ctx, const float *signal, int n, int N, const double *levels, const int32_t *offsets, int ref_rep,
-                          const double *window, int Kmax, int32_t *breakpoints, int8_t *ok, double *cost)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    if (!signal || !levels || !breakpoints || !ok || !cost) return fail(ctx, XB_ERR_INVALID, "xb_dtw_segment: null host pointer");
-    if (n < 1 || N < 1 || N > xb::DTW_MAX_SAMPLES || !offsets || offsets[0] != 0 || Kmax < 1 || Kmax > xb::DTW_MAX_COLUMNS)
-        return fail(ctx, XB_ERR_INVALID, "xb_dtw_segment: n = %d chunks of %d samples, breakpoint rows of %d entries; need n >= 1, "
-                    "1 <= N <= %d, offsets from 0 with a level or more per chunk, 1 <= Kmax <= %d", n, N, Kmax, xb::DTW_MAX_SAMPLES,
-                    xb::DTW_MAX_COLUMNS);
-    for (int c = 0; c < n; ++c)
-        if (offsets[c + 1] <= offsets[c]) return fail(ctx, XB_ERR_INVALID, "xb_dtw_segment: chunk %d has %d levels; at least one is needed",
-                                                      c, offsets[c + 1] - offsets[c]);
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
-    bool band = false;
-    for (int c = 0; window && c < n; ++c) band = band || window[c] >= 0.0;
-    // staging: signal | levels | window | cost | breakpoints | ok, each 256-byte aligned
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t C = (size_t)n, total = (size_t)offsets[n];
-    const size_t b_sig = al(C * N * 4), b_lev = al(total * 8), b_f64 = al(C * 8), b_bp = al(C * Kmax * 4), b_ok = al(C);
-    if (b_sig + b_lev + 2 * b_f64 + b_bp + b_ok > ((size_t)2 << 30))
-        return fail(ctx, XB_ERR_INVALID, "xb_dtw_segment: %d chunks of %d samples in one call; split the batch", n, N);
-    if (int rc = map_grow(ctx, &ctx->dtw.staging, b_sig + b_lev + 2 * b_f64 + b_bp + b_ok)) return rc;
-    uint8_t *base = static_cast<uint8_t *>(ctx->dtw.staging.p);
-    float *d_sig = reinterpret_cast<float *>(base);
-    double *d_lev = reinterpret_cast<double *>(base + b_sig);
-    double *d_win = reinterpret_cast<double *>(base + b_sig + b_lev), *d_cost = d_win + b_f64 / 8;
-    int32_t *d_bp = reinterpret_cast<int32_t *>(base + b_sig + b_lev + 2 * b_f64);
-    int8_t *d_ok = reinterpret_cast<int8_t *>(d_bp) + b_bp;
-    XB_HIP(ctx, hipMemcpyAsync(d_sig, signal, C * N * 4, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(d_lev, levels, total * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (band) XB_HIP(ctx, hipMemcpyAsync(d_win, window, C * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = dtw_run(ctx, d_sig, n, N, d_lev, offsets, ref_rep, d_win, band, Kmax, {d_bp, d_ok, d_cost})) return rc;
-    XB_HIP(ctx, hipMemcpyAsync(breakpoints, d_bp, C * Kmax * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(ok, d_ok, C, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(cost, d_cost, C * 8, hipMemcpyDeviceToHost, ctx->stream));
-    return xb_synchronize(ctx);
-}
-
-XB_API int64_t xb_dtw_scratch_bytes(const xb_ctx *ctx) { return ctx ? (int64_t)ctx->dtw.scratch_written : 0; }
-
-// ---- XNA spliced augmentation (xb_splice_library, xb_splice_chunks) ---------------------------------------------------
-XB_API int xb_splice_library(xb_ctx *ctx, const uint16_t *pool, int64_t pool_len, const int32_t *rows, int n_rows,
-                             const int32_t *table, int table_len)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    if (!pool || !rows || !table) return fail(ctx, XB_ERR_INVALID, "xb_splice_library: null host pointer");
-    if (pool_len < 1 || pool_len > 0x7fffffffLL || n_rows < 1 || table_len != xb::SPLICE_TABLE_LEN)
-        return fail(ctx, XB_ERR_INVALID, "xb_splice_library: a pool of %lld samples, %d rows, a table of %d groups; need 1 <= pool < 2^31, "
-                    "n_rows >= 1 and %d groups", (long long)pool_len, n_rows, table_len, xb::SPLICE_TABLE_LEN);
-    for (int r = 0; r < n_rows; ++r) {
-        const int64_t off = rows[2 * r], len = rows[2 * r + 1];
-        if (off < 0 || len < 1 || len > xb::SPLICE_MAX_KMER || off + len > pool_len)
-            return fail(ctx, XB_ERR_INVALID, "xb_splice_library: row %d has %lld samples at offset %lld of a pool of %lld; 1 .. %d samples "
-                        "inside the pool are supported", r, (long long)len, (long long)off, (long long)pool_len, xb::SPLICE_MAX_KMER);
-    }
-    for (int g = 0; g < table_len; ++g) {
-        const int64_t first = table[2 * g], count = table[2 * g + 1];
-        if (count < 0 || (count > 0 && (first < 0 || first + count > n_rows)))
-            return fail(ctx, XB_ERR_INVALID, "xb_splice_library: group %d holds rows %lld .. %lld of %d", g, (long long)first,
-                        (long long)(first + count), n_rows);
-    }
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
-    xb_ctx::SpliceState &s = ctx->splice;
-    s.loaded = false;
-    XB_HIP(ctx, hipStreamSynchronize(ctx->stream));                     // nothing in flight reads the library it replaces
-    if (int rc = map_grow(ctx, &s.pool, (size_t)pool_len * 2)) return rc;
-    if (int rc = map_grow(ctx, &s.rows, (size_t)n_rows * 8)) return rc;
-    if (int rc = map_grow(ctx, &s.table, (size_t)table_len * 8)) return rc;
-    XB_HIP(ctx, hipMemcpyAsync(s.pool.p, pool, (size_t)pool_len * 2, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(s.rows.p, rows, (size_t)n_rows * 8, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(s.table.p, table, (size_t)table_len * 8, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    s.loaded = true;
-    return XB_OK;
-}
-
-namespace {
-
-struct SpliceArgs {
-    int n, N, Lt;
-    int64_t first_index;
-    uint64_t seed;
-    int ubs_mask;
-    double prop, var_prop;
-    int cand, pad;
-};
-
-// the limits of the contract, before any launch
-int splice_check(xb_ctx *ctx, const SpliceArgs &a)
-{
-    if (!ctx->splice.loaded) return fail(ctx, XB_ERR_STATE, "xb_splice_chunks: no library: call xb_splice_library first");
-    if (a.n < 1 || a.N < 1 || a.N > xb::SPLICE_MAX_SAMPLES || a.Lt < 1 || a.Lt > xb::SPLICE_MAX_LABELS)
-        return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: n = %d chunks of %d samples, label rows of %d entries; need n >= 1, "
-                    "1 <= N <= %d, 1 <= Lt <= %d", a.n, a.N, a.Lt, xb::SPLICE_MAX_SAMPLES, xb::SPLICE_MAX_LABELS);
-    if (a.cand < 1 || a.cand > xb::SPLICE_MAX_CAND)
-        return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: cand_sample_size = %d; 1 .. %d are supported", a.cand, xb::SPLICE_MAX_CAND);
-    if (a.pad < 0) return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: pad = %d is negative", a.pad);
-    if (a.ubs_mask < 1 || a.ubs_mask > 3) return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: ubs_mask = %d; 1 (X), 2 (Y) or 3 (both)", a.ubs_mask);
-    if (!(a.prop >= 0.0) || !(a.var_prop >= 0.0) || !(a.prop + a.var_prop <= 1.0))
-        return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: prop = %g, var_prop = %g; both at least 0, their sum at most 1", a.prop, a.var_prop);
-    if (a.first_index < 0) return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: first_index = %lld is negative", (long long)a.first_index);
-    return XB_OK;
-}
-
-int splice_run(xb_ctx *ctx, const SpliceArgs &a, const float *d_signal, const uint8_t *d_targets, const int32_t *d_lengths,
-               const uint16_t *d_bkps, float *d_out_signal, uint8_t *d_out_targets, int8_t *d_success, int32_t *d_inserted)
-{
-    xb::SpliceParams p{};
-    p.signal = d_signal; p.targets = d_targets; p.lengths = d_lengths; p.bkps = d_bkps;
-    p.n = a.n; p.N = a.N; p.Lt = a.Lt;
-    p.first_index = (unsigned long long)a.first_index; p.seed = a.seed;
-    p.n_ubs = 0;
-    if (a.ubs_mask & 1) p.ubs[p.n_ubs++] = 5;
-    if (a.ubs_mask & 2) p.ubs[p.n_ubs++] = 6;
-    p.prop = a.prop; p.var_prop = a.var_prop; p.cand = a.cand; p.pad = a.pad;
-    p.pool = static_cast<const xb::half_t *>(ctx->splice.pool.p);
-    p.rows = static_cast<const int32_t *>(ctx->splice.rows.p);
-    p.table = static_cast<const int32_t *>(ctx->splice.table.p);
-    p.out_signal = d_out_signal; p.out_targets = d_out_targets; p.success = d_success; p.inserted = d_inserted;
-    XB_HIP(ctx, xb::launch_splice(p, ctx->stream));
-    return XB_OK;
-}
-
-}  // namespace
-
-XB_API int xb_splice_chunks_dev(xb_ctx *ctx, const float *d_signal, const uint8_t *d_targets, const int32_t *d_lengths,
-                                const uint16_t *d_breakpoints, int n, int N, int Lt, int64_t first_index, uint64_t seed, int ubs_mask,
-                                double prop, double var_prop, int cand_sample_size, int pad, float *d_out_signal,
-                                uint8_t *d_out_targets, int8_t *d_success, int32_t *d_inserted)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    if (!d_signal || !d_targets || !d_lengths || !d_breakpoints || !d_out_signal || !d_out_targets || !d_success || !d_inserted)
-        return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: null device pointer");
-    if (d_signal == d_out_signal || d_targets == d_out_targets) return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: outputs alias inputs");
-    const SpliceArgs a{n, N, Lt, first_index, seed, ubs_mask, prop, var_prop, cand_sample_size, pad};
-    if (int rc = splice_check(ctx, a)) return rc;
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
-    ctx->result_stream = ctx->stream;
-    return splice_run(ctx, a, d_signal, d_targets, d_lengths, d_breakpoints, d_out_signal, d_out_targets, d_success, d_inserted);
-}
-
-XB_API int xb_splice_chunks(xb_ctx *ctx, const float *signal, const uint8_t *targets, const int32_t *lengths,
-                            const uint16_t *breakpoints, int n, int N, int Lt, int64_t first_index, uint64_t seed, int ubs_mask,
-                            double prop, double var_prop, int cand_sample_size, int pad, float *out_signal, uint8_t *out_targets,
-                            int8_t *success, int32_t *inserted)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    if (!signal || !targets || !lengths || !breakpoints || !out_signal || !out_targets || !success || !inserted)
-        return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: null host pointer");
-    const SpliceArgs a{n, N, Lt, first_index, seed, ubs_mask, prop, var_prop, cand_sample_size, pad};
-    if (int rc = splice_check(ctx, a)) return rc;
-    for (int c = 0; c < n; ++c) {                                       // what the kernel would otherwise clamp
-        const int len = lengths[c];
-        if (len < 0 || len > Lt) return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: chunk %d has %d labels in a row of %d", c, len, Lt);
-        const uint16_t *b = breakpoints + (size_t)c * Lt;
-        for (int l = 0; l < len; ++l)
-            if (b[l] > N || (l && b[l] < b[l - 1]))
-                return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: chunk %d: breakpoint %d of base %d (the one before: %d, samples: %d)", c,
-                            (int)b[l], l, l ? (int)b[l - 1] : 0, N);
-    }
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
-    // staging: signal | out_signal | inserted | lengths | breakpoints | targets | out_targets | success, each 256-byte aligned
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t C = (size_t)n, b_sig = al(C * N * 4), b_i32 = al(C * 4), b_bk = al(C * Lt * 2), b_t = al(C * Lt), b_ok = al(C);
-    const size_t total = 2 * b_sig + 2 * b_i32 + b_bk + 2 * b_t + b_ok;
-    if (total > ((size_t)2 << 30)) return fail(ctx, XB_ERR_INVALID, "xb_splice_chunks: %d chunks of %d samples in one call; split the batch", n, N);
-    if (int rc = map_grow(ctx, &ctx->splice.staging, total)) return rc;
-    uint8_t *base = static_cast<uint8_t *>(ctx->splice.staging.p);
-    float *d_sig = reinterpret_cast<float *>(base), *d_out = reinterpret_cast<float *>(base + b_sig);
-    int32_t *d_ins = reinterpret_cast<int32_t *>(base + 2 * b_sig), *d_len = reinterpret_cast<int32_t *>(base + 2 * b_sig + b_i32);
-    uint16_t *d_bk = reinterpret_cast<uint16_t *>(base + 2 * b_sig + 2 * b_i32);
-    uint8_t *d_t = base + 2 * b_sig + 2 * b_i32 + b_bk, *d_ot = d_t + b_t;
-    int8_t *d_ok = reinterpret_cast<int8_t *>(d_ot + b_t);
-    XB_HIP(ctx, hipMemcpyAsync(d_sig, signal, C * N * 4, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(d_len, lengths, C * 4, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(d_bk, breakpoints, C * Lt * 2, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(d_t, targets, C * Lt, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = splice_run(ctx, a, d_sig, d_t, d_len, d_bk, d_out, d_ot, d_ok, d_ins)) return rc;
-    XB_HIP(ctx, hipMemcpyAsync(out_signal, d_out, C * N * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(out_targets, d_ot, C * Lt, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(success, d_ok, C, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(inserted, d_ins, C * 4, hipMemcpyDeviceToHost, ctx->stream));
-    return xb_synchronize(ctx);
 }
 
 XB_API int xb_set_profiling(xb_ctx *ctx, int on)

@@ -1,0 +1,260 @@
+// xb_ctx.h -- the context behind the C ABI, shared by its two translation units: xb_api.hip (context lifetime, weights, the
+// encoder schedule, decode, pairing, the host pipeline) and xb_api_data.hip (the ctc-data tools).  Private to csrc/.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/xna_basecaller.h"
+#include "xb_internal.h"
+
+using xb::half_t;
+
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+};
+
+struct StageEvent {
+    int stage;
+    hipEvent_t a, b;
+};
+
+// What a Viterbi decode writes beside the bases (seq, len), by output level: 0 nothing, 1 qualities and moves (the kernel's
+// quality variant), 2 those and the letter probabilities (its UB variant).  Device pointers, except in the bodies of the
+// host-pointer entry points.
+struct DecodeOut {
+    int level = 0;
+    float qscale = 1.0f, qoffset = 0.0f;
+    int8_t *qstr = nullptr;      // (n, T), level >= 1
+    uint8_t *moves = nullptr;    // (n, T) or nullptr, level >= 1
+    uint8_t *probs = nullptr;    // (n, nb, T), level 2
+};
+
+// A decode's outputs as byte planes: seq (T bytes per chunk), len (4), qstring (T), moves (T), probs (nb T).  A level writes
+// the first plane_count(level); len and moves may be null.
+constexpr int PLANES = 5;
+struct Planes {
+    void *p[PLANES];
+};
+
+struct xb_ctx {
+    xb_config cfg{};
+    int device = 0;
+    int cu_count = 256;
+    hipStream_t stream = nullptr;    // main stream (highest priority): everything except the overlapped GEMM slabs
+    hipStream_t stream2 = nullptr;   // low-priority stream: the next layer's input GEMM, slab by slab, beside the recurrence
+    hipStream_t stream3 = nullptr;   // low-priority stream: CRF decode of batch k beside the encoder of batch k+1
+    hipEvent_t dec_done[2] = {};     // decode that last read scores buffer p has finished
+    bool dec_pending[2] = {};
+    unsigned batch_idx = 0;
+    hipStream_t result_stream = nullptr;   // stream that produces the outputs of the most recent *_dev call
+    // host pipeline (xb_submit_chunks / xb_collect_chunks): two slots of pinned staging + device buffers
+    struct Slot {
+        float *h_signal = nullptr, *d_signal = nullptr;
+        // pinned + device outputs of max_batch chunks, plane by plane: those of an output level are allocated by the slot's
+        // first submission at that level
+        Planes h{}, d{};
+        unsigned *h_err = nullptr;             // snapshot of the device error word taken on the result stream behind this batch
+        hipEvent_t h2d = nullptr, done = nullptr;
+        int n = 0;
+        bool busy = false;
+        int level = 0;                         // output level of the batch in flight
+    } slots[XB_PIPELINE_SLOTS];
+    bool pipeline_failed = false;          // a collected batch reported a lost rendezvous: every batch in flight fails with it
+    hipStream_t stream_copy = nullptr;     // H2D of the next batch beside the compute of the current one
+    std::vector<hipEvent_t> deps;    // timing-less events for the cross-stream dependencies (reused every call)
+    size_t dep_next = 0;
+    int overlap = 1, time_slabs = 16;   // XB_OVERLAP / XB_TIME_SLABS (upper bound; a slab is at least 125 steps)
+    int slab_steps = 0;                 // XB_SLAB_STEPS: minimum steps per time slab (default 125)
+    // one recurrence launch per layer that reports its time slabs to the GEMM stream (XB_LSTM_SIGNAL, default on where
+    // hipStreamWaitValue32 is supported): flag word, the value the last slab of the previous layer published, slab counters
+    int lstm_signal = 2;                // 0 off, 1 whenever one launch holds the batch, 2 (default) only above 512 chunks (two groups per workgroup)
+    unsigned *sig_flag = nullptr, *sig_done = nullptr;
+    unsigned sig_seq = 0;
+    mutable std::string err;
+    int T = 0, S = 0, hi = 0, O = 0, kp = 0, ld_nb = 0;
+    bool weights_ready = false;
+    std::map<std::string, std::vector<float>> host_w;
+    std::vector<DevBuf> bufs;
+    std::vector<DevBuf> wsbufs;                // the batch-sized workspaces (alloc_workspaces)
+    bool alloc_ws = false;
+
+    // weights on device
+    float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *b3 = nullptr;
+    half_t *w3_hi = nullptr, *w3_lo = nullptr;
+    half_t *wih_hi[5] = {}, *wih_lo[5] = {}, *whh_hi[5] = {}, *whh_lo[5] = {};
+    float *lbias[5] = {};
+    half_t *wl_hi = nullptr, *wl_lo = nullptr;
+    float *bl = nullptr;
+    int w3_exp = 0, wih_exp[5] = {}, whh_exp[5] = {}, wl_exp = 0;   // q8 exponents (XB_PREC_F16F8)
+    // fragment-major images of the GEMM B operands (gemm4p_kernel, xb_internal.h) and their k-tile strides; the input
+    // projections also as hi-only images for XB_PREC_F16F8_IN1
+    unsigned char *w3_f4 = nullptr, *wih_f4[5] = {}, *wih_f4h[5] = {}, *wl_f4 = nullptr;
+    size_t w3_ks = 0, wih_ks = 0, wih_ksh = 0, wl_ks = 0;
+    int gemm_sn = 0;                           // XB_GEMM_SN: N tiles per XCD super-tile of gemm4p_kernel (0 = gemm_super_n's rule; experiments)
+    int gemm_shadow_kernel = 0;                // XB_GEMM_SHADOW: 0 auto (by batch size), 4 gemm4p_kernel, 8 gemm8r_kernel for the slabs beside the recurrence
+    int gemm_shadow_wgs = 2;                   // XB_GEMM_SHADOW_WGS=1: GEMM slabs beside the recurrence run one workgroup per CU
+    int gemm4 = 1;                             // XB_GEMM4=0: gemm8r_kernel (one workgroup per CU) instead of gemm4p_kernel (A/B comparisons)
+    std::vector<void *> wbufs;                 // weight allocations of the current xb_weights_ready (freed by the next one)
+    int8_t *whh_q1[5] = {}, *whh_q0[5] = {};   // int8-limb recurrence (lstm_i8): balanced digits of W_hh, gate-interleaved rows
+    float *whh_sc[5] = {};                     // ... and the factor that turns the integer sum into the recurrent term
+    int lstm_i8 = 0;                           // XB_LSTM_I8 (with precision f16f8 / f16f8i): recurrence on int8 digits; 1 = all
+                                               // four digit products, 2 = without d0 x d0
+
+    // activations / workspaces
+    float *d_signal = nullptr;
+    half_t *im_hi = nullptr, *im_lo = nullptr;
+    half_t *x_hi[2] = {}, *x_lo[2] = {};
+    float *gin = nullptr, *gin2 = nullptr, *c_state = nullptr, *scores = nullptr, *scores2 = nullptr;
+    half_t *xh = nullptr;        // LSTM exchange buffer: 64 groups x 2 parity x 2 parts x 64 chunks x F
+    float *alpha = nullptr, *beta = nullptr, *bmax = nullptr, *qbuf = nullptr, *logz = nullptr;
+    // beam search workspaces and staging (lazily allocated: most contexts never use them)
+    uint32_t *beam_hist = nullptr;
+    int32_t *beam_path = nullptr;
+    float *beam_prob = nullptr, *beam_score = nullptr;
+    int8_t *beam_seq = nullptr, *beam_q = nullptr;
+    uint8_t *beam_moves = nullptr;
+    int8_t *labels = nullptr, *seq = nullptr;
+    int32_t *seq_len = nullptr;
+    // the planes of output levels 1 (qstring, moves) and 2 (probs), lazily allocated by ensure_staging: the device staging
+    // of the host-pointer calls (max_batch chunks) and the results of a co-scheduled pair before they are split
+    // (2 max_batch); level 2 also the per-step letter mass workspace (cap, T, nb) fp32
+    int8_t *q_seq = nullptr, *q_fseq = nullptr;
+    uint8_t *q_moves = nullptr, *q_fmoves = nullptr;
+    uint8_t *u_probs = nullptr, *u_fprobs = nullptr;
+    float *u_buf = nullptr;
+    unsigned *sync = nullptr;    // [64 groups * 32] counters + error word at the end
+    unsigned *error = nullptr;
+    int lstm_mode = 0;
+    // workgroups of the persistent kernel admitted per CU, by recurrence arithmetic (nsplit 1..5) and one / two groups per
+    // workgroup (occupancy query, lazily; -1 = not asked yet)
+    int lstm_resident[6][2] = {{-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}};
+    // Arithmetic of every contraction stage (GemmParams::nsplit: 1 fp16 product, 2 + FP8 corrections, 3 three fp16 products):
+    // conv3, the five input projections, the five recurrences, the CRF linear layer.  One value everywhere for the plain
+    // precisions; XB_PREC_MIXED (and the diagnostic XB_X3_STAGES mask) mix 2 and 3.  An activation tensor's second part
+    // (q8 image or fp16 residual) follows the stage that CONSUMES it.
+    int ns_conv = 3, ns_in[5] = {3, 3, 3, 3, 3}, ns_rec[5] = {3, 3, 3, 3, 3}, ns_lin = 3;
+    int in1_layers = 31;         // XB_IN1_LAYERS (diagnostic): layers whose input projection XB_PREC_F16F8_IN1 reduces
+    int decode_async = 0;        // XB_DECODE_ASYNC=1: the decode of a batch runs on the third stream beside the next batch's conv + first
+                                 // GEMM (rounds 2-3) instead of on the main stream with the chip to itself (round 4 default: the same step
+                                 // time at every batch size -- the step is bound by the kernels' summed CU-time -- and the decode at 0.49-0.52
+                                 // of the HBM roofline instead of 0.35-0.42: profiles/r04_decode_placement.txt)
+    int lstm_local = 1;          // XB_LSTM_LOCAL=0: always exchange h with write-through stores (A/B)
+    int lstm_wide = 1;           // XB_LSTM_WIDE: 1 (default) batches just above a launch's XCD-local capacity get up to cu_count / members group
+                                 // slots with the groups dealt over all XCDs instead of a second round (run_lstm_layer); 0: never
+    int lstm_dual = 1;           // XB_LSTM_DUAL: 0 never, 1 when a launch would otherwise need a second chunk slab, 2 always
+
+    // Two asynchronous basecalls in flight are co-scheduled once the caller has opted in with xb_reserve_pairing (contexts of at
+    // most 512 chunks; XB_FUSE=0 refuses): the first xb_basecall_chunks_dev of a pair is held back until the second arrives, then
+    // both batches go through the encoder and the decode as ONE batch (the recurrence then runs two chunk groups per workgroup,
+    // DESIGN.md 4.1 / 4.5).  Every other entry point, xb_synchronize and xb_result_stream first launch a held-back call on its own.
+    // Without the opt-in every asynchronous call is enqueued before it returns.
+    struct Call {
+        const float *signal = nullptr;
+        int n = 0;
+        char alphabet[16] = {};
+        int8_t *seq = nullptr;
+        int32_t *len = nullptr;
+        int slot = -1;                          // host pipeline slot whose D2H copies and done event follow the launch
+        void (*after)(void *) = nullptr;        // xb_comm: the gather of this call's results, enqueued right behind it
+        void *after_arg = nullptr;
+        DecodeOut out;                          // output level (xb_basecall_chunks_q / _ub, xb_submit_chunks_q / _ub) and its planes
+    };
+    int fuse_ok = 1;                            // pairing is possible in this context (schedule, batch size, XB_FUSE)
+    int fuse = 0;                               // ... and the caller asked for it (xb_reserve_pairing)
+    int cap = 0;                                // chunks the workspaces hold (2 * max_batch when fusing is possible)
+    Call held;
+    bool holding = false, flushing = false;
+    int deferred_rc = 0;                        // failure of a held-back call that was launched where no status could be returned
+    int8_t *fseq = nullptr;                     // (cap, T) / (cap) results of a fused pair before they are split
+    int32_t *flen = nullptr;
+
+    // The device staging of the ctc-data tools' host-pointer forms (xb_api_data.hip, Staging): one buffer for all of them --
+    // each returns synchronised, so no two are ever live at once.  Grows with the calls; freed by xb_ctx_destroy.
+    DevBuf staging;
+
+    // template mapper (xb_map_templates): the library last passed in (host copy and its device image: codes, offsets, the
+    // chunks of the score pass) and buffers that grow with the calls -- the score pass's records, the trace pass's direction
+    // scratch.  Owned here, freed by xb_ctx_destroy.
+    struct MapState {
+        std::vector<char> lib;
+        std::vector<int32_t> off;
+        int Lmax = 0, nchunks = 0;
+        DevBuf image, partial, scratch;
+        // the image's layout: codes | offsets, 16-byte aligned | the first template of every chunk and the count of templates
+        static size_t off_at(size_t total) { return (total + 15) & ~(size_t)15; }
+        const uint8_t *tcodes() const { return static_cast<const uint8_t *>(image.p); }
+        const int32_t *toff() const { return reinterpret_cast<const int32_t *>(tcodes() + off_at(lib.size())); }
+        const int32_t *chunk_first() const { return toff() + off.size(); }
+    } map;
+
+    // DTW segmentation (xb_dtw_segment): the choice-bit scratch of the launches in flight and the chunks' level offsets on
+    // their way to the device -- two pinned slots in rotation, so that a call returns without waiting for its own device
+    // work.  Owned here, freed by xb_ctx_destroy.
+    struct DtwState {
+        DevBuf scratch;
+        struct Slot {
+            int32_t *h = nullptr, *d = nullptr;
+            size_t count = 0;
+            hipEvent_t copied = nullptr;
+        } off[2];
+        unsigned calls = 0;
+        size_t scratch_written = 0;                 // bytes of choice words the last call's launches were sized for
+    } dtw;
+
+    // XNA spliced augmentation (xb_splice_library / xb_splice_chunks): the library's device image, kept until the next
+    // xb_splice_library.  Owned here, freed by xb_ctx_destroy.
+    struct SpliceState {
+        DevBuf pool, rows, table;
+        bool loaded = false;
+    } splice;
+
+    bool profiling = false;
+    std::vector<StageEvent> events;
+    float stage_ms[XB_STAGE_COUNT] = {};
+    int64_t stage_launches[XB_STAGE_COUNT] = {};
+};
+
+int fail(const xb_ctx *ctx, int code, const char *fmt, ...);     // sets the context's (or, without one, the thread's) last error
+
+#define XB_HIP(ctx, call)                                                                     \
+    do {                                                                                      \
+        hipError_t e_ = (call);                                                               \
+        if (e_ != hipSuccess)                                                                 \
+            return fail(ctx, e_ == hipErrorOutOfMemory ? XB_ERR_NOMEM : XB_ERR_HIP,           \
+                        "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+// a buffer that grows with the calls: at least `bytes` afterwards, contents not kept
+inline int grow(xb_ctx *ctx, DevBuf *b, size_t bytes)
+{
+    if (bytes <= b->bytes) return XB_OK;
+    XB_HIP(ctx, hipStreamSynchronize(ctx->stream));                     // nothing in flight reads the old buffer
+    if (b->p) (void)hipFree(b->p);
+    b->p = nullptr;
+    b->bytes = 0;
+    bytes = (bytes + 255) & ~(size_t)255;
+    hipError_t e = hipMalloc(&b->p, bytes);
+    if (e != hipSuccess) return fail(ctx, XB_ERR_NOMEM, "hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+    b->bytes = bytes;
+    return XB_OK;
+}
+
+// the core (xb_api.hip) as the ctc-data tools call it; none is exported (the library is built with hidden visibility)
+int check_ready(xb_ctx *ctx, int n);     // a context with weights and room for a batch of n
+int check_alphabet(xb_ctx *ctx, const char *alphabet);
+int join_async_decode(xb_ctx *ctx);      // flush_held, then the main stream waits for decodes in flight on the third stream
+// ... and two from inside its extern "C" block, beside the pairing logic: flush_held launches a held-back asynchronous basecall;
+// basecall_async makes one of n chunks at d_signal into device outputs (seq, len, out), of pipeline slot `slot` or none
+extern "C" int flush_held(xb_ctx *ctx);
+extern "C" int basecall_async(xb_ctx *ctx, const float *d_signal, int n, const char *alphabet, int8_t *seq, int32_t *len,
+                              const DecodeOut &out, int slot = -1);
