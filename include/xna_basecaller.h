@@ -621,6 +621,75 @@ XB_API int xb_splice_chunks_dev(xb_ctx *ctx, const float *d_signal, const uint8_
                                 double prop, double var_prop, int cand_sample_size, int pad, float *d_out_signal,
                                 uint8_t *d_out_targets, int8_t *d_success, int32_t *d_inserted);
 
+/* ---- XNA synthetic spiking of ctc-data (an extension of the device path: `spike`) ---------------------------------------
+ * The reference's ub-bonito/bonito/spike_chunks.py (`bonito train --spike`, the default of its training recipe) replaces the
+ * signal of the six k-mers around chosen bases of a DNA chunk with a synthetic squiggle drawn from a k-mer pore model and
+ * normalised with the med / mad of the whole chunk's synthetic squiggle, per read, in the data loader.  Here one wave per
+ * chunk does it.  Everything but the random stream restates spike_read (:247-297) with equal_kmer_reps=False, mix_ubs=True,
+ * legacy_pos=False, fully_synth=False and is pinned to the reference (tests/golden/spike.json); the DRAWS are this library's
+ * own: parity unpinned.  The kernel is bit-exact against a CPU restatement of the contract (tests/spike_ref.py).
+ *
+ * xb_spike_model keeps a k-mer table on the device until the next call or until the context is destroyed (host pointers; the
+ * call waits): n = 7^6 level means and standard deviations; a k-mer is indexed by its six labels as base-7 digits, the first
+ * letter the most significant (N A C G T X Y = 0 .. 6); mean = NaN: the model lacks the k-mer.  Other means must be finite,
+ * their stdv finite and >= 0.
+ *
+ * xb_spike_chunks: signal, targets, lengths, breakpoints, n, N, Lt, first_index as xb_splice_chunks takes them.  A chunk's
+ * result depends only on its data, the model, the parameters, `seed` and its GLOBAL index c = first_index + row.
+ *   draws      z = mix(mix(mix(seed + G (c + 1)) + G (s + 1)) + G (k + 1)), with splice's mix, G, bounded(m) and unit: draw k of
+ *              stream s of chunk c, so that a lane computes the index of its own draw.  s = 0: proportion, positions and the UB
+ *              shuffle, k counting from 0 in that order, spent exactly where the reference calls its generator.  s = 1: the
+ *              squiggle, k = the sample 0 .. 100 length - 1.  s = 2 + j: the j-th position in ascending order; k = 0 the shift
+ *              choice, k = 1 the variable noise std, k = 2 + i the level noise of window sample i, k = 2 + len + i its added
+ *              noise (len = the window's samples).
+ *   proportion, n_pos, positions   as xb_splice_chunks (spike_chunks.py:194-215 = stitch_chunks.py:104-125).
+ *   UBs        ubs_mask 1 = X, 2 = Y: every position gets it, no draw.  3 = both (:273-277): the list X, Y, X, Y, .. of
+ *              m = n + n % 2 entries (n = the positions found) is shuffled from its end (i = m - 1 .. 1: j = bounded(i + 1), swap
+ *              entries i and j), trimmed to n and zipped with the ascending positions.  0 = the reference's --ubs N: the DNA
+ *              k-mers are re-synthesised and the labels stay.
+ *   k-mers     a k-mer with a NaN mean among those named below ends the chunk before anything else: out_signal / out_targets
+ *              are the inputs, spiked = 0, status = 2, mad = NaN and med = the table index of the first such k-mer (those of
+ *              med / mad by base, then the windows' by position and k-mer).
+ *   med, mad   (:44-52, :150-151) from the ORIGINAL labels: the k-mers of target[:length] + ATATA (TATAT when the last letter
+ *              is A), one per base, each repeated 100 times; sample k = mean + (lo + (s - lo) * unit) with lo = -s, in float64
+ *              as written.  med = (a + b) / 2.0 of the two middle order statistics of the 100 length values (-0 counted as +0);
+ *              mad = the same median of |x - med|, * 1.4826 + 2^-23.  Exact selection, no floating-point accumulation.
+ *   per position (:156-190)  the window is [breakpoints[pos - 6], breakpoints[pos]); k-mer i = 0 .. 5 covers its samples
+ *              breakpoints[pos - 6 + i] .. breakpoints[pos - 5 + i] (none is allowed) and is letters i .. i + 5 of the ORIGINAL
+ *              target[pos - 5 .. pos + 5] with the middle letter replaced by the UB (ubs_mask 0: not replaced).  Level noise of
+ *              a sample with stdv s: dist_rows = 0 (`uniform`): lo + (s - lo) * unit, lo = -s.  dist_rows >= 1 (truncated
+ *              normal): row r = bounded(dist_rows) of `phi` (the reference's shift choice; `truncnorm` is one row), p =
+ *              phi[r][0] + unit * phi[r][1], noise = PPND16(p) * s.  phi is (dist_rows + 1, 2) float64 on the HOST in both
+ *              forms: per shift value Phi(a) and Phi(b) - Phi(a) of the truncation a, b; the last row is the truncation of the
+ *              added noise (-3, 3), read when noise_std > 0.  Added noise: sigma = noise_std, or 0.0 + (noise_std - 0.0) * unit
+ *              with variable_noise; noise = PPND16(phi[dist_rows][0] + unit * phi[dist_rows][1]) * sigma.  The pasted value is
+ *              ((mean + level) + noise - med) / mad -- without the noise term when noise_std = 0 -- rounded ONCE to float32; the
+ *              label at pos becomes the UB.  Later windows overwrite earlier ones where they overlap (pad < 5).
+ *   PPND16     Wichura's AS241 with the coefficients and the operation order of CPython's statistics._normal_dist_inv_cdf;
+ *              its sqrt is the correctly rounded one, its log this library's own, from IEEE + - * / and bit operations only:
+ *              x = m 2^e with m in [1, 2) from the bits; m > 1.4142135623730951: m = m * 0.5, e = e + 1; f = m - 1; s = f / (2 +
+ *              f); z = s * s; q = Horner in z over 1/21, 1/19, .. 1/3 (q = q * z + c); t = (s * z) * q; logm = 2 * (s + t);
+ *              log = e * 6.93147180369123816490e-01 + (logm + e * 1.90821492927058770002e-10).
+ *   outputs    out_signal / out_targets are copies of the inputs elsewhere; spiked (n) int32: the positions pasted; med, mad
+ *              (n) float64 (a chunk of length 0: 0, 0); status (n) int8: 0, or 2 (a k-mer is missing).
+ * Limits: those of xb_splice_chunks for N, Lt, pad, prop, var_prop, first_index; ubs_mask 0 .. 3; 0 <= dist_rows <= 32; every
+ * row read has 1e-300 <= phi[r][0], 0 < phi[r][1], phi[r][0] + phi[r][1] < 1; noise_std finite and >= 0 (XB_ERR_INVALID with
+ * the figures otherwise, before any launch; the context stays usable); XB_ERR_STATE without a model.  Outputs must not alias
+ * inputs.  The host form checks lengths and breakpoints and names the chunk; the _dev form (device pointers but for phi,
+ * returns without waiting: xb_synchronize) clamps them instead, so that no access leaves the rows.
+ */
+XB_API int xb_spike_model(xb_ctx *ctx, const double *mean, const double *stdv, int64_t n);
+XB_API int xb_spike_chunks(xb_ctx *ctx, const float *signal, const uint8_t *targets, const int32_t *lengths,
+                           const uint16_t *breakpoints, int n, int N, int Lt, int64_t first_index, uint64_t seed, int ubs_mask,
+                           double prop, double var_prop, int pad, int dist_rows, const double *phi, double noise_std,
+                           int variable_noise, float *out_signal, uint8_t *out_targets, int32_t *spiked, double *med, double *mad,
+                           int8_t *status);
+XB_API int xb_spike_chunks_dev(xb_ctx *ctx, const float *d_signal, const uint8_t *d_targets, const int32_t *d_lengths,
+                               const uint16_t *d_breakpoints, int n, int N, int Lt, int64_t first_index, uint64_t seed, int ubs_mask,
+                               double prop, double var_prop, int pad, int dist_rows, const double *phi, double noise_std,
+                               int variable_noise, float *d_out_signal, uint8_t *d_out_targets, int32_t *d_spiked, double *d_med,
+                               double *d_mad, int8_t *d_status);
+
 /* ---- introspection / measurement ---------------------------------------------------------- */
 
 enum { XB_STAGE_CONV = 0, XB_STAGE_LSTM_IN = 1, XB_STAGE_LSTM_REC = 2, XB_STAGE_LINEAR = 3,

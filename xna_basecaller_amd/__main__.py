@@ -2,11 +2,12 @@
 --directory CTC_DATA` == `bonito evaluate ...` (bonito/__init__.py:10-33); `... segment CTC_DATA` == the reference's
 `src/tools/dtw_segmentation.py CTC_DATA`; `... analyze LIB.fasta CALLS.paf -R CALLS.fastq` == the reference's
 `src/tools/analyze_paf.py -p`; `... splice DNA_CTC XNA_CTC OUT --ubs XY --prop-ubs P` == the XNA spliced augmentation of
-`bonito train -m per_kmer` (bonito/stitch_chunks.py) written out as ctc-data."""
+`bonito train -m per_kmer` (bonito/stitch_chunks.py) written out as ctc-data; `... spike CTC OUT -r KMER.model --ubs XY
+--prop-ubs P` == the synthetic spiking of `bonito train --spike` (bonito/spike_chunks.py), likewise."""
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 
 from . import __version__
-from .cli import analyze, basecaller, evaluate, segment, splice
+from .cli import analyze, basecaller, evaluate, segment, spike, splice
 
 
 def main():
@@ -25,6 +26,8 @@ def main():
     p.set_defaults(func=analyze.main)
     p = sub.add_parser("splice", parents=[splice.argparser()])
     p.set_defaults(func=splice.main)
+    p = sub.add_parser("spike", parents=[spike.argparser()])
+    p.set_defaults(func=spike.main)
     args = parser.parse_args()
     args.func(args)
 

@@ -33,6 +33,7 @@ EXPORTS = [
     "xb_map_templates", "xb_map_templates_dev", "xb_ctc_targets", "xb_ctc_targets_dev", "xb_ctc_chunks",
     "xb_ub_tally", "xb_ub_tally_dev", "xb_dtw_segment", "xb_dtw_segment_dev", "xb_dtw_scratch_bytes",
     "xb_splice_library", "xb_splice_chunks", "xb_splice_chunks_dev",
+    "xb_spike_model", "xb_spike_chunks", "xb_spike_chunks_dev",
 ]
 XB_COMM_ID_BYTES = 128
 # xb_status (include/xna_basecaller.h)
@@ -138,6 +139,9 @@ def load():
     lib.xb_splice_library.argtypes = [vp, vp, C.c_int64, vp, ip, vp, ip]
     lib.xb_splice_chunks.argtypes = [vp] * 5 + [ip, ip, ip, C.c_int64, C.c_uint64, ip, db, db, ip, ip] + [vp] * 4
     lib.xb_splice_chunks_dev.argtypes = lib.xb_splice_chunks.argtypes
+    lib.xb_spike_model.argtypes = [vp, vp, vp, C.c_int64]
+    lib.xb_spike_chunks.argtypes = [vp] * 5 + [ip, ip, ip, C.c_int64, C.c_uint64, ip, db, db, ip, ip, vp, db, ip] + [vp] * 6
+    lib.xb_spike_chunks_dev.argtypes = lib.xb_spike_chunks.argtypes
     lib.xb_result_stream.argtypes = [vp]
     lib.xb_result_stream.restype = C.c_void_p
     lib.xb_set_profiling.argtypes = [vp, ip]
@@ -685,6 +689,57 @@ class Context:
                                                   int(n), int(N), int(Lt), int(first_index), int(seed) & (2 ** 64 - 1), int(ubs_mask),
                                                   float(prop), float(var_prop or 0.0), int(cand_sample_size), int(pad),
                                                   _ptr(d_out_signal), _ptr(d_out_targets), _ptr(d_success), _ptr(d_inserted)))
+
+    # ---- XNA synthetic spiking (xb_spike_model, xb_spike_chunks): draws parity unpinned ----------
+    def spike_model(self, mean, stdv):
+        """xb_spike_model: (7^6,) float64 level means (NaN: no such k-mer) and stdvs (spike.model_table's arrays); replaces the
+        table of an earlier call."""
+        mean = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
+        stdv = np.ascontiguousarray(stdv, dtype=np.float64).reshape(-1)
+        if mean.shape != stdv.shape:
+            raise ValueError("spike_model: mean and stdv of one shape expected")
+        self._check(self.lib.xb_spike_model(self.h, mean.ctypes.data, stdv.ctypes.data, mean.size))
+
+    @staticmethod
+    def _spike_phi(phi, dist_rows):
+        phi = np.ascontiguousarray(np.zeros((1, 2)) if phi is None else phi, dtype=np.float64).reshape(-1, 2)
+        if phi.shape[0] < int(dist_rows) + 1:
+            raise ValueError("spike_chunks: a distribution table of %d rows, dist_rows + 1 = %d expected" % (phi.shape[0], dist_rows + 1))
+        return phi
+
+    def spike_chunks(self, signal, targets, lengths, breakpoints, first_index, seed, ubs_mask, prop, var_prop=0.0, pad=5,
+                     dist_rows=0, phi=None, noise_std=0.0, variable_noise=False):
+        """xb_spike_chunks: signal (n, N) fp32, targets (n, Lt) uint8, lengths (n), breakpoints (n, Lt) uint16, phi
+        (dist_rows + 1, 2) float64 -> (signal (n, N) float32, targets (n, Lt) uint8, spiked (n,) int32, med (n,), mad (n,)
+        float64, status (n,) int8)."""
+        signal = np.ascontiguousarray(signal, dtype=np.float32)
+        targets = np.ascontiguousarray(targets, dtype=np.uint8)
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32)
+        bk = np.ascontiguousarray(breakpoints, dtype=np.uint16)
+        n, N = signal.shape
+        if targets.ndim != 2 or targets.shape[0] != n or bk.shape != targets.shape or lengths.shape != (n,):
+            raise ValueError("spike_chunks: signal (n, N), targets (n, Lt), lengths (n), breakpoints (n, Lt) expected")
+        phi = self._spike_phi(phi, dist_rows)
+        out, out_t = np.empty_like(signal), np.empty_like(targets)
+        spiked, status = np.empty((n,), np.int32), np.empty((n,), np.int8)
+        med, mad = np.empty((n,), np.float64), np.empty((n,), np.float64)
+        self._check(self.lib.xb_spike_chunks(self.h, signal.ctypes.data, targets.ctypes.data, lengths.ctypes.data, bk.ctypes.data,
+                                             n, N, targets.shape[1], int(first_index), int(seed) & (2 ** 64 - 1), int(ubs_mask),
+                                             float(prop), float(var_prop or 0.0), int(pad), int(dist_rows), phi.ctypes.data,
+                                             float(noise_std), int(bool(variable_noise)), out.ctypes.data, out_t.ctypes.data,
+                                             spiked.ctypes.data, med.ctypes.data, mad.ctypes.data, status.ctypes.data))
+        return out, out_t, spiked, med, mad, status
+
+    def spike_chunks_dev(self, d_signal, d_targets, d_lengths, d_breakpoints, n, N, Lt, first_index, seed, ubs_mask, prop, var_prop,
+                         pad, dist_rows, phi, noise_std, variable_noise, d_out_signal, d_out_targets, d_spiked, d_med, d_mad,
+                         d_status):
+        """xb_spike_chunks_dev: device pointers but for `phi` (host); returns without waiting."""
+        phi = self._spike_phi(phi, dist_rows)
+        self._check(self.lib.xb_spike_chunks_dev(self.h, _ptr(d_signal), _ptr(d_targets), _ptr(d_lengths), _ptr(d_breakpoints),
+                                                 int(n), int(N), int(Lt), int(first_index), int(seed) & (2 ** 64 - 1), int(ubs_mask),
+                                                 float(prop), float(var_prop or 0.0), int(pad), int(dist_rows), phi.ctypes.data,
+                                                 float(noise_std), int(bool(variable_noise)), _ptr(d_out_signal),
+                                                 _ptr(d_out_targets), _ptr(d_spiked), _ptr(d_med), _ptr(d_mad), _ptr(d_status)))
 
     # ---- host pipeline: two batches in flight (xb_submit_chunks / xb_collect_chunks) ----------
     def submit_chunks(self, slot, signal, alphabet, qscale=1.0, qoffset=0.0, level=0):

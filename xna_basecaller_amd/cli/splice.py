@@ -19,7 +19,7 @@ REFUSED = (   # attribute, its neutral value, why not
                                  "numpy's pairwise sums"),
     ("stitch_noise_std", 0, "--stitch-noise-std draws from a host random stream"),
     ("permute_win_size", 0, "--permute-win-size draws from a host random stream"),
-    ("spike", False, "--spike (synthetic signal) is a different feature"),
+    ("spike", False, "--spike (synthetic signal) is the `spike` command"),
 )
 
 

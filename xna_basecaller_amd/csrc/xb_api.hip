@@ -856,7 +856,7 @@ XB_API void xb_ctx_destroy(xb_ctx *ctx)
     for (auto &b : ctx->bufs) (void)hipFree(b.p);
     for (auto &b : ctx->wsbufs) (void)hipFree(b.p);
     for (DevBuf *b : {&ctx->staging, &ctx->map.image, &ctx->map.partial, &ctx->map.scratch, &ctx->dtw.scratch, &ctx->splice.pool,
-                      &ctx->splice.rows, &ctx->splice.table})
+                      &ctx->splice.rows, &ctx->splice.table, &ctx->spike.model})
         if (b->p) (void)hipFree(b->p);
     for (auto &o : ctx->dtw.off) {
         if (o.h) (void)hipHostFree(o.h);

@@ -1,5 +1,5 @@
-// xb_api_data.hip -- the ctc-data tools of the C ABI: template mapping, ctc labels, the UB tally, DTW segmentation and spliced
-// augmentation.  Each has a _dev form on device pointers and a host-pointer form that stages through xb_ctx::staging.
+// xb_api_data.hip -- the ctc-data tools of the C ABI: template mapping, ctc labels, the UB tally, DTW segmentation, spliced
+// augmentation and synthetic spiking.  Each has a _dev form on device pointers and a host-pointer form that stages through xb_ctx::staging.
 #include "xb_ctx.h"
 
 namespace {
@@ -707,6 +707,163 @@ XB_API int xb_splice_chunks(xb_ctx *ctx, const float *signal, const uint8_t *tar
     XB_HIP(ctx, hipMemcpyAsync(out_targets, d_ot, C * Lt, hipMemcpyDeviceToHost, ctx->stream));
     XB_HIP(ctx, hipMemcpyAsync(success, d_ok, C, hipMemcpyDeviceToHost, ctx->stream));
     XB_HIP(ctx, hipMemcpyAsync(inserted, d_ins, C * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return xb_synchronize(ctx);
+}
+
+// ---- XNA synthetic spiking (xb_spike_model, xb_spike_chunks) -----------------------------------------------------------
+XB_API int xb_spike_model(xb_ctx *ctx, const double *mean, const double *stdv, int64_t n)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    if (!mean || !stdv) return fail(ctx, XB_ERR_INVALID, "xb_spike_model: null host pointer");
+    if (n != xb::SPIKE_MODEL_KMERS)
+        return fail(ctx, XB_ERR_INVALID, "xb_spike_model: a table of %lld k-mers; need 7^6 = %d", (long long)n, xb::SPIKE_MODEL_KMERS);
+    std::vector<double> rows(2 * (size_t)n);
+    for (int64_t k = 0; k < n; ++k) {
+        const double m = mean[k], s = stdv[k];
+        if (m == m && (std::isinf(m) || !(s >= 0.0) || std::isinf(s)))
+            return fail(ctx, XB_ERR_INVALID, "xb_spike_model: k-mer %lld has mean %g, stdv %g; a finite mean (or NaN: no such k-mer) "
+                        "and a finite stdv >= 0 are supported", (long long)k, m, s);
+        rows[2 * k] = m;
+        rows[2 * k + 1] = m == m ? s : 0.0;
+    }
+    if (int rc = enter(ctx, false)) return rc;
+    xb_ctx::SpikeState &s = ctx->spike;
+    s.loaded = false;
+    XB_HIP(ctx, hipStreamSynchronize(ctx->stream));                     // nothing in flight reads the table it replaces
+    if (int rc = grow(ctx, &s.model, rows.size() * 8)) return rc;
+    XB_HIP(ctx, hipMemcpyAsync(s.model.p, rows.data(), rows.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s.loaded = true;
+    return XB_OK;
+}
+
+namespace {
+
+struct SpikeArgs {
+    int n, N, Lt;
+    int64_t first_index;
+    uint64_t seed;
+    int ubs_mask;
+    double prop, var_prop;
+    int pad, dist_rows;
+    const double *phi;
+    double noise_std;
+    int variable_noise;
+};
+
+// the limits of the contract, before any launch
+int spike_check(xb_ctx *ctx, const SpikeArgs &a)
+{
+    if (!ctx->spike.loaded) return fail(ctx, XB_ERR_STATE, "xb_spike_chunks: no model: call xb_spike_model first");
+    if (a.n < 1 || a.N < 1 || a.N > xb::SPLICE_MAX_SAMPLES || a.Lt < 1 || a.Lt > xb::SPLICE_MAX_LABELS)
+        return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: n = %d chunks of %d samples, label rows of %d entries; need n >= 1, "
+                    "1 <= N <= %d, 1 <= Lt <= %d", a.n, a.N, a.Lt, xb::SPLICE_MAX_SAMPLES, xb::SPLICE_MAX_LABELS);
+    if (a.pad < 0) return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: pad = %d is negative", a.pad);
+    if (a.ubs_mask < 0 || a.ubs_mask > 3)
+        return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: ubs_mask = %d; 0 (none), 1 (X), 2 (Y) or 3 (both)", a.ubs_mask);
+    if (!(a.prop >= 0.0) || !(a.var_prop >= 0.0) || !(a.prop + a.var_prop <= 1.0))
+        return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: prop = %g, var_prop = %g; both at least 0, their sum at most 1", a.prop, a.var_prop);
+    if (a.first_index < 0) return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: first_index = %lld is negative", (long long)a.first_index);
+    if (a.dist_rows < 0 || a.dist_rows > xb::SPIKE_MAX_ROWS)
+        return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: dist_rows = %d; 0 (uniform) .. %d shift values are supported", a.dist_rows,
+                    xb::SPIKE_MAX_ROWS);
+    if (!(a.noise_std >= 0.0) || std::isinf(a.noise_std))
+        return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: noise_std = %g; a finite value >= 0 is supported", a.noise_std);
+    // the rows the kernel reads: every quantile pa + unit * pw must stay inside (0, 1) and normal
+    for (int r = 0; r <= a.dist_rows; ++r) {
+        if (r == a.dist_rows && !(a.noise_std > 0.0)) break;
+        if (!a.phi) return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: null distribution table");
+        const double pa = a.phi[2 * r], pw = a.phi[2 * r + 1];
+        if (!(pa >= 1e-300) || !(pw > 0.0) || !(pa + pw < 1.0))
+            return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: distribution row %d is Phi(a) = %g, Phi(b) - Phi(a) = %g; need "
+                        "1e-300 <= Phi(a), 0 < Phi(b) - Phi(a), Phi(b) < 1", r, pa, pw);
+    }
+    return XB_OK;
+}
+
+int spike_run(xb_ctx *ctx, const SpikeArgs &a, const float *d_signal, const uint8_t *d_targets, const int32_t *d_lengths,
+              const uint16_t *d_bkps, float *d_out_signal, uint8_t *d_out_targets, int32_t *d_spiked, double *d_med, double *d_mad,
+              int8_t *d_status)
+{
+    xb::SpikeParams p{};
+    p.signal = d_signal; p.targets = d_targets; p.lengths = d_lengths; p.bkps = d_bkps;
+    p.n = a.n; p.N = a.N; p.Lt = a.Lt;
+    p.first_index = (unsigned long long)a.first_index; p.seed = a.seed;
+    p.ubs_mask = a.ubs_mask; p.prop = a.prop; p.var_prop = a.var_prop; p.pad = a.pad;
+    p.dist_rows = a.dist_rows;
+    for (int r = 0; r <= a.dist_rows; ++r) {
+        const bool read = r < a.dist_rows || a.noise_std > 0.0;
+        p.phi[r][0] = read ? a.phi[2 * r] : 0.25;
+        p.phi[r][1] = read ? a.phi[2 * r + 1] : 0.5;
+    }
+    p.noise_std = a.noise_std; p.variable_noise = a.variable_noise != 0;
+    p.model = static_cast<const double *>(ctx->spike.model.p);
+    p.out_signal = d_out_signal; p.out_targets = d_out_targets; p.spiked = d_spiked; p.med = d_med; p.mad = d_mad; p.status = d_status;
+    XB_HIP(ctx, xb::launch_spike(p, ctx->stream));
+    return XB_OK;
+}
+
+}  // namespace
+
+XB_API int xb_spike_chunks_dev(xb_ctx *ctx, const float *d_signal, const uint8_t *d_targets, const int32_t *d_lengths,
+                               const uint16_t *d_breakpoints, int n, int N, int Lt, int64_t first_index, uint64_t seed, int ubs_mask,
+                               double prop, double var_prop, int pad, int dist_rows, const double *phi, double noise_std,
+                               int variable_noise, float *d_out_signal, uint8_t *d_out_targets, int32_t *d_spiked, double *d_med,
+                               double *d_mad, int8_t *d_status)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    if (!d_signal || !d_targets || !d_lengths || !d_breakpoints || !d_out_signal || !d_out_targets || !d_spiked || !d_med || !d_mad ||
+        !d_status)
+        return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: null device pointer");
+    if (d_signal == d_out_signal || d_targets == d_out_targets) return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: outputs alias inputs");
+    const SpikeArgs a{n, N, Lt, first_index, seed, ubs_mask, prop, var_prop, pad, dist_rows, phi, noise_std, variable_noise};
+    if (int rc = spike_check(ctx, a)) return rc;
+    if (int rc = enter(ctx, true)) return rc;
+    return spike_run(ctx, a, d_signal, d_targets, d_lengths, d_breakpoints, d_out_signal, d_out_targets, d_spiked, d_med, d_mad, d_status);
+}
+
+XB_API int xb_spike_chunks(xb_ctx *ctx, const float *signal, const uint8_t *targets, const int32_t *lengths,
+                           const uint16_t *breakpoints, int n, int N, int Lt, int64_t first_index, uint64_t seed, int ubs_mask,
+                           double prop, double var_prop, int pad, int dist_rows, const double *phi, double noise_std,
+                           int variable_noise, float *out_signal, uint8_t *out_targets, int32_t *spiked, double *med, double *mad,
+                           int8_t *status)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    if (!signal || !targets || !lengths || !breakpoints || !out_signal || !out_targets || !spiked || !med || !mad || !status)
+        return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: null host pointer");
+    const SpikeArgs a{n, N, Lt, first_index, seed, ubs_mask, prop, var_prop, pad, dist_rows, phi, noise_std, variable_noise};
+    if (int rc = spike_check(ctx, a)) return rc;
+    for (int c = 0; c < n; ++c) {                                       // what the kernel would otherwise clamp
+        const int len = lengths[c];
+        if (len < 0 || len > Lt) return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: chunk %d has %d labels in a row of %d", c, len, Lt);
+        const uint16_t *b = breakpoints + (size_t)c * Lt;
+        for (int l = 0; l < len; ++l)
+            if (b[l] > N || (l && b[l] < b[l - 1]))
+                return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: chunk %d: breakpoint %d of base %d (the one before: %d, samples: %d)", c,
+                            (int)b[l], l, l ? (int)b[l - 1] : 0, N);
+    }
+    if (int rc = enter(ctx, false)) return rc;
+    const size_t C = (size_t)n;
+    Staging st{ctx};
+    const auto d_sig = st.take<float>(C * N), d_out = st.take<float>(C * N);
+    const auto d_med = st.take<double>(C), d_mad = st.take<double>(C);
+    const auto d_cnt = st.take<int32_t>(C), d_len = st.take<int32_t>(C);
+    const auto d_bk = st.take<uint16_t>(C * Lt);
+    const auto d_t = st.take<uint8_t>(C * Lt), d_ot = st.take<uint8_t>(C * Lt);
+    const auto d_st = st.take<int8_t>(C);
+    if (st.used > ((size_t)2 << 30)) return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: %d chunks of %d samples in one call; split the batch", n, N);
+    if (int rc = st.ready()) return rc;
+    XB_HIP(ctx, hipMemcpyAsync(d_sig, signal, C * N * 4, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(d_len, lengths, C * 4, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(d_bk, breakpoints, C * Lt * 2, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(d_t, targets, C * Lt, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = spike_run(ctx, a, d_sig, d_t, d_len, d_bk, d_out, d_ot, d_cnt, d_med, d_mad, d_st)) return rc;
+    XB_HIP(ctx, hipMemcpyAsync(out_signal, d_out, C * N * 4, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(out_targets, d_ot, C * Lt, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(spiked, d_cnt, C * 4, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(med, d_med, C * 8, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(mad, d_mad, C * 8, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(status, d_st, C, hipMemcpyDeviceToHost, ctx->stream));
     return xb_synchronize(ctx);
 }
 

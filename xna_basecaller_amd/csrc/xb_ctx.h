@@ -218,6 +218,13 @@ struct xb_ctx {
         bool loaded = false;
     } splice;
 
+    // XNA synthetic spiking (xb_spike_model / xb_spike_chunks): the k-mer table, kept until the next xb_spike_model.  Owned
+    // here, freed by xb_ctx_destroy.
+    struct SpikeState {
+        DevBuf model;
+        bool loaded = false;
+    } spike;
+
     bool profiling = false;
     std::vector<StageEvent> events;
     float stage_ms[XB_STAGE_COUNT] = {};

@@ -338,6 +338,36 @@ struct SpliceParams {
 };
 hipError_t launch_splice(const SpliceParams &p, hipStream_t stream);
 
+// ---------------------------------------------------------------- XNA synthetic spiking (xb_spike.hip)
+// xb_spike_chunks: per DNA chunk the positions, med / mad of its synthetic squiggle by exact selection, the synthetic signal
+// of the six k-mers around every position pasted over the chunk's own (the contract is in the public header).  One wave per
+// chunk.  The limits of the rows are splice's.
+constexpr int SPIKE_MODEL_KMERS = 117649;   // 7^6
+constexpr int SPIKE_KMER_REPS = 100;        // squiggle samples per base (compute_med_mad_squiggly's kmer_rep)
+constexpr int SPIKE_MAX_ROWS = 32;          // shift values of a truncated-normal level distribution
+struct SpikeParams {
+    const float *signal;         // (n, N) fp32
+    const uint8_t *targets;      // (n, Lt) labels 0 .. 6
+    const int32_t *lengths;      // (n)
+    const uint16_t *bkps;        // (n, Lt): the sample where every base's signal ends
+    int n, N, Lt;
+    unsigned long long first_index, seed;
+    int ubs_mask;                // 0: none (DNA re-synthesised), 1: X, 2: Y, 3: both
+    double prop, var_prop;
+    int pad;
+    int dist_rows;               // 0: uniform level noise; else the shift values of the truncated normal
+    double phi[SPIKE_MAX_ROWS + 1][2];   // per shift value Phi(a), Phi(b) - Phi(a); row dist_rows: the added noise's truncation
+    double noise_std;
+    int variable_noise;
+    const double *model;         // (7^6, 2) level mean (NaN: no such k-mer) and stdv
+    float *out_signal;           // (n, N)
+    uint8_t *out_targets;        // (n, Lt)
+    int32_t *spiked;             // (n)
+    double *med, *mad;           // (n)
+    int8_t *status;              // (n)
+};
+hipError_t launch_spike(const SpikeParams &p, hipStream_t stream);
+
 #ifdef XB_LSTM_STAMPS
 void lstm_read_stamps(unsigned long long out[10], bool reset);   // diagnostic build only
 void gemm_read_stamps(unsigned long long out[8], bool reset);    // diagnostic build only (XB_GEMM_STAMPS)

@@ -4,9 +4,10 @@
 //
 // One wave per chunk, one launch per call.  The wave copies its signal and label rows (16-byte accesses when the rows allow
 // it), then works on the copy:
-//   positions   the validity mask of the chunk's bases is a bit set in LDS (a word per lane and pass); a round finds the k-th
-//               valid base from the words' popcounts (a wave scan), marks it in a second bit set and clears its surroundings.
-//               Walking the second set in word order handles the positions in ascending order without a sort.
+//   positions   (xb_positions.h, shared with xb_spike.hip) the validity mask of the chunk's bases is a bit set in LDS (a word
+//               per lane and pass); a round finds the k-th valid base from the words' popcounts (a wave scan), marks it in a
+//               second bit set and clears its surroundings.  Walking the second set in word order handles the positions in
+//               ascending order without a sort.
 //   draws       draw k is a pure function of (seed, global chunk index, k): every lane computes the wave-uniform ones
 //               itself; the up to 32 draws of a candidate sample are taken one per lane and the partial Fisher-Yates
 //               permutation is then resolved in wave-uniform steps (ballot for "who wrote this slot last").
@@ -22,66 +23,16 @@
 #include <hip/hip_runtime.h>
 
 #include "xb_internal.h"
+#include "xb_positions.h"
 
 namespace {
 
 using xb::SpliceParams;
-typedef unsigned long long u64;
+using namespace xb_pos;       // the draws and the position chooser, shared with xb_spike.hip
 
 constexpr int KM = xb::SPLICE_KMERS;
 constexpr int MAX_SLICE = KM * xb::SPLICE_MAX_KMER;       // samples of the six library rows of one paste
 constexpr int MASK_WORDS = (xb::SPLICE_MAX_LABELS + 32) / 32;
-constexpr u64 GAMMA = 0x9E3779B97F4A7C15ULL;
-
-__device__ inline u64 mix(u64 z)
-{
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-__device__ inline unsigned bounded(u64 z, unsigned m) { return (unsigned)(((z >> 32) * (u64)m) >> 32); }
-
-__device__ inline int wave_sum(int v)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-__device__ inline int wave_min(int v)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_xor(v, d);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
-// clears bits lo .. hi - 1 (clipped to 0 .. length); returns how many were set.  Ends with a barrier.
-__device__ int clear_range(unsigned *bits, long long lo, long long hi, int length, int lane)
-{
-    if (lo < 0) lo = 0;
-    if (hi > length) hi = length;
-    int cleared = 0;
-    if (lo < hi) {
-        const int w0 = (int)(lo >> 5), w1 = (int)((hi - 1) >> 5);
-        for (int w = w0 + lane; w <= w1; w += 64) {
-            unsigned m = 0xffffffffu;
-            if (w == w0) m &= 0xffffffffu << (int)(lo & 31);
-            if (w == w1) {
-                const int e = (int)(hi - ((long long)w1 << 5));          // 1 .. 32 bits of the last word
-                if (e < 32) m &= (1u << e) - 1u;
-            }
-            const unsigned old = bits[w];
-            cleared += __popc(old & m);
-            bits[w] = old & ~m;
-        }
-    }
-    __syncthreads();
-    return wave_sum(cleared);
-}
 
 // numpy.linspace(0, stop, num, dtype=int)[i]: floor(i * (stop / (num - 1))), the last value stop itself
 __device__ inline int linspace_floor(int i, int stop, int num)
@@ -106,94 +57,20 @@ __global__ __launch_bounds__(64) void splice_kernel(const SpliceParams p)
     const uint16_t *bk = p.bkps + (size_t)c * Lt;
 
     // ---- the rows' copy
-    if ((N & 3) == 0 && (((uintptr_t)p.signal | (uintptr_t)p.out_signal) & 15) == 0) {
-        const float4 *s4 = reinterpret_cast<const float4 *>(sig);
-        float4 *o4 = reinterpret_cast<float4 *>(out);
-        for (int i = lane; i < (N >> 2); i += 64) o4[i] = s4[i];
-    } else {
-        for (int i = lane; i < N; i += 64) out[i] = sig[i];
-    }
-    if ((Lt & 15) == 0 && (((uintptr_t)p.targets | (uintptr_t)p.out_targets) & 15) == 0) {
-        const uint4 *s4 = reinterpret_cast<const uint4 *>(tgt);
-        uint4 *o4 = reinterpret_cast<uint4 *>(out_t);
-        for (int i = lane; i < (Lt >> 4); i += 64) o4[i] = s4[i];
-    } else {
-        for (int i = lane; i < Lt; i += 64) out_t[i] = tgt[i];
-    }
+    copy_row(out, sig, N, p.signal, p.out_signal, lane);
+    copy_row(out_t, tgt, Lt, p.targets, p.out_targets, lane);
 
     int length = p.lengths[c];
     length = length < 0 ? 0 : (length > Lt ? Lt : length);
     const int W = (length + 31) >> 5;
-    for (int w = lane; w < W; w += 64) {
-        valid[w] = 0xffffffffu;
-        chosen[w] = 0;
-    }
-    __syncthreads();                                     // also: the copy has landed before a paste overwrites it
-    const long long pad = p.pad;
-    clear_range(valid, 0, 10, length, lane);
-    clear_range(valid, (long long)length - 10, (long long)W << 5, W << 5, lane);
-
-    // ---- existing UBs: counted, and nothing is inserted within 2 pad of one
-    int n_exist = 0;
-    for (int b0 = 0; b0 < length; b0 += 64) {
-        const int i = b0 + lane;
-        u64 m = __ballot(i < length && tgt[i] > 4);
-        n_exist += __popcll(m);
-        while (m) {
-            const int pos = b0 + __ffsll((long long)m) - 1;
-            m &= m - 1;
-            clear_range(valid, pos - 2 * pad, pos + 2 * pad + 1, length, lane);
-        }
-    }
-    int nvalid = 0;
-    for (int w = lane; w < W; w += 64) nvalid += __popc(valid[w]);
-    nvalid = wave_sum(nvalid);
 
     // ---- draws
     const u64 base = mix(p.seed + GAMMA * (p.first_index + (u64)c + 1));
     u64 kdraw = 0;
     auto next = [&]() { return mix(base + GAMMA * ++kdraw); };
 
-    double prop = p.prop;
-    if (p.var_prop > 0.0) {
-        const double lo = p.prop - p.var_prop, hi = p.prop + p.var_prop;
-        const double unit = (double)(next() >> 11) * 0x1p-53;
-        prop = lo + (hi - lo) * unit;
-    }
-    long long n_pos = (long long)rint((double)length * prop) - n_exist;
-    if (n_pos < 1) n_pos = 1;
-
-    // ---- positions
-    for (long long round = 0; round < n_pos && nvalid > 0; ++round) {
-        unsigned k = bounded(next(), (unsigned)nvalid);
-        int pos = -1;
-        for (int blk = 0; blk < W; blk += 64) {
-            const int w = blk + lane;
-            const unsigned bits = w < W ? valid[w] : 0u;
-            const int cnt = __popc(bits);
-            int incl = cnt;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int t = __shfl_up(incl, d);
-                if (lane >= d) incl += t;
-            }
-            const unsigned tot = (unsigned)__shfl(incl, 63);
-            if (k < tot) {
-                const u64 m = __ballot(incl > (int)k);
-                const int L = __ffsll((long long)m) - 1;
-                unsigned wb = (unsigned)__shfl((int)bits, L);
-                int r = (int)k - __shfl(incl - cnt, L);
-                while (r-- > 0) wb &= wb - 1;
-                pos = ((blk + L) << 5) + __ffs((int)wb) - 1;
-                break;
-            }
-            k -= tot;
-        }
-        if (pos < 0) break;                              // cannot happen while nvalid counts the set bits
-        pos = __builtin_amdgcn_readfirstlane(pos);
-        if (lane == 0) chosen[pos >> 5] |= 1u << (pos & 31);
-        nvalid -= clear_range(valid, pos - pad, pos + pad + 1, length, lane);
-    }
+    // ---- positions (its first barrier also: the copy has landed before a paste overwrites it)
+    choose_positions(valid, chosen, tgt, length, p.pad, p.prop, p.var_prop, next, lane);
 
     // ---- per position, ascending
     int inserted = 0;

@@ -2,7 +2,7 @@
 Validation data of `bonito evaluate` (ub-bonito/bonito/data.py:104-163): a directory with chunks.npy (N, L) signal
 chunks, references.npy (N, Lmax) integer-coded references (0 = padding) and reference_lengths.npy (N,), optionally an
 indices.npy subsample and a validation/ sub-directory.  Only what evaluation needs: the reference's training-side
-stitching of XNA segments is `splice` (splice.py), its synthetic spiking is outside the MI355X path.
+stitching of XNA segments is `splice` (splice.py), its synthetic spiking is `spike` (spike.py).
 """
 import os
 
