@@ -523,6 +523,47 @@ XB_API int xb_ub_tally_dev(xb_ctx *ctx, const int8_t *d_seq, const int32_t *d_se
                            const int32_t *d_r_st, const int32_t *d_r_en, const uint8_t *d_ops, const int32_t *d_n_ops,
                            int32_t *d_counts, int32_t *d_reads, int32_t *d_err, int64_t *d_cm);
 
+/* ---- barcode distance of mapped rows (`basecaller --ub-report --max-bc-dist`, `analyze -d`) ---------------------------------
+ * The templates of an XNA library share their primers and differ in a barcode; the reference's analyze_paf.py -d N keeps a PAF
+ * row only when the read carries the barcode of the template it was mapped to, at an edit distance of at most N
+ * (utils.py:1387-1434 get_barcode_match_score per row, analyze_paf.py:623-643 the filter).  Here the mapping is
+ * xb_map_templates': PARITY UNPINNED for the mapping, the per-row function pinned by tests/golden/bcdist.json (what the
+ * reference's own function returned); the kernel is equal, integer for integer, to a CPU restatement of the contract below
+ * (tests/bcdist_ref.py).
+ *   inputs     the rows the mapper saw: seq (n, W) int8 ASCII, left-packed, and seq_len (clamped to [0, W]); the mapper's tmpl,
+ *              strand, q_st, r_st; the library as xb_map_templates takes it (HOST pointers; the context's cached device image is
+ *              reused).  q_st is clamped to [0, seq_len], r_st to [0, L] (L = the template's length).  strand < 0 is the reverse
+ *              strand, anything else the forward.  bc_pos: where the barcode starts in every template (the reference's
+ *              left_primer_len), bc_len its length, relax the windows tried to either side (n_relax_bases); the reference's
+ *              values are 25 / 24 / 3 (POC) and 23 / 30 / 3 (CPLX).
+ *   barcode    B = template[bc_pos : bc_pos + bc_len], clipped to the template (short, or empty when bc_pos >= L), a-z in upper
+ *              case, every other byte as it is -- the LETTERS, not the mapper's codes: an 'N' of the template equals an 'N' only.
+ *   query      Q[i] on the aligned strand, exactly xb_ub_tally's Q: upper case; on strand -1 the row reversed with A <-> T,
+ *              C <-> G and X <-> Y (utils.py:26-31), every other byte unchanged.
+ *   start      max(q_st + bc_pos - r_st, 0): the two branches of utils.py:1400-1404 in the mapper's own coordinates.
+ *   windows    i = max(start - relax, 0) .. start + relax in ascending order; obs = Q[i : min(i + bc_len, seq_len)], empty when
+ *              i >= seq_len (Python's slice); d = the unit-cost Levenshtein distance of B and obs, bytes compared as they are;
+ *              the first strictly smaller d wins.
+ *   outputs    (n) int32 each: bc_dist = the winning d, bc_start = its i, bc_end = i + bc_len (NOT clipped, as the reference
+ *              reports it), bc_obs_len = len(obs).  A row whose tmpl lies outside [0, R) is unmapped: bc_dist = -1, zeros
+ *              elsewhere.
+ * Everything is an integer.  Limits: 0 <= bc_pos <= 2^30, 1 <= bc_len <= 64, 0 <= relax <= 8, and the mapper's -- W <= 4096,
+ * templates of 1 .. 4096 letters, a library of at most 2^20 letters (XB_ERR_INVALID with the figures otherwise; the context
+ * stays usable).  One launch on the main stream, one wavefront per row: B as one 64-bit word per query letter (which barcode
+ * positions it matches), a lane per window running the bit-vector recurrence of the global distance, the windows side by
+ * side; no scratch, no atomics; not a stage of xb_get_stage_times.  The _dev form takes device pointers for the rows, the
+ * mapper's outputs and the four outputs and returns without waiting (xb_synchronize); the host form uploads, runs, waits and
+ * copies back.
+ */
+XB_API int xb_barcode_dist(xb_ctx *ctx, const int8_t *seq, const int32_t *seq_len, int n, int W, const char *templates,
+                           const int32_t *offsets, int R, const int32_t *tmpl, const int8_t *strand, const int32_t *q_st,
+                           const int32_t *r_st, int bc_pos, int bc_len, int relax, int32_t *bc_dist, int32_t *bc_start, int32_t *bc_end,
+                           int32_t *bc_obs_len);
+XB_API int xb_barcode_dist_dev(xb_ctx *ctx, const int8_t *d_seq, const int32_t *d_seq_len, int n, int W, const char *templates,
+                               const int32_t *offsets, int R, const int32_t *d_tmpl, const int8_t *d_strand, const int32_t *d_q_st,
+                               const int32_t *d_r_st, int bc_pos, int bc_len, int relax, int32_t *d_bc_dist, int32_t *d_bc_start,
+                               int32_t *d_bc_end, int32_t *d_bc_obs_len);
+
 /* ---- DTW signal segmentation of ctc-data (an extension of the device path: `segment`) --------------------------------
  * The reference's src/tools/dtw_segmentation.py aligns every training chunk to the expected current levels of its reference
  * sequence with dtw-python (dtw(chunk, reference, step_pattern=my_asymmetric, window_type='slantedband'), :128-202) on the

@@ -31,7 +31,7 @@ EXPORTS = [
     "xb_decode_q", "xb_decode_q_dev", "xb_basecall_chunks_q", "xb_submit_chunks_q", "xb_collect_chunks_q",
     "xb_decode_ub", "xb_decode_ub_dev", "xb_basecall_chunks_ub", "xb_submit_chunks_ub", "xb_collect_chunks_ub",
     "xb_map_templates", "xb_map_templates_dev", "xb_ctc_targets", "xb_ctc_targets_dev", "xb_ctc_chunks",
-    "xb_ub_tally", "xb_ub_tally_dev", "xb_dtw_segment", "xb_dtw_segment_dev", "xb_dtw_scratch_bytes",
+    "xb_ub_tally", "xb_ub_tally_dev", "xb_barcode_dist", "xb_barcode_dist_dev", "xb_dtw_segment", "xb_dtw_segment_dev", "xb_dtw_scratch_bytes",
     "xb_splice_library", "xb_splice_chunks", "xb_splice_chunks_dev",
     "xb_spike_model", "xb_spike_chunks", "xb_spike_chunks_dev",
 ]
@@ -132,6 +132,8 @@ def load():
     lib.xb_ctc_chunks.argtypes = [vp, vp, ip, C.c_char_p, C.c_char_p, vp, ip] + [ip] * 5 + [db, db, ip, ip, ip] + [vp] * 17
     lib.xb_ub_tally.argtypes = [vp, vp, vp, ip, ip, C.c_char_p, vp, ip] + [vp] * 11
     lib.xb_ub_tally_dev.argtypes = lib.xb_ub_tally.argtypes
+    lib.xb_barcode_dist.argtypes = [vp, vp, vp, ip, ip, C.c_char_p, vp, ip] + [vp] * 4 + [ip] * 3 + [vp] * 4
+    lib.xb_barcode_dist_dev.argtypes = lib.xb_barcode_dist.argtypes
     lib.xb_dtw_segment.argtypes = [vp, vp, ip, ip, vp, vp, ip, vp, ip, vp, vp, vp]
     lib.xb_dtw_segment_dev.argtypes = lib.xb_dtw_segment.argtypes
     lib.xb_dtw_scratch_bytes.argtypes = [vp]
@@ -615,6 +617,35 @@ class Context:
                                              off.size - 1, *[_ptr(d_got[k]) for k in self.UB_INPUTS], _ptr(d_counts), _ptr(d_reads),
                                              _ptr(d_err), _ptr(d_cm)))
 
+    # ---- barcode distance of mapped rows (xb_barcode_dist): the per-row function pinned, the mapping unpinned ----------
+    BC_INPUTS = ("tmpl", "strand", "q_st", "r_st")
+    BC_OUTPUTS = ("bc_dist", "bc_start", "bc_end", "bc_obs_len")
+
+    def barcode_dist(self, rows, lens, got, library, offsets, bc_pos, bc_len, relax=3):
+        """xb_barcode_dist: the rows the mapper saw (rows (n, W) int8, lens (n)) and its outputs `got` (map_templates' dict) ->
+        dict of bc_dist (-1 for an unmapped row), bc_start, bc_end, bc_obs_len, (n) int32 each (BC_OUTPUTS)."""
+        rows = np.ascontiguousarray(rows, dtype=np.int8)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        n, W = rows.shape
+        dts = dict(self.MAP_OUTPUTS)
+        ins = [np.ascontiguousarray(got[k], dtype=dts[k]) for k in self.BC_INPUTS]
+        if lens.shape != (n,) or any(a.shape != (n,) for a in ins):
+            raise ValueError("barcode_dist: %d rows, but lens and the mapper's outputs are %s" % (n, [lens.shape] + [a.shape for a in ins]))
+        out = {k: np.empty((n,), np.int32) for k in self.BC_OUTPUTS}
+        self._check(self.lib.xb_barcode_dist(self.h, rows.ctypes.data, lens.ctypes.data, n, W, bytes(library), off.ctypes.data,
+                                             off.size - 1, *[a.ctypes.data for a in ins], int(bc_pos), int(bc_len), int(relax),
+                                             *[out[k].ctypes.data for k in self.BC_OUTPUTS]))
+        return out
+
+    def barcode_dist_dev(self, d_rows, d_lens, n, width, d_got, library, offsets, bc_pos, bc_len, relax, d_out):
+        """xb_barcode_dist_dev: device pointers for the rows, the mapper's outputs (d_got: name -> pointer, BC_INPUTS) and the
+        outputs (d_out: name -> pointer, BC_OUTPUTS); returns without waiting."""
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        self._check(self.lib.xb_barcode_dist_dev(self.h, _ptr(d_rows), _ptr(d_lens), int(n), int(width), bytes(library),
+                                                 off.ctypes.data, off.size - 1, *[_ptr(d_got[k]) for k in self.BC_INPUTS],
+                                                 int(bc_pos), int(bc_len), int(relax), *[_ptr(d_out[k]) for k in self.BC_OUTPUTS]))
+
     # ---- DTW signal segmentation (xb_dtw_segment): an extension, parity unpinned ----------
     @staticmethod
     def _dtw_offsets(levels):
@@ -800,9 +831,9 @@ class Context:
 
 
 def mapper_context(device=0):
-    """A Context for the entry points that need no model (xb_map_templates, xb_ctc_targets, xb_ub_tally): xb_ctx_create
-    wants a model geometry, so this is the smallest one it accepts -- 4 bases, 32 features, one chunk of 200 samples --
-    and no weights are ever loaded into it."""
+    """A Context for the entry points that need no model (xb_map_templates, xb_ctc_targets, xb_ub_tally, xb_barcode_dist):
+    xb_ctx_create wants a model geometry, so this is the smallest one it accepts -- 4 bases, 32 features, one chunk of 200
+    samples -- and no weights are ever loaded into it."""
     return Context(device, 4, 3, 32, 19, 5, 5.0, 2.0, 200, 1)
 
 

@@ -223,6 +223,8 @@ class TemplateAligner:
         sequences = list(sequences)
         out = [None] * len(sequences)
         todo = [i for i, s in enumerate(sequences) if 0 < len(s) <= MAX_ROW]
+        if self.ub_report is not None:              # every read counts in the report's denominators, mapped or not
+            self.ub_report.shown.update(read_ids if read_ids is not None else [str(i) for i in range(len(sequences))])
         if len(todo) < sum(1 for s in sequences if s):
             from logging import getLogger
             getLogger("bonito").warning("> %d calls longer than the mapper's %d letters are left unmapped",

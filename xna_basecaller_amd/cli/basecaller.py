@@ -11,7 +11,8 @@ and a library with unnatural positions under a model that cannot call them; --re
 TEMPLATE LIBRARY on the device (aligner.py: exhaustive alignment, this package's own contract, not minimap2) and, as in
 the reference, makes SAM the default output;
 --paf PATH (an extension) writes the mappings as PAF beside it; --ub-report PREFIX (an extension) tallies the mapped calls'
-per-position UB accuracy on the device (xb_ub_tally) and writes the reference's analyze_paf.py figures; under torchrun (WORLD_SIZE > 1) reads are sharded over the
+per-position UB accuracy on the device (xb_ub_tally) and writes the reference's analyze_paf.py figures, with --max-bc-dist N
+only of the calls that carry their template's barcode within N edits (xb_barcode_dist, analyze_paf.py -d); under torchrun (WORLD_SIZE > 1) reads are sharded over the
 ranks and gathered to rank 0 over RCCL before writing.  Extension: --qscores writes the Viterbi decode's device
 qualities (xb_decode_q) in place of the reference's placeholder 'O'; --ub-probs adds per-base probabilities of every
 letter outside A, C, G, T as `u<letter>:B:C` tags (xb_decode_ub); without them the output is unchanged.
@@ -162,6 +163,19 @@ def ub_report_refusal(args, world=1):
     return None
 
 
+def max_bc_dist_refusal(args):
+    """Why `--max-bc-dist` cannot run with these arguments (the message, without the "> " prefix), or None."""
+    if args.max_bc_dist is None:
+        return None
+    if not args.ub_report:
+        return "error: --max-bc-dist filters the reads of --ub-report by barcode distance; there is no report to filter"
+    if args.max_bc_dist < 0 or args.barcode_start < 0 or not 1 <= args.barcode_len <= 64 or not 0 <= args.barcode_relax <= 8:
+        return ("error: --max-bc-dist %d --barcode-start %d --barcode-len %d --barcode-relax %d: distance and start must not be "
+                "negative, the barcode has 1 .. 64 letters, 0 .. 8 windows to either side"
+                % (args.max_bc_dist, args.barcode_start, args.barcode_len, args.barcode_relax))
+    return None
+
+
 def reader_procs(world=1):
     """Reader workers of this rank: the reference's 8 (cli/basecaller.py:107-111) when the host has them to give -- the cores
     this process may run on, divided by the ranks that share the node (LOCAL_WORLD_SIZE under torchrun, else the world size),
@@ -183,7 +197,7 @@ def main(args):
     # initialises HIP and starts runtime threads) is only joined once the pool exists.  Under torchrun every rank only
     # ever loads its own shard of the reads.
     rank, world = xdist.env_rank_world()
-    why = ub_report_refusal(args, world)
+    why = ub_report_refusal(args, world) or max_bc_dist_refusal(args)
     if why is not None:
         sys.stderr.write("> %s\n" % why)
         exit(1)
@@ -268,7 +282,10 @@ def main(args):
 
     if args.ub_report:                  # --ub-report (an extension): every mapper call's rows also go through xb_ub_tally
         from ..ubreport import Report
-        aligner.ub_report = Report(aligner.names, aligner.templates)
+        demux = None                    # --max-bc-dist: a mapped call counts only when it carries its template's barcode
+        if args.max_bc_dist is not None:
+            demux = (args.max_bc_dist, args.barcode_start, args.barcode_len, args.barcode_relax)
+        aligner.ub_report = Report(aligner.names, aligner.templates, demux=demux)
     if aligner is not None:             # every rank maps its own reads, before the gather
         from ..aligner import align_map
         results = align_map(aligner, results)
@@ -353,6 +370,12 @@ def argparser():
                         help="with --reference: per-position UB accuracy of the mapped calls, tallied on the device, as "
                              "PREFIX.csv, PREFIX-by_tar.csv, PREFIX-by_read.csv.gz and PREFIX-confusion_matrix.npy (the figures of "
                              "the reference's analyze_paf.py -p); not in the reference CLI")
+    parser.add_argument("--max-bc-dist", type=int, default=None,
+                        help="with --ub-report: count a mapped call only when its template's barcode lies within this many edits "
+                             "of the call (the reference's analyze_paf.py -d: 5 for POC, 8 for CPLX); the summary gains demux and align")
+    parser.add_argument("--barcode-start", type=int, default=25, help="with --max-bc-dist: where the barcode starts in every template")
+    parser.add_argument("--barcode-len", type=int, default=24, help="with --max-bc-dist: letters of the barcode (1 .. 64)")
+    parser.add_argument("--barcode-relax", type=int, default=3, help="with --max-bc-dist: windows tried to either side (0 .. 8)")
     parser.add_argument("--modified-bases", nargs="+")
     parser.add_argument("--modified-base-model")
     parser.add_argument("--read-ids")

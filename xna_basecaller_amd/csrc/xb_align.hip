@@ -87,7 +87,7 @@ extern "C" XB_API int xb_align_accuracy(const char *ref, int ref_len, const char
 // ---------------------------------------------------------------------------------------------------------------------
 // xb_map_templates: exhaustive local alignment of every called row against every template, both strands (contract: the
 // public header).  Two kernels.  xb_ctc_targets, the ctc-data verdict and label row of a mapped row, follows them, and
-// xb_ub_tally, the per-position UB accuracy tallies of a mapped row, follows that.
+// xb_ub_tally, the per-position UB accuracy tallies of a mapped row, follows that, and xb_barcode_dist, its barcode distance.
 //
 // Score pass: grid (read, template chunk), a workgroup stages its chunk's template codes and the read's codes in LDS once,
 // its waves take the (template, strand) pairs of the chunk in turn.  One wave runs one pair as a systolic array: the
@@ -690,6 +690,105 @@ __global__ __launch_bounds__(64) void ub_tally_kernel(const xb::UbTallyParams p)
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// xb_barcode_dist: the reference's get_barcode_match_score (utils.py:1387-1434) over the mapper's outputs.  One workgroup
+// of one wave per row.  The barcode B (at most 64 letters) and the stretch of the query the windows can touch (at most
+// bc_len + 2 relax = 80 letters from the first window's start) live in LDS, a byte per letter.
+//   masks     lane j keeps B[j] in a register; for every letter of the stretch one ballot of (B[j] == letter) is the bit
+//             mask of the barcode positions that letter matches: 80 ballots at most, a 64-bit word each, kept in LDS
+//   windows   lane w owns window lo + w and runs Myers' bit-vector recurrence (in Hyyro's form) for the GLOBAL distance
+//             over its letters: B is the pattern of one word, the vertical deltas start at +1 everywhere (D[j][0] = j) and a
+//             +1 is shifted into the horizontal deltas at every letter (D[0][k] = k); the score follows bit len(B) - 1.
+//             The 2 relax + 1 <= 17 windows run side by side, each step one letter of every window; a clipped window
+//             stops early under a predicate.
+//   winner    min over the lanes of (distance, window) packed in one int: the smallest distance, the lowest window.
+// No global scratch, no atomics; lane 0 writes the four integers.
+constexpr int BC_STRETCH = xb::BC_MAX_LEN + 2 * xb::BC_MAX_RELAX;
+
+__global__ __launch_bounds__(64) void barcode_dist_kernel(const xb::BarcodeDistParams p)
+{
+    __shared__ uint8_t Qs[BC_STRETCH];
+    __shared__ unsigned long long Eq[BC_STRETCH];
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const int t = p.tmpl[r];
+    if (t < 0 || t >= p.R) {                           // unmapped (the whole wave leaves)
+        if (lane == 0) { p.dist[r] = -1; p.start[r] = 0; p.end[r] = 0; p.obs_len[r] = 0; }
+        return;
+    }
+    int sl = p.seq_len[r];
+    sl = sl < 0 ? 0 : (sl > p.W ? p.W : sl);
+    const int tb = p.toff[t], L = p.toff[t + 1] - tb;
+    int r0 = p.r_st[r], q0 = p.q_st[r];
+    r0 = r0 < 0 ? 0 : (r0 > L ? L : r0);
+    q0 = q0 < 0 ? 0 : (q0 > sl ? sl : q0);
+    const bool minus = p.strand[r] < 0;
+    int start = q0 + p.bc_pos - r0;                     // q0 <= 4096, bc_pos <= 2^30: no overflow
+    start = start < 0 ? 0 : start;
+    const int lo = start - p.relax < 0 ? 0 : start - p.relax;
+    const int nwin = start + p.relax - lo + 1;          // 1 .. 2 relax + 1
+    // the barcode: lane j holds B[j], m letters in all
+    int m = L - p.bc_pos;
+    m = m < 0 ? 0 : (m > p.bc_len ? p.bc_len : m);
+    unsigned bj = 0x100u;                               // no byte
+    if (lane < m) {
+        bj = p.tletters[tb + p.bc_pos + lane];
+        if (bj >= 'a' && bj <= 'z') bj -= 32u;
+    }
+    // the stretch Q[lo, lo + ns): what window lo .. lo + nwin - 1 of bc_len letters can touch, clipped to the row
+    int ns = sl - lo;
+    ns = ns < 0 ? 0 : (ns > nwin - 1 + p.bc_len ? nwin - 1 + p.bc_len : ns);
+    const int8_t *row = p.seq + (size_t)r * p.W;
+    for (int k = lane; k < ns; k += 64) Qs[k] = (uint8_t)ub_query_letter(row, sl, lo + k, minus);
+    __syncthreads();
+    for (int k = 0; k < ns; ++k) {
+        const unsigned long long eq = __ballot(bj == (unsigned)Qs[k]);
+        if (lane == (k & 63)) Eq[k] = eq;
+    }
+    __syncthreads();
+    // lane w: window i = lo + w, obs = Q[i, i + len)
+    const bool mine = lane < nwin;
+    int len = sl - (lo + lane);
+    len = !mine || len < 0 ? 0 : (len > p.bc_len ? p.bc_len : len);
+    int len0 = sl - lo;                                // the first window is the longest
+    len0 = len0 < 0 ? 0 : (len0 > p.bc_len ? p.bc_len : len0);
+    int score = m;
+    if (m == 0) {
+        score = len;                                   // an empty barcode: every letter is an insertion
+    } else {
+        unsigned long long pv = ~0ull, mv = 0ull;
+        const unsigned long long top = 1ull << (m - 1);
+        for (int s = 0; s < len0; ++s) {
+            if (s < len) {
+                const unsigned long long eq = Eq[lane + s];     // lane + s < nwin - 1 + bc_len <= BC_STRETCH
+                const unsigned long long xv = eq | mv;
+                const unsigned long long xh = (((eq & pv) + pv) ^ pv) | eq;
+                unsigned long long ph = mv | ~(xh | pv);
+                unsigned long long mh = pv & xh;
+                score += (ph & top) ? 1 : ((mh & top) ? -1 : 0);
+                ph = (ph << 1) | 1ull;
+                mh <<= 1;
+                pv = mh | ~(xv | ph);
+                mv = ph & xv;
+            }
+        }
+    }
+    int key = mine ? score * 32 + lane : 0x7fffffff;   // score <= 64, lane <= 16
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const int other = __shfl_xor(key, d);
+        key = other < key ? other : key;
+    }
+    if (lane == 0) {
+        const int w = key & 31, i = lo + w;
+        int ol = sl - i;
+        ol = ol < 0 ? 0 : (ol > p.bc_len ? p.bc_len : ol);
+        p.dist[r] = key >> 5;
+        p.start[r] = i;
+        p.end[r] = i + p.bc_len;
+        p.obs_len[r] = ol;
+    }
+}
+
 }  // namespace
 
 namespace xb {
@@ -735,6 +834,12 @@ hipError_t launch_ctc_targets(const CtcTargetParams &p, hipStream_t stream)
 hipError_t launch_ub_tally(const UbTallyParams &p, hipStream_t stream)
 {
     hipLaunchKernelGGL(ub_tally_kernel, dim3(p.n), dim3(64), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_barcode_dist(const BarcodeDistParams &p, hipStream_t stream)
+{
+    hipLaunchKernelGGL(barcode_dist_kernel, dim3(p.n), dim3(64), 0, stream, p);
     return hipGetLastError();
 }
 

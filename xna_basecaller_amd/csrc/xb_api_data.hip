@@ -1,4 +1,4 @@
-// xb_api_data.hip -- the ctc-data tools of the C ABI: template mapping, ctc labels, the UB tally, DTW segmentation, spliced
+// xb_api_data.hip -- the ctc-data tools of the C ABI: template mapping, ctc labels, the UB tally, the barcode distance, DTW segmentation, spliced
 // augmentation and synthetic spiking.  Each has a _dev form on device pointers and a host-pointer form that stages through xb_ctx::staging.
 #include "xb_ctx.h"
 
@@ -99,13 +99,15 @@ int map_library(xb_ctx *ctx, const char *who, int n, int W, const char *template
         }
         chunks.push_back(R);
         const size_t a_off = m.off_at(total), a_chunk = a_off + sizeof(int32_t) * (R + 1);     // what toff() / chunk_first() read
+        const size_t a_letters = a_chunk + sizeof(int32_t) * chunks.size();                    // what tletters() reads
         m.lib.clear();                                                  // no image while it is being replaced
-        if (int rc = grow(ctx, &m.image, a_chunk + sizeof(int32_t) * chunks.size())) return rc;
+        if (int rc = grow(ctx, &m.image, a_letters + total)) return rc;
         XB_HIP(ctx, hipStreamSynchronize(ctx->stream));
         uint8_t *img = static_cast<uint8_t *>(m.image.p);
         XB_HIP(ctx, hipMemcpy(img, codes.data(), total, hipMemcpyHostToDevice));
         XB_HIP(ctx, hipMemcpy(img + a_off, offsets, sizeof(int32_t) * (R + 1), hipMemcpyHostToDevice));
         XB_HIP(ctx, hipMemcpy(img + a_chunk, chunks.data(), sizeof(int32_t) * chunks.size(), hipMemcpyHostToDevice));
+        XB_HIP(ctx, hipMemcpy(img + a_letters, templates, total, hipMemcpyHostToDevice));
         m.lib.assign(templates, templates + total);
         m.off.assign(offsets, offsets + R + 1);
         m.Lmax = *lmax;
@@ -441,6 +443,102 @@ XB_API int xb_ub_tally(xb_ctx *ctx, const int8_t *seq, const int32_t *seq_len, i
     XB_HIP(ctx, hipMemcpyAsync(reads, o.reads, b_reads, hipMemcpyDeviceToHost, ctx->stream));
     XB_HIP(ctx, hipMemcpyAsync(err, o.err, b_err, hipMemcpyDeviceToHost, ctx->stream));
     XB_HIP(ctx, hipMemcpyAsync(cm, o.cm, b_cm, hipMemcpyDeviceToHost, ctx->stream));
+    return xb_synchronize(ctx);
+}
+
+// ---- barcode distance of mapped rows (xb_barcode_dist) ------------------------------------------------------------------
+namespace {
+
+struct BcIn {
+    const int8_t *seq; const int32_t *seq_len, *tmpl; const int8_t *strand; const int32_t *q_st, *r_st;
+};
+struct BcOut {
+    int32_t *dist, *start, *end, *obs_len;
+};
+struct BcRule {
+    int bc_pos, bc_len, relax;
+};
+
+bool bc_complete(const BcIn &i, const BcOut &o)
+{
+    return i.seq && i.seq_len && i.tmpl && i.strand && i.q_st && i.r_st && o.dist && o.start && o.end && o.obs_len;
+}
+
+// the limits of the contract, before anything is staged or launched
+int bc_check(xb_ctx *ctx, const BcRule &rule)
+{
+    if (rule.bc_pos < 0 || rule.bc_pos > xb::BC_MAX_POS || rule.bc_len < 1 || rule.bc_len > xb::BC_MAX_LEN || rule.relax < 0 ||
+        rule.relax > xb::BC_MAX_RELAX)
+        return fail(ctx, XB_ERR_INVALID, "xb_barcode_dist: bc_pos = %d, bc_len = %d, relax = %d; need 0 <= bc_pos <= %d, 1 <= bc_len <= %d, "
+                    "0 <= relax <= %d", rule.bc_pos, rule.bc_len, rule.relax, xb::BC_MAX_POS, xb::BC_MAX_LEN, xb::BC_MAX_RELAX);
+    return XB_OK;
+}
+
+// validation, the library's device image, the launch: i and o are device pointers
+int bc_run(xb_ctx *ctx, const BcIn &i, int n, int W, const char *templates, const int32_t *offsets, int R, const BcRule &rule,
+           const BcOut &o)
+{
+    if (int rc = bc_check(ctx, rule)) return rc;
+    int Lmax = 0;
+    if (int rc = map_library(ctx, "xb_barcode_dist", n, W, templates, offsets, R, nullptr, &Lmax)) return rc;
+    xb::BarcodeDistParams p{};
+    p.seq = i.seq; p.seq_len = i.seq_len; p.n = n; p.W = W;
+    p.tmpl = i.tmpl; p.strand = i.strand; p.q_st = i.q_st; p.r_st = i.r_st;
+    p.tletters = ctx->map.tletters(); p.toff = ctx->map.toff();
+    p.R = R;
+    p.bc_pos = rule.bc_pos; p.bc_len = rule.bc_len; p.relax = rule.relax;
+    p.dist = o.dist; p.start = o.start; p.end = o.end; p.obs_len = o.obs_len;
+    XB_HIP(ctx, xb::launch_barcode_dist(p, ctx->stream));
+    return XB_OK;
+}
+
+}  // namespace
+
+XB_API int xb_barcode_dist_dev(xb_ctx *ctx, const int8_t *d_seq, const int32_t *d_seq_len, int n, int W, const char *templates,
+                               const int32_t *offsets, int R, const int32_t *d_tmpl, const int8_t *d_strand, const int32_t *d_q_st,
+                               const int32_t *d_r_st, int bc_pos, int bc_len, int relax, int32_t *d_bc_dist, int32_t *d_bc_start,
+                               int32_t *d_bc_end, int32_t *d_bc_obs_len)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    const BcIn i = {d_seq, d_seq_len, d_tmpl, d_strand, d_q_st, d_r_st};
+    const BcOut o = {d_bc_dist, d_bc_start, d_bc_end, d_bc_obs_len};
+    if (!bc_complete(i, o)) return fail(ctx, XB_ERR_INVALID, "xb_barcode_dist: null device pointer");
+    if (int rc = enter(ctx, true)) return rc;
+    return bc_run(ctx, i, n, W, templates, offsets, R, {bc_pos, bc_len, relax}, o);
+}
+
+XB_API int xb_barcode_dist(xb_ctx *ctx, const int8_t *seq, const int32_t *seq_len, int n, int W, const char *templates,
+                           const int32_t *offsets, int R, const int32_t *tmpl, const int8_t *strand, const int32_t *q_st,
+                           const int32_t *r_st, int bc_pos, int bc_len, int relax, int32_t *bc_dist, int32_t *bc_start, int32_t *bc_end,
+                           int32_t *bc_obs_len)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    const BcIn h = {seq, seq_len, tmpl, strand, q_st, r_st};
+    const BcOut ho = {bc_dist, bc_start, bc_end, bc_obs_len};
+    if (!bc_complete(h, ho)) return fail(ctx, XB_ERR_INVALID, "xb_barcode_dist: null host pointer");
+    if (n < 1 || W < 1 || W > xb::MAP_MAX_ROW || !offsets || R < 1 || offsets[0] != 0)
+        return fail(ctx, XB_ERR_INVALID, "xb_barcode_dist: n = %d rows of width %d, %d templates; need n >= 1, 1 <= W <= %d, R >= 1", n, W, R,
+                    xb::MAP_MAX_ROW);
+    if (int rc = bc_check(ctx, {bc_pos, bc_len, relax})) return rc;
+    int Lmax = 0;
+    if (int rc = library_extent(ctx, "xb_barcode_dist", templates, offsets, R, &Lmax)) return rc;
+    if (int rc = enter(ctx, false)) return rc;
+    const size_t N = (size_t)n;
+    if (N * W > ((size_t)2 << 30)) return fail(ctx, XB_ERR_INVALID, "xb_barcode_dist: %d rows of width %d in one call; split the batch", n, W);
+    Staging st{ctx};
+    Staging::Piece<int32_t> i32[8];                     // seq_len, tmpl, q_st, r_st | bc_dist, bc_start, bc_end, bc_obs_len
+    for (auto &piece : i32) piece = st.take<int32_t>(N);
+    const auto d_strand = st.take<int8_t>(N), d_seq = st.take<int8_t>(N * W);
+    if (int rc = st.ready()) return rc;
+    const int32_t *const src[4] = {seq_len, tmpl, q_st, r_st};
+    for (int k = 0; k < 4; ++k) XB_HIP(ctx, hipMemcpyAsync(i32[k], src[k], N * 4, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(d_strand, strand, N, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(d_seq, seq, N * W, hipMemcpyHostToDevice, ctx->stream));
+    const BcIn d = {d_seq, i32[0], i32[1], d_strand, i32[2], i32[3]};
+    const BcOut o = {i32[4], i32[5], i32[6], i32[7]};
+    if (int rc = bc_run(ctx, d, n, W, templates, offsets, R, {bc_pos, bc_len, relax}, o)) return rc;
+    int32_t *const dst[4] = {bc_dist, bc_start, bc_end, bc_obs_len};
+    for (int k = 0; k < 4; ++k) XB_HIP(ctx, hipMemcpyAsync(dst[k], i32[4 + k], N * 4, hipMemcpyDeviceToHost, ctx->stream));
     return xb_synchronize(ctx);
 }
 

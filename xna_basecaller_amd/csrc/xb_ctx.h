@@ -190,11 +190,13 @@ struct xb_ctx {
         std::vector<int32_t> off;
         int Lmax = 0, nchunks = 0;
         DevBuf image, partial, scratch;
-        // the image's layout: codes | offsets, 16-byte aligned | the first template of every chunk and the count of templates
+        // the image's layout: codes | offsets, 16-byte aligned | the first template of every chunk and the count of templates |
+        // the letters as they were passed in (xb_barcode_dist compares bytes, not codes)
         static size_t off_at(size_t total) { return (total + 15) & ~(size_t)15; }
         const uint8_t *tcodes() const { return static_cast<const uint8_t *>(image.p); }
         const int32_t *toff() const { return reinterpret_cast<const int32_t *>(tcodes() + off_at(lib.size())); }
         const int32_t *chunk_first() const { return toff() + off.size(); }
+        const uint8_t *tletters() const { return reinterpret_cast<const uint8_t *>(chunk_first() + nchunks + 1); }
     } map;
 
     // DTW segmentation (xb_dtw_segment): the choice-bit scratch of the launches in flight and the chunks' level offsets on

@@ -278,6 +278,25 @@ struct UbTallyParams {
 };
 hipError_t launch_ub_tally(const UbTallyParams &p, hipStream_t stream);
 
+// xb_barcode_dist: per mapped row the edit distance of the template's barcode to the row's letters where the mapping puts
+// them, over 2 relax + 1 windows (the contract is in the public header).  One wave per row, a lane per window.
+constexpr int BC_MAX_LEN = 64;              // letters of a barcode: one bit each of a 64-bit word
+constexpr int BC_MAX_RELAX = 8;             // windows to either side of the expected start
+constexpr int BC_MAX_POS = 1 << 30;         // bc_pos: start + relax + bc_len stays an int32
+struct BarcodeDistParams {
+    const int8_t *seq;           // (n, W) ASCII rows, left-packed
+    const int32_t *seq_len;      // (n)
+    int n, W;
+    const int32_t *tmpl, *q_st, *r_st;   // (n) the mapper's outputs
+    const int8_t *strand;        // (n)
+    const uint8_t *tletters;     // the library image: the letters as passed in, and the offsets
+    const int32_t *toff;
+    int R;
+    int bc_pos, bc_len, relax;
+    int32_t *dist, *start, *end, *obs_len;   // (n)
+};
+hipError_t launch_barcode_dist(const BarcodeDistParams &p, hipStream_t stream);
+
 // ---------------------------------------------------------------- DTW signal segmentation (xb_dtw.hip)
 // xb_dtw_segment: every signal chunk against the expected levels of its reference by dynamic time warping (the contract is
 // in the public header).  One wave per chunk; the columns lie across the lanes, cols consecutive columns per lane, in

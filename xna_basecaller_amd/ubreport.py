@@ -6,8 +6,10 @@ the accumulators reads / err / cm).  Pure host code; the per-read walk, the poli
                  fdr, fpr and the four outcomes -- quotients of the device's integer counts
   per position   100 * err / reads per (template, strand), labelled by distance to the UB (analyze_paf.py:111-190)
   summary        analyze_paf.py:904-1022: means over reads and over labelled positions, specificity, precision, F1, F2
+  demux          analyze_paf.py:623-643 and :977-983 (`-d`): rows whose barcode distance (xb_barcode_dist, on the device) is over
+                 the limit are dropped before anything is tallied; the summary gains demux and align
 Departures from the reference are listed in INTEGRATION.md: the library FASTA stands in for XNA_refs, a template without a UB
-site is of type PC, and there is no barcode / demux stage.
+site is of type PC, and the barcode's place in a template comes from the caller, not from XNA_refs.
 """
 import gzip
 import io
@@ -25,6 +27,7 @@ MAX_DIST = 10                  # dist_ub_d-1 .. d-10, then d-11+
 SUMMARY_DIST = 4               # err_ub_d_1 .. 4 in the summary row
 BY_TAR_COLUMNS = ("percent_match", "target_acc", "read_acc", "ub_acc", "ub_area_acc", "non_ub_area_acc", "fpr", "ub_area_acc_plus")
 STRAND_NAMES = ("F", "R")
+BARCODE_COLUMNS = ("barcode_distance", "barcode_start", "barcode_end")
 
 
 def ub_positions(template):
@@ -116,9 +119,11 @@ def _mean(values):
 
 
 class Report:
-    """Collects the reads of a run: per mapped read its identity and counts, and the accumulators."""
+    """Collects the reads of a run: per mapped read its identity and counts, and the accumulators.  demux: None, or
+    (max_dist, bc_pos, bc_len, relax) -- the reference's `-d`: a row counts only when the barcode of its template lies within
+    max_dist edits of the read where the mapping puts it (xb_barcode_dist)."""
 
-    def __init__(self, names, templates):
+    def __init__(self, names, templates, demux=None):
         from ._lib import UbAccumulators
         self.names, self.templates = list(names), list(templates)
         self.offsets = np.zeros(len(self.templates) + 1, np.int32)
@@ -128,9 +133,29 @@ class Report:
         self.kind = ["XNA" if ub_positions(t) else "PC" for t in self.templates]
         self.read_ids, self.tmpl, self.strand, self.counts = [], [], [], []
         self.ral, self.mlen, self.blen = [], [], []
+        self.demux = None if demux is None else tuple(int(v) for v in demux)
+        self.barcode = []                         # per recorded row (distance, start, end), with demux only
+        # the denominators of demux / align: every read id shown (n_reads overrides their number: the reads on file),
+        # those that were mapped at all, those left after the barcode filter
+        self.shown, self.aligned, self.demuxed, self.n_reads = set(), set(), set(), None
 
-    def add(self, ctx, rows, lens, got, read_ids):
-        """The rows of one mapper call through xb_ub_tally on ctx; records every mapped row."""
+    def barcodes(self, ctx, rows, lens, got):
+        """xb_barcode_dist on ctx over the rows of one mapper call with this report's demux setting."""
+        _, bc_pos, bc_len, relax = self.demux
+        return ctx.barcode_dist(rows, lens, got, self.library, self.offsets, bc_pos, bc_len, relax)
+
+    def add(self, ctx, rows, lens, got, read_ids, barcodes=None):
+        """The rows of one mapper call through xb_ub_tally on ctx; records every mapped row.  With demux the rows go through
+        xb_barcode_dist first (or `barcodes`, what it returned for them earlier) and a row over the limit is passed on as
+        unmapped: it adds nothing."""
+        self.shown.update(read_ids)
+        if self.demux is not None:
+            bc = self.barcodes(ctx, rows, lens, got) if barcodes is None else barcodes
+            dist = np.asarray(bc["bc_dist"])
+            fail = (dist < 0) | (dist > self.demux[0])
+            self.aligned.update(rid for rid, t in zip(read_ids, got["tmpl"]) if int(t) >= 0)
+            self.demuxed.update(rid for rid, f in zip(read_ids, fail) if not f)
+            got = dict(got, tmpl=np.where(fail, -1, got["tmpl"]).astype(np.int32))
         counts, self.acc = ctx.ub_tally(rows, lens, got, self.library, self.offsets, self.acc)
         for k, rid in enumerate(read_ids):
             t = int(got["tmpl"][k])
@@ -145,6 +170,8 @@ class Report:
             self.ral.append(int(got["q_en"][k]) - int(got["q_st"][k]))
             self.mlen.append(int((ops == ord("=")).sum()))
             self.blen.append(n_ops)
+            if self.demux is not None:
+                self.barcode.append((int(bc["bc_dist"][k]), int(bc["bc_start"][k]), int(bc["bc_end"][k])))
 
     # ---- the figures ----
     def table(self):
@@ -158,6 +185,9 @@ class Report:
                "percent_match": _div(np.asarray(self.mlen, np.int64), np.asarray(self.blen, np.int64)).reshape(n)}
         out.update({k: counts[:, i] for i, k in enumerate(COUNTS)})
         out.update(per_read_metrics(counts, np.asarray(self.ral, np.int64).reshape(n), tl))
+        if self.demux is not None:
+            bc = np.asarray(self.barcode, np.int64).reshape(n, len(BARCODE_COLUMNS))
+            out.update({k: bc[:, i] for i, k in enumerate(BARCODE_COLUMNS)})
         return out
 
     def summary(self):
@@ -177,6 +207,10 @@ class Report:
             row["err_ub_d_%d" % d] = err("dist_ub_d-%d" % d)
         row["acc_xna"] = 100 * _mean(tab["percent_match"][xna])
         row["acc_pc"] = 100 * _mean(tab["percent_match"][pc]) if pc.any() else float("nan")
+        if self.demux is not None:
+            total = len(self.shown) if self.n_reads is None else self.n_reads
+            row["demux"] = float(100 * _div(len(self.demuxed), total))
+            row["align"] = float(100 * _div(len(self.aligned), total))
         row["specificity"] = 100 * (1 - _mean(tab["fpr"]))
         row["precision"] = 100 * (1 - _mean(tab["fdr"]))
         tp, fn, fp, tn = (int(tab[k].sum()) for k in ("true_pos", "false_neg", "false_pos", "true_neg"))
@@ -212,7 +246,7 @@ class Report:
         if by_read:
             paths.append(prefix + "-by_read.csv.gz")
             tab = self.table()
-            cols = ("percent_match",) + COUNTS + METRICS
+            cols = ("percent_match",) + COUNTS + METRICS + (BARCODE_COLUMNS if self.demux is not None else ())
             text = io.StringIO()
             text.write("read_id,target_id,strand,type," + ",".join(cols) + "\n")
             for k, rid in enumerate(self.read_ids):
@@ -323,8 +357,9 @@ def read_sequences(path):
     return seqs
 
 
-def tally_paf(report, ctx, alignments, sequences, batch=512):
-    """The PAF rows `alignments` (read_paf) with the reads `sequences` through xb_ub_tally on ctx into `report`."""
+def _paf_batches(report, alignments, sequences, batch):
+    """The PAF rows `alignments` with the reads `sequences` as the mapper would have left them, `batch` at a time: (rows, lens,
+    got, read ids)."""
     index = {n: t for t, n in enumerate(report.names)}
     lmax = int(np.diff(report.offsets).max())
     for at in range(0, len(alignments), batch):
@@ -359,4 +394,48 @@ def tally_paf(report, ctx, alignments, sequences, batch=512):
             # the mapper's coordinates on the aligned strand
             got["q_st"][k] = a["q_st"] if a["strand"] > 0 else len(s) - a["q_en"]
             got["q_en"][k] = a["q_en"] if a["strand"] > 0 else len(s) - a["q_st"]
-        report.add(ctx, rows, np.array([len(s) for s in seqs], np.int32), got, [a["read_id"] for a in take])
+        yield rows, np.array([len(s) for s in seqs], np.int32), got, take
+
+
+BARCODE_KEYS = ("bc_dist", "bc_start", "bc_end", "bc_obs_len")
+
+
+def tally_paf(report, ctx, alignments, sequences, batch=512):
+    """The PAF rows `alignments` (read_paf) with the reads `sequences` through xb_ub_tally on ctx into `report`.  For a report
+    with demux the rows are those demux_paf kept, each with its "barcode"; rows without one get the first step of the filter
+    alone (the limit), not the second (the read's smallest distance)."""
+    for rows, lens, got, take in _paf_batches(report, alignments, sequences, batch):
+        bc = None
+        if report.demux is not None and all("barcode" in a for a in take):
+            bc = {k: np.array([a["barcode"][i] for a in take], np.int32) for i, k in enumerate(BARCODE_KEYS)}
+        report.add(ctx, rows, lens, got, [a["read_id"] for a in take], barcodes=bc)
+
+
+def paf_barcodes(report, ctx, alignments, sequences, batch=512):
+    """xb_barcode_dist over every PAF row: per alignment the tuple (bc_dist, bc_start, bc_end, bc_obs_len)."""
+    out = []
+    for rows, lens, got, _ in _paf_batches(report, alignments, sequences, batch):
+        bc = report.barcodes(ctx, rows, lens, got)
+        out.extend(zip(*[bc[k].tolist() for k in BARCODE_KEYS]))
+    return out
+
+
+def demux_filter(dist, read_ids, max_dist):
+    """analyze_paf.py:628-632 over alignment rows: those with 0 <= dist <= max_dist, and of those, per read id, the rows whose
+    distance equals that read's smallest; ties stay, all of them.  Returns the indices kept, ascending."""
+    ok = [k for k, d in enumerate(dist) if 0 <= int(d) <= max_dist]
+    low = {}
+    for k in ok:
+        low[read_ids[k]] = min(low.get(read_ids[k], int(dist[k])), int(dist[k]))
+    return [k for k in ok if int(dist[k]) == low[read_ids[k]]]
+
+
+def demux_paf(report, ctx, alignments, sequences, batch=512):
+    """The first pass of `analyze -d`: distances for all alignments, the two-step filter, and the report's denominators (the
+    reads on file, the read ids of the PAF, those left).  Returns the alignments kept, each with its "barcode", for tally_paf."""
+    report.n_reads = len(sequences)
+    report.aligned = {a["read_id"] for a in alignments}
+    bc = paf_barcodes(report, ctx, alignments, sequences, batch)
+    keep = demux_filter([b[0] for b in bc], [a["read_id"] for a in alignments], report.demux[0])
+    report.demuxed = {alignments[k]["read_id"] for k in keep}
+    return [dict(alignments[k], barcode=bc[k]) for k in keep]
