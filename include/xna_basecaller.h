@@ -731,6 +731,46 @@ XB_API int xb_spike_chunks_dev(xb_ctx *ctx, const float *d_signal, const uint8_t
                                int variable_noise, float *d_out_signal, uint8_t *d_out_targets, int32_t *d_spiked, double *d_med,
                                double *d_mad, int8_t *d_status);
 
+/* ---- XNA fully synthetic chunks of ctc-data (an extension of the device path: `synth`) ------------------------------------
+ * The reference's `bonito train --spike --fully_synth` (the -Z runs of its training recipe) does not paste windows: it throws
+ * the chunk's signal away and synthesises all of it from the spiked labels and the breakpoints.  xb_synth_chunks restates
+ * spike_read(..., fully_synth=True, equal_kmer_reps=False, mix_ubs=True, legacy_pos=False) -> sim_target -> sim_signals(append=
+ * True) (spike_chunks.py:217-297) and is pinned to the reference (tests/golden/synth.json); the draws are this library's own:
+ * parity unpinned.  The kernel is bit-exact against a CPU restatement of the contract (tests/synth_ref.py).  The arguments are
+ * xb_spike_chunks', the model is the one xb_spike_model uploaded; mix, G, bounded, unit, the streams, PPND16 and its logarithm
+ * are those of the section above.  What differs:
+ *   draws      s = 0: proportion, positions and the UB shuffle, unchanged.  s = 1: the squiggle.  s = 2 serves the WHOLE chunk:
+ *              k = 0 the shift choice, k = 1 the variable noise std, k = 2 + i the level noise of chunk sample i, k = 2 + total +
+ *              i its added noise, total = min(breakpoints[length - 1], N).
+ *   labels     positions and UBs are chosen as in xb_spike_chunks; the spiked row is the input row with the UB written at every
+ *              position (ubs_mask 0: nothing is written, the chunk is re-synthesised DNA).
+ *   k-mers     one per base i of the SPIKED row plus its tail (ATATA, or TATAT when the last letter is A).  The first base, in
+ *              base order, whose k-mer has a NaN mean ends the chunk: out_signal / out_targets are the inputs, spiked = 0, status
+ *              = 2, mad = NaN and med = that k-mer's table index.  The k-mers of the original row are never looked up.
+ *   med, mad   as xb_spike_chunks (100 squiggle samples per base, exact selection, * 1.4826 + 2^-23), over the SPIKED row's
+ *              k-mers (:223-224).
+ *   samples    base b covers the samples breakpoints[b - 1] .. breakpoints[b] - 1 (breakpoints[-1] = 0); a base with no sample
+ *              draws nothing.  Sample i < total becomes ((mean + level) [+ noise] - med) / mad of its base's k-mer, rounded ONCE
+ *              to float32; level and noise exactly as in xb_spike_chunks (uniform, or PPND16(phi[r][0] + unit * phi[r][1]) * s),
+ *              r and sigma drawn once per chunk.  Samples i >= total keep the input's value (the reference returns a shorter
+ *              array there).
+ *   outputs    spiked: the number of positions; it may be 0 (no base was free) with the chunk still synthesised.  A chunk of
+ *              length 0: the inputs, spiked = med = mad = status = 0.
+ * Limits, messages (under the name xb_synth_chunks), XB_ERR_STATE without a model and the host / _dev conventions are those of
+ * xb_spike_chunks.  The _dev form clamps lengths, labels and breakpoints so that no access leaves the rows whatever they hold;
+ * the values of rows the host form would refuse are unspecified.
+ */
+XB_API int xb_synth_chunks(xb_ctx *ctx, const float *signal, const uint8_t *targets, const int32_t *lengths,
+                           const uint16_t *breakpoints, int n, int N, int Lt, int64_t first_index, uint64_t seed, int ubs_mask,
+                           double prop, double var_prop, int pad, int dist_rows, const double *phi, double noise_std,
+                           int variable_noise, float *out_signal, uint8_t *out_targets, int32_t *spiked, double *med, double *mad,
+                           int8_t *status);
+XB_API int xb_synth_chunks_dev(xb_ctx *ctx, const float *d_signal, const uint8_t *d_targets, const int32_t *d_lengths,
+                               const uint16_t *d_breakpoints, int n, int N, int Lt, int64_t first_index, uint64_t seed, int ubs_mask,
+                               double prop, double var_prop, int pad, int dist_rows, const double *phi, double noise_std,
+                               int variable_noise, float *d_out_signal, uint8_t *d_out_targets, int32_t *d_spiked, double *d_med,
+                               double *d_mad, int8_t *d_status);
+
 /* ---- introspection / measurement ---------------------------------------------------------- */
 
 enum { XB_STAGE_CONV = 0, XB_STAGE_LSTM_IN = 1, XB_STAGE_LSTM_REC = 2, XB_STAGE_LINEAR = 3,

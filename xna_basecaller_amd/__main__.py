@@ -3,11 +3,12 @@
 `src/tools/dtw_segmentation.py CTC_DATA`; `... analyze LIB.fasta CALLS.paf -R CALLS.fastq` == the reference's
 `src/tools/analyze_paf.py -p`; `... splice DNA_CTC XNA_CTC OUT --ubs XY --prop-ubs P` == the XNA spliced augmentation of
 `bonito train -m per_kmer` (bonito/stitch_chunks.py) written out as ctc-data; `... spike CTC OUT -r KMER.model --ubs XY
---prop-ubs P` == the synthetic spiking of `bonito train --spike` (bonito/spike_chunks.py), likewise."""
+--prop-ubs P` == the synthetic spiking of `bonito train --spike` (bonito/spike_chunks.py), likewise; `... synth CTC OUT -r
+KMER.model --ubs XY --prop-ubs P` == the fully synthetic chunks of `bonito train --spike --fully_synth`, likewise."""
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 
 from . import __version__
-from .cli import analyze, basecaller, evaluate, segment, spike, splice
+from .cli import analyze, basecaller, evaluate, segment, spike, splice, synth
 
 
 def main():
@@ -28,6 +29,8 @@ def main():
     p.set_defaults(func=splice.main)
     p = sub.add_parser("spike", parents=[spike.argparser()])
     p.set_defaults(func=spike.main)
+    p = sub.add_parser("synth", parents=[synth.argparser()])
+    p.set_defaults(func=synth.main)
     args = parser.parse_args()
     args.func(args)
 

@@ -33,7 +33,7 @@ EXPORTS = [
     "xb_map_templates", "xb_map_templates_dev", "xb_ctc_targets", "xb_ctc_targets_dev", "xb_ctc_chunks",
     "xb_ub_tally", "xb_ub_tally_dev", "xb_barcode_dist", "xb_barcode_dist_dev", "xb_dtw_segment", "xb_dtw_segment_dev", "xb_dtw_scratch_bytes",
     "xb_splice_library", "xb_splice_chunks", "xb_splice_chunks_dev",
-    "xb_spike_model", "xb_spike_chunks", "xb_spike_chunks_dev",
+    "xb_spike_model", "xb_spike_chunks", "xb_spike_chunks_dev", "xb_synth_chunks", "xb_synth_chunks_dev",
 ]
 XB_COMM_ID_BYTES = 128
 # xb_status (include/xna_basecaller.h)
@@ -144,6 +144,8 @@ def load():
     lib.xb_spike_model.argtypes = [vp, vp, vp, C.c_int64]
     lib.xb_spike_chunks.argtypes = [vp] * 5 + [ip, ip, ip, C.c_int64, C.c_uint64, ip, db, db, ip, ip, vp, db, ip] + [vp] * 6
     lib.xb_spike_chunks_dev.argtypes = lib.xb_spike_chunks.argtypes
+    lib.xb_synth_chunks.argtypes = lib.xb_spike_chunks.argtypes
+    lib.xb_synth_chunks_dev.argtypes = lib.xb_spike_chunks.argtypes
     lib.xb_result_stream.argtypes = [vp]
     lib.xb_result_stream.restype = C.c_void_p
     lib.xb_set_profiling.argtypes = [vp, ip]
@@ -738,39 +740,58 @@ class Context:
             raise ValueError("spike_chunks: a distribution table of %d rows, dist_rows + 1 = %d expected" % (phi.shape[0], dist_rows + 1))
         return phi
 
-    def spike_chunks(self, signal, targets, lengths, breakpoints, first_index, seed, ubs_mask, prop, var_prop=0.0, pad=5,
-                     dist_rows=0, phi=None, noise_std=0.0, variable_noise=False):
-        """xb_spike_chunks: signal (n, N) fp32, targets (n, Lt) uint8, lengths (n), breakpoints (n, Lt) uint16, phi
-        (dist_rows + 1, 2) float64 -> (signal (n, N) float32, targets (n, Lt) uint8, spiked (n,) int32, med (n,), mad (n,)
-        float64, status (n,) int8)."""
+    def _spike_call(self, fn, name, signal, targets, lengths, breakpoints, first_index, seed, ubs_mask, prop, var_prop, pad, dist_rows,
+                    phi, noise_std, variable_noise):
         signal = np.ascontiguousarray(signal, dtype=np.float32)
         targets = np.ascontiguousarray(targets, dtype=np.uint8)
         lengths = np.ascontiguousarray(lengths, dtype=np.int32)
         bk = np.ascontiguousarray(breakpoints, dtype=np.uint16)
         n, N = signal.shape
         if targets.ndim != 2 or targets.shape[0] != n or bk.shape != targets.shape or lengths.shape != (n,):
-            raise ValueError("spike_chunks: signal (n, N), targets (n, Lt), lengths (n), breakpoints (n, Lt) expected")
+            raise ValueError("%s: signal (n, N), targets (n, Lt), lengths (n), breakpoints (n, Lt) expected" % name)
         phi = self._spike_phi(phi, dist_rows)
         out, out_t = np.empty_like(signal), np.empty_like(targets)
         spiked, status = np.empty((n,), np.int32), np.empty((n,), np.int8)
         med, mad = np.empty((n,), np.float64), np.empty((n,), np.float64)
-        self._check(self.lib.xb_spike_chunks(self.h, signal.ctypes.data, targets.ctypes.data, lengths.ctypes.data, bk.ctypes.data,
-                                             n, N, targets.shape[1], int(first_index), int(seed) & (2 ** 64 - 1), int(ubs_mask),
-                                             float(prop), float(var_prop or 0.0), int(pad), int(dist_rows), phi.ctypes.data,
-                                             float(noise_std), int(bool(variable_noise)), out.ctypes.data, out_t.ctypes.data,
-                                             spiked.ctypes.data, med.ctypes.data, mad.ctypes.data, status.ctypes.data))
+        self._check(fn(self.h, signal.ctypes.data, targets.ctypes.data, lengths.ctypes.data, bk.ctypes.data, n, N, targets.shape[1],
+                       int(first_index), int(seed) & (2 ** 64 - 1), int(ubs_mask), float(prop), float(var_prop or 0.0), int(pad),
+                       int(dist_rows), phi.ctypes.data, float(noise_std), int(bool(variable_noise)), out.ctypes.data,
+                       out_t.ctypes.data, spiked.ctypes.data, med.ctypes.data, mad.ctypes.data, status.ctypes.data))
         return out, out_t, spiked, med, mad, status
 
-    def spike_chunks_dev(self, d_signal, d_targets, d_lengths, d_breakpoints, n, N, Lt, first_index, seed, ubs_mask, prop, var_prop,
-                         pad, dist_rows, phi, noise_std, variable_noise, d_out_signal, d_out_targets, d_spiked, d_med, d_mad,
-                         d_status):
-        """xb_spike_chunks_dev: device pointers but for `phi` (host); returns without waiting."""
+    def _spike_call_dev(self, fn, d_signal, d_targets, d_lengths, d_breakpoints, n, N, Lt, first_index, seed, ubs_mask, prop, var_prop,
+                        pad, dist_rows, phi, noise_std, variable_noise, d_out_signal, d_out_targets, d_spiked, d_med, d_mad, d_status):
         phi = self._spike_phi(phi, dist_rows)
-        self._check(self.lib.xb_spike_chunks_dev(self.h, _ptr(d_signal), _ptr(d_targets), _ptr(d_lengths), _ptr(d_breakpoints),
-                                                 int(n), int(N), int(Lt), int(first_index), int(seed) & (2 ** 64 - 1), int(ubs_mask),
-                                                 float(prop), float(var_prop or 0.0), int(pad), int(dist_rows), phi.ctypes.data,
-                                                 float(noise_std), int(bool(variable_noise)), _ptr(d_out_signal),
-                                                 _ptr(d_out_targets), _ptr(d_spiked), _ptr(d_med), _ptr(d_mad), _ptr(d_status)))
+        self._check(fn(self.h, _ptr(d_signal), _ptr(d_targets), _ptr(d_lengths), _ptr(d_breakpoints), int(n), int(N), int(Lt),
+                       int(first_index), int(seed) & (2 ** 64 - 1), int(ubs_mask), float(prop), float(var_prop or 0.0), int(pad),
+                       int(dist_rows), phi.ctypes.data, float(noise_std), int(bool(variable_noise)), _ptr(d_out_signal),
+                       _ptr(d_out_targets), _ptr(d_spiked), _ptr(d_med), _ptr(d_mad), _ptr(d_status)))
+
+    def spike_chunks(self, signal, targets, lengths, breakpoints, first_index, seed, ubs_mask, prop, var_prop=0.0, pad=5,
+                     dist_rows=0, phi=None, noise_std=0.0, variable_noise=False):
+        """xb_spike_chunks: signal (n, N) fp32, targets (n, Lt) uint8, lengths (n), breakpoints (n, Lt) uint16, phi
+        (dist_rows + 1, 2) float64 -> (signal (n, N) float32, targets (n, Lt) uint8, spiked (n,) int32, med (n,), mad (n,)
+        float64, status (n,) int8)."""
+        return self._spike_call(self.lib.xb_spike_chunks, "spike_chunks", signal, targets, lengths, breakpoints, first_index, seed,
+                                ubs_mask, prop, var_prop, pad, dist_rows, phi, noise_std, variable_noise)
+
+    def spike_chunks_dev(self, *args):
+        """xb_spike_chunks_dev(d_signal, d_targets, d_lengths, d_breakpoints, n, N, Lt, first_index, seed, ubs_mask, prop, var_prop,
+        pad, dist_rows, phi, noise_std, variable_noise, d_out_signal, d_out_targets, d_spiked, d_med, d_mad, d_status): device
+        pointers but for `phi` (host); returns without waiting."""
+        self._spike_call_dev(self.lib.xb_spike_chunks_dev, *args)
+
+    # ---- XNA fully synthetic chunks (xb_synth_chunks): xb_spike_chunks' arguments and model, the whole chunk synthesised ----------
+    def synth_chunks(self, signal, targets, lengths, breakpoints, first_index, seed, ubs_mask, prop, var_prop=0.0, pad=5,
+                     dist_rows=0, phi=None, noise_std=0.0, variable_noise=False):
+        """xb_synth_chunks: what spike_chunks takes and returns; every sample below a chunk's last breakpoint is synthesised
+        from the spiked labels, and `spiked` may be 0 with the chunk still synthesised."""
+        return self._spike_call(self.lib.xb_synth_chunks, "synth_chunks", signal, targets, lengths, breakpoints, first_index, seed,
+                                ubs_mask, prop, var_prop, pad, dist_rows, phi, noise_std, variable_noise)
+
+    def synth_chunks_dev(self, *args):
+        """xb_synth_chunks_dev: spike_chunks_dev's arguments; returns without waiting."""
+        self._spike_call_dev(self.lib.xb_synth_chunks_dev, *args)
 
     # ---- host pipeline: two batches in flight (xb_submit_chunks / xb_collect_chunks) ----------
     def submit_chunks(self, slot, signal, alphabet, qscale=1.0, qoffset=0.0, level=0):

@@ -1,11 +1,11 @@
 """
-`python -m xna_basecaller_amd spike CTC_DIR OUT_DIR -r KMER.model --ubs XY --prop-ubs 0.1`: the reference's synthetic XNA
-spiking (`bonito train --spike`, ub-bonito/bonito/spike_chunks.py, the default of its training recipe) as a tool of its own.
-At chosen bases the signal of the six k-mers around the base is replaced on the device (xb_spike_chunks) by a synthetic
-squiggle of the pore model's levels; OUT_DIR is a ctc-data directory that `evaluate`, `segment` and `bonito train
---directory` read.  Run on `splice`'s output it is the reference's mixed mode (--synth-prop-ubs): the unnatural bases already
-there are counted and kept clear of.  The argument names and defaults are `bonito train`'s (cli/train.py:218-273); its
---fully_synth is a command of its own here, `synth` (cli/synth.py), and stays refused under this one.
+`python -m xna_basecaller_amd synth CTC_DIR OUT_DIR -r KMER.model --ubs XY --prop-ubs 0.1`: the reference's fully synthetic XNA
+chunks (`bonito train --spike --fully_synth`, ub-bonito/bonito/spike_chunks.py: sim_target; the -Z runs of its training recipe)
+as a tool of its own.  The positions and unnatural bases are chosen as `spike` chooses them; then every chunk's signal is
+re-synthesised on the device (xb_synth_chunks) from its spiked labels and its breakpoints -- one k-mer per base, held for the
+samples the base had, normalised by the med / mad of the spiked labels' squiggle -- and nothing of the measured signal is
+kept.  OUT_DIR is a ctc-data directory that `evaluate`, `segment` and `bonito train --directory` read.  The arguments are
+`spike`'s, which are `bonito train`'s (cli/train.py:218-273).
 """
 import os
 import sys
@@ -18,10 +18,7 @@ from .. import spike as sk
 from .splice import load_ctc
 
 REFUSED = (   # attribute, its neutral value, why not
-    ("fully_synth", False, "--fully_synth (whole chunks of synthetic signal) is not offered here: it is the `synth` command, with "
-                           "these arguments"),
-    ("equal_kmer_reps", False, "--equal-kmer-reps is not offered: the data loader of the reference always spreads a window's "
-                               "samples as the breakpoints do"),
+    ("equal_kmer_reps", False, "--equal-kmer-reps is not offered: a base is held for the samples its breakpoints give it"),
     ("legacy_pos", False, "--legacy-pos (the count of positions of the first experiments) is not offered"),
 )
 
@@ -33,7 +30,7 @@ def main(args, make_run=None):
             raise SystemExit("> error: %s" % why)
     if args.ubs not in ("X", "Y", "XY", "N"):
         raise SystemExit("> error: --ubs takes X, Y, XY or N")
-    outputs = [os.path.join(args.out_dir, f) for f in sk.FILES + ("spike_stats.csv",)]
+    outputs = [os.path.join(args.out_dir, f) for f in sk.FILES + ("synth_stats.csv",)]
     if any(os.path.exists(f) for f in outputs) and not args.overwrite:
         raise SystemExit("> error: %s already holds output files; pass --overwrite to replace them" % args.out_dir)
     if not os.path.isfile(args.reference):
@@ -45,7 +42,7 @@ def main(args, make_run=None):
         model = sk.load_model(args.reference)
         t1 = time.perf_counter()
         timings = {}
-        chunks, targets, spiked, med, mad = sk.spike(*dna, model, ubs=args.ubs, prop_ubs=args.prop_ubs, var_prop_ubs=args.var_prop_ubs,
+        chunks, targets, spiked, med, mad = sk.synth(*dna, model, ubs=args.ubs, prop_ubs=args.prop_ubs, var_prop_ubs=args.var_prop_ubs,
                                                      pad=args.ub_pad, std_dist=args.std_dist, noise_std=args.noise_std,
                                                      variable_noise=args.variable_noise, seed=args.seed, batch=args.batchsize,
                                                      device=args.device, run=None if make_run is None else make_run(model),
@@ -56,36 +53,35 @@ def main(args, make_run=None):
     np.save(outputs[0], chunks.astype(np.float16))
     np.save(outputs[1], targets)
     np.save(outputs[2], np.asarray(dna[2]))
-    np.save(outputs[3], np.asarray(dna[3]))            # exact: a window keeps its length
+    np.save(outputs[3], np.asarray(dna[3]))            # exact: a base keeps its samples
     with open(outputs[4], "w") as fh:
         fh.write("index,spiked,med,mad\n")
         for c in range(len(spiked)):
             fh.write("%d,%d,%r,%r\n" % (c, int(spiked[c]), float(med[c]), float(mad[c])))
     sys.stderr.write("> model: %d k-mers, read in %.2f s\n" % (int(np.isfinite(model[0]).sum()), t1 - t0))
-    sys.stderr.write("> %d chunks in %.2f s (device calls %.2f s): %d positions spiked; %d chunks kept unchanged because no base "
-                     "was free\n" % (len(spiked), time.perf_counter() - t1, timings["device"], int(spiked.sum()),
-                                     int((spiked == 0).sum())))
+    sys.stderr.write("> %d chunks in %.2f s (device calls %.2f s): every chunk synthesised, %d positions spiked; %d chunks without "
+                     "an unnatural base because no base was free\n" % (len(spiked), time.perf_counter() - t1, timings["device"],
+                                                                       int(spiked.sum()), int((spiked == 0).sum())))
     return chunks, targets, spiked, med, mad
 
 
 def argparser():
     parser = ArgumentParser(formatter_class=ArgumentDefaultsHelpFormatter, add_help=False)
-    parser.add_argument("ctc_dir", help="ctc-data directory of the chunks to spike (with breakpoints.npy)")
+    parser.add_argument("ctc_dir", help="ctc-data directory of the chunks to synthesise (with breakpoints.npy)")
     parser.add_argument("out_dir", help="ctc-data directory to write")
     parser.add_argument("-r", "--reference", required=True, help="k-mer pore model (tab-separated: kmer, level_mean, level_stdv)")
-    parser.add_argument("--ubs", default="XY", type=str, help="unnatural bases to insert: X, Y, XY, or N to re-synthesise the DNA")
+    parser.add_argument("--ubs", default="XY", type=str, help="unnatural bases to insert: X, Y, XY, or N to synthesise the DNA as it is")
     parser.add_argument("--prop-ubs", default=0, type=float, help="proportion of bases to become unnatural (0.01 = 1%%)")
     parser.add_argument("--var-prop-ubs", default=None, type=float, help="draw the proportion per chunk from prop-ubs +- this")
     parser.add_argument("--ub-pad", default=5, type=int, help="bases kept free around a spiked base")
     parser.add_argument("--std-dist", default="uniform", type=str,
                         help="level noise: uniform, truncnorm or truncnorm_shift_<len>_<range>")
     parser.add_argument("--noise-std", default=0, type=float, help="std of the truncated normal noise added to the squiggle")
-    parser.add_argument("--variable-noise", action="store_true", help="draw the noise std per position from 0 .. noise-std")
+    parser.add_argument("--variable-noise", action="store_true", help="draw the noise std per chunk from 0 .. noise-std")
     parser.add_argument("--seed", default=2012, type=int, help="seed of the draws")
     parser.add_argument("--batchsize", default=4096, type=int, help="chunks per device call")
     parser.add_argument("--device", default="cuda")
     parser.add_argument("--overwrite", action="store_true", help="replace existing output files")
-    parser.add_argument("--fully_synth", action="store_true", help="refused")
     parser.add_argument("--equal-kmer-reps", dest="equal_kmer_reps", action="store_true", help="refused")
     parser.add_argument("--legacy-pos", dest="legacy_pos", action="store_true", help="refused")
     return parser

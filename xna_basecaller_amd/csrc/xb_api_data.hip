@@ -1,5 +1,5 @@
 // xb_api_data.hip -- the ctc-data tools of the C ABI: template mapping, ctc labels, the UB tally, the barcode distance, DTW segmentation, spliced
-// augmentation and synthetic spiking.  Each has a _dev form on device pointers and a host-pointer form that stages through xb_ctx::staging.
+// augmentation, synthetic spiking and fully synthetic chunks.  Each has a _dev form on device pointers and a host-pointer form that stages through xb_ctx::staging.
 #include "xb_ctx.h"
 
 namespace {
@@ -848,43 +848,59 @@ struct SpikeArgs {
     double noise_std;
     int variable_noise;
 };
+struct SpikeIn {
+    const float *signal; const uint8_t *targets; const int32_t *lengths; const uint16_t *bkps;
+};
+struct SpikeOut {
+    float *signal; uint8_t *targets; int32_t *spiked; double *med, *mad; int8_t *status;
+};
+// the two entry points over one model and one argument list: windows around the positions, or the whole chunk
+struct SpikeCall {
+    const char *who;
+    hipError_t (*launch)(const xb::SpikeParams &, hipStream_t);
+};
+constexpr SpikeCall SPIKE_WINDOWS{"xb_spike_chunks", xb::launch_spike}, SPIKE_WHOLE{"xb_synth_chunks", xb::launch_synth};
+
+bool spike_complete(const SpikeIn &i, const SpikeOut &o)
+{
+    return i.signal && i.targets && i.lengths && i.bkps && o.signal && o.targets && o.spiked && o.med && o.mad && o.status;
+}
 
 // the limits of the contract, before any launch
-int spike_check(xb_ctx *ctx, const SpikeArgs &a)
+int spike_check(xb_ctx *ctx, const char *who, const SpikeArgs &a)
 {
-    if (!ctx->spike.loaded) return fail(ctx, XB_ERR_STATE, "xb_spike_chunks: no model: call xb_spike_model first");
+    if (!ctx->spike.loaded) return fail(ctx, XB_ERR_STATE, "%s: no model: call xb_spike_model first", who);
     if (a.n < 1 || a.N < 1 || a.N > xb::SPLICE_MAX_SAMPLES || a.Lt < 1 || a.Lt > xb::SPLICE_MAX_LABELS)
-        return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: n = %d chunks of %d samples, label rows of %d entries; need n >= 1, "
-                    "1 <= N <= %d, 1 <= Lt <= %d", a.n, a.N, a.Lt, xb::SPLICE_MAX_SAMPLES, xb::SPLICE_MAX_LABELS);
-    if (a.pad < 0) return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: pad = %d is negative", a.pad);
+        return fail(ctx, XB_ERR_INVALID, "%s: n = %d chunks of %d samples, label rows of %d entries; need n >= 1, "
+                    "1 <= N <= %d, 1 <= Lt <= %d", who, a.n, a.N, a.Lt, xb::SPLICE_MAX_SAMPLES, xb::SPLICE_MAX_LABELS);
+    if (a.pad < 0) return fail(ctx, XB_ERR_INVALID, "%s: pad = %d is negative", who, a.pad);
     if (a.ubs_mask < 0 || a.ubs_mask > 3)
-        return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: ubs_mask = %d; 0 (none), 1 (X), 2 (Y) or 3 (both)", a.ubs_mask);
+        return fail(ctx, XB_ERR_INVALID, "%s: ubs_mask = %d; 0 (none), 1 (X), 2 (Y) or 3 (both)", who, a.ubs_mask);
     if (!(a.prop >= 0.0) || !(a.var_prop >= 0.0) || !(a.prop + a.var_prop <= 1.0))
-        return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: prop = %g, var_prop = %g; both at least 0, their sum at most 1", a.prop, a.var_prop);
-    if (a.first_index < 0) return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: first_index = %lld is negative", (long long)a.first_index);
+        return fail(ctx, XB_ERR_INVALID, "%s: prop = %g, var_prop = %g; both at least 0, their sum at most 1", who, a.prop, a.var_prop);
+    if (a.first_index < 0) return fail(ctx, XB_ERR_INVALID, "%s: first_index = %lld is negative", who, (long long)a.first_index);
     if (a.dist_rows < 0 || a.dist_rows > xb::SPIKE_MAX_ROWS)
-        return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: dist_rows = %d; 0 (uniform) .. %d shift values are supported", a.dist_rows,
+        return fail(ctx, XB_ERR_INVALID, "%s: dist_rows = %d; 0 (uniform) .. %d shift values are supported", who, a.dist_rows,
                     xb::SPIKE_MAX_ROWS);
     if (!(a.noise_std >= 0.0) || std::isinf(a.noise_std))
-        return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: noise_std = %g; a finite value >= 0 is supported", a.noise_std);
+        return fail(ctx, XB_ERR_INVALID, "%s: noise_std = %g; a finite value >= 0 is supported", who, a.noise_std);
     // the rows the kernel reads: every quantile pa + unit * pw must stay inside (0, 1) and normal
     for (int r = 0; r <= a.dist_rows; ++r) {
         if (r == a.dist_rows && !(a.noise_std > 0.0)) break;
-        if (!a.phi) return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: null distribution table");
+        if (!a.phi) return fail(ctx, XB_ERR_INVALID, "%s: null distribution table", who);
         const double pa = a.phi[2 * r], pw = a.phi[2 * r + 1];
         if (!(pa >= 1e-300) || !(pw > 0.0) || !(pa + pw < 1.0))
-            return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: distribution row %d is Phi(a) = %g, Phi(b) - Phi(a) = %g; need "
-                        "1e-300 <= Phi(a), 0 < Phi(b) - Phi(a), Phi(b) < 1", r, pa, pw);
+            return fail(ctx, XB_ERR_INVALID, "%s: distribution row %d is Phi(a) = %g, Phi(b) - Phi(a) = %g; need "
+                        "1e-300 <= Phi(a), 0 < Phi(b) - Phi(a), Phi(b) < 1", who, r, pa, pw);
     }
     return XB_OK;
 }
 
-int spike_run(xb_ctx *ctx, const SpikeArgs &a, const float *d_signal, const uint8_t *d_targets, const int32_t *d_lengths,
-              const uint16_t *d_bkps, float *d_out_signal, uint8_t *d_out_targets, int32_t *d_spiked, double *d_med, double *d_mad,
-              int8_t *d_status)
+// the launch: i and o are device pointers
+int spike_run(xb_ctx *ctx, const SpikeCall &call, const SpikeArgs &a, const SpikeIn &i, const SpikeOut &o)
 {
     xb::SpikeParams p{};
-    p.signal = d_signal; p.targets = d_targets; p.lengths = d_lengths; p.bkps = d_bkps;
+    p.signal = i.signal; p.targets = i.targets; p.lengths = i.lengths; p.bkps = i.bkps;
     p.n = a.n; p.N = a.N; p.Lt = a.Lt;
     p.first_index = (unsigned long long)a.first_index; p.seed = a.seed;
     p.ubs_mask = a.ubs_mask; p.prop = a.prop; p.var_prop = a.var_prop; p.pad = a.pad;
@@ -896,48 +912,36 @@ int spike_run(xb_ctx *ctx, const SpikeArgs &a, const float *d_signal, const uint
     }
     p.noise_std = a.noise_std; p.variable_noise = a.variable_noise != 0;
     p.model = static_cast<const double *>(ctx->spike.model.p);
-    p.out_signal = d_out_signal; p.out_targets = d_out_targets; p.spiked = d_spiked; p.med = d_med; p.mad = d_mad; p.status = d_status;
-    XB_HIP(ctx, xb::launch_spike(p, ctx->stream));
+    p.out_signal = o.signal; p.out_targets = o.targets; p.spiked = o.spiked; p.med = o.med; p.mad = o.mad; p.status = o.status;
+    XB_HIP(ctx, call.launch(p, ctx->stream));
     return XB_OK;
 }
 
-}  // namespace
-
-XB_API int xb_spike_chunks_dev(xb_ctx *ctx, const float *d_signal, const uint8_t *d_targets, const int32_t *d_lengths,
-                               const uint16_t *d_breakpoints, int n, int N, int Lt, int64_t first_index, uint64_t seed, int ubs_mask,
-                               double prop, double var_prop, int pad, int dist_rows, const double *phi, double noise_std,
-                               int variable_noise, float *d_out_signal, uint8_t *d_out_targets, int32_t *d_spiked, double *d_med,
-                               double *d_mad, int8_t *d_status)
+// the _dev form of either entry point
+int spike_dev(xb_ctx *ctx, const SpikeCall &call, const SpikeArgs &a, const SpikeIn &i, const SpikeOut &o)
 {
     if (!ctx) return XB_ERR_INVALID;
-    if (!d_signal || !d_targets || !d_lengths || !d_breakpoints || !d_out_signal || !d_out_targets || !d_spiked || !d_med || !d_mad ||
-        !d_status)
-        return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: null device pointer");
-    if (d_signal == d_out_signal || d_targets == d_out_targets) return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: outputs alias inputs");
-    const SpikeArgs a{n, N, Lt, first_index, seed, ubs_mask, prop, var_prop, pad, dist_rows, phi, noise_std, variable_noise};
-    if (int rc = spike_check(ctx, a)) return rc;
+    if (!spike_complete(i, o)) return fail(ctx, XB_ERR_INVALID, "%s: null device pointer", call.who);
+    if (i.signal == o.signal || i.targets == o.targets) return fail(ctx, XB_ERR_INVALID, "%s: outputs alias inputs", call.who);
+    if (int rc = spike_check(ctx, call.who, a)) return rc;
     if (int rc = enter(ctx, true)) return rc;
-    return spike_run(ctx, a, d_signal, d_targets, d_lengths, d_breakpoints, d_out_signal, d_out_targets, d_spiked, d_med, d_mad, d_status);
+    return spike_run(ctx, call, a, i, o);
 }
 
-XB_API int xb_spike_chunks(xb_ctx *ctx, const float *signal, const uint8_t *targets, const int32_t *lengths,
-                           const uint16_t *breakpoints, int n, int N, int Lt, int64_t first_index, uint64_t seed, int ubs_mask,
-                           double prop, double var_prop, int pad, int dist_rows, const double *phi, double noise_std,
-                           int variable_noise, float *out_signal, uint8_t *out_targets, int32_t *spiked, double *med, double *mad,
-                           int8_t *status)
+// the host-pointer form of either entry point
+int spike_host(xb_ctx *ctx, const SpikeCall &call, const SpikeArgs &a, const SpikeIn &h, const SpikeOut &ho)
 {
     if (!ctx) return XB_ERR_INVALID;
-    if (!signal || !targets || !lengths || !breakpoints || !out_signal || !out_targets || !spiked || !med || !mad || !status)
-        return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: null host pointer");
-    const SpikeArgs a{n, N, Lt, first_index, seed, ubs_mask, prop, var_prop, pad, dist_rows, phi, noise_std, variable_noise};
-    if (int rc = spike_check(ctx, a)) return rc;
+    if (!spike_complete(h, ho)) return fail(ctx, XB_ERR_INVALID, "%s: null host pointer", call.who);
+    if (int rc = spike_check(ctx, call.who, a)) return rc;
+    const int n = a.n, N = a.N, Lt = a.Lt;
     for (int c = 0; c < n; ++c) {                                       // what the kernel would otherwise clamp
-        const int len = lengths[c];
-        if (len < 0 || len > Lt) return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: chunk %d has %d labels in a row of %d", c, len, Lt);
-        const uint16_t *b = breakpoints + (size_t)c * Lt;
+        const int len = h.lengths[c];
+        if (len < 0 || len > Lt) return fail(ctx, XB_ERR_INVALID, "%s: chunk %d has %d labels in a row of %d", call.who, c, len, Lt);
+        const uint16_t *b = h.bkps + (size_t)c * Lt;
         for (int l = 0; l < len; ++l)
             if (b[l] > N || (l && b[l] < b[l - 1]))
-                return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: chunk %d: breakpoint %d of base %d (the one before: %d, samples: %d)", c,
+                return fail(ctx, XB_ERR_INVALID, "%s: chunk %d: breakpoint %d of base %d (the one before: %d, samples: %d)", call.who, c,
                             (int)b[l], l, l ? (int)b[l - 1] : 0, N);
     }
     if (int rc = enter(ctx, false)) return rc;
@@ -949,20 +953,63 @@ XB_API int xb_spike_chunks(xb_ctx *ctx, const float *signal, const uint8_t *targ
     const auto d_bk = st.take<uint16_t>(C * Lt);
     const auto d_t = st.take<uint8_t>(C * Lt), d_ot = st.take<uint8_t>(C * Lt);
     const auto d_st = st.take<int8_t>(C);
-    if (st.used > ((size_t)2 << 30)) return fail(ctx, XB_ERR_INVALID, "xb_spike_chunks: %d chunks of %d samples in one call; split the batch", n, N);
+    if (st.used > ((size_t)2 << 30)) return fail(ctx, XB_ERR_INVALID, "%s: %d chunks of %d samples in one call; split the batch", call.who, n, N);
     if (int rc = st.ready()) return rc;
-    XB_HIP(ctx, hipMemcpyAsync(d_sig, signal, C * N * 4, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(d_len, lengths, C * 4, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(d_bk, breakpoints, C * Lt * 2, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(d_t, targets, C * Lt, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = spike_run(ctx, a, d_sig, d_t, d_len, d_bk, d_out, d_ot, d_cnt, d_med, d_mad, d_st)) return rc;
-    XB_HIP(ctx, hipMemcpyAsync(out_signal, d_out, C * N * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(out_targets, d_ot, C * Lt, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(spiked, d_cnt, C * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(med, d_med, C * 8, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(mad, d_mad, C * 8, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(status, d_st, C, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(d_sig, h.signal, C * N * 4, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(d_len, h.lengths, C * 4, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(d_bk, h.bkps, C * Lt * 2, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(d_t, h.targets, C * Lt, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = spike_run(ctx, call, a, {d_sig, d_t, d_len, d_bk}, {d_out, d_ot, d_cnt, d_med, d_mad, d_st})) return rc;
+    XB_HIP(ctx, hipMemcpyAsync(ho.signal, d_out, C * N * 4, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(ho.targets, d_ot, C * Lt, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(ho.spiked, d_cnt, C * 4, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(ho.med, d_med, C * 8, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(ho.mad, d_mad, C * 8, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(ho.status, d_st, C, hipMemcpyDeviceToHost, ctx->stream));
     return xb_synchronize(ctx);
+}
+
+}  // namespace
+
+XB_API int xb_spike_chunks_dev(xb_ctx *ctx, const float *d_signal, const uint8_t *d_targets, const int32_t *d_lengths,
+                               const uint16_t *d_breakpoints, int n, int N, int Lt, int64_t first_index, uint64_t seed, int ubs_mask,
+                               double prop, double var_prop, int pad, int dist_rows, const double *phi, double noise_std,
+                               int variable_noise, float *d_out_signal, uint8_t *d_out_targets, int32_t *d_spiked, double *d_med,
+                               double *d_mad, int8_t *d_status)
+{
+    return spike_dev(ctx, SPIKE_WINDOWS, {n, N, Lt, first_index, seed, ubs_mask, prop, var_prop, pad, dist_rows, phi, noise_std, variable_noise},
+                     {d_signal, d_targets, d_lengths, d_breakpoints}, {d_out_signal, d_out_targets, d_spiked, d_med, d_mad, d_status});
+}
+
+XB_API int xb_spike_chunks(xb_ctx *ctx, const float *signal, const uint8_t *targets, const int32_t *lengths,
+                           const uint16_t *breakpoints, int n, int N, int Lt, int64_t first_index, uint64_t seed, int ubs_mask,
+                           double prop, double var_prop, int pad, int dist_rows, const double *phi, double noise_std,
+                           int variable_noise, float *out_signal, uint8_t *out_targets, int32_t *spiked, double *med, double *mad,
+                           int8_t *status)
+{
+    return spike_host(ctx, SPIKE_WINDOWS, {n, N, Lt, first_index, seed, ubs_mask, prop, var_prop, pad, dist_rows, phi, noise_std, variable_noise},
+                      {signal, targets, lengths, breakpoints}, {out_signal, out_targets, spiked, med, mad, status});
+}
+
+// ---- XNA fully synthetic chunks (xb_synth_chunks): xb_spike_chunks' arguments, model and checks, the whole chunk synthesised
+XB_API int xb_synth_chunks_dev(xb_ctx *ctx, const float *d_signal, const uint8_t *d_targets, const int32_t *d_lengths,
+                               const uint16_t *d_breakpoints, int n, int N, int Lt, int64_t first_index, uint64_t seed, int ubs_mask,
+                               double prop, double var_prop, int pad, int dist_rows, const double *phi, double noise_std,
+                               int variable_noise, float *d_out_signal, uint8_t *d_out_targets, int32_t *d_spiked, double *d_med,
+                               double *d_mad, int8_t *d_status)
+{
+    return spike_dev(ctx, SPIKE_WHOLE, {n, N, Lt, first_index, seed, ubs_mask, prop, var_prop, pad, dist_rows, phi, noise_std, variable_noise},
+                     {d_signal, d_targets, d_lengths, d_breakpoints}, {d_out_signal, d_out_targets, d_spiked, d_med, d_mad, d_status});
+}
+
+XB_API int xb_synth_chunks(xb_ctx *ctx, const float *signal, const uint8_t *targets, const int32_t *lengths,
+                           const uint16_t *breakpoints, int n, int N, int Lt, int64_t first_index, uint64_t seed, int ubs_mask,
+                           double prop, double var_prop, int pad, int dist_rows, const double *phi, double noise_std,
+                           int variable_noise, float *out_signal, uint8_t *out_targets, int32_t *spiked, double *med, double *mad,
+                           int8_t *status)
+{
+    return spike_host(ctx, SPIKE_WHOLE, {n, N, Lt, first_index, seed, ubs_mask, prop, var_prop, pad, dist_rows, phi, noise_std, variable_noise},
+                      {signal, targets, lengths, breakpoints}, {out_signal, out_targets, spiked, med, mad, status});
 }
 
 }  // extern "C"

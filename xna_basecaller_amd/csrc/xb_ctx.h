@@ -220,7 +220,7 @@ struct xb_ctx {
         bool loaded = false;
     } splice;
 
-    // XNA synthetic spiking (xb_spike_model / xb_spike_chunks): the k-mer table, kept until the next xb_spike_model.  Owned
+    // XNA synthetic spiking (xb_spike_model / xb_spike_chunks / xb_synth_chunks): the k-mer table, kept until the next xb_spike_model.  Owned
     // here, freed by xb_ctx_destroy.
     struct SpikeState {
         DevBuf model;

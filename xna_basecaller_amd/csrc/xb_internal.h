@@ -386,6 +386,9 @@ struct SpikeParams {
     int8_t *status;              // (n)
 };
 hipError_t launch_spike(const SpikeParams &p, hipStream_t stream);
+// xb_synth_chunks: the same parameters, positions, selection and draws; the whole chunk is synthesised from the spiked labels
+// and the breakpoints (med / mad from the spiked labels too), `spiked` may be 0 with the chunk still synthesised.
+hipError_t launch_synth(const SpikeParams &p, hipStream_t stream);
 
 #ifdef XB_LSTM_STAMPS
 void lstm_read_stamps(unsigned long long out[10], bool reset);   // diagnostic build only

@@ -1,7 +1,8 @@
-// xb_spike.hip -- xb_spike_chunks: the reference's synthetic XNA spiking (ub-bonito/bonito/spike_chunks.py; contract: the
-// public header).  Built with -ffp-contract=off: every float64 operation is the contract's, in its order, bit-equal to the
-// CPU restatement (tests/spike_ref.py).
+// xb_spike.hip -- xb_spike_chunks and xb_synth_chunks: the reference's synthetic XNA spiking and its fully synthetic chunks
+// (ub-bonito/bonito/spike_chunks.py; contract: the public header).  Built with -ffp-contract=off: every float64 operation is
+// the contract's, in its order, bit-equal to the CPU restatements (tests/spike_ref.py, tests/synth_ref.py).
 //
+// spike_kernel
 // One wave per chunk, one launch per call.  The wave copies its signal and label rows, then:
 //   k-mers      the chunk's own k-mers (one per base, over the labels and their ATATA / TATAT tail) are looked up first: a
 //               missing one ends the chunk with status 2 before anything is drawn.
@@ -20,6 +21,18 @@
 //
 // The kernel reads lengths, labels and breakpoints it did not validate (the _dev form): lengths are clamped to the row,
 // labels to 6, breakpoints to the chunk and to non-decreasing order, so that no access leaves the rows whatever they hold.
+//
+// synth_kernel
+// The same wave per chunk, the same positions, shuffle, selection and draws; what differs is what they are applied to:
+//   labels      the unnatural bases are written into the output row FIRST, and every k-mer after that -- the check, the
+//               squiggle of med / mad, the synthesis -- is read from that row (a barrier between).  A missing k-mer puts the
+//               input's letters back.  The k-mers of the input row are never looked up.
+//   samples     lanes stride over the chunk's samples 0 .. total - 1 (total = the last breakpoint); a sample finds its base by
+//               an upper-bound search over the clamped breakpoints, which skips bases without a sample by itself.  One shift
+//               row and one noise std serve the whole chunk (stream 2), the draw index is the sample index.  Samples past
+//               total keep the input's value.
+// A breakpoint row that is not non-decreasing (the _dev form only) makes the search end at some base of the row: the values
+// are unspecified, every access stays inside the rows.
 #include <hip/hip_runtime.h>
 
 #include "xb_internal.h"
@@ -208,6 +221,26 @@ __device__ double median(const Squiggle &sq, bool dev, double med)
     return (a + b) / 2.0;
 }
 
+// the X / Y list of n_pos > 0 positions (ubs_mask 3): X, Y, X, Y, .. of n_pos + n_pos % 2 entries, a bit per entry in LDS (set:
+// Y), shuffled from its end by lane 0 with the chunk's next sequential draws.  Ends with a barrier.
+template <class Next> __device__ inline void shuffle_ubs(unsigned *yset, int n_pos, Next &next, int lane)
+{
+    const int m = n_pos + (n_pos & 1);
+    for (int w = lane; w <= (m - 1) >> 5; w += 64) yset[w] = 0xAAAAAAAAu;
+    __syncthreads();
+    if (lane == 0) {
+        for (int i = m - 1; i >= 1; --i) {
+            const int j = (int)bounded(next(), (unsigned)i + 1u);
+            const unsigned bi = yset[i >> 5] >> (i & 31) & 1u, bj = yset[j >> 5] >> (j & 31) & 1u;
+            if (bi != bj) {
+                yset[i >> 5] ^= 1u << (i & 31);
+                yset[j >> 5] ^= 1u << (j & 31);
+            }
+        }
+    }
+    __syncthreads();
+}
+
 __global__ __launch_bounds__(64) void spike_kernel(const SpikeParams p)
 {
     __shared__ unsigned valid[MASK_WORDS], chosen[MASK_WORDS], yset[MASK_WORDS];
@@ -259,22 +292,7 @@ __global__ __launch_bounds__(64) void spike_kernel(const SpikeParams p)
     u64 kdraw = 0;
     auto next = [&]() { return mix(base0 + GAMMA * ++kdraw); };
     const int n_pos = choose_positions(valid, chosen, tgt, length, p.pad, p.prop, p.var_prop, next, lane);
-    if (p.ubs_mask == 3 && n_pos > 0) {
-        const int m = n_pos + (n_pos & 1);
-        for (int w = lane; w <= (m - 1) >> 5; w += 64) yset[w] = 0xAAAAAAAAu;       // X, Y, X, Y, ..: bit i = entry i is Y
-        __syncthreads();
-        if (lane == 0) {
-            for (int i = m - 1; i >= 1; --i) {
-                const int j = (int)bounded(next(), (unsigned)i + 1u);
-                const unsigned bi = yset[i >> 5] >> (i & 31) & 1u, bj = yset[j >> 5] >> (j & 31) & 1u;
-                if (bi != bj) {
-                    yset[i >> 5] ^= 1u << (i & 31);
-                    yset[j >> 5] ^= 1u << (j & 31);
-                }
-            }
-        }
-        __syncthreads();
-    }
+    if (p.ubs_mask == 3 && n_pos > 0) shuffle_ubs(yset, n_pos, next, lane);
     // the unnatural base of the ordinal-th position: 0 = none (ubs_mask 0: the DNA k-mers are re-synthesised)
     auto ub_of = [&](int ordinal) {
         if (p.ubs_mask == 3) return 5 + (int)(yset[ordinal >> 5] >> (ordinal & 31) & 1u);
@@ -385,9 +403,133 @@ __global__ __launch_bounds__(64) void spike_kernel(const SpikeParams p)
     finish(ordinal, med, mad, 0);
 }
 
+__global__ __launch_bounds__(64) void synth_kernel(const SpikeParams p)
+{
+    __shared__ unsigned valid[MASK_WORDS], chosen[MASK_WORDS], yset[MASK_WORDS];
+    const int lane = threadIdx.x;
+    const int c = blockIdx.x;
+    const int N = p.N, Lt = p.Lt;
+    const float *sig = p.signal + (size_t)c * N;
+    float *out = p.out_signal + (size_t)c * N;
+    const unsigned char *tgt = p.targets + (size_t)c * Lt;
+    unsigned char *out_t = p.out_targets + (size_t)c * Lt;
+    const uint16_t *bk = p.bkps + (size_t)c * Lt;
+
+    copy_row(out, sig, N, p.signal, p.out_signal, lane);
+    copy_row(out_t, tgt, Lt, p.targets, p.out_targets, lane);
+
+    int length = p.lengths[c];
+    length = length < 0 ? 0 : (length > Lt ? Lt : length);
+    const int W = (length + 31) >> 5;
+    auto finish = [&](int spiked, double med, double mad, int status) {
+        if (lane == 0) {
+            p.spiked[c] = spiked;
+            p.med[c] = med;
+            p.mad[c] = mad;
+            p.status[c] = (int8_t)status;
+        }
+    };
+    if (length == 0) {
+        finish(0, 0.0, 0.0, 0);
+        return;
+    }
+
+    // ---- stream 0: proportion, positions, the shuffle of the X / Y list (as spike_kernel)
+    const u64 chunk_base = mix(p.seed + GAMMA * (p.first_index + (u64)c + 1));
+    const u64 base0 = mix(chunk_base + GAMMA * 1);
+    u64 kdraw = 0;
+    auto next = [&]() { return mix(base0 + GAMMA * ++kdraw); };
+    const int n_pos = choose_positions(valid, chosen, tgt, length, p.pad, p.prop, p.var_prop, next, lane);
+    if (p.ubs_mask == 3 && n_pos > 0) shuffle_ubs(yset, n_pos, next, lane);
+
+    // ---- the spiked row: the copy is in place (barrier), then the unnatural bases, then every reader (barrier)
+    __syncthreads();
+    if (p.ubs_mask != 0 && lane == 0) {
+        for (int w = 0, ordinal = 0; w < W; ++w) {
+            unsigned cw = chosen[w];
+            while (cw) {
+                const int pos = (w << 5) + __ffs((int)cw) - 1;
+                cw &= cw - 1;
+                out_t[pos] = (unsigned char)(p.ubs_mask == 3 ? 5 + (int)(yset[ordinal >> 5] >> (ordinal & 31) & 1u) : 4 + p.ubs_mask);
+                ++ordinal;
+            }
+        }
+    }
+    __syncthreads();
+    const Letters letters{out_t, length, out_t[length - 1] == 1 ? 4 : 1};
+    const double quiet_nan = __longlong_as_double(0x7FF8000000000000LL);
+
+    // ---- the spiked row's k-mers: the first missing one, in base order, ends the chunk with the input's letters back
+    int missing = 0x7fffffff;
+    for (int i = lane; i < length; i += 64) {
+        const double mean = p.model[2 * letters.kmer(i)];
+        if (mean != mean && i < missing) missing = i;
+    }
+    missing = wave_min(missing);
+    if (missing != 0x7fffffff) {
+        const int t = letters.kmer(missing);
+        __syncthreads();                                                // every lane has read the row it is about to lose
+        for (int i = lane; i < length; i += 64)
+            if (chosen[i >> 5] >> (i & 31) & 1u) out_t[i] = tgt[i];
+        finish(0, (double)t, quiet_nan, 2);
+        return;
+    }
+
+    // ---- med, mad of the spiked row's squiggle (stream 1)
+    const Squiggle sq{letters, p.model, mix(chunk_base + GAMMA * 2), lane};
+    const double med = median(sq, false, 0.0);
+    const double mad = median(sq, true, med) * 1.4826 + 0x1p-23;
+
+    // ---- the chunk's samples (stream 2): one shift row, one noise std
+    int total = bk[length - 1];
+    total = total > N ? N : total;
+    const u64 base = mix(chunk_base + GAMMA * 3);
+    auto draw = [&](u64 k) { return mix(base + GAMMA * (k + 1)); };
+    const int rows = p.dist_rows;
+    const double noise_pa = p.phi[rows][0], noise_pw = p.phi[rows][1];
+    double level_pa = 0.0, level_pw = 0.0;
+    if (rows > 0) {
+        const int r = (int)bounded(draw(0), (unsigned)rows);
+        level_pa = p.phi[r][0];
+        level_pw = p.phi[r][1];
+    }
+    double sigma = p.noise_std;
+    if (p.noise_std > 0.0 && p.variable_noise) sigma = 0.0 + (p.noise_std - 0.0) * unit(draw(1));
+    for (int i = lane; i < total; i += 64) {
+        int lo_b = 0, hi_b = length - 1;                                // the first base whose breakpoint is past sample i
+        while (lo_b < hi_b) {
+            const int mid = (lo_b + hi_b) >> 1;
+            int v = bk[mid];
+            v = v > N ? N : v;
+            if (v > i) hi_b = mid;
+            else lo_b = mid + 1;
+        }
+        const int t = letters.kmer(lo_b);
+        const double m = p.model[2 * t], s = p.model[2 * t + 1];
+        const double u = unit(draw(2 + (u64)i));
+        double level;
+        if (rows == 0) {
+            const double lo = -s;
+            level = lo + (s - lo) * u;
+        } else {
+            level = ppnd16(level_pa + u * level_pw) * s;
+        }
+        double v = m + level;
+        if (p.noise_std > 0.0) v = v + ppnd16(noise_pa + unit(draw(2 + (u64)total + (u64)i)) * noise_pw) * sigma;
+        out[i] = (float)((v - med) / mad);
+    }
+    finish(n_pos, med, mad, 0);
+}
+
 }  // namespace
 
 namespace xb {
+
+hipError_t launch_synth(const SpikeParams &p, hipStream_t stream)
+{
+    hipLaunchKernelGGL(synth_kernel, dim3(p.n), dim3(64), 0, stream, p);
+    return hipGetLastError();
+}
 
 hipError_t launch_spike(const SpikeParams &p, hipStream_t stream)
 {

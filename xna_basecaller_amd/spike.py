@@ -4,13 +4,15 @@ its training recipe): at chosen bases of a DNA chunk the signal of the six k-mer
 squiggle -- the k-mers' pore-model levels, each held for as many samples as the base had, plus level noise and added noise --
 normalised by the med / mad of the whole chunk's synthetic squiggle, and the base is relabelled X or Y.  The reference does
 this per read in the data loader, in numpy; here one device pass (xb_spike_chunks, include/xna_basecaller.h) chooses the
-positions, selects med and mad exactly, synthesises and pastes.  This module is the host side: the model table, the level
-distribution, validation, batching.
+positions, selects med and mad exactly, synthesises and pastes.  `synth` is the reference's third recipe, `bonito train
+--spike --fully_synth`: the whole chunk is re-synthesised from the spiked labels and the breakpoints (xb_synth_chunks), med and
+mad taken from the spiked labels, one shift and one noise std per chunk.  This module is the host side of both: the model
+table, the level distribution, validation, batching.
 
 Departures from the reference, all stated in INTEGRATION.md: the random stream is the contract's counter-based one (draws:
 parity unpinned; everything else is pinned to the reference through tests/golden/spike.json); the truncated normal is drawn
-through AS241's quantile instead of scipy's; fully synthetic chunks, the distributions `normal`, `uniform_shift_*` and
-`truncnorm_prerep`, equal_kmer_reps and legacy_pos are refused.
+through AS241's quantile instead of scipy's; the distributions `normal`, `uniform_shift_*` and `truncnorm_prerep`,
+equal_kmer_reps and legacy_pos are refused; a fully synthetic chunk keeps its length (the breakpoints must end at it).
 """
 import math
 import time
@@ -121,32 +123,35 @@ def check_params(prop_ubs, var_prop_ubs, pad, noise_std):
     return var
 
 
-def _device_call(device, model):
+def _device_call(device, model, call):
     from . import _lib
     _lib.require_gpu()
     index = int(str(device).split(":")[1]) if ":" in str(device) else 0
     ctx = _lib.mapper_context(index)       # no network is needed
     ctx.spike_model(*model)
-    return ctx, ctx.spike_chunks
+    return ctx, getattr(ctx, call)
 
 
-def spike(chunks, targets, lengths, bkps, model, ubs="XY", prop_ubs=0.0, var_prop_ubs=None, pad=5, std_dist="uniform",
-          noise_std=0.0, variable_noise=False, seed=2012, batch=4096, device="cuda", run=None, timings=None):
-    """chunks (n, N), targets (n, Lt), lengths (n), bkps (n, Lt) and a model (mean, stdv: model_table) -> (chunks float32,
-    targets uint8, spiked (n,) int32, med (n,), mad (n,) float64), rows in the input's order.  `run`: the batch call,
-    Context.spike_chunks' signature (default: a context on `device` with the model uploaded once).  A chunk's result depends
-    on its global index, never on `batch`.  A chunk that needs a k-mer the model lacks is a ValueError that names both.
-    `timings` (a dict) receives the seconds spent in the device calls ('device')."""
+def _batches(call, chunks, targets, lengths, bkps, model, ubs, prop_ubs, var_prop_ubs, pad, std_dist, noise_std, variable_noise, seed,
+             batch, device, run, timings):
+    """What spike and synth share: validation, the batches over `run` (default: Context.<call> on `device`), the results."""
     mask = ubs_mask(ubs)
     var = check_params(prop_ubs, var_prop_ubs, pad, noise_std)
     dist_rows, table = phi_table(std_dist)
     check_ctc("DNA", chunks, targets, lengths, bkps, empty_bases=True)     # a k-mer without a sample is synthesised as none
+    if call == "synth_chunks":             # the reference's sim_target returns breakpoints[-1] samples: a shorter row cannot be batched
+        lens = np.asarray(lengths).astype(np.int64)
+        last = np.asarray(bkps)[np.arange(len(lens)), np.maximum(lens, 1) - 1].astype(np.int64)
+        short = np.flatnonzero((lens > 0) & (last != chunks.shape[1]))
+        if short.size:
+            raise ValueError("DNA chunk %d: its last breakpoint is %d, the chunk has %d samples; a fully synthetic chunk is as long as "
+                             "its breakpoints say (`segment` always ends them at the chunk)" % (short[0], last[short[0]], chunks.shape[1]))
     if int(batch) < 1:
         raise ValueError("batch must be at least 1")
     n = chunks.shape[0]
     ctx = None
     if run is None:
-        ctx, run = _device_call(device, model)
+        ctx, run = _device_call(device, model, call)
     out = np.empty(chunks.shape, np.float32)
     out_t = np.empty(targets.shape, np.uint8)
     spiked = np.zeros(n, np.int32)
@@ -170,3 +175,24 @@ def spike(chunks, targets, lengths, bkps, model, ubs="XY", prop_ubs=0.0, var_pro
     if timings is not None:
         timings.update(device=t_dev)
     return out, out_t, spiked, med, mad
+
+
+def spike(chunks, targets, lengths, bkps, model, ubs="XY", prop_ubs=0.0, var_prop_ubs=None, pad=5, std_dist="uniform",
+          noise_std=0.0, variable_noise=False, seed=2012, batch=4096, device="cuda", run=None, timings=None):
+    """chunks (n, N), targets (n, Lt), lengths (n), bkps (n, Lt) and a model (mean, stdv: model_table) -> (chunks float32,
+    targets uint8, spiked (n,) int32, med (n,), mad (n,) float64), rows in the input's order.  `run`: the batch call,
+    Context.spike_chunks' signature (default: a context on `device` with the model uploaded once).  A chunk's result depends
+    on its global index, never on `batch`.  A chunk that needs a k-mer the model lacks is a ValueError that names both.
+    `timings` (a dict) receives the seconds spent in the device calls ('device')."""
+    return _batches("spike_chunks", chunks, targets, lengths, bkps, model, ubs, prop_ubs, var_prop_ubs, pad, std_dist, noise_std,
+                    variable_noise, seed, batch, device, run, timings)
+
+
+def synth(chunks, targets, lengths, bkps, model, ubs="XY", prop_ubs=0.0, var_prop_ubs=None, pad=5, std_dist="uniform",
+          noise_std=0.0, variable_noise=False, seed=2012, batch=4096, device="cuda", run=None, timings=None):
+    """Fully synthetic chunks: spike's arguments and return tuple; `run` has Context.synth_chunks' signature.  Every sample of
+    a chunk is synthesised from its spiked labels (`chunks` gives only the shape), `spiked` may be 0 with the chunk still
+    synthesised.  A chunk whose last breakpoint is not its number of samples is a ValueError that names it, and so is a chunk
+    whose spiked labels need a k-mer the model lacks."""
+    return _batches("synth_chunks", chunks, targets, lengths, bkps, model, ubs, prop_ubs, var_prop_ubs, pad, std_dist, noise_std,
+                    variable_noise, seed, batch, device, run, timings)
