@@ -261,6 +261,36 @@ XB_API int xb_ctc_logz(xb_ctx *ctx, const float *scores, int T, int n, const int
 XB_API int xb_ctc_alignments(xb_ctx *ctx, const float *scores, int T, int n, const int32_t *targets, int Lt,
                              const int32_t *target_lengths, float *alignments, float *max_score);
 
+/*
+ * The validation loss from RAW scores where they lie (validate_one_step, training.py:159-173:
+ * CTC_CRF.ctc_loss(scores, targets, lengths, normalise_scores=True, reduction='none', loss_clip=None), crf/model.py:118-131).
+ *   scores  (T, n, C) fp32 RAW encoder scores, 1 <= T <= the context's T; has_blank = 1: C = S*(n_base+1); has_blank = 0:
+ *           C = S*n_base, the fused path's layout: a stay edge scores the context's blank_score, the move edge into position
+ *           l + 1 reads column state*n_base + base (the correspondence of xb_decode and xb_beam_search).
+ *   targets (n, Lt) uint8 CTC labels as references.npy holds them (1..n_base, 0 = padding, read as clamp(label - 1, 0));
+ *           target_lengths (n) int32 in bases, state_len <= length <= Lt; Lt - state_len + 1 <= 2048 positions.  The gather
+ *           columns of prepare_ctc_scores (crf/model.py:102-116) are derived from the labels on the device.
+ *   Arithmetic: logz_crf = xb_crf_logz of the scores; every score the lattice reads is s - (logz_crf / (float)T) in fp32 (one
+ *           division per chunk, one subtraction per score, as CTC_CRF.normalise; not folded into the result); the forward
+ *           recurrence of xb_ctc_logz (sum2 = max, exp, exp, add, log; the stay term before the move term; zero = -1e38);
+ *           logz (n) [optional] = alpha_T[length - state_len]; loss (n) = -(logz / (float)length).
+ *   A length outside [state_len, Lt] or a label above n_base inside a row's length: XB_ERR_INVALID -- from the host form before
+ *           anything is staged, with the chunk's index; from the _dev form, which has nothing on the host to check and returns
+ *           without waiting, by the next xb_synchronize (the chunk's loss is then not written).  The context stays usable.
+ *   No allocation per call: logz_crf lies in the decode's workspace, the host form stages through the context's buffers.
+ * xb_validate_chunks = validate_one_step's device half in one call: signal (n, chunk_len) -> encoder (blank-less scores) ->
+ *   Viterbi decode (seq (n, T), seq_len (n): bit-identical to xb_basecall_chunks on the same signal) -> loss (n) from the same
+ *   scores; only seq, seq_len and n floats come back.  Joins anything asynchronous first.
+ * Parity unpinned: seqdist is absent; bit-equal to the oracle's restatement (oracle.ctc_logz on the normalised,
+ * blank-expanded scores).
+ */
+XB_API int xb_ctc_loss(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, const uint8_t *targets, int Lt,
+                       const int32_t *target_lengths, float *loss, float *logz);
+XB_API int xb_ctc_loss_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const uint8_t *d_targets, int Lt,
+                           const int32_t *d_target_lengths, float *d_loss, float *d_logz);
+XB_API int xb_validate_chunks(xb_ctx *ctx, const float *signal, int n, const char *alphabet, const uint8_t *targets, int Lt,
+                              const int32_t *target_lengths, int8_t *seq, int32_t *seq_len, float *loss);
+
 /* compute_scores (crf/basecall.py:27-82), viterbi branch: encode + decode without materialising
  * the blank column or copying scores off the device. */
 XB_API int xb_basecall_chunks(xb_ctx *ctx, const float *signal, int n, const char *alphabet,

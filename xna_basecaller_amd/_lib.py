@@ -34,6 +34,7 @@ EXPORTS = [
     "xb_ub_tally", "xb_ub_tally_dev", "xb_barcode_dist", "xb_barcode_dist_dev", "xb_dtw_segment", "xb_dtw_segment_dev", "xb_dtw_scratch_bytes",
     "xb_splice_library", "xb_splice_chunks", "xb_splice_chunks_dev",
     "xb_spike_model", "xb_spike_chunks", "xb_spike_chunks_dev", "xb_synth_chunks", "xb_synth_chunks_dev",
+    "xb_ctc_loss", "xb_ctc_loss_dev", "xb_validate_chunks",
 ]
 XB_COMM_ID_BYTES = 128
 # xb_status (include/xna_basecaller.h)
@@ -146,6 +147,9 @@ def load():
     lib.xb_spike_chunks_dev.argtypes = lib.xb_spike_chunks.argtypes
     lib.xb_synth_chunks.argtypes = lib.xb_spike_chunks.argtypes
     lib.xb_synth_chunks_dev.argtypes = lib.xb_spike_chunks.argtypes
+    lib.xb_ctc_loss.argtypes = [vp, vp, ip, ip, ip, vp, ip, vp, vp, vp]
+    lib.xb_ctc_loss_dev.argtypes = lib.xb_ctc_loss.argtypes
+    lib.xb_validate_chunks.argtypes = [vp, vp, ip, C.c_char_p, vp, ip, vp, vp, vp, vp]
     lib.xb_result_stream.argtypes = [vp]
     lib.xb_result_stream.restype = C.c_void_p
     lib.xb_set_profiling.argtypes = [vp, ip]
@@ -395,6 +399,46 @@ class Context:
         self._check(self.lib.xb_ctc_alignments(self.h, scores.ctypes.data, T, n, targets.ctypes.data, Lt, tl.ctypes.data,
                                                al.ctypes.data, best.ctypes.data))
         return al, best
+
+    @staticmethod
+    def _labels(targets, lengths, n):
+        """(n, Lt) label rows as contiguous uint8 (references.npy's own type) and their lengths as int32."""
+        t = np.asarray(targets)
+        if t.ndim != 2 or t.shape[0] != n or (t.size and (t.min() < 0 or t.max() > 255)):
+            raise ValueError("targets: (n, Lt) labels 0 .. 255 expected")
+        tl = np.ascontiguousarray(lengths, dtype=np.int32)
+        if tl.shape != (n,):
+            raise ValueError("target_lengths: (n) expected")
+        return np.ascontiguousarray(t, dtype=np.uint8), tl
+
+    def ctc_loss(self, scores, targets, target_lengths, has_blank=True, want_logz=False):
+        """xb_ctc_loss: RAW scores (T, n, C) in either layout, targets (n, Lt) CTC labels, target_lengths (n) -> loss (n,) fp32 =
+        CTC_CRF.ctc_loss(..., normalise_scores=True, reduction='none'); with want_logz (loss, logz_ctc)."""
+        scores, has_blank = self._scores(scores, has_blank)
+        T, n, _ = scores.shape
+        targets, tl = self._labels(targets, target_lengths, n)
+        loss = np.empty((n,), np.float32)
+        logz = np.empty((n,), np.float32) if want_logz else None
+        self._check(self.lib.xb_ctc_loss(self.h, scores.ctypes.data, T, n, has_blank, targets.ctypes.data, targets.shape[1],
+                                         tl.ctypes.data, loss.ctypes.data, _ptr(logz)))
+        return (loss, logz) if want_logz else loss
+
+    def ctc_loss_dev(self, d_scores, T, n, has_blank, d_targets, Lt, d_lengths, d_loss, d_logz=None):
+        self._check(self.lib.xb_ctc_loss_dev(self.h, _ptr(d_scores), int(T), int(n), int(bool(has_blank)), _ptr(d_targets), int(Lt),
+                                             _ptr(d_lengths), _ptr(d_loss), _ptr(d_logz)))
+
+    def validate_chunks(self, signal, alphabet, targets, target_lengths):
+        """xb_validate_chunks: signal (n, chunk_len), targets (n, Lt), target_lengths (n) -> (seq (n, T) int8 left-packed ASCII,
+        lens (n,), loss (n,) fp32): basecall_chunks' calls and ctc_loss of the same scores, which never leave the device."""
+        signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1, self.chunk_len)
+        n = signal.shape[0]
+        targets, tl = self._labels(targets, target_lengths, n)
+        seq, lens = self._outputs(0, n, self.T)
+        loss = np.empty((n,), np.float32)
+        self._check(self.lib.xb_validate_chunks(self.h, signal.ctypes.data, n, "".join(alphabet).encode(), targets.ctypes.data,
+                                                targets.shape[1], tl.ctypes.data, seq.ctypes.data, lens.ctypes.data,
+                                                loss.ctypes.data))
+        return seq, lens, loss
 
     def crf_scans_dev(self, d_scores, T, n, has_blank, d_alpha=None, d_beta=None, d_logz=None, d_post=None):
         self._check(self.lib.xb_crf_scans_dev(self.h, _ptr(d_scores), T, n, int(bool(has_blank)), _ptr(d_alpha), _ptr(d_beta),

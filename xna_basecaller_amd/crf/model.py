@@ -409,6 +409,14 @@ class Model(torch.nn.Module):
         ctx = self.context(sig.shape[1], sig.shape[0])
         return ctx.basecall_chunks(sig, self.alphabet, *self.qscore_params(), level=_lib.output_level(qscores, ub_probs))
 
+    def validate_chunks(self, batch, targets, lengths):
+        """validate_one_step's device half (training.py:159-173) of a (N,1,L) batch with its (N,Lt) label rows and (N,) lengths ->
+        (seq, lens, loss): basecall_chunks' calls and seqdist.ctc_loss(model(batch), targets, lengths, reduction='none') from
+        the same blank-less scores, in one device call (xb_validate_chunks)."""
+        sig = self._as_signal(batch)
+        ctx = self.context(sig.shape[1], sig.shape[0])
+        return ctx.validate_chunks(sig, self.alphabet, targets, lengths)
+
     def _decode_rows(self, scores, op):
         if hasattr(scores, "detach"):
             scores = scores.detach().to(torch.float32).cpu().numpy()

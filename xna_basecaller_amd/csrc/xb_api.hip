@@ -284,6 +284,7 @@ int check_device_error(xb_ctx *ctx)
     if (e != 0) {
         (void)hipMemsetAsync(ctx->error, 0, sizeof(unsigned), ctx->stream);
         if (e == 2u) return fail(ctx, XB_ERR_DEVICE, "CTC scan: a target length was outside the lattice");
+        if (e == 4u) return fail(ctx, XB_ERR_INVALID, "xb_ctc_loss: a target length outside [state_len, Lt] or a label above n_base inside it");
         return fail(ctx, XB_ERR_DEVICE, "LSTM inter-workgroup sync timed out (persistent kernel was not fully resident?)");
     }
     return XB_OK;
@@ -684,6 +685,30 @@ int sync_all(xb_ctx *ctx)
 }
 
 }  // namespace
+
+// The validation loss of n chunks from device-resident RAW scores (T, n, ld), for xb_api_data.hip (xb_ctc_loss, xb_validate_chunks):
+// the Log forward scan leaves logZ_crf in the decode's own (max_batch) buffer, the CTC forward scan of the labels reads it
+// there.  Two launches on the main stream, nothing waited for; the callers have checked n and the pointers.
+int ctc_loss_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int n, int has_blank, int ld, const uint8_t *d_targets,
+                 int Lt, const int32_t *d_len, float *d_loss, float *d_logz)
+{
+    const xb_config &c = ctx->cfg;
+    const int np = Lt - (c.state_len - 1);
+    if (np < 1 || np > xb::ctc_max_positions())
+        return fail(ctx, XB_ERR_INVALID, "%s: target width %d gives %d positions, supported: 1..%d", who, Lt, np, xb::ctc_max_positions());
+    ScanOut so;
+    so.logz = ctx->logz;
+    if (int rc = run_decode(ctx, d_scores, T, n, has_blank, ld, nullptr, nullptr, nullptr, nullptr, nullptr, &so)) return rc;
+    xb::CtcLossParams p{};
+    p.scores = d_scores; p.T = T; p.N = n; p.ld = ld; p.has_blank = has_blank; p.blank = c.blank_score;
+    p.nb = c.n_base; p.sl = c.state_len; p.targets = d_targets; p.Lt = Lt; p.tlen = d_len;
+    p.logz_crf = ctx->logz; p.loss = d_loss; p.logz = d_logz; p.error = ctx->error;
+    if (const char *e = getenv("XB_CTC_LOSS_THREADS")) p.threads = atoi(e);
+    StageScope sc(ctx, XB_STAGE_DECODE, 1);
+    hipError_t e = xb::launch_ctc_loss(p, ctx->stream);
+    if (e != hipSuccess) return fail(ctx, e == hipErrorInvalidValue ? XB_ERR_INVALID : XB_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+    return XB_OK;
+}
 
 // ===========================================================================================
 extern "C" {
@@ -1465,6 +1490,7 @@ static int launch_calls(xb_ctx *ctx, const xb_ctx::Call &a, const xb_ctx::Call *
     hipStream_t rs;
     if (!ctx->overlap || !ctx->stream3 || !ctx->scores2 || !ctx->decode_async) {
         rs = ctx->result_stream = ctx->stream;
+        ctx->last_scores = ctx->scores; ctx->last_n = n;
         rc = run_encoder(ctx, a.signal, n, 0, ctx->scores, ctx->ld_nb, sig2, a.n);
         if (rc) return rc;
         rc = run_decode(ctx, ctx->scores, ctx->T, n, 0, ctx->ld_nb, a.alphabet, nullptr, d_seq, d_len, nullptr, nullptr, &out);
@@ -1474,6 +1500,7 @@ static int launch_calls(xb_ctx *ctx, const xb_ctx::Call &a, const xb_ctx::Call *
         // still be reading buffer p ^ 1 on the third stream; the decode that used buffer p two calls ago must be done first
         const int pb = (int)(ctx->batch_idx++ & 1u);
         float *sc = pb ? ctx->scores2 : ctx->scores;
+        ctx->last_scores = sc; ctx->last_n = n;
         rs = ctx->result_stream = ctx->stream3;
         if (ctx->dec_pending[pb]) XB_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->dec_done[pb], 0));
         rc = run_encoder(ctx, a.signal, n, 0, sc, ctx->ld_nb, sig2, a.n);

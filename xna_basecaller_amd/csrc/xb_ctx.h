@@ -177,6 +177,8 @@ struct xb_ctx {
     int deferred_rc = 0;                        // failure of a held-back call that was launched where no status could be returned
     int8_t *fseq = nullptr;                     // (cap, T) / (cap) results of a fused pair before they are split
     int32_t *flen = nullptr;
+    const float *last_scores = nullptr;         // the blank-less scores (T, last_n, ld_nb) of the most recent basecall pass, until the
+    int last_n = 0;                             // next encoder run (xb_validate_chunks reads them where they lie)
 
     // The device staging of the ctc-data tools' host-pointer forms (xb_api_data.hip, Staging): one buffer for all of them --
     // each returns synchronised, so no two are ever live at once.  Grows with the calls; freed by xb_ctx_destroy.
@@ -262,6 +264,8 @@ inline int grow(xb_ctx *ctx, DevBuf *b, size_t bytes)
 int check_ready(xb_ctx *ctx, int n);     // a context with weights and room for a batch of n
 int check_alphabet(xb_ctx *ctx, const char *alphabet);
 int join_async_decode(xb_ctx *ctx);      // flush_held, then the main stream waits for decodes in flight on the third stream
+int ctc_loss_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int n, int has_blank, int ld, const uint8_t *d_targets,
+                 int Lt, const int32_t *d_len, float *d_loss, float *d_logz);
 // ... and two from inside its extern "C" block, beside the pairing logic: flush_held launches a held-back asynchronous basecall;
 // basecall_async makes one of n chunks at d_signal into device outputs (seq, len, out), of pipeline slot `slot` or none
 extern "C" int flush_held(xb_ctx *ctx);

@@ -60,6 +60,27 @@ struct CtcParams {
 hipError_t launch_ctc_scan(const CtcParams &p, hipStream_t stream);
 int ctc_max_positions();
 
+// ---------------------------------------------------------------- CTC-CRF validation loss (xb_ctc.hip)
+// The forward Log scan of the same lattice on the encoder's own scores: RAW scores in either layout, the labels as
+// references.npy holds them; the gather columns and the normalisation (s - logz_crf / T) are the kernel's (the contract is in
+// the public header: xb_ctc_loss).
+struct CtcLossParams {
+    const float *scores;         // (T, N, ld) fp32 RAW scores
+    int T, N, ld, has_blank;
+    float blank;                 // the stay score when the scores come without the blank column
+    int nb, sl;
+    const uint8_t *targets;      // (N, Lt) CTC labels 1 .. nb (0 reads as base 0)
+    int Lt;
+    const int32_t *tlen;         // (N) target lengths (in bases); positions in use = tlen + 1 - sl
+    const float *logz_crf;       // (N) the CRF's log partition function of the same scores
+    float *loss;                 // (N) -logz_ctc / tlen
+    float *logz;                 // (N) or nullptr: logz_ctc
+    unsigned *error;             // bit 2 set when a target length or a label inside it is out of range
+    int threads;                 // 0 = the rule ctc_loss_threads; 64, 128, 256 (experiments: XB_CTC_LOSS_THREADS)
+};
+int ctc_loss_threads(int positions);       // threads per chunk for a label row that gives `positions` lattice positions
+hipError_t launch_ctc_loss(const CtcLossParams &p, hipStream_t stream);
+
 // ---------------------------------------------------------------- beam search (xb_beam.hip)
 // koi.decode.beam_search as compute_scores calls it (crf/basecall.py:43-46): back-guided beam over the CRF with sequence
 // hashes, stay / step merging, qualities from k-mer posteriors, moves.  One wave per chunk.
