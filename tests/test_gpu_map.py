@@ -1,5 +1,9 @@
 """GPU: xb_map_templates through the C ABI against the CPU restatement of its contract (tests/map_ref.py): every output array
-bit-equal.  minimap2 is in no image: parity unpinned, the contract is the header's."""
+bit-equal, and every mapped row of the device's output replayed column by column (map_cases.replay).  The second half takes the
+kernels to their limits with the families of tests/map_cases.py -- stripe hand-off, score workgroup sizes, the LDS / scratch trace
+boundary, the widest row against the longest templates, chunk packing, the scoring's range, odd bytes and lengths -- and the
+library cache through a sequence of libraries and consumers.  minimap2 is in no image: parity unpinned, the contract is the
+header's."""
 import os
 import subprocess
 import sys
@@ -7,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+import map_cases
 import map_ref
 from conftest import GOLDEN, ROOT, make_config
 
@@ -28,54 +33,69 @@ def _library(templates):
     return "".join(templates).encode("ascii"), off
 
 
-def _check(ctx, reads, templates, scoring=map_ref.DEFAULT_SCORING, width=None):
-    rows, lens = map_ref.pack_rows(reads, width)
-    lib, off = _library(templates)
-    got = ctx.map_templates(rows, lens, lib, off, scoring)
-    want = map_ref.map_rows(rows, lens, templates, scoring)
+def _plan(templates):
+    """What the kernels make of the library's longest template: Lmax, columns per lane K, stripes of 64 K columns."""
+    lmax = max(len(t) for t in templates)
+    k = 1 if lmax <= 64 else (2 if lmax <= 128 else 4)
+    return "Lmax %d, K %d, %d stripe(s)" % (lmax, k, -(-lmax // (64 * k)))
+
+
+def _equal(got, want, case, lens):
+    """Every output array bit-equal; the first differing rows printed with their length, the winner in both outputs and the
+    kernels' plan for the library."""
     for k in KEYS:
-        bad = np.flatnonzero((got[k] != want[k]).reshape(len(reads), -1).any(axis=1))
-        assert bad.size == 0, (k, bad[:5], [(reads[b], got[k][b], want[k][b]) for b in bad[:2]])
+        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, (k, got[k].shape, want[k].shape)
+        bad = np.flatnonzero((got[k] != want[k]).reshape(len(case.reads), -1).any(axis=1))
+        if bad.size:
+            rows = [dict(row=int(b), seq_len=int(lens[b]), read=case.reads[b][:80],
+                         device={x: got[x][b].tolist() for x in KEYS[:9]}, restatement={x: want[x][b].tolist() for x in KEYS[:9]},
+                         device_ops=got["ops"][b].tobytes().rstrip(b"\0")[:200], restatement_ops=want["ops"][b].tobytes().rstrip(b"\0")[:200])
+                    for b in bad[:2]]
+            raise AssertionError((k, bad[:5].tolist(), _plan(case.templates), "scoring %s" % (case.scoring,), rows))
+
+
+def _check(ctx, reads, templates, scoring=map_ref.DEFAULT_SCORING, width=None, lens=None, want=None):
+    """The host form on the device against the restatement (want: its outputs when they are at hand), bit-equal on all ten
+    outputs; then every mapped row of the device's output on its own through map_cases.replay."""
+    case = map_cases.Case(reads, templates, tuple(scoring), width, lens)
+    rows, lens = map_cases.pack(case)
+    lib, off = map_cases.library(templates)
+    got = ctx.map_templates(rows, lens, lib, off, scoring)
+    want = map_ref.map_rows(rows, lens, templates, scoring) if want is None else want
+    _equal(got, want, case, lens)
+    map_cases.replay_all(case, got)
     return got
 
 
-def _revcomp(s):
-    return s[::-1].translate(str.maketrans("ACGTXY", "TGCAYX"))
+def _dev_form(ctx, rows, lens, lib, off, scoring, like):
+    """xb_map_templates_dev on device copies of the rows -> the ten outputs as numpy arrays (shapes and types of `like`)."""
+    import torch
+    n, W = rows.shape
+    dev = torch.device("cuda:0")
+    d_seq, d_len = torch.from_numpy(rows).to(dev), torch.from_numpy(lens).to(dev)
+    d_out = {k: torch.full(like[k].shape, 77, dtype=getattr(torch, str(like[k].dtype)), device=dev) for k in KEYS}
+    torch.cuda.synchronize()
+    ctx.map_templates_dev(d_seq.data_ptr(), d_len.data_ptr(), n, W, lib, off, scoring, {k: v.data_ptr() for k, v in d_out.items()})
+    ctx.synchronize()
+    return {k: v.cpu().numpy() for k, v in d_out.items()}
 
 
-def _mutated_reads(templates, count, rng):
-    """Seeded reads off the templates: substitutions, indels, the unnatural base (the template's N) called X / Y / a natural
-    letter / dropped, both strands, random flanks; 5 % unrelated sequences, empty rows, rows of one base."""
-    letters = np.array(list("ACGT"))
-    reads = []
-    for k in range(count):
-        u = rng.random()
-        if u < 0.05:
-            reads.append("".join(rng.choice(letters, rng.integers(20, 140))))
-            continue
-        if u < 0.07:
-            reads.append("")
-            continue
-        if u < 0.09:
-            reads.append(str(rng.choice(list("ACGTXY"))))
-            continue
-        out = []
-        for c in templates[rng.integers(len(templates))]:
-            if c == "N":
-                c = str(rng.choice(["X", "Y", "A", "G", ""], p=[0.5, 0.2, 0.1, 0.1, 0.1]))
-            v = rng.random()
-            if v < 0.04:
-                c = str(rng.choice(letters))
-            elif v < 0.06:
-                c = ""
-            elif v < 0.08:
-                c = c + "".join(rng.choice(letters, rng.integers(1, 4)))
-            out.append(c)
-        s = "".join(rng.choice(letters, rng.integers(0, 12))) + "".join(out) + "".join(rng.choice(letters, rng.integers(0, 12)))
-        lo, hi = rng.integers(0, 15), len(s) - rng.integers(0, 15)
-        s = s[lo:max(hi, lo + 1)] if rng.random() < 0.3 else s
-        reads.append(_revcomp(s) if rng.random() < 0.5 else s)
-    return reads
+def _family(family, arg=None, dev_form=False):
+    """Every case of a family of tests/map_cases.py on one context against the restatement's outputs for it."""
+    ctx = _ctx()
+    for case, want in zip(map_cases.cases(family, arg), map_cases.expected(family, arg)):
+        got = _check(ctx, case.reads, case.templates, case.scoring, case.width, case.lens, want)
+        if dev_form:
+            rows, lens = map_cases.pack(case)
+            lib, off = map_cases.library(case.templates)
+            dev = _dev_form(ctx, rows, lens, lib, off, case.scoring, got)
+            for k in KEYS:
+                assert np.array_equal(dev[k], got[k]), k
+    ctx.close()
+
+
+_revcomp = map_cases.revcomp
+_mutated_reads = map_cases.mutated_reads
 
 
 def _poc():
@@ -238,3 +258,128 @@ def test_cli_reference_end_to_end(tmp_path):
     summary = (tmp_path / "out_summary.tsv").read_bytes().decode().strip().split("\r\n")
     assert len(summary) == 13 and all(len(l.split("\t")) == 27 for l in summary)
     assert len((tmp_path / "calls_summary.tsv").read_bytes().decode().split("\r\n")[0].split("\t")) == 11
+
+
+# ---- the mapper at its limits: the families of tests/map_cases.py, whose conditions tests/test_map_host.py holds on the
+# restatement's outputs -------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("length", map_cases.STRIPE_LENGTHS)
+def test_stripes(length):
+    _family("stripes", length)
+
+
+def test_mixed_lengths():
+    _family("mixed_lengths")
+
+
+@pytest.mark.parametrize("W", map_cases.WAVE_WIDTHS)
+def test_wave_counts(W):
+    _family("wave_counts", W, dev_form=W == 4096)
+
+
+@pytest.mark.parametrize("W", map_cases.TRACE_WIDTHS)
+def test_trace_boundary(W):
+    _family("trace_boundary", W)
+
+
+def test_full_size():
+    _family("full_size", dev_form=True)
+
+
+def test_chunking():
+    _family("chunking")
+
+
+def test_scorings():
+    _family("scorings")
+
+
+def test_letters_and_lengths():
+    _family("letters_and_lengths")
+
+
+def test_scoring_out_of_range_is_refused_and_the_context_survives():
+    from xna_basecaller_amd import _lib
+    ctx = _ctx()
+    templates = _poc()
+    reads = _mutated_reads(templates, 12, np.random.default_rng(29))
+    case = map_cases.Case(reads, templates, map_ref.DEFAULT_SCORING, None)
+    rows, lens = map_cases.pack(case)
+    lib, off = map_cases.library(templates)
+    want = map_ref.map_rows(rows, lens, templates)
+    for at in range(5):
+        for value in (-1, 1001):
+            scoring = list(map_ref.DEFAULT_SCORING)
+            scoring[at] = value
+            with pytest.raises(_lib.XbError) as e:
+                ctx.map_templates(rows, lens, lib, off, scoring)
+            assert e.value.code == _lib.XB_ERR_INVALID and "[0, 1000]" in str(e.value), (at, value)
+            _check(ctx, reads, templates, want=want)
+    for at in range(5):                                    # the ends of the range are inside it
+        scoring = list(map_ref.DEFAULT_SCORING)
+        scoring[at] = 1000
+        _check(ctx, reads[:4], templates, scoring)
+    ctx.close()
+
+
+def test_library_cache_follows_letters_offsets_and_the_consumers():
+    """One context: POC; POC with one letter changed at equal offsets; the same letters with one boundary moved; POC again.
+    Then xb_ctc_targets, xb_ub_tally and xb_barcode_dist, which share the library image, each put another library in its place
+    between two mapper calls on POC.  The restatement keeps no image: a stale one shows as a mismatch."""
+    import bcdist_ref
+    import savectc_ref
+    import ubtally_ref
+    ctx = _ctx()
+    poc = _poc()
+    rng = np.random.default_rng(41)
+    reads = [map_cases.mutate(rng, poc[7], keep=6), poc[3], poc[4], map_cases.revcomp(poc[4])] + _mutated_reads(poc, 20, rng)
+    case = map_cases.Case(reads, poc, map_ref.DEFAULT_SCORING, None)
+    rows, lens = map_cases.pack(case)
+    W = rows.shape[1]
+    want1 = map_ref.map_rows(rows, lens, poc)
+    _check(ctx, reads, poc, want=want1)
+    # one letter of the template that wins read 0, under an '=' column of its alignment
+    t0, r_st = int(want1["tmpl"][0]), int(want1["r_st"][0])
+    ops0 = want1["ops"][0][:want1["n_ops"][0]].tobytes().decode()
+    run = max(ops0.replace("I", "X").replace("D", "X").split("X"), key=len)
+    col = ops0.index(run) + len(run) // 2                   # the middle of the longest run of '='
+    pos = r_st + sum(ops0[k] in "=XD" for k in range(col))
+    assert t0 == 7 and want1["strand"][0] == 1
+    letters2 = list(poc[t0])
+    letters2[pos] = "A" if letters2[pos] != "A" else "C"
+    lib2 = poc[:t0] + ["".join(letters2)] + poc[t0 + 1:]
+    assert [len(t) for t in lib2] == [len(t) for t in poc]
+    want2 = map_ref.map_rows(rows, lens, lib2)
+    assert want2["score"][0] < want1["score"][0]
+    got2 = _check(ctx, reads, lib2, want=want2)
+    # the same letters, the boundary between templates 3 and 4 one letter on
+    lib3 = lib2[:3] + [lib2[3] + lib2[4][:1], lib2[4][1:]] + lib2[5:]
+    assert "".join(lib3) == "".join(lib2)
+    want3 = map_ref.map_rows(rows, lens, lib3)
+    assert want3["score"][2] == want2["score"][2] - 2 and want3["score"][3] == want2["score"][3] - 2
+    _check(ctx, reads, lib3, want=want3)
+    _check(ctx, reads, poc, want=want1)
+    # the consumers on the library of step 2 with the mapper's outputs for it, the mapper on POC behind each
+    lib, off = map_cases.library(lib2)
+    rule = dict(min_accuracy=0.8, min_coverage=0.5)
+    got = ctx.ctc_targets(lens, W, got2, lib, off, **rule)
+    want = savectc_ref.targets(lens, W, got2, lib2, **rule)
+    for k in ("mlen", "blen", "verdict", "target", "target_len"):
+        assert np.array_equal(got[k], want[k]), k
+    assert not np.array_equal(want["target"], savectc_ref.targets(lens, W, got2, poc, **rule)["target"])      # the two libraries differ here
+    _check(ctx, reads, poc, want=want1)
+    counts, acc = ctx.ub_tally(rows, lens, got2, lib, off)
+    want_counts, want_acc = ubtally_ref.tally(rows, lens, got2, lib2)
+    assert np.array_equal(counts, want_counts)
+    for k in ("reads", "err", "cm"):
+        assert np.array_equal(getattr(acc, k), want_acc[k]), k
+    assert not np.array_equal(want_acc["err"], ubtally_ref.tally(rows, lens, got2, poc)[1]["err"])
+    _check(ctx, reads, poc, want=want1)
+    bc = (pos - 8, 20, 3)
+    out = ctx.barcode_dist(rows, lens, got2, lib, off, *bc)
+    want = bcdist_ref.dist(rows, lens, got2, lib2, *bc)
+    for k in bcdist_ref.OUTPUTS:
+        assert np.array_equal(out[k], want[k]), k
+    assert any(not np.array_equal(want[k], bcdist_ref.dist(rows, lens, got2, poc, *bc)[k]) for k in bcdist_ref.OUTPUTS)
+    _check(ctx, reads, poc, want=want1)
+    ctx.close()

@@ -8,7 +8,10 @@ import types
 
 import numpy as np
 
+import pytest
+
 import evalloop_metrics as em
+import map_cases
 import map_ref
 from conftest import GOLDEN
 from xna_basecaller_amd import io as xio
@@ -94,6 +97,62 @@ def test_restatement_against_brute_force_on_tiny_cases():
         q, t = rng.integers(0, 5, rng.integers(1, 20)), rng.integers(0, 5, rng.integers(1, 20))
         for a, b in zip(map_ref.matrices(q, t), map_ref.matrices_by_rows(q, t)):
             assert np.array_equal(a[1:, 1:], b[1:, 1:])
+
+
+def test_cell_by_cell_matrices_equal_the_row_recurrence_at_every_scoring():
+    """The row recurrence (what map_read runs) against the cell-by-cell matrices at the corners of the scoring's range: open = 0,
+    extend = 0, no penalties at all, every value 1000 -- H, E and F, cell for cell, on pairs with ambiguous letters."""
+    rng = np.random.default_rng(8)
+    pairs = [(rng.integers(0, 5, rng.integers(1, 22)), rng.integers(0, 5, rng.integers(1, 22))) for _ in range(36)]
+    pairs += [(np.array([0, 0, 1, 1, 4, 2]), np.array([0, 1, 1, 0, 0, 1, 4, 2])), (np.array([3]), np.array([3])), (np.array([4]), np.array([4, 4]))]
+    for scoring in map_cases.SCORINGS + ((1000, 0, 0, 0, 0), map_ref.DEFAULT_SCORING, (5, 4, 8, 4, 1)):
+        for q, t in pairs:
+            for name, a, b in zip("HEF", map_ref.matrices(q, t, scoring), map_ref.matrices_by_rows(q, t, scoring)):
+                assert np.array_equal(a[1:, 1:], b[1:, 1:]), (scoring, name, q, t)
+
+
+def _family_params():
+    return [pytest.param(f, a, id=f if a is None else "%s-%s" % (f, a)) for f, (_, args, _) in map_cases.FAMILIES.items() for a in args]
+
+
+@pytest.mark.parametrize("family,arg", _family_params())
+def test_every_case_family_is_at_its_limit_in_the_restatement(family, arg):
+    """The condition of every family of tests/map_cases.py on the restatement's outputs alone (the GPU tier compares the device
+    with these same outputs), and replay() on every mapped row of them: the restatement's columns add up to its scores."""
+    map_cases.condition(family, arg)
+    mapped = sum(map_cases.replay_all(case, want) for case, want in zip(map_cases.cases(family, arg), map_cases.expected(family, arg)))
+    assert mapped > 0
+
+
+def test_replay_accepts_the_restatement_and_refuses_corrupted_rows():
+    rng = np.random.default_rng(31)
+    templates = [map_cases.random_letters(rng, L, 0.05) for L in (40, 33, 7)]
+    reads = map_cases.mutated_reads(templates, 40, rng)
+    for scoring in (map_ref.DEFAULT_SCORING, (5, 4, 8, 4, 1), (1, 0, 0, 0, 0), (2, 4, 0, 2, 1), (2, 4, 4, 0, 1)):
+        case = map_cases.Case(reads, templates, scoring, None)
+        rows, lens = map_cases.pack(case)
+        assert map_cases.replay_all(case, map_ref.map_rows(rows, lens, templates, scoring)) >= 30
+    # a read with a substitution, a deletion and an insertion against its template; then the row corrupted by hand
+    t = map_cases.random_letters(rng, 64)
+    read = "TT" + t[:15] + ("A" if t[15] != "A" else "C") + t[16:30] + t[31:46] + "GG" + t[46:]
+    case = map_cases.Case([read, map_cases.revcomp(read)], [t], map_ref.DEFAULT_SCORING, None)
+    rows, lens = map_cases.pack(case)
+    want = map_ref.map_rows(rows, lens, [t], case.scoring)
+    assert map_cases.replay_all(case, want) == 2
+    assert all(c in want["ops"][0].tobytes() for c in b"=XID") and want["strand"].tolist() == [1, -1]
+    for r in range(2):
+        good = {k: want[k][r].copy() for k in want}
+        map_cases.replay(rows[r], lens[r], t, good, case.scoring)
+        flipped = dict(good, ops=good["ops"].copy())
+        at = int(np.flatnonzero(flipped["ops"] == ord("="))[3])
+        flipped["ops"][at] = ord("X")
+        shorter = dict(good, ops=good["ops"].copy())
+        shorter["ops"][at] = ord("D")                                  # a column turned into a gap: the walk ends elsewhere
+        for bad in (flipped, shorter, dict(good, q_st=good["q_st"] + 1), dict(good, score=good["score"] + case.scoring[0]),
+                    dict(good, score=good["score"] - case.scoring[0]), dict(good, strand=np.int8(-good["strand"])),
+                    dict(good, second=good["score"] + 1), dict(good, n_ops=good["n_ops"] - 1), dict(good, r_en=good["r_en"] + 1)):
+            with pytest.raises(AssertionError):
+                map_cases.replay(rows[r], lens[r], t, bad, case.scoring)
 
 
 def test_tie_rules_of_the_restatement():
