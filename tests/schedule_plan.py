@@ -1,6 +1,7 @@
 """
-Python restatement of the encoder's host scheduler (run_encoder / run_lstm_layer, xna_basecaller_amd/csrc/xb_api.hip) and
-the table of schedules that tests/test_gpu_schedules.py runs.
+Python restatement of the encoder's host scheduler (plan_layer, xna_basecaller_amd/csrc/xb_schedule.h, as run_encoder /
+run_lstm_layer of xb_api.hip execute it) and the table of schedules that tests/test_gpu_schedules.py runs.
+tests/test_schedule_host.py holds the C++ planner to this restatement, case by case, without a GPU.
 
 plan(F, n, T, cu_count, env) predicts, for one encoder pass over n chunks of T steps, which plan every LSTM layer takes and
 how many launches the stage counters (xb_get_stage_times) record: `lstm_rec` recurrence launches, `lstm_in` input
@@ -14,7 +15,7 @@ LG_BN = 64          # chunks per group (xb_lstm.hip LG_BN)
 LG_UNITS = 32       # hidden units per member workgroup (xb_lstm.hip LG_UNITS)
 LAYERS = 5
 
-# the knobs the scheduler reads (xb_ctx_create), with the library's defaults
+# the knobs the scheduler reads (xb::knobs_from_env), with the library's defaults
 DEFAULTS = {"XB_LSTM_MODE": 0, "XB_OVERLAP": 1, "XB_TIME_SLABS": 16, "XB_SLAB_STEPS": 0, "XB_LSTM_SIGNAL": 2,
             "XB_LSTM_DUAL": 1, "XB_LSTM_WIDE": 1, "XB_LSTM_LOCAL": 1, "XB_LSTM_SPREAD": 0, "XB_FUSE": 1}
 
@@ -41,7 +42,7 @@ def knobs(env):
     k = dict(DEFAULTS)
     for name, v in (env or {}).items():
         k[name] = int(v)
-    # the clamps of xb_ctx_create
+    # the clamps of xb::knobs_from_env
     k["XB_TIME_SLABS"] = k["XB_TIME_SLABS"] if k["XB_TIME_SLABS"] > 0 else 1
     k["XB_SLAB_STEPS"] = k["XB_SLAB_STEPS"] if k["XB_SLAB_STEPS"] >= 8 else 0
     k["XB_LSTM_SIGNAL"] = k["XB_LSTM_SIGNAL"] if 0 <= k["XB_LSTM_SIGNAL"] <= 2 else 2
@@ -49,7 +50,7 @@ def knobs(env):
 
 
 def time_slabs(T, nts):
-    """Boundaries of nts time slabs over T steps (run_lstm_layer: s_i = T * i / nts)."""
+    """Boundaries of nts time slabs over T steps (LayerPlan::step0: s_i = T * i / nts)."""
     return [T * i // nts for i in range(nts + 1)]
 
 
@@ -57,16 +58,18 @@ def plan(F, n, T, cu_count, env=None, dual_ok=True, signal_ok=True):
     """-> dict(label, tags, lstm_rec, lstm_in, linear, nts, chunk_slabs) for one encoder pass of n chunks."""
     k = knobs(env)
     members, bn = F // LG_UNITS, LG_BN
+    gmax = 8 * ((cu_count // 8) // members)
     tags = []
-    if k["XB_LSTM_MODE"] == 1 or (k["XB_LSTM_MODE"] == 0 and 8 * ((cu_count // 8) // members) < 1):
+    if k["XB_LSTM_MODE"] == 1 or (k["XB_LSTM_MODE"] == 0 and gmax < 1):
         if n > 64 * bn:
             raise ValueError("the one-launch-per-step mode handles at most %d chunks" % (64 * bn))
         tags = ["per-step"]
         rec, gemms = T, 1
         nts, nslabs = 1, 1
     else:
+        if gmax < 1:
+            raise ValueError("the persistent mode needs %d co-resident workgroups, %d CUs hold no group" % (members, cu_count))
         dual_ok = dual_ok and k["XB_LSTM_DUAL"] != 0
-        gmax = 8 * ((cu_count // 8) // members)
         gslab0 = min(gmax, 64)
         slots = cu_count // members
         gwide = min(slots, 64) if k["XB_LSTM_WIDE"] and slots > gslab0 else gslab0

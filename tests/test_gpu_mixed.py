@@ -9,6 +9,7 @@ import pytest
 
 import oracle
 from conftest import encoder_shapes, seeded_state_dict
+from pack_ref import e4m3_decode as _e4m3
 from xna_basecaller_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -31,14 +32,6 @@ def _model(F, nb, L, N, seed):
     sd = seeded_state_dict(keys, shapes, seed=seed)
     x = np.random.default_rng(seed).standard_normal((N, L)).astype(np.float32)
     return sd, x
-
-
-def _e4m3(b):
-    """OCP e4m3 (fn) bytes -> float64."""
-    b = b.astype(np.int64)
-    s, e, m = (b >> 7) & 1, (b >> 3) & 15, b & 7
-    v = np.where(e == 0, m * 2.0 ** -9, (8 + m) * 2.0 ** (e - 10.0))
-    return np.where(s == 1, -v, v)
 
 
 @pytest.mark.parametrize("F,N,L", [(64, 5, 600), (128, 70, 400)])

@@ -1,4 +1,4 @@
-"""GPU: every encoder schedule the host scheduler (run_lstm_layer) can pick, at the shapes the CLI runs, against the serial
+"""GPU: every encoder schedule the host scheduler (plan_layer, executed by run_lstm_layer) can pick, at the shapes the CLI runs, against the serial
 one-launch-per-step order -- byte for byte -- and, on a few seam chunks, against the fp32 oracle.
 
 The table (tests/schedule_plan.py ROWS / PAIR_ROWS) covers uneven time slabs (T 800 / 720 in 6 / 5 slabs), one and two

@@ -1,9 +1,10 @@
 """CPU: the schedule table of tests/test_gpu_schedules.py covers every branch of the encoder's host scheduler.
 
-schedule_plan.plan() restates run_lstm_layer / run_encoder (xb_api.hip); on the 256 CUs of an MI355X every row must plan
-the label it names, and together the rows must reach every branch tag plan() can return.  This checks the table against the
-restatement only: an edit of plan() or of the table that moves a row off its branch, or a tag no row reaches, fails here.
-Whether the C++ planner still agrees with plan() is checked on the GPU, by the launch counts of tests/test_gpu_schedules.py.
+schedule_plan.plan() restates the C++ planner (plan_layer, csrc/xb_schedule.h); on the 256 CUs of an MI355X every row must
+plan the label it names, and together the rows must reach every branch tag plan() can return.  This checks the table against
+the restatement only: an edit of plan() or of the table that moves a row off its branch, or a tag no row reaches, fails here.
+That the C++ planner agrees with plan() is checked on the CPU as well, case by case and launch by launch
+(tests/test_schedule_host.py); the launch counts of tests/test_gpu_schedules.py show that the plan is what the GPU rows execute.
 """
 import pytest
 
@@ -36,7 +37,7 @@ def test_table_reaches_every_branch():
 
 
 def test_planned_launch_counts():
-    """A few counts written out by hand from run_lstm_layer, so that plan() itself is pinned."""
+    """A few counts written out by hand from the planner, so that plan() itself is pinned."""
     T = sp.chunk_T(4000)
     assert T == 800 and sp.time_slabs(T, 6) == [0, 133, 266, 400, 533, 666, 800]
     # 6 event-ordered slabs: a recurrence launch and a GEMM per slab and layer
@@ -58,5 +59,9 @@ def test_planned_launch_counts():
     assert (p["lstm_rec"], p["lstm_in"], p["linear"]) == (5 * 800, 5, 1)
     with pytest.raises(ValueError):
         sp.plan(768, 4097, T, CU, sp.REFERENCE_ENV)
+    # 64 CUs hold no group of 24 members: one launch per step, and the persistent mode is refused when asked for by name
+    assert sp.plan(768, 65, T, 64)["label"] == "per-step"
+    with pytest.raises(ValueError):
+        sp.plan(768, 65, T, 64, {"XB_LSTM_MODE": "2"})
     # a device whose CU count gives no wide range: 513 chunks take the two-groups-per-workgroup kernel
     assert sp.plan(768, 513, T, 192)["label"] == "dual/signal/uneven/ragged"

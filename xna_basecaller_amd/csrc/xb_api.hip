@@ -90,10 +90,10 @@ int alloc_workspaces(xb_ctx *ctx, int cap)
     }
     // + 64 rows: the recurrence's LDS-DMA of a ragged last group reads (and ignores) up to 63 rows past the last chunk
     rc = rc ? rc : dev_alloc(ctx, &ctx->gin, (T * N + 64) * 4 * F);
-    if (ctx->overlap) rc = rc ? rc : dev_alloc(ctx, &ctx->gin2, (T * N + 64) * 4 * F);
+    if (ctx->knobs.overlap) rc = rc ? rc : dev_alloc(ctx, &ctx->gin2, (T * N + 64) * 4 * F);
     rc = rc ? rc : dev_alloc(ctx, &ctx->c_state, N * F);
     rc = rc ? rc : dev_alloc(ctx, &ctx->scores, T * N * Cmax);
-    if (ctx->overlap && ctx->decode_async) rc = rc ? rc : dev_alloc(ctx, &ctx->scores2, T * N * (size_t)ctx->ld_nb);
+    if (ctx->knobs.overlap && ctx->knobs.decode_async) rc = rc ? rc : dev_alloc(ctx, &ctx->scores2, T * N * (size_t)ctx->ld_nb);
     rc = rc ? rc : dev_alloc(ctx, &ctx->alpha, (T + 1) * N * S);
     rc = rc ? rc : dev_alloc(ctx, &ctx->beta, (T + 1) * N * S);
     rc = rc ? rc : dev_alloc(ctx, &ctx->bmax, (T + 1) * N * S);
@@ -163,102 +163,6 @@ int64_t expected_size(const xb_ctx *c, const std::string &name)
     if (name == "encoder.9.linear.weight") return (int64_t)c->O * F;
     if (name == "encoder.9.linear.bias") return c->O;
     return -1;
-}
-
-// OCP e4m3 (fn) encoding of x: round to nearest even, saturating at +-448 (the MFMA's operand format on gfx950)
-uint8_t f32_to_e4m3(float x)
-{
-    const uint8_t sign = std::signbit(x) ? 0x80 : 0x00;
-    const float a = std::fabs(x);
-    if (!(a == a)) return sign | 0x7f;
-    if (a >= 448.0f) return sign | 0x7e;
-    if (a < 0.015625f) {                                   // subnormal: steps of 2^-9
-        const int q = (int)std::nearbyint(std::ldexp(a, 9));
-        return sign | (uint8_t)q;                          // q == 8 is the smallest normal, encoded 0x08 as well
-    }
-    int ex;
-    (void)std::frexp(a, &ex);                              // a = m * 2^ex, m in [0.5, 1)
-    int e = ex - 1;
-    int q = (int)std::nearbyint(std::ldexp(a, 3 - e));     // 8 .. 16
-    if (q == 16) { q = 8; ++e; }
-    const int code = ((e + 7) << 3) | (q - 8);
-    return sign | (uint8_t)(code > 0x7e ? 0x7e : code);
-}
-
-// rows of `cols` floats -> split fp16 (hi, lo) with leading dimension ld.  q8_exp != nullptr: `lo` receives the q8
-// image instead (xb_internal.h): per row and 32 columns [32 x e4m3(hi * 2^e) | 32 x e4m3(lo * 2^(e+11))], e chosen so
-// that the largest |value| lands near 224, and *q8_exp = e.
-void split_rows(const float *src, int rows, int cols, int ld, std::vector<half_t> &hi, std::vector<half_t> &lo,
-                int *q8_exp = nullptr)
-{
-    hi.assign((size_t)rows * ld, (half_t)0.0f);
-    lo.assign((size_t)rows * ld, (half_t)0.0f);
-    int e = 0;
-    if (q8_exp) {
-        float amax = 0.0f;
-        for (size_t i = 0; i < (size_t)rows * cols; ++i) amax = std::fmax(amax, std::fabs(src[i]));
-        if (amax > 0.0f && std::isfinite(amax)) e = (int)std::floor(std::log2(448.0f / amax)) - 1;
-        e = e < -16 ? -16 : (e > 32 ? 32 : e);
-        *q8_exp = e;
-    }
-    uint8_t *q = reinterpret_cast<uint8_t *>(lo.data());
-    for (int r = 0; r < rows; ++r)
-        for (int c = 0; c < cols; ++c) {
-            const float v = src[(size_t)r * cols + c];
-            const half_t h = (half_t)v;
-            const float l = v - (float)h;
-            hi[(size_t)r * ld + c] = h;
-            if (!q8_exp) {
-                lo[(size_t)r * ld + c] = (half_t)l;
-            } else {
-                uint8_t *blk = q + ((size_t)r * ld + (c & ~31)) * 2;
-                blk[c & 31] = f32_to_e4m3(std::ldexp((float)h, e));
-                blk[32 + (c & 31)] = f32_to_e4m3(std::ldexp(l, e + 11));
-            }
-        }
-}
-
-// Fragment-major image of a GEMM B operand for gemm4p_kernel (layout: xb_internal.h, GemmParams::b4).  `hi` / `lo` are
-// split_rows outputs with leading dimension ld (lo = the fp16 residual for nsplit 3, the q8 image for nsplit 2, unused for
-// nsplit 1); rows are padded with zeros to a multiple of 256 so that no tile needs a bounds check.
-void fragment_major(const std::vector<half_t> &hi, const std::vector<half_t> &lo, int rows, int ld, int K, int nsplit,
-                    std::vector<unsigned char> &out, size_t *kstride)
-{
-    const int rows4 = (rows + 255) & ~255, nt32 = rows4 / 32, npc = xb::gemm4_pieces(nsplit), nk = K / 32;
-    *kstride = (size_t)nt32 * npc * 1024;
-    out.assign((size_t)nk * *kstride, 0);
-    const unsigned char *hib = reinterpret_cast<const unsigned char *>(hi.data());
-    const unsigned char *lob = reinterpret_cast<const unsigned char *>(lo.data());
-    if (nsplit == 3) {
-        // the 16x16x32 arithmetic: piece 2 * part + c = rows 16 c .. 16 c + 15 of the block, lane l = row (l & 15), k 8 (l >> 4) .. + 8
-        for (int kt = 0; kt < nk; ++kt)
-            for (int nt = 0; nt < nt32; ++nt)
-                for (int c = 0; c < 2; ++c)
-                    for (int l = 0; l < 64; ++l) {
-                        const int r = nt * 32 + c * 16 + (l & 15);
-                        if (r >= rows) continue;
-                        unsigned char *blk = out.data() + (size_t)kt * *kstride + (size_t)nt * npc * 1024 + (size_t)l * 16;
-                        const size_t e0 = (size_t)r * ld + (size_t)kt * 32 + (size_t)(l >> 4) * 8;
-                        memcpy(blk + c * 1024, hib + e0 * 2, 16);
-                        memcpy(blk + (2 + c) * 1024, lob + e0 * 2, 16);
-                    }
-        return;
-    }
-    for (int kt = 0; kt < nk; ++kt)
-        for (int nt = 0; nt < nt32; ++nt)
-            for (int l = 0; l < 64; ++l) {
-                const int r = nt * 32 + (l & 31), h = l >> 5;
-                if (r >= rows) continue;
-                unsigned char *blk = out.data() + (size_t)kt * *kstride + (size_t)nt * npc * 1024 + (size_t)l * 16;
-                const size_t e0 = (size_t)r * ld + (size_t)kt * 32;          // element offset of the row's k-tile
-                for (int ks = 0; ks < 2; ++ks) memcpy(blk + ks * 1024, hib + (e0 + ks * 16 + h * 8) * 2, 16);
-                if (nsplit == 2) {
-                    // q8 block of the 32 columns: [h8 x 32 | l8 x 32]; the B role reads l8 in lanes 0-31, h8 in lanes 32-63
-                    const unsigned char *q = lob + e0 * 2 + (h == 0 ? 32 : 0);
-                    memcpy(blk + 2 * 1024, q, 16);
-                    memcpy(blk + 3 * 1024, q + 16, 16);
-                }
-            }
 }
 
 // weight upload: the allocation belongs to the current weight set (ctx->wbufs), which the next xb_weights_ready releases
@@ -333,20 +237,20 @@ int launch_row_gemm(xb_ctx *ctx, const NextGemm &ng, int n, int ta, int tb, hipS
     g.a_hi = ng.x_hi + r0 * F; g.a_lo = ng.x_lo + r0 * F;
     g.M = (tb - ta) * n; g.K = F; g.lda = F; g.ldb = F; g.nsplit = ng.layer < 5 ? ctx->ns_in[ng.layer] : ctx->ns_lin;
     g.ldc = ng.ldc; g.out_f32 = ng.out + r0 * ng.ldc;
-    g.one_per_cu = shadow && ctx->gemm_shadow_wgs == 1;
-    g.sn = ctx->gemm_sn;
+    g.one_per_cu = shadow && ctx->knobs.gemm_shadow_wgs == 1;
+    g.sn = ctx->knobs.gemm_sn;
     // which kernel: gemm4p_kernel, except for the slabs that run beside the two-groups-per-workgroup recurrence of a batch
     // above 1024 chunks, where the one-workgroup-per-CU gemm8r_kernel disturbs the recurrence less (same box, ms per step at
     // batch 2048: 477 vs 488 (gemm4p, one workgroup per CU) vs 499; batch 1024: 240 vs 246 vs 235; batch 512: 126.7 vs 129.7 vs
     // 123.0 -- profiles/r03_gemm_kernel_by_batch.txt).  XB_GEMM_SHADOW=4 / 8 forces one of them.
-    const bool use4 = ctx->gemm4 && !(shadow && (ctx->gemm_shadow_kernel == 8 || (ctx->gemm_shadow_kernel == 0 && n > 1024)));
+    const bool use4 = ctx->knobs.gemm4 && !(shadow && (ctx->knobs.gemm_shadow_kernel == 8 || (ctx->knobs.gemm_shadow_kernel == 0 && n > 1024)));
     if (ng.layer < 5) {
         StageScope sc(ctx, XB_STAGE_LSTM_IN, 1, st);
         g.b_hi = ctx->wih_hi[ng.layer]; g.b_lo = ctx->wih_lo[ng.layer]; g.Nn = 4 * F; g.bias = ctx->lbias[ng.layer];
         // main product only (the q8 images stay unused) -- in1_layers: bit l = input projection of layer l (diagnostic
         // XB_IN1_LAYERS, default all five)
         if (use4) { g.b4 = ctx->wih_f4[ng.layer]; g.b4_kstride = ctx->wih_ks; }
-        if (ctx->cfg.precision == XB_PREC_F16F8_IN1 && ((ctx->in1_layers >> ng.layer) & 1)) {
+        if (ctx->cfg.precision == XB_PREC_F16F8_IN1 && ((ctx->knobs.in1_layers >> ng.layer) & 1)) {
             g.nsplit = 1;
             if (use4) { g.b4 = ctx->wih_f4h[ng.layer]; g.b4_kstride = ctx->wih_ksh; }
         }
@@ -380,30 +284,46 @@ int sync_all(xb_ctx *ctx);
 // Recurrence of one layer from `gin` into (xout_hi, xout_lo).  With `next` set, the GEMM that consumes this layer's output
 // is issued as well: either afterwards on the main stream, or -- overlapped mode -- slab by slab on the second stream while
 // the recurrence (192 of the 256 CUs, latency bound) is still running; the main stream then waits for the last slab.
+// Which launches, over which chunks and steps, in which order: xb::plan_layer (xb_schedule.h); this function executes its plan.
 // the arrival counters: SYNC_SLOTS x 32 words, i.e. the 64 group slots of 64 chunks at 64 words each (lstm_kernel LG_SYNC)
 constexpr int SYNC_SLOTS = 128;
+static_assert(xb::PLAN_ERR_INVALID == XB_ERR_INVALID, "a refused plan is an invalid argument");
+
+void set_launch(xb::LstmParams &p, const xb::PlanLaunch &l)
+{
+    p.n0 = l.n0; p.nslab = l.nslab; p.s_begin = l.s_begin; p.s_end = l.s_end; p.dual = l.dual;
+    p.grp0 = l.grp0; p.slab = l.slab; p.xcd_local = l.xcd_local; p.sync_base = l.sync_base;
+}
+
+// the main stream waits for what the second stream has been given so far
+int join_stream2(xb_ctx *ctx)
+{
+    hipEvent_t ev;
+    if (int rc = next_dep(ctx, &ev)) return rc;
+    XB_HIP(ctx, hipEventRecord(ev, ctx->stream2));
+    XB_HIP(ctx, hipStreamWaitEvent(ctx->stream, ev, 0));
+    return XB_OK;
+}
 
 int run_lstm_layer(xb_ctx *ctx, int layer, int n, const float *gin, half_t *xout_hi, half_t *xout_lo, const NextGemm *next)
 {
     const int F = ctx->cfg.features, T = ctx->T;
-    const int members = xb::lstm_members(F), bn = xb::lstm_group_chunks();
-    int mode = ctx->lstm_mode;
-    // groups per persistent launch: every workgroup must be resident at once, and workgroups are dealt to the 8 XCDs
-    // strictly round-robin (block b -> XCD b % 8), i.e. groups g, g + 8, .. share ONE XCD's CUs: F = 768 (24 members per
-    // group, 32 CUs per XCD) allows one group per XCD = 8 groups = 512 chunks per launch
-    // ... and the occupancy calculator has to admit at least one such workgroup per CU (queried once per context); a
-    // context that cannot keep the persistent kernel resident falls back to one launch per time step
     // what the GEMM that reads this layer's output needs as the second part; the int8-limb recurrence writes hi + q8 only
     const int y_need = second_part(layer < 4 ? ctx->ns_in[layer + 1] : ctx->ns_lin);
-    const bool i8 = ctx->lstm_i8 && ctx->whh_q1[layer] && ctx->ns_rec[layer] == 2 && y_need != 1;
-    const int rec_nsplit = i8 ? (ctx->lstm_i8 == 2 ? 5 : 4) : ctx->ns_rec[layer];
+    const bool i8 = ctx->knobs.lstm_i8 && ctx->whh_q1[layer] && ctx->ns_rec[layer] == 2 && y_need != 1;
+    const int rec_nsplit = i8 ? (ctx->knobs.lstm_i8 == 2 ? 5 : 4) : ctx->ns_rec[layer];
+    // the occupancy calculator's word on the persistent kernel, asked once per context and arithmetic
     int (&res)[2] = ctx->lstm_resident[rec_nsplit];
     if (res[0] < 0) res[0] = xb::lstm_resident_per_cu(F, rec_nsplit, 0);
     if (res[1] < 0) res[1] = xb::lstm_resident_per_cu(F, rec_nsplit, 1);
-    const bool dual_ok = ctx->lstm_dual != 0 && res[1] >= 1;
-    const int gmax = res[0] >= 1 ? 8 * ((ctx->cu_count / 8) / members) : 0;
-    if (mode == 0) mode = gmax >= 1 ? 2 : 1;
-    if (mode == 2 && gmax < 1) return fail(ctx, XB_ERR_INVALID, "persistent LSTM needs %d co-resident workgroups, device has %d CUs", members, ctx->cu_count);
+    xb::PlanQuery q{};
+    q.F = F; q.n = n; q.T = T; q.cu_count = ctx->cu_count; q.knobs = ctx->knobs;
+    if (const char *e = getenv("XB_LSTM_SPREAD")) q.spread = atoi(e) != 0;
+    q.has_next = next && ctx->stream2;
+    q.resident1 = res[0] >= 1; q.resident2 = res[1] >= 1; q.signal_ok = ctx->sig_flag != nullptr;
+    const xb::LayerPlan plan = xb::plan_layer(q);
+    if (plan.error) return fail(ctx, plan.error, "%s", plan.message);
+
     XB_HIP(ctx, hipMemsetAsync(ctx->c_state, 0, sizeof(float) * (size_t)n * F, ctx->stream));
     xb::LstmParams p{};
     p.gin = gin; p.w_hi = ctx->whh_hi[layer]; p.w_lo = ctx->whh_lo[layer];
@@ -412,46 +332,26 @@ int run_lstm_layer(xb_ctx *ctx, int layer, int n, const float *gin, half_t *xout
     p.sync = ctx->sync; p.error = ctx->error; p.nsplit = ctx->ns_rec[layer]; p.w_exp = ctx->whh_exp[layer];
     p.y_alt = (p.nsplit == 2 || p.nsplit == 3) && y_need != 0 && y_need != second_part(p.nsplit);
     if (i8) {
-        p.nsplit = ctx->lstm_i8 == 2 ? 5 : 4; p.wq1 = ctx->whh_q1[layer]; p.wq0 = ctx->whh_q0[layer]; p.wscale = ctx->whh_sc[layer];
+        p.nsplit = rec_nsplit; p.wq1 = ctx->whh_q1[layer]; p.wq0 = ctx->whh_q0[layer]; p.wscale = ctx->whh_sc[layer];
     }
-    if (const char *e = getenv("XB_LSTM_SPREAD")) p.spread = atoi(e) != 0;
-    bool overlapped = false;
-    if (mode == 2) {
-        // a workgroup can serve two groups alternately (lstm_kernel DUAL): a launch then holds 2 * gmax groups, and a
-        // group's hand-off latency is covered by the other group's step.  Used when the batch does not fit gmax groups.
-        // WIDE (round 5, the batch cliffs): the XCD-local placement holds gmax = 8 group slots (one group's 24 member workgroups per
-        // XCD), so 513 chunks -- nine groups -- used to take the two-groups-per-workgroup kernel over five slots, i.e. the time of
-        // 1024 chunks, and 1025 chunks a second launch.  The device has cu_count / members = 10 slots' worth of CUs: with a
-        // group's members dealt over ALL XCDs (LstmParams.spread: 3 per XCD and group, 30 of an XCD's 32 CUs at ten slots; the
-        // exchange then goes through write-through stores, a few percent slower per step) a launch holds up to 640 chunks with
-        // one group per workgroup and 1280 with two.  Used exactly where it saves a round: 513..640 and 1025..1280 chunks.
-        const int gslab0 = gmax > 64 ? 64 : gmax;
-        const int gwide = ctx->lstm_wide && ctx->cu_count / members > gslab0 ? (ctx->cu_count / members > 64 ? 64 : ctx->cu_count / members) : gslab0;
-        const bool wide = gwide > gslab0 && ((n > gslab0 * bn && n <= gwide * bn) ||
-                                             (dual_ok && ctx->lstm_dual == 1 && n > 2 * gslab0 * bn && n <= 2 * gwide * bn));
-        const int gslab = wide ? gwide : gslab0;
-        if (wide) p.spread = 1;
-        const bool dual_batch = dual_ok && (ctx->lstm_dual == 2 ? n > bn : n > gslab * bn);
-        const int slab = (dual_batch ? (2 * gslab > 64 ? 64 : 2 * gslab) : gslab) * bn;
-        // the exchange buffer and the counters have 64 group slots: with the whole batch inside them every group keeps its
-        // own slot across launches, so chunk slabs and time slabs combine freely; a larger batch falls back to one launch
-        // per chunk slab over all steps with launch-local slots
-        const bool global_groups = n <= 64 * bn;
-        const int min_steps = ctx->slab_steps > 0 ? ctx->slab_steps : 125;
-        int nts = T / min_steps < ctx->time_slabs ? T / min_steps : ctx->time_slabs;
-        overlapped = next && ctx->overlap && ctx->stream2 && global_groups && nts >= 2;
-        if (!overlapped) nts = 1;
-        int launches = 0;
-        for (int n0 = 0; n0 < n; n0 += slab) launches += nts;
-        if (global_groups) XB_HIP(ctx, hipMemsetAsync(ctx->sync, 0, sizeof(unsigned) * SYNC_SLOTS * 32, ctx->stream));
-        // One launch over all steps that reports its time slabs: the GEMM stream waits on the flag word instead of on an event
-        // behind a slab launch, so the recurrence is not relaunched 16 times per layer (each relaunch costs ~30 us: its
-        // workgroups find their CUs taken by GEMM workgroups that slipped in at the boundary).
-        // Measured (profiles/r03_lstm_slab_signal.txt): the recurrence itself gets 13 % faster (98 -> 85 ms per step at batch 512,
-        // 187 -> 152 ms at 1024), but at batch 512 the GEMM then gets that much less of the chip and the step stays where it was
-        // (120.5 vs 121.2 ms); with two groups per workgroup (batch 1024) the step gains 2 %.  Default: only there.
-        const bool signal_mode = ctx->lstm_signal == 1 || (ctx->lstm_signal == 2 && dual_batch);
-        if (overlapped && ctx->overlap == 1 && signal_mode && ctx->sig_flag && n <= slab && nts <= 64) {
+    p.spread = plan.spread;
+    p.persistent = plan.mode == 2;
+    // the GEMM of time slab i beside the recurrence, on the second stream
+    auto slab_gemm = [&](int i) {
+        int ta, tb;
+        plan.gemm_rows(i, p.reverse != 0, &ta, &tb);
+        return launch_row_gemm(ctx, *next, n, ta, tb, ctx->stream2, true);
+    };
+    if (!p.persistent) {
+        StageScope sc(ctx, XB_STAGE_LSTM_REC, plan.rec_launches);
+        set_launch(p, plan.launch(0, 0));
+        for (int s = 0; s < T; ++s) {
+            p.s_begin = s; p.s_end = s + 1;
+            XB_HIP(ctx, xb::launch_lstm(p, ctx->stream));
+        }
+    } else {
+        if (plan.global_groups) XB_HIP(ctx, hipMemsetAsync(ctx->sync, 0, sizeof(unsigned) * SYNC_SLOTS * 32, ctx->stream));
+        if (plan.ordering == xb::PLAN_SIGNAL) {
             if (ctx->sig_seq > (1u << 30)) {           // keep the 32-bit flag monotonic: start over from an idle device
                 int rc = sync_all(ctx);
                 if (rc) return rc;
@@ -460,78 +360,41 @@ int run_lstm_layer(xb_ctx *ctx, int layer, int n, const float *gin, half_t *xout
             }
             XB_HIP(ctx, hipMemsetAsync(ctx->sig_done, 0, sizeof(unsigned) * 64, ctx->stream));
             {
-                StageScope sc(ctx, XB_STAGE_LSTM_REC, 1);
-                p.n0 = 0; p.nslab = n; p.s_begin = 0; p.s_end = T; p.persistent = 1;
-                p.dual = dual_batch && (ctx->lstm_dual == 2 ? n > bn : n > gslab * bn);
-                p.grp0 = 0; p.slab = 0; p.xcd_local = ctx->lstm_local; p.sync_base = 0;
-                p.sig_flag = ctx->sig_flag; p.sig_done = ctx->sig_done; p.sig_base = ctx->sig_seq; p.sig_nts = nts;
+                StageScope sc(ctx, XB_STAGE_LSTM_REC, plan.rec_launches);
+                set_launch(p, plan.launch(0, 0));
+                p.sig_flag = ctx->sig_flag; p.sig_done = ctx->sig_done; p.sig_base = ctx->sig_seq; p.sig_nts = plan.nts;
                 XB_HIP(ctx, xb::launch_lstm(p, ctx->stream));
             }
-            for (int i = 0; i < nts; ++i) {
-                const int s0 = (int)((long long)T * i / nts), s1 = (int)((long long)T * (i + 1) / nts);
+            for (int i = 0; i < plan.nts; ++i) {
                 XB_HIP(ctx, hipStreamWaitValue32(ctx->stream2, ctx->sig_flag, ctx->sig_seq + (unsigned)i + 1u, hipStreamWaitValueGte,
                                                  0xffffffffu));
-                const int ta = p.reverse ? T - s1 : s0, tb = p.reverse ? T - s0 : s1;
-                if (int rc = launch_row_gemm(ctx, *next, n, ta, tb, ctx->stream2, true)) return rc;
+                if (int rc = slab_gemm(i)) return rc;
             }
-            ctx->sig_seq += (unsigned)nts;
-            hipEvent_t ev;
-            int rc = next_dep(ctx, &ev);
-            if (rc) return rc;
-            XB_HIP(ctx, hipEventRecord(ev, ctx->stream2));
-            XB_HIP(ctx, hipStreamWaitEvent(ctx->stream, ev, 0));
-            return XB_OK;
+            ctx->sig_seq += (unsigned)plan.nts;
+            return join_stream2(ctx);
         }
-        unsigned arrivals = 0;       // per member and group so far in this layer (a launch of k steps arrives k - 1 times)
-        for (int i = 0; i < nts; ++i) {
-            const int s0 = (int)((long long)T * i / nts), s1 = (int)((long long)T * (i + 1) / nts);
+        for (int i = 0; i < plan.nts; ++i) {
             {
-                StageScope sc(ctx, XB_STAGE_LSTM_REC, i == 0 ? launches : 0);
-                for (int n0 = 0; n0 < n; n0 += slab) {
-                    p.n0 = n0; p.nslab = (n - n0) < slab ? (n - n0) : slab;
-                    p.s_begin = s0; p.s_end = s1; p.persistent = 1;
-                    // a tail slab that fits the single-group launch gets one workgroup per group (twice the CUs at work)
-                    p.dual = dual_batch && (ctx->lstm_dual == 2 ? p.nslab > bn : p.nslab > gslab * bn);
-                    // counters are zeroed once per layer (above): consecutive launches follow each other without a memset in
-                    // between, so the next launch's workgroups are dispatched the moment the previous one retires
-                    p.grp0 = global_groups ? n0 / bn : 0;
-                    p.slab = i; p.xcd_local = ctx->lstm_local && i < 16;   // 16 mask bytes per group slot
-                    p.sync_base = global_groups ? arrivals : 0;
-                    if (!global_groups) XB_HIP(ctx, hipMemsetAsync(ctx->sync, 0, sizeof(unsigned) * SYNC_SLOTS * 32, ctx->stream));
+                StageScope sc(ctx, XB_STAGE_LSTM_REC, i == 0 ? plan.rec_launches : 0);
+                for (int j = 0; j < plan.chunk_slabs; ++j) {
+                    set_launch(p, plan.launch(i, j));
+                    if (!plan.global_groups) XB_HIP(ctx, hipMemsetAsync(ctx->sync, 0, sizeof(unsigned) * SYNC_SLOTS * 32, ctx->stream));
                     XB_HIP(ctx, xb::launch_lstm(p, ctx->stream));
                 }
             }
-            arrivals += (unsigned)(s1 - s0 - 1);
-            if (overlapped && ctx->overlap == 1) {
+            if (plan.ordering == xb::PLAN_EVENTS) {
                 hipEvent_t ev;
                 int rc = next_dep(ctx, &ev);
                 if (rc) return rc;
                 XB_HIP(ctx, hipEventRecord(ev, ctx->stream));
                 XB_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ev, 0));
-                const int ta = p.reverse ? T - s1 : s0, tb = p.reverse ? T - s0 : s1;
-                if ((rc = launch_row_gemm(ctx, *next, n, ta, tb, ctx->stream2, true))) return rc;
+                if ((rc = slab_gemm(i))) return rc;
             }
         }
-        if (overlapped && ctx->overlap == 1) {
-            hipEvent_t ev;
-            int rc = next_dep(ctx, &ev);
-            if (rc) return rc;
-            XB_HIP(ctx, hipEventRecord(ev, ctx->stream2));
-            XB_HIP(ctx, hipStreamWaitEvent(ctx->stream, ev, 0));
-        } else if (overlapped) {
-            overlapped = false;     // XB_OVERLAP=2: the GEMM follows on the main stream
-        }
-    } else {
-        if (n > 64 * bn) return fail(ctx, XB_ERR_INVALID, "one-launch-per-step LSTM mode handles at most %d chunks per batch", 64 * bn);
-        StageScope sc(ctx, XB_STAGE_LSTM_REC, T);
-        p.n0 = 0; p.nslab = n; p.persistent = 0;
-        p.dual = dual_ok && ctx->lstm_dual == 2 && n > bn;      // tests only: the per-step variant of the dual kernel
-        for (int s = 0; s < T; ++s) {
-            p.s_begin = s; p.s_end = s + 1;
-            XB_HIP(ctx, xb::launch_lstm(p, ctx->stream));
-        }
+        if (plan.ordering == xb::PLAN_EVENTS) return join_stream2(ctx);
     }
-    if (next && !overlapped) return launch_row_gemm(ctx, *next, n, 0, T, ctx->stream);
+    // PLAN_SERIAL, PLAN_SLABS_SERIAL_GEMM: the GEMM follows on the main stream
+    if (next) return launch_row_gemm(ctx, *next, n, 0, T, ctx->stream);
     return XB_OK;
 }
 
@@ -556,7 +419,7 @@ int run_encoder(xb_ctx *ctx, const float *d_signal, int n, int expand, float *sc
         g.bias = ctx->b3; g.out_hi = ctx->x_hi[0]; g.out_lo = ctx->x_lo[0]; g.ldc = F; g.nsplit = nsplit;
         g.a_exp = 0; g.b_exp = ctx->w3_exp; g.out_exp = 0;
         g.out_fmt = second_part(ctx->ns_in[0]);            // (0: hi only is read -- the GEMM's own form)
-        if (ctx->gemm4) { g.b4 = ctx->w3_f4; g.b4_kstride = ctx->w3_ks; }
+        if (ctx->knobs.gemm4) { g.b4 = ctx->w3_f4; g.b4_kstride = ctx->w3_ks; }
         XB_HIP(ctx, xb::launch_gemm(g, xb::EPI_SILU_SPLIT, ctx->stream));
     }
     // layer l reads gin[l & 1] while the next layer's input projection is written into the other buffer
@@ -753,23 +616,12 @@ XB_API int xb_ctx_create(xb_ctx **out, int device, const xb_config *cfg)
     ctx->O = (int)(S * cfg->n_base);
     ctx->kp = (16 * cfg->winlen + 31) & ~31;
     ctx->ld_nb = (ctx->O + 3) & ~3;
-    ctx->lstm_mode = cfg->lstm_mode;
     {
-        int x3 = cfg->precision == XB_PREC_MIXED ? X3_MIXED_STAGES : 0;
-        if (const char *e = getenv("XB_X3_STAGES")) x3 = (int)strtol(e, nullptr, 0) & 0xfff;      // diagnostic (tools/x3_stages.py)
-        set_stage_arithmetic(ctx, x3);
+        xb::Knobs k;
+        k.lstm_mode = cfg->lstm_mode;
+        ctx->knobs = xb::knobs_from_env(k);
     }
-    if (const char *e = getenv("XB_LSTM_MODE")) ctx->lstm_mode = atoi(e);
-    if (const char *e = getenv("XB_LSTM_DUAL")) ctx->lstm_dual = atoi(e);
-    if (const char *e = getenv("XB_LSTM_WIDE")) ctx->lstm_wide = atoi(e) != 0;
-    if (const char *e = getenv("XB_LSTM_LOCAL")) ctx->lstm_local = atoi(e) != 0;
-    if (const char *e = getenv("XB_DECODE_ASYNC")) ctx->decode_async = atoi(e) != 0;
-    if (const char *e = getenv("XB_IN1_LAYERS")) ctx->in1_layers = atoi(e) & 31;
-    if (const char *e = getenv("XB_LSTM_I8")) ctx->lstm_i8 = atoi(e) == 2 ? 2 : (atoi(e) != 0);
-    if (const char *e = getenv("XB_GEMM4")) ctx->gemm4 = atoi(e) != 0;
-    if (const char *e = getenv("XB_GEMM_SN")) ctx->gemm_sn = atoi(e) > 0 && atoi(e) <= 64 ? atoi(e) : 0;
-    if (const char *e = getenv("XB_GEMM_SHADOW_WGS")) ctx->gemm_shadow_wgs = atoi(e) == 1 ? 1 : 2;
-    if (const char *e = getenv("XB_GEMM_SHADOW")) ctx->gemm_shadow_kernel = atoi(e) == 4 ? 4 : (atoi(e) == 8 ? 8 : 0);
+    set_stage_arithmetic(ctx, ctx->knobs.x3_stages >= 0 ? ctx->knobs.x3_stages : (cfg->precision == XB_PREC_MIXED ? X3_MIXED_STAGES : 0));
 
 #define XB_CREATE_HIP(call)                                                                   \
     do {                                                                                      \
@@ -797,29 +649,14 @@ XB_API int xb_ctx_create(xb_ctx **out, int device, const xb_config *cfg)
         // (a high-priority decode stream was measured: no difference, 6.64 vs 6.69 ms per decode, 125.0 vs 124.7 ms per step)
         XB_CREATE_HIP(hipStreamCreateWithPriority(&ctx->stream3, hipStreamNonBlocking, least));
         for (int p = 0; p < 2; ++p) XB_CREATE_HIP(hipEventCreateWithFlags(&ctx->dec_done[p], hipEventDisableTiming));
-        if (const char *e = getenv("XB_OVERLAP")) ctx->overlap = atoi(e);   // 0 serial, 1 overlapped, 2 time slabs but serial GEMM (A/B)
-        if (const char *e = getenv("XB_TIME_SLABS")) ctx->time_slabs = atoi(e) > 0 ? atoi(e) : 1;
-        if (const char *e = getenv("XB_SLAB_STEPS")) ctx->slab_steps = atoi(e) >= 8 ? atoi(e) : 0;
-        if (const char *e = getenv("XB_LSTM_SIGNAL")) ctx->lstm_signal = atoi(e) < 0 || atoi(e) > 2 ? 2 : atoi(e);
-        if (const char *e = getenv("XB_FUSE")) ctx->fuse_ok = atoi(e) != 0;
         // rocprofv3 counter collection (--pmc) runs one kernel at a time; hipStreamWaitValue32 is a spinning kernel
         // (__amd_rocclr_streamOpsWait) there, which would wait for a flag the serialised recurrence can never raise: slab launches
-        {
-            const char *cc = getenv("ROCPROF_COUNTER_COLLECTION"), *cn = getenv("ROCPROF_COUNTERS");
-            if ((cc && atoi(cc) != 0) || (cn && *cn)) ctx->lstm_signal = 0;
-        }
+        if (xb::counter_collection_from_env()) ctx->knobs.lstm_signal = 0;
     }
 
     // co-scheduling two calls: only where the pair fits one launch of two groups per workgroup
-    // (512 = the XCD-local capacity of a launch at features 768; with the wide placement -- run_lstm_layer -- a pair of up to
-    //  2 x 640 chunks still is ONE launch of two groups per workgroup, so batch sizes 513..640 pair as well)
-    int pair_cap = 512;
-    {
-        const int members = xb::lstm_members(cfg->features), slots = members > 0 ? ctx->cu_count / members : 0;
-        if (ctx->lstm_wide && members > 0 && 8 * ((ctx->cu_count / 8) / members) * xb::lstm_group_chunks() == 512 && slots > 8)
-            pair_cap = (slots > 64 ? 64 : slots) * xb::lstm_group_chunks();
-    }
-    if (!(ctx->fuse_ok && ctx->overlap == 1 && ctx->lstm_dual != 0 && cfg->max_batch <= pair_cap)) ctx->fuse_ok = 0;
+    ctx->fuse_ok = ctx->knobs.fuse && ctx->knobs.overlap == 1 && ctx->knobs.lstm_dual != 0 &&
+                   cfg->max_batch <= xb::pair_capacity(cfg->features, ctx->cu_count, ctx->knobs.lstm_wide);
     const size_t F = cfg->features;
     int rc = alloc_workspaces(ctx, cfg->max_batch);
     rc = rc ? rc : dev_alloc(ctx, &ctx->xh, (size_t)64 * 2 * 2 * 64 * F);
@@ -832,10 +669,10 @@ XB_API int xb_ctx_create(xb_ctx **out, int device, const xb_config *cfg)
     ctx->error = ctx->sync + SYNC_SLOTS * 32;
     XB_CREATE_HIP(hipMemset(ctx->sync, 0, sizeof(unsigned) * (SYNC_SLOTS * 32 + 32 + 64)));
     ctx->sig_done = ctx->sync + SYNC_SLOTS * 32 + 32;
-    if (ctx->lstm_signal) {
+    if (ctx->knobs.lstm_signal) {
         int can = 0;
         if (hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, device) != hipSuccess || !can) {
-            ctx->lstm_signal = 0;
+            ctx->knobs.lstm_signal = 0;
         } else {
             void *fp = nullptr;
             if (hipExtMallocWithFlags(&fp, 8, hipMallocSignalMemory) != hipSuccess) {
@@ -847,7 +684,7 @@ XB_API int xb_ctx_create(xb_ctx **out, int device, const xb_config *cfg)
                 ctx->sig_flag = static_cast<unsigned *>(fp);
                 XB_CREATE_HIP(hipMemset(fp, 0, 8));
             } else {
-                ctx->lstm_signal = 0;
+                ctx->knobs.lstm_signal = 0;
             }
         }
     }
@@ -944,64 +781,45 @@ XB_API int xb_weights_ready(xb_ctx *ctx)
     if ((rc = upload(ctx, &ctx->b3, *need("encoder.2.conv.bias")))) return rc;
     std::vector<half_t> hi, lo;
     // every weight tensor in the form its stage's arithmetic reads (q8 image for nsplit 2, fp16 residual for 3)
-    split_rows(need("encoder.2.conv.weight")->data(), F, 16 * W, ctx->kp, hi, lo, ctx->ns_conv == 2 ? &ctx->w3_exp : nullptr);
+    xb::split_rows(need("encoder.2.conv.weight")->data(), F, 16 * W, ctx->kp, hi, lo, ctx->ns_conv == 2 ? &ctx->w3_exp : nullptr);
     if ((rc = upload(ctx, &ctx->w3_hi, hi))) return rc;
     if ((rc = upload(ctx, &ctx->w3_lo, lo))) return rc;
     std::vector<unsigned char> f4;
-    fragment_major(hi, lo, F, ctx->kp, ctx->kp, ctx->ns_conv, f4, &ctx->w3_ks);
+    xb::fragment_major(hi, lo, F, ctx->kp, ctx->kp, ctx->ns_conv, f4, &ctx->w3_ks);
     if ((rc = upload(ctx, &ctx->w3_f4, f4))) return rc;
     for (int l = 0; l < 5; ++l) {
         const std::string pre = "encoder." + std::to_string(4 + l) + ".rnn.";
         const float *wih = need(pre + "weight_ih_l0")->data(), *whh = need(pre + "weight_hh_l0")->data();
         const float *bih = need(pre + "bias_ih_l0")->data(), *bhh = need(pre + "bias_hh_l0")->data();
-        // gate-interleaved row order: row' = unit*4 + gate  <-  row = gate*F + unit  (gates i,f,g,o)
-        std::vector<float> wi((size_t)4 * F * F), wh((size_t)4 * F * F), bb((size_t)4 * F);
-        for (int u = 0; u < F; ++u)
-            for (int q = 0; q < 4; ++q) {
-                memcpy(&wi[((size_t)u * 4 + q) * F], &wih[((size_t)q * F + u) * F], sizeof(float) * F);
-                memcpy(&wh[((size_t)u * 4 + q) * F], &whh[((size_t)q * F + u) * F], sizeof(float) * F);
-                bb[(size_t)u * 4 + q] = bih[(size_t)q * F + u] + bhh[(size_t)q * F + u];
-            }
-        split_rows(wi.data(), 4 * F, F, F, hi, lo, ctx->ns_in[l] == 2 ? &ctx->wih_exp[l] : nullptr);
+        std::vector<float> wi, wh, bb;
+        xb::gate_interleave(wih, whh, bih, bhh, F, wi, wh, bb);
+        xb::split_rows(wi.data(), 4 * F, F, F, hi, lo, ctx->ns_in[l] == 2 ? &ctx->wih_exp[l] : nullptr);
         if ((rc = upload(ctx, &ctx->wih_hi[l], hi))) return rc;
         if ((rc = upload(ctx, &ctx->wih_lo[l], lo))) return rc;
-        fragment_major(hi, lo, 4 * F, F, F, ctx->ns_in[l], f4, &ctx->wih_ks);       // (the k-tile stride is the same for nsplit 2 and 3)
+        xb::fragment_major(hi, lo, 4 * F, F, F, ctx->ns_in[l], f4, &ctx->wih_ks);       // (the k-tile stride is the same for nsplit 2 and 3)
         if ((rc = upload(ctx, &ctx->wih_f4[l], f4))) return rc;
         if (ctx->cfg.precision == XB_PREC_F16F8_IN1) {
-            fragment_major(hi, lo, 4 * F, F, F, 1, f4, &ctx->wih_ksh);
+            xb::fragment_major(hi, lo, 4 * F, F, F, 1, f4, &ctx->wih_ksh);
             if ((rc = upload(ctx, &ctx->wih_f4h[l], f4))) return rc;
         }
-        split_rows(wh.data(), 4 * F, F, F, hi, lo, ctx->ns_rec[l] == 2 ? &ctx->whh_exp[l] : nullptr);
+        xb::split_rows(wh.data(), 4 * F, F, F, hi, lo, ctx->ns_rec[l] == 2 ? &ctx->whh_exp[l] : nullptr);
         if ((rc = upload(ctx, &ctx->whh_hi[l], hi))) return rc;
         if ((rc = upload(ctx, &ctx->whh_lo[l], lo))) return rc;
         ctx->whh_q1[l] = nullptr;
-        if (ctx->lstm_i8 && ctx->ns_rec[l] == 2 && (F == 64 || F % 128 == 0)) {
-            // int8-limb image: per row q = round(W / s * 32512), s = max |W| of the row; q = 256 d1 + d0 with both digits in
-            // [-128, 127]; h is published as round(h * 32512) the same way, so W h = s / 32512^2 * sum q_w q_h
-            std::vector<int8_t> d1((size_t)4 * F * F), d0((size_t)4 * F * F);
-            std::vector<float> sc((size_t)4 * F);
-            for (int r = 0; r < 4 * F; ++r) {
-                float mx = 0.0f;
-                for (int k = 0; k < F; ++k) mx = std::max(mx, std::fabs(wh[(size_t)r * F + k]));
-                const float sr = mx > 0.0f ? mx : 1.0f;
-                sc[r] = sr / (32512.0f * 32512.0f);
-                for (int k = 0; k < F; ++k) {
-                    const int q = (int)std::lrintf(wh[(size_t)r * F + k] / sr * 32512.0f);
-                    const int lo8 = ((q + 128) & 255) - 128;
-                    d0[(size_t)r * F + k] = (int8_t)lo8;
-                    d1[(size_t)r * F + k] = (int8_t)((q - lo8) >> 8);
-                }
-            }
+        if (ctx->knobs.lstm_i8 && ctx->ns_rec[l] == 2 && (F == 64 || F % 128 == 0)) {
+            std::vector<int8_t> d1, d0;
+            std::vector<float> sc;
+            xb::i8_limbs(wh.data(), 4 * F, F, d1, d0, sc);
             if ((rc = upload(ctx, &ctx->whh_q1[l], d1))) return rc;
             if ((rc = upload(ctx, &ctx->whh_q0[l], d0))) return rc;
             if ((rc = upload(ctx, &ctx->whh_sc[l], sc))) return rc;
         }
         if ((rc = upload(ctx, &ctx->lbias[l], bb))) return rc;
     }
-    split_rows(need("encoder.9.linear.weight")->data(), ctx->O, F, F, hi, lo, ctx->ns_lin == 2 ? &ctx->wl_exp : nullptr);
+    xb::split_rows(need("encoder.9.linear.weight")->data(), ctx->O, F, F, hi, lo, ctx->ns_lin == 2 ? &ctx->wl_exp : nullptr);
     if ((rc = upload(ctx, &ctx->wl_hi, hi))) return rc;
     if ((rc = upload(ctx, &ctx->wl_lo, lo))) return rc;
-    fragment_major(hi, lo, ctx->O, F, F, ctx->ns_lin, f4, &ctx->wl_ks);
+    xb::fragment_major(hi, lo, ctx->O, F, F, ctx->ns_lin, f4, &ctx->wl_ks);
     if ((rc = upload(ctx, &ctx->wl_f4, f4))) return rc;
     if ((rc = upload(ctx, &ctx->bl, *need("encoder.9.linear.bias")))) return rc;
     ctx->host_w.clear();
@@ -1039,6 +857,63 @@ extern "C" __attribute__((visibility("default"))) int xb_internal_defer_after(xb
     ctx->held.after_arg = arg;
     return 1;
 }
+
+// The host logic on its own, for the CPU tests (tests/host_logic.py): the planner and the knobs of xb_schedule.h, the packer
+// of xb_pack.h.  None touches the device or needs a context.  Not part of the public header.
+#define XB_INTERNAL extern "C" __attribute__((visibility("default")))
+XB_INTERNAL void xb_internal_knobs_from_env(xb::Knobs *out) { *out = xb::knobs_from_env(); }
+XB_INTERNAL int xb_internal_pair_capacity(int F, int cu_count, int lstm_wide) { return xb::pair_capacity(F, cu_count, lstm_wide); }
+// -> the plan's error, or the number of its launch records (xb::LayerPlan::launch), of which the first max_launches are written
+XB_INTERNAL int xb_internal_plan_layer(const xb::PlanQuery *q, xb::LayerPlan *plan, xb::PlanLaunch *launches, int max_launches)
+{
+    *plan = xb::plan_layer(*q);
+    if (plan->error) return plan->error;
+    const bool one = plan->mode != 2 || plan->ordering == xb::PLAN_SIGNAL;
+    const int nts = one ? 1 : plan->nts, slabs = one ? 1 : plan->chunk_slabs;
+    for (int i = 0, r = 0; i < nts; ++i)
+        for (int j = 0; j < slabs && r < max_launches; ++j) launches[r++] = plan->launch(i, j);
+    return nts * slabs;
+}
+XB_INTERNAL int xb_internal_f32_to_e4m3(float x) { return xb::f32_to_e4m3(x); }
+// hi, lo: (rows, ld) fp16; q8_exp as xb::split_rows takes it
+XB_INTERNAL void xb_internal_split_rows(const float *src, int rows, int cols, int ld, half_t *hi, half_t *lo, int *q8_exp)
+{
+    std::vector<half_t> h, l;
+    xb::split_rows(src, rows, cols, ld, h, l, q8_exp);
+    memcpy(hi, h.data(), h.size() * sizeof(half_t));
+    memcpy(lo, l.data(), l.size() * sizeof(half_t));
+}
+// -> the image's bytes; written to `out` when it has room for them
+XB_INTERNAL size_t xb_internal_fragment_major(const half_t *hi, const half_t *lo, int rows, int ld, int K, int nsplit, unsigned char *out,
+                                              size_t out_bytes, size_t *kstride)
+{
+    const std::vector<half_t> h(hi, hi + (size_t)rows * ld), l(lo, lo + (size_t)rows * ld);
+    std::vector<unsigned char> f4;
+    xb::fragment_major(h, l, rows, ld, K, nsplit, f4, kstride);
+    if (out && out_bytes >= f4.size()) memcpy(out, f4.data(), f4.size());
+    return f4.size();
+}
+// wi, wh: (4F, F); bb: (4F)
+XB_INTERNAL void xb_internal_gate_interleave(const float *wih, const float *whh, const float *bih, const float *bhh, int F, float *wi,
+                                             float *wh, float *bb)
+{
+    std::vector<float> a, b, c;
+    xb::gate_interleave(wih, whh, bih, bhh, F, a, b, c);
+    memcpy(wi, a.data(), a.size() * sizeof(float));
+    memcpy(wh, b.data(), b.size() * sizeof(float));
+    memcpy(bb, c.data(), c.size() * sizeof(float));
+}
+// d1, d0: (rows, cols); scale: (rows)
+XB_INTERNAL void xb_internal_i8_limbs(const float *w, int rows, int cols, int8_t *d1, int8_t *d0, float *scale)
+{
+    std::vector<int8_t> a, b;
+    std::vector<float> c;
+    xb::i8_limbs(w, rows, cols, a, b, c);
+    memcpy(d1, a.data(), a.size());
+    memcpy(d0, b.data(), b.size());
+    memcpy(scale, c.data(), c.size() * sizeof(float));
+}
+#undef XB_INTERNAL
 
 XB_API int xb_stream_wait_event(xb_ctx *ctx, void *hip_event)
 {
@@ -1488,7 +1363,7 @@ static int launch_calls(xb_ctx *ctx, const xb_ctx::Call &a, const xb_ctx::Call *
     if (b) { out.qstr = ctx->q_fseq; out.moves = ctx->q_fmoves; out.probs = ctx->u_fprobs; }
     int rc;
     hipStream_t rs;
-    if (!ctx->overlap || !ctx->stream3 || !ctx->scores2 || !ctx->decode_async) {
+    if (!ctx->knobs.overlap || !ctx->stream3 || !ctx->scores2 || !ctx->knobs.decode_async) {
         rs = ctx->result_stream = ctx->stream;
         ctx->last_scores = ctx->scores; ctx->last_n = n;
         rc = run_encoder(ctx, a.signal, n, 0, ctx->scores, ctx->ld_nb, sig2, a.n);

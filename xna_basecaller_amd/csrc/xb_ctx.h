@@ -1,5 +1,7 @@
-// xb_ctx.h -- the context behind the C ABI, shared by its two translation units: xb_api.hip (context lifetime, weights, the
-// encoder schedule, decode, pairing, the host pipeline) and xb_api_data.hip (the ctc-data tools).  Private to csrc/.
+// xb_ctx.h -- the context behind the C ABI, shared by its two translation units: xb_api.hip (context lifetime, weight upload,
+// the execution of the encoder's plans, decode, pairing, the host pipeline) and xb_api_data.hip (the ctc-data tools).  The host
+// arithmetic xb_api.hip acts on lives in two headers without HIP that are checked on their own: xb_schedule.h (the knobs and the
+// planner of the encoder schedule) and xb_pack.h (the forms a weight tensor is uploaded in).  Private to csrc/.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,6 +17,8 @@
 
 #include "../../include/xna_basecaller.h"
 #include "xb_internal.h"
+#include "xb_pack.h"
+#include "xb_schedule.h"
 
 using xb::half_t;
 
@@ -73,11 +77,11 @@ struct xb_ctx {
     hipStream_t stream_copy = nullptr;     // H2D of the next batch beside the compute of the current one
     std::vector<hipEvent_t> deps;    // timing-less events for the cross-stream dependencies (reused every call)
     size_t dep_next = 0;
-    int overlap = 1, time_slabs = 16;   // XB_OVERLAP / XB_TIME_SLABS (upper bound; a slab is at least 125 steps)
-    int slab_steps = 0;                 // XB_SLAB_STEPS: minimum steps per time slab (default 125)
-    // one recurrence launch per layer that reports its time slabs to the GEMM stream (XB_LSTM_SIGNAL, default on where
-    // hipStreamWaitValue32 is supported): flag word, the value the last slab of the previous layer published, slab counters
-    int lstm_signal = 2;                // 0 off, 1 whenever one launch holds the batch, 2 (default) only above 512 chunks (two groups per workgroup)
+    // the environment knobs (xb_schedule.h), read once by xb_ctx_create; lstm_mode starts from xb_config's, and lstm_signal is
+    // switched off where the device or a profiler cannot serve the signal-ordered slabs
+    xb::Knobs knobs;
+    // one recurrence launch per layer that reports its time slabs to the GEMM stream (knobs.lstm_signal): flag word, the value
+    // the last slab of the previous layer published, slab counters
     unsigned *sig_flag = nullptr, *sig_done = nullptr;
     unsigned sig_seq = 0;
     mutable std::string err;
@@ -100,15 +104,9 @@ struct xb_ctx {
     // projections also as hi-only images for XB_PREC_F16F8_IN1
     unsigned char *w3_f4 = nullptr, *wih_f4[5] = {}, *wih_f4h[5] = {}, *wl_f4 = nullptr;
     size_t w3_ks = 0, wih_ks = 0, wih_ksh = 0, wl_ks = 0;
-    int gemm_sn = 0;                           // XB_GEMM_SN: N tiles per XCD super-tile of gemm4p_kernel (0 = gemm_super_n's rule; experiments)
-    int gemm_shadow_kernel = 0;                // XB_GEMM_SHADOW: 0 auto (by batch size), 4 gemm4p_kernel, 8 gemm8r_kernel for the slabs beside the recurrence
-    int gemm_shadow_wgs = 2;                   // XB_GEMM_SHADOW_WGS=1: GEMM slabs beside the recurrence run one workgroup per CU
-    int gemm4 = 1;                             // XB_GEMM4=0: gemm8r_kernel (one workgroup per CU) instead of gemm4p_kernel (A/B comparisons)
     std::vector<void *> wbufs;                 // weight allocations of the current xb_weights_ready (freed by the next one)
-    int8_t *whh_q1[5] = {}, *whh_q0[5] = {};   // int8-limb recurrence (lstm_i8): balanced digits of W_hh, gate-interleaved rows
+    int8_t *whh_q1[5] = {}, *whh_q0[5] = {};   // int8-limb recurrence (knobs.lstm_i8): balanced digits of W_hh, gate-interleaved rows
     float *whh_sc[5] = {};                     // ... and the factor that turns the integer sum into the recurrent term
-    int lstm_i8 = 0;                           // XB_LSTM_I8 (with precision f16f8 / f16f8i): recurrence on int8 digits; 1 = all
-                                               // four digit products, 2 = without d0 x d0
 
     // activations / workspaces
     float *d_signal = nullptr;
@@ -134,7 +132,6 @@ struct xb_ctx {
     float *u_buf = nullptr;
     unsigned *sync = nullptr;    // [64 groups * 32] counters + error word at the end
     unsigned *error = nullptr;
-    int lstm_mode = 0;
     // workgroups of the persistent kernel admitted per CU, by recurrence arithmetic (nsplit 1..5) and one / two groups per
     // workgroup (occupancy query, lazily; -1 = not asked yet)
     int lstm_resident[6][2] = {{-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}};
@@ -143,15 +140,6 @@ struct xb_ctx {
     // precisions; XB_PREC_MIXED (and the diagnostic XB_X3_STAGES mask) mix 2 and 3.  An activation tensor's second part
     // (q8 image or fp16 residual) follows the stage that CONSUMES it.
     int ns_conv = 3, ns_in[5] = {3, 3, 3, 3, 3}, ns_rec[5] = {3, 3, 3, 3, 3}, ns_lin = 3;
-    int in1_layers = 31;         // XB_IN1_LAYERS (diagnostic): layers whose input projection XB_PREC_F16F8_IN1 reduces
-    int decode_async = 0;        // XB_DECODE_ASYNC=1: the decode of a batch runs on the third stream beside the next batch's conv + first
-                                 // GEMM (rounds 2-3) instead of on the main stream with the chip to itself (round 4 default: the same step
-                                 // time at every batch size -- the step is bound by the kernels' summed CU-time -- and the decode at 0.49-0.52
-                                 // of the HBM roofline instead of 0.35-0.42: profiles/r04_decode_placement.txt)
-    int lstm_local = 1;          // XB_LSTM_LOCAL=0: always exchange h with write-through stores (A/B)
-    int lstm_wide = 1;           // XB_LSTM_WIDE: 1 (default) batches just above a launch's XCD-local capacity get up to cu_count / members group
-                                 // slots with the groups dealt over all XCDs instead of a second round (run_lstm_layer); 0: never
-    int lstm_dual = 1;           // XB_LSTM_DUAL: 0 never, 1 when a launch would otherwise need a second chunk slab, 2 always
 
     // Two asynchronous basecalls in flight are co-scheduled once the caller has opted in with xb_reserve_pairing (contexts of at
     // most 512 chunks; XB_FUSE=0 refuses): the first xb_basecall_chunks_dev of a pair is held back until the second arrives, then

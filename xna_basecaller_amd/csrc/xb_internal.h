@@ -152,7 +152,8 @@ struct GemmParams {
     int gin_n;                   // EPI_BIAS_F32: > 0 selects the member-major gin layout (below) with gin_n chunks per time step
     // gemm4p_kernel (two workgroups per CU, B straight from a fragment-major weight image, see xb_encoder.hip): used when b4
     // is set; otherwise gemm8r_kernel (one 256 x 256 workgroup per CU, both operands through LDS; kept as the A/B reference)
-    const unsigned char *b4;     // [K / 32][rows4 / 32][pieces][64 lanes][16 B], rows4 = Nn rounded up to 256 (zero rows)
+    const unsigned char *b4;     // [K / 32][rows4 / 32][pieces][64 lanes][16 B], rows4 = Nn rounded up to 256 (zero rows); the pieces:
+                                 // xb_pack.h (gemm4_pieces), which builds the image
     size_t b4_kstride;           // bytes between consecutive k-tiles of b4 = rows4 / 32 * pieces * 1024
     int one_per_cu;              // gemm4p: 1 = at most one workgroup per CU (launches beside the recurrence)
     int sn;                      // gemm4p: N tiles per XCD super-tile (0 = the rule gemm_super_n; XB_GEMM_SN, experiments)
@@ -160,13 +161,6 @@ struct GemmParams {
 // The three-product arithmetic (nsplit 3) of both GEMM kernels runs on v_mfma_f32_16x16x32_f16 -- per accumulator and k-tile of 32:
 // lo*hi, hi*lo, hi*hi (round 5; rounds 1-4 ran it on 32x32x16 per k-step of 16, which sums the same products in another order).
 // The chip holds a 13 % higher clock on the 16x16x32 shape (profiles/r05_mfma_shape_ubench.txt).
-// pieces per 32-row block and k-tile of the fragment-major image for a given nsplit (lane l = 32 h + r holds row r):
-//   nsplit 1, 2: piece 0, 1: the 8 fp16 `hi` values of columns 32 kt + 16 ks + 8 h .. + 8, ks = 0, 1
-//   nsplit 2: pieces 2, 3 = bytes 0..15 / 16..31 of the q8 half the B role reads (h = 0: the l8 codes of the 32 columns, h = 1:
-//   the h8 codes)
-//   nsplit 3 (16x16x32 fragments): lane l = 16 g + r; piece 2 part + c (part 0 = hi, 1 = lo; c = 0, 1) holds row 16 c + r's eight
-//   values of columns 32 kt + 8 g .. + 8
-inline int gemm4_pieces(int nsplit) { return nsplit == 1 ? 2 : 4; }
 // gin layout (input projection of an LSTM layer, written by the GEMM, read by lstm_kernel): row m = t * n + chunk, column
 // c = unit * 4 + gate.  Stored member-major, [t][c / 128][chunk][c % 128]: the 64 chunks x 128 gate columns a recurrence
 // workgroup (32 units) needs per step are ONE contiguous 32 KiB block instead of 64 segments 4F floats apart.
@@ -220,12 +214,10 @@ struct LstmParams {
     int sig_nts;
 };
 hipError_t launch_lstm(const LstmParams &p, hipStream_t stream);
-// members (workgroups per group) and chunks per group of the LSTM kernel for feature size F
+// (members -- workgroups per group -- and chunks per group of the LSTM kernel: xb_schedule.h, lstm_members / lstm_group_chunks)
 // workgroups of the persistent kernel the occupancy calculator admits per CU for feature size F (0: the kernel cannot be
 // resident at all, e.g. LDS or registers taken by another tenant's limits); the persistent mode needs >= 1
 int lstm_resident_per_cu(int F, int nsplit, int dual);
-int lstm_members(int F);
-int lstm_group_chunks();
 bool lstm_supported_features(int F);
 // ---------------------------------------------------------------- template mapper (xb_align.hip)
 // xb_map_templates: every called row against every template of a small library on both strands (the contract is in the

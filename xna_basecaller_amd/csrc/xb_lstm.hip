@@ -3,6 +3,7 @@
 //
 // Replaces the LSTM x5 of Model.forward (ub-bonito/bonito/nn.py:176-193,216-220; crf/model.py:147-160).
 #include "xb_enc_common.h"
+#include "xb_schedule.h"
 
 namespace {
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -26,8 +27,8 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // (bounded spin), workgroup barrier, then EVERY load of the exchanged bytes is an sc1 load
 // (LDS-DMA with the sc1 bit), so no L1 line can be stale and no fence is needed.
 // ======================================================================================
-constexpr int LG_BN = 64;        // chunks per group (2 MFMA column tiles)
-constexpr int LG_UNITS = 32;     // hidden units per member workgroup
+using xb::LG_BN;                 // chunks per group (2 MFMA column tiles) -- both in xb_schedule.h, which the host planner shares
+using xb::LG_UNITS;              // hidden units per member workgroup
 constexpr int LG_SYNC = 64;      // words between the counter slots of consecutive 64-chunk groups
 constexpr unsigned long long LG_SPIN_CYCLES = 4000000000ull;   // ~2 s at 2 GHz
 constexpr int ST_LD = 68;        // dword stride of one unit-pair row of the h staging (64 chunks + 4: 2-way reads)
@@ -1014,9 +1015,6 @@ int lstm_resident_per_cu(int F, int nsplit, int dual)
     default: return 0;
     }
 }
-
-int lstm_members(int F) { return F / LG_UNITS; }
-int lstm_group_chunks() { return LG_BN; }
 
 hipError_t launch_lstm(const LstmParams &p, hipStream_t stream)
 {
