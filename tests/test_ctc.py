@@ -11,38 +11,8 @@ import torch
 
 import oracle
 from conftest import make_config, random_scores
+from ctc_wide_cases import ctc_logz_f64 as _ctc_logz_f64, label_rows as _targets
 from pairs import PAIR_IDS, PAIRS
-
-
-def _targets(rng, N, Lt, nb, sl, lens=None):
-    t = rng.integers(1, nb + 1, (N, Lt)).astype(np.int32)
-    if lens is None:
-        lens = rng.integers(sl, Lt + 1, N)
-        lens[0], lens[-1] = Lt, sl                      # the longest and the shortest legal targets
-    lens = np.asarray(lens, dtype=np.int32)
-    for b in range(N):
-        t[b, lens[b]:] = 0
-    return t, lens
-
-
-def _ctc_logz_f64(x, stay_idx, move_idx, npos, semiring="log"):
-    """float64 torch restatement over the dense scores x (T, N, C): returns logz (N,) as a differentiable tensor."""
-    T, N, _ = x.shape
-    n = stay_idx.shape[1]
-    out = []
-    zero = torch.full((1,), -1e38, dtype=torch.float64)
-    for b in range(N):
-        a = torch.full((n,), -1e38, dtype=torch.float64)
-        a[0] = 0.0
-        si = torch.as_tensor(stay_idx[b], dtype=torch.long)
-        mi = torch.as_tensor(move_idx[b], dtype=torch.long)
-        for t in range(T):
-            x0 = a + x[t, b, si]
-            x1 = torch.cat([zero, a[:-1] + x[t, b, mi]])
-            st = torch.stack([x0, x1])
-            a = torch.logsumexp(st, 0) if semiring == "log" else st.max(0).values
-        out.append(a[npos[b] - 1])
-    return torch.stack(out)
 
 
 @pytest.mark.parametrize("nb,sl", PAIRS, ids=PAIR_IDS)

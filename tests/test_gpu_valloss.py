@@ -5,12 +5,15 @@ the contract is bit-equality with the composition the parent commit ran on the h
 float32, oracle.ctc_logz on the result, `-(logz / length)`.  Shapes are tests/test_ctc.py's GPU_CASES (T not a multiple of
 the prefetch depth, more than 256 positions, a single position, length = Lt, every state length and base count) plus T = 3 on
 a larger context and a batch of one."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 import oracle
 from conftest import encoder_shapes, make_config, random_scores, seeded_state_dict
+from ctc_wide_cases import BLANK, ctc_logz_f64 as _ctc_logz_f64, label_rows, loss_reference as _reference
 from xna_basecaller_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -20,38 +23,7 @@ GPU_CASES = [(4, 37, 3, 9, 3), (5, 120, 5, 40, 3), (6, 200, 7, 130, 3), (6, 64, 
 # (nb, T, N, Lt, sl, T of the context): the shapes above on a context of their own T, then the two added cases
 CASES = [c + (c[1],) for c in GPU_CASES] + [(5, 3, 3, 9, 3, 64), (6, 50, 1, 20, 3, 50)]
 IDS = ["%d-%d-%d-%d-sl%d-ctx%d" % c for c in CASES]
-BLANK = 2.0
-
-
-def _targets(rng, N, Lt, nb, sl, lens=None):
-    """tests/test_ctc.py's ragged label rows, as references.npy holds them (uint8)."""
-    t = rng.integers(1, nb + 1, (N, Lt)).astype(np.uint8)
-    if lens is None:
-        lens = rng.integers(sl, Lt + 1, N)
-        lens[0], lens[-1] = Lt, sl                      # the longest and the shortest legal targets (N = 1: the shortest)
-    lens = np.asarray(lens, dtype=np.int32)
-    for b in range(N):
-        t[b, lens[b]:] = 0
-    return t, lens
-
-
-def _with_blank(blankless, nb, blank=BLANK):
-    T, N, C = blankless.shape
-    full = np.empty((T, N, C // nb, nb + 1), np.float32)
-    full[..., 0] = np.float32(blank)
-    full[..., 1:] = blankless.reshape(T, N, C // nb, nb)
-    return full.reshape(T, N, -1)
-
-
-def _reference(ctx, scores, targets, lens, nb, sl, has_blank):
-    """The parent commit's host composition: (loss, logz_ctc)."""
-    T = scores.shape[0]
-    lz = ctx.crf_logz(scores, has_blank=has_blank)
-    full = scores if has_blank else _with_blank(scores, nb)
-    x = full - (lz / np.float32(T))[None, :, None]
-    assert x.dtype == np.float32
-    logz = oracle.ctc_logz(x, targets.astype(np.int32), lens, nb, sl)["logz"]
-    return -(logz / lens.astype(np.float32)), logz
+_targets = functools.partial(label_rows, dtype=np.uint8)        # the ragged label rows as references.npy holds them
 
 
 def _case(nb, T, N, Lt, sl):
@@ -79,25 +51,6 @@ def test_loss_of_given_scores_is_the_host_composition_bit_for_bit(nb, T, N, Lt, 
     assert np.array_equal(logz0, ref0_logz)
     assert np.array_equal(loss0, ref0)
     ctx.close()
-
-
-def _ctc_logz_f64(x, stay_idx, move_idx, npos):
-    """tests/test_ctc.py's float64 lattice, restated: logz (N,) over the dense scores x (T, N, C)."""
-    T, N, _ = x.shape
-    n = stay_idx.shape[1]
-    out = []
-    zero = torch.full((1,), -1e38, dtype=torch.float64)
-    for b in range(N):
-        a = torch.full((n,), -1e38, dtype=torch.float64)
-        a[0] = 0.0
-        si = torch.as_tensor(stay_idx[b], dtype=torch.long)
-        mi = torch.as_tensor(move_idx[b], dtype=torch.long)
-        for t in range(T):
-            x0 = a + x[t, b, si]
-            x1 = torch.cat([zero, a[:-1] + x[t, b, mi]])
-            a = torch.logsumexp(torch.stack([x0, x1]), 0)
-        out.append(a[npos[b] - 1])
-    return torch.stack(out)
 
 
 @pytest.mark.parametrize("labels", ["NACGT", "NACGTXY"])
