@@ -291,6 +291,43 @@ XB_API int xb_ctc_loss_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int
 XB_API int xb_validate_chunks(xb_ctx *ctx, const float *signal, int n, const char *alphabet, const uint8_t *targets, int Lt,
                               const int32_t *target_lengths, int8_t *seq, int32_t *seq_len, float *loss);
 
+/*
+ * The training criterion with its gradient, where the scores lie: the loss of
+ * CTC_CRF.ctc_loss(scores, targets, lengths, loss_clip, reduction, normalise_scores=True) (crf/model.py:118-131) per chunk, and
+ * d (reduced loss) / d RAW scores -- what the reference obtains by autograd through seqdist.
+ *   scores, targets, target_lengths, has_blank, the limits and the lattice arithmetic: those of xb_ctc_loss (every fetched score
+ *           is s - logz_crf / (float)T; forward recurrence with alpha_0 .. alpha_T kept; the backward recurrence of xb_ctc_logz:
+ *           beta_t[l] = sum2(stay + beta_{t+1}[l], move + beta_{t+1}[l+1]), sum2 = max, exp, exp, add, log, zero = -1e38).
+ *   loss_clip > 0 clips (<= 0: no clipping); mean != 0: reduction 'mean', else 'none'.
+ *   R[t, col] = the sum, over the positions l of the chunk whose stay (move) column is col, in ASCENDING l and starting from
+ *           0.0f, of the restricted posteriors of xb_ctc_logz (gstay / gmove):
+ *           exp(((alpha_t[l] + stay) + beta_{t+1}[l]) - logz),  exp(((alpha_t[l] + move) + beta_{t+1}[l+1]) - logz).
+ *           Positions that share a column (a repeated k-mer) are added in that order and no other: the result is the same
+ *           bytes on every run (no floating-point atomics), and the bytes of np.add.at over the positions.
+ *   P[t, col] = the CRF edge posterior of xb_crf_scans (post) of the same raw scores.
+ *   w[b]    = -(1.0f / (float)length[b]), then / (float)n when mean; 0 where loss_clip > 0 and the unclipped loss lies outside
+ *           [0, loss_clip].
+ *   grad (T, n, C) fp32, dense, in the layout of scores: grad[t, b, col] = (R - P) * w[b], three fp32 operations, no
+ *           contraction; columns no position maps to get (0.0f - P) * w.  has_blank = 0: the C = S*n_base columns are the
+ *           with-blank gradient without the blank columns (the blank is a constant): the stay edges add nothing, the move
+ *           column state*n_base + base takes P from column state*(n_base+1) + base + 1.
+ *   loss (n) = xb_ctc_loss's, clamped to [0, loss_clip] when loss_clip > 0 (the mean over the chunks is the caller's).
+ *   Validation as xb_ctc_loss: the host form refuses a bad length or label with the chunk's index before anything is staged; the
+ *           _dev form reports it by the next xb_synchronize (XB_ERR_INVALID), the offending chunk's loss is not written and its
+ *           gradient is all zero (either sign), the other chunks' results are right, and the context stays usable.
+ *   Precondition: every row has a path, T >= length - state_len.  A row without one gives unspecified values.
+ *   Workspace: the alpha stash ((T + 1) x (Lt - state_len + 1) floats per chunk) belongs to the context and grows with the calls;
+ *           one launch owns at most XB_CTC_SCRATCH_MB megabytes of it (default 1024, read on every call), so a call runs as
+ *           launches of as many chunks as fit, at least one; the result does not depend on the split.  P lies in the decode's
+ *           workspace.  Not a stage of xb_get_stage_times.  The _dev form returns without waiting, its outputs are ordered on
+ *           xb_result_stream.
+ * Parity unpinned: seqdist is absent; bit-equal to the restatement tests/ctcgrad_ref.py (oracle.decode, oracle.ctc_logz, np.add.at).
+ */
+XB_API int xb_ctc_loss_grad(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, const uint8_t *targets, int Lt,
+                            const int32_t *target_lengths, float loss_clip, int mean, float *loss, float *grad);
+XB_API int xb_ctc_loss_grad_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const uint8_t *d_targets, int Lt,
+                                const int32_t *d_target_lengths, float loss_clip, int mean, float *d_loss, float *d_grad);
+
 /* compute_scores (crf/basecall.py:27-82), viterbi branch: encode + decode without materialising
  * the blank column or copying scores off the device. */
 XB_API int xb_basecall_chunks(xb_ctx *ctx, const float *signal, int n, const char *alphabet,

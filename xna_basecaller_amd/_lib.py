@@ -34,7 +34,7 @@ EXPORTS = [
     "xb_ub_tally", "xb_ub_tally_dev", "xb_barcode_dist", "xb_barcode_dist_dev", "xb_dtw_segment", "xb_dtw_segment_dev", "xb_dtw_scratch_bytes",
     "xb_splice_library", "xb_splice_chunks", "xb_splice_chunks_dev",
     "xb_spike_model", "xb_spike_chunks", "xb_spike_chunks_dev", "xb_synth_chunks", "xb_synth_chunks_dev",
-    "xb_ctc_loss", "xb_ctc_loss_dev", "xb_validate_chunks",
+    "xb_ctc_loss", "xb_ctc_loss_dev", "xb_validate_chunks", "xb_ctc_loss_grad", "xb_ctc_loss_grad_dev",
 ]
 XB_COMM_ID_BYTES = 128
 # xb_status (include/xna_basecaller.h)
@@ -150,6 +150,8 @@ def load():
     lib.xb_ctc_loss.argtypes = [vp, vp, ip, ip, ip, vp, ip, vp, vp, vp]
     lib.xb_ctc_loss_dev.argtypes = lib.xb_ctc_loss.argtypes
     lib.xb_validate_chunks.argtypes = [vp, vp, ip, C.c_char_p, vp, ip, vp, vp, vp, vp]
+    lib.xb_ctc_loss_grad.argtypes = [vp, vp, ip, ip, ip, vp, ip, vp, C.c_float, ip, vp, vp]
+    lib.xb_ctc_loss_grad_dev.argtypes = lib.xb_ctc_loss_grad.argtypes
     lib.xb_result_stream.argtypes = [vp]
     lib.xb_result_stream.restype = C.c_void_p
     lib.xb_set_profiling.argtypes = [vp, ip]
@@ -208,6 +210,15 @@ def output_level(qscores=False, ub_probs=False):
     """Output level of the Viterbi decode: 0 the bases, 1 also qualities and moves (the _q entry points), 2 also the letter
     probabilities (_ub; they imply the qualities)."""
     return 2 if ub_probs else int(bool(qscores))
+
+
+def _mean_flag(reduction):
+    """CTC_CRF.ctc_loss's reduction as the flag of xb_ctc_loss_grad."""
+    if reduction == "mean":
+        return 1
+    if reduction in ("none", None):
+        return 0
+    raise ValueError("Unknown reduction type {}".format(reduction))
 
 
 def _lens_last(out):
@@ -426,6 +437,25 @@ class Context:
     def ctc_loss_dev(self, d_scores, T, n, has_blank, d_targets, Lt, d_lengths, d_loss, d_logz=None):
         self._check(self.lib.xb_ctc_loss_dev(self.h, _ptr(d_scores), int(T), int(n), int(bool(has_blank)), _ptr(d_targets), int(Lt),
                                              _ptr(d_lengths), _ptr(d_loss), _ptr(d_logz)))
+
+    def ctc_loss_grad(self, scores, targets, target_lengths, has_blank=None, loss_clip=None, reduction="mean"):
+        """xb_ctc_loss_grad: RAW scores (T, n, C) in either layout -> (loss (n,) fp32, clamped when clipping; grad (T, n, C) fp32 =
+        d CTC_CRF.ctc_loss(..., loss_clip, reduction, normalise_scores=True) / d scores)."""
+        scores, has_blank = self._scores(scores, has_blank)
+        T, n, _ = scores.shape
+        targets, tl = self._labels(targets, target_lengths, n)
+        loss = np.empty((n,), np.float32)
+        grad = np.empty_like(scores)
+        self._check(self.lib.xb_ctc_loss_grad(self.h, scores.ctypes.data, T, n, has_blank, targets.ctypes.data, targets.shape[1],
+                                              tl.ctypes.data, float(loss_clip or 0.0), _mean_flag(reduction), loss.ctypes.data,
+                                              grad.ctypes.data))
+        return loss, grad
+
+    def ctc_loss_grad_dev(self, d_scores, T, n, has_blank, d_targets, Lt, d_lengths, d_loss, d_grad, loss_clip=None,
+                          reduction="mean"):
+        self._check(self.lib.xb_ctc_loss_grad_dev(self.h, _ptr(d_scores), int(T), int(n), int(bool(has_blank)), _ptr(d_targets),
+                                                  int(Lt), _ptr(d_lengths), float(loss_clip or 0.0), _mean_flag(reduction),
+                                                  _ptr(d_loss), _ptr(d_grad)))
 
     def validate_chunks(self, signal, alphabet, targets, target_lengths):
         """xb_validate_chunks: signal (n, chunk_len), targets (n, Lt), target_lengths (n) -> (seq (n, T) int8 left-packed ASCII,

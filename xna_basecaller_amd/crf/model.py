@@ -98,8 +98,15 @@ class CTC_CRF:
         -(R - P) / length per chunk, with R the restricted posteriors scattered over (stay_idx, move_idx) and, when the
         scores were normalised here, P = the CRF's edge posteriors (every time step carries exactly one edge of a path,
         so the normalisation's own derivative is -P); zero where the loss was clipped, / N for the mean.
+        Scores that are a torch tensor on the device take the autograd route instead (crf/loss.py: xb_ctc_loss_grad_dev where
+        the scores lie) and return a tensor with a grad_fn.
         """
         m = self._owner()
+        if isinstance(scores, torch.Tensor) and scores.is_cuda:
+            if want_grad:
+                raise ValueError("want_grad belongs to the numpy route: a device tensor's gradient comes by loss.backward()")
+            from .loss import ctc_loss
+            return ctc_loss(self, m, scores, targets, target_lengths, loss_clip, reduction, normalise_scores)
         scores = np.ascontiguousarray(scores, dtype=np.float32)
         T, N, _ = scores.shape
         tl = np.asarray(target_lengths, dtype=np.int32)

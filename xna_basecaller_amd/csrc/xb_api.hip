@@ -573,6 +573,45 @@ int ctc_loss_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int
     return XB_OK;
 }
 
+// The loss and d loss / d scores of n chunks from device-resident RAW scores (T, n, ld), for xb_api_data.hip (xb_ctc_loss_grad): the
+// Log scans leave logZ_crf and the edge posteriors in the decode's own workspaces (logz, qbuf); the lattice kernel runs over
+// as many chunks per launch as the stash bound holds, then the fill kernel over all.  All on the main stream, nothing waited for
+// unless a workspace grows.
+int ctc_grad_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int n, int has_blank, int ld, const uint8_t *d_targets,
+                 int Lt, const int32_t *d_len, float loss_clip, int mean, float *d_loss, float *d_grad)
+{
+    const xb_config &c = ctx->cfg;
+    const int np = Lt - (c.state_len - 1);
+    if (np < 1 || np > xb::ctc_max_positions())
+        return fail(ctx, XB_ERR_INVALID, "%s: target width %d gives %d positions, supported: 1..%d", who, Lt, np, xb::ctc_max_positions());
+    const size_t slot = xb::ctc_grad_slot_floats(T, np);
+    const size_t per_launch = xb::ctc_grad_chunks_per_launch(T, np, n, xb::ctc_scratch_bound(getenv("XB_CTC_SCRATCH_MB")));
+    if (int rc = grow(ctx, &ctx->ctcgrad.stash, per_launch * slot * sizeof(float))) return rc;
+    if (int rc = grow(ctx, &ctx->ctcgrad.w, sizeof(float) * (size_t)c.max_batch)) return rc;
+    ScanOut so;
+    so.logz = ctx->logz; so.post = ctx->qbuf;
+    if (int rc = run_decode(ctx, d_scores, T, n, has_blank, ld, nullptr, nullptr, nullptr, nullptr, nullptr, &so)) return rc;
+    xb::CtcGradParams q{};
+    xb::CtcLossParams &p = q.l;
+    p.scores = d_scores; p.T = T; p.N = n; p.ld = ld; p.has_blank = has_blank; p.blank = c.blank_score;
+    p.nb = c.n_base; p.sl = c.state_len; p.targets = d_targets; p.Lt = Lt; p.tlen = d_len;
+    p.logz_crf = ctx->logz; p.loss = d_loss; p.error = ctx->error;
+    if (const char *e = getenv("XB_CTC_LOSS_THREADS")) p.threads = atoi(e);
+    q.post = ctx->qbuf; q.ldq = (ctx->S * (c.n_base + 1) + 3) & ~3;
+    q.stash = static_cast<float *>(ctx->ctcgrad.stash.p); q.slot = slot;
+    q.loss_clip = loss_clip; q.mean = mean ? 1 : 0;
+    q.w = static_cast<float *>(ctx->ctcgrad.w.p); q.grad = d_grad;
+    for (size_t first = 0; first < (size_t)n; first += per_launch) {
+        q.first = (int)first;
+        q.count = (int)std::min<size_t>(per_launch, (size_t)n - first);
+        hipError_t e = xb::launch_ctc_grad(q, ctx->stream);
+        if (e != hipSuccess) return fail(ctx, e == hipErrorInvalidValue ? XB_ERR_INVALID : XB_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+    }
+    hipError_t e = xb::launch_ctc_grad_fill(q, ctx->stream);
+    if (e != hipSuccess) return fail(ctx, e == hipErrorInvalidValue ? XB_ERR_INVALID : XB_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+    return XB_OK;
+}
+
 // ===========================================================================================
 extern "C" {
 
@@ -717,7 +756,7 @@ XB_API void xb_ctx_destroy(xb_ctx *ctx)
     for (auto &ev : ctx->events) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto &b : ctx->bufs) (void)hipFree(b.p);
     for (auto &b : ctx->wsbufs) (void)hipFree(b.p);
-    for (DevBuf *b : {&ctx->staging, &ctx->map.image, &ctx->map.partial, &ctx->map.scratch, &ctx->dtw.scratch, &ctx->splice.pool,
+    for (DevBuf *b : {&ctx->staging, &ctx->map.image, &ctx->map.partial, &ctx->map.scratch, &ctx->dtw.scratch, &ctx->ctcgrad.stash, &ctx->ctcgrad.w, &ctx->splice.pool,
                       &ctx->splice.rows, &ctx->splice.table, &ctx->spike.model})
         if (b->p) (void)hipFree(b->p);
     for (auto &o : ctx->dtw.off) {

@@ -1073,6 +1073,47 @@ XB_API int xb_ctc_loss(xb_ctx *ctx, const float *scores, int T, int n, int has_b
     return xb_synchronize(ctx);
 }
 
+// the loss with d loss / d scores (the contract is in the public header)
+XB_API int xb_ctc_loss_grad_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const uint8_t *d_targets, int Lt,
+                                const int32_t *d_target_lengths, float loss_clip, int mean, float *d_loss, float *d_grad)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    if (!d_scores || !d_targets || !d_target_lengths || !d_loss || !d_grad)
+        return fail(ctx, XB_ERR_INVALID, "xb_ctc_loss_grad: null device pointer");
+    int ld = 0;
+    if (int rc = loss_args(ctx, "xb_ctc_loss_grad", T, n, has_blank, Lt, &ld)) return rc;
+    if (int rc = enter(ctx, true)) return rc;
+    return ctc_grad_run(ctx, "xb_ctc_loss_grad", d_scores, T, n, has_blank ? 1 : 0, ld, d_targets, Lt, d_target_lengths, loss_clip, mean,
+                        d_loss, d_grad);
+}
+
+XB_API int xb_ctc_loss_grad(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, const uint8_t *targets, int Lt,
+                            const int32_t *target_lengths, float loss_clip, int mean, float *loss, float *grad)
+{
+    if (!ctx) return XB_ERR_INVALID;
+    if (!scores || !targets || !target_lengths || !loss || !grad) return fail(ctx, XB_ERR_INVALID, "xb_ctc_loss_grad: null host pointer");
+    int ld = 0;
+    if (int rc = loss_args(ctx, "xb_ctc_loss_grad", T, n, has_blank, Lt, &ld)) return rc;
+    if (int rc = labels_ok(ctx, "xb_ctc_loss_grad", targets, n, Lt, target_lengths)) return rc;
+    if (int rc = enter(ctx, false)) return rc;
+    const size_t N = (size_t)n, cells = (size_t)T * N * ld;
+    Staging st{ctx};
+    const auto d_targets = st.take<uint8_t>(N * Lt);
+    const auto d_len = st.take<int32_t>(N);
+    const auto d_loss = st.take<float>(N);
+    const auto d_grad = st.take<float>(cells);
+    if (int rc = st.ready()) return rc;
+    XB_HIP(ctx, hipMemcpyAsync(ctx->scores, scores, sizeof(float) * cells, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(d_targets, targets, N * Lt, hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(d_len, target_lengths, N * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = ctc_grad_run(ctx, "xb_ctc_loss_grad", ctx->scores, T, n, has_blank ? 1 : 0, ld, d_targets, Lt, d_len, loss_clip, mean,
+                              d_loss, d_grad))
+        return rc;
+    XB_HIP(ctx, hipMemcpyAsync(loss, d_loss, N * 4, hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(grad, d_grad, sizeof(float) * cells, hipMemcpyDeviceToHost, ctx->stream));
+    return xb_synchronize(ctx);
+}
+
 // validate_one_step's device half: signal -> encoder (blank-less scores) -> Viterbi decode, as xb_basecall_chunks runs them, then the
 // loss from the scores the decode read
 XB_API int xb_validate_chunks(xb_ctx *ctx, const float *signal, int n, const char *alphabet, const uint8_t *targets, int Lt,

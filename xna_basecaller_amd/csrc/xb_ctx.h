@@ -217,6 +217,12 @@ struct xb_ctx {
         bool loaded = false;
     } spike;
 
+    // The loss gradient (xb_ctc_loss_grad): the alpha stash of one launch of the lattice kernel (bounded by XB_CTC_SCRATCH_MB)
+    // and the chunks' weights; the posteriors lie in the decode's qbuf.  Grow with the calls; freed by xb_ctx_destroy.
+    struct CtcGradState {
+        DevBuf stash, w;
+    } ctcgrad;
+
     bool profiling = false;
     std::vector<StageEvent> events;
     float stage_ms[XB_STAGE_COUNT] = {};
@@ -254,6 +260,8 @@ int check_alphabet(xb_ctx *ctx, const char *alphabet);
 int join_async_decode(xb_ctx *ctx);      // flush_held, then the main stream waits for decodes in flight on the third stream
 int ctc_loss_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int n, int has_blank, int ld, const uint8_t *d_targets,
                  int Lt, const int32_t *d_len, float *d_loss, float *d_logz);
+int ctc_grad_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int n, int has_blank, int ld, const uint8_t *d_targets,
+                 int Lt, const int32_t *d_len, float loss_clip, int mean, float *d_loss, float *d_grad);
 // ... and two from inside its extern "C" block, beside the pairing logic: flush_held launches a held-back asynchronous basecall;
 // basecall_async makes one of n chunks at d_signal into device outputs (seq, len, out), of pipeline slot `slot` or none
 extern "C" int flush_held(xb_ctx *ctx);

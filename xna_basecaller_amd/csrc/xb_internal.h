@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "xb_ctc_split.h"
+
 namespace xb {
 
 typedef _Float16 half_t;
@@ -80,6 +82,25 @@ struct CtcLossParams {
 };
 int ctc_loss_threads(int positions);       // threads per chunk for a label row that gives `positions` lattice positions
 hipError_t launch_ctc_loss(const CtcLossParams &p, hipStream_t stream);
+
+// The loss with d loss / d scores (the contract is in the public header: xb_ctc_loss_grad).  launch_ctc_grad runs the lattice
+// of chunks [first, first + count) -- forward with alpha stashed, backward with the restricted posteriors summed per score
+// column in ascending position -- and writes loss, w and the gradient's columns that the chunk's positions map to;
+// launch_ctc_grad_fill, after all of them, writes the remaining columns of all N chunks and zeroes the refused chunks.
+struct CtcGradParams {
+    CtcLossParams l;             // l.ld = the columns of the layout (dense rows); l.loss (N): clamped to [0, loss_clip] when clipping
+    int first, count;            // launch_ctc_grad: workgroup i serves chunk first + i with stash slot i
+    const float *post;           // (T, N, ldq) the CRF's edge posteriors of the same scores, blank layout (xb_crf_scans)
+    int ldq;
+    float *stash;                // count slots of `slot` floats, slot >= ctc_grad_slot_floats(T, Lt - sl + 1) (xb_ctc_split.h)
+    size_t slot;
+    float loss_clip;             // > 0: chunks whose loss lies outside [0, loss_clip] get a zero gradient
+    int mean;                    // 1: w = -(1 / length) / N, else -(1 / length)
+    float *w;                    // (N) workspace: the lattice kernel leaves a chunk's weight here for the fill kernel
+    float *grad;                 // (T, N, l.ld)
+};
+hipError_t launch_ctc_grad(const CtcGradParams &q, hipStream_t stream);
+hipError_t launch_ctc_grad_fill(const CtcGradParams &q, hipStream_t stream);
 
 // ---------------------------------------------------------------- beam search (xb_beam.hip)
 // koi.decode.beam_search as compute_scores calls it (crf/basecall.py:43-46): back-guided beam over the CRF with sequence
