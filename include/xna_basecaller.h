@@ -328,6 +328,80 @@ XB_API int xb_ctc_loss_grad(xb_ctx *ctx, const float *scores, int T, int n, int 
 XB_API int xb_ctc_loss_grad_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const uint8_t *d_targets, int Lt,
                                 const int32_t *d_target_lengths, float loss_clip, int mean, float *d_loss, float *d_grad);
 
+/*
+ * Training the CRF head with everything below it frozen: `bonito train -F` at --num-unfreeze-top 1 (cli/train.py:134-158), where
+ * the one trainable layer is LinearCRFEncoder, scores = scale * tanh(X W^T + b) (encoder.9.linear.{weight,bias}), and no
+ * gradient with respect to X is needed.  C = S * n_base blank-less columns, F = features.
+ *
+ * xb_head_grad: the gradient of W and b from the gradient of the scores.
+ *   y, dy   (rows, C) fp32, dense: the RAW blank-less scores as xb_encode(expand_blanks = 0) writes them, and d loss / d scores
+ *           in that layout (xb_ctc_loss_grad with has_blank = 0).
+ *   x_hi, x_lo  (rows, F) fp16 bit patterns, value = hi + lo, 16-byte aligned.  Both NULL: the last LSTM layer's output that
+ *           the most recent encoder pass left in the context (what xb_debug_layer_output(which = 1) reads); rows must then be
+ *           T * n of that pass (XB_ERR_STATE otherwise).
+ *   dw (C, F), db (C) fp32:  dZ = dy * (scale - y * y / scale);  dw[o, f] = sum_m dZ[m, o] X[m, f];  db[o] = sum_m dZ[m, o].
+ *   Arithmetic: e = 14 - exponent(max |dy| * scale) (frexp's exponent; 0 for a gradient of zeros): dZ is formed in fp32 as
+ *           (dy * 2^e) * (((scale - y) * (scale + y)) / scale) -- scale - y^2 / scale in the form that does not cancel where
+ *           tanh saturates -- no contraction, and split into fp16 hi + lo where the operand is loaded
+ *           -- it is never written to memory, and a mean loss's gradients of 1e-6 and less do not underflow fp16.  The
+ *           products hi*hi + hi*lo + lo*hi run on the fp16 MFMA with fp32 accumulation, as the forward's head does; db sums the
+ *           scaled fp32 dZ in float64.  The rows are cut into slabs of whole 32-row tiles, one workgroup per slab and output
+ *           tile; a second kernel adds the slabs' partial sums in ascending slab order and multiplies by 2^-e.  No
+ *           floating-point atomics: the same bytes on every run.  Measured error: DESIGN.md 4.2.5.
+ *   Workspace: the partial sums belong to the context; one launch owns at most XB_HEAD_SCRATCH_MB megabytes of them (default
+ *           256, read on every call).  A call that needs more is split over blocks of 64 output rows with the slabs unchanged
+ *           -- the same bytes -- and only when one block's slabs alone exceed the bound are the slabs made fewer and longer
+ *           (csrc/xb_head_split.h).
+ *   Refused (XB_ERR_INVALID, with a message): a context whose head is not computed in three fp16 products (any precision but
+ *           XB_PREC_MIXED and XB_PREC_F16X3); a scale that is not positive.  The activation is always tanh here; a model with
+ *           another one is refused where its config is read (Model.head_trainer).
+ *   The host form stages through the context and returns synchronised; the _dev form returns without waiting, its outputs
+ *   are ordered on xb_result_stream.  No counterpart in the reference (autograd through torch.nn.Linear and Tanh).
+ */
+XB_API int xb_head_grad(xb_ctx *ctx, const float *y, const float *dy, const uint16_t *x_hi, const uint16_t *x_lo, int64_t rows, float *dw,
+                        float *db);
+XB_API int xb_head_grad_dev(xb_ctx *ctx, const float *d_y, const float *d_dy, const uint16_t *d_x_hi, const uint16_t *d_x_lo, int64_t rows,
+                            float *d_dw, float *d_db);
+
+/* *d_norm = (float)sqrt(sum dw^2 + sum db^2), summed in float64 in a fixed order (256 interleaved partial sums, each a tree,
+ * then a tree over them): clip_grad_norm_'s total norm (training.py:113). */
+XB_API int xb_grad_norm_dev(xb_ctx *ctx, const float *d_dw, int64_t len_w, const float *d_db, int64_t len_b, float *d_norm);
+
+/*
+ * torch.optim.AdamW's single-tensor update with torch's defaults (betas 0.9 / 0.999, eps 1e-8; the weight decay arrives in
+ * `decay`), one pass over len elements of (p, g, m, v) fp32, every operation rounded to nearest on its own, in this order:
+ *   g = g * clip;  p = p * decay;  m = 0.9f * m + (float)(1 - 0.9) * g;  v = 0.999f * v + ((float)(1 - 0.999) * g) * g;
+ *   p = p - (step_size * m) / (sqrt(v) / bc2_sqrt + 1e-8f)
+ * with, for step t = 1, 2, .. at learning rate lr, computed by the caller in double and rounded once:
+ *   decay = 1 - lr * 0.01,  step_size = lr / (1 - 0.9^t),  bc2_sqrt = sqrt(1 - 0.999^t).
+ * g keeps the clipped gradient.  Bit-equal to tests/adamw_ref.py; a few ulps from torch, which forms m by lerp.
+ */
+XB_API int xb_adamw_step_dev(xb_ctx *ctx, float *d_p, float *d_g, float *d_m, float *d_v, int64_t len, float clip, float decay,
+                             float step_size, float bc2_sqrt);
+
+/* Rebuild, from fp32 weights (C, F) and bias (C) on the device, what the forward's head reads: the split fp16 rows, the
+ * fragment-major image and the bias, byte for byte what xb_weights_ready uploads for the same floats.  Three-product heads only. */
+XB_API int xb_head_repack_dev(xb_ctx *ctx, const float *d_w, const float *d_b);
+
+/*
+ * The trainer.  xb_head_train_begin takes the head's fp32 master weights (C, F) and bias (C) from the host, zeroes AdamW's moments
+ * and the step count on the device and repacks, so the forward reads exactly these floats.  While it is open xb_load_weights is
+ * refused (XB_ERR_STATE).  xb_head_train_step runs one step on n chunks (signal (n, chunk_len), targets (n, Lt) uint8 labels,
+ * lengths (n), validated as xb_ctc_loss's host form does), with nothing score-sized leaving the device:
+ *   encoder, blank-less scores -> xb_ctc_loss_grad (reduction mean, no loss_clip) -> xb_head_grad on the encoder's own layer
+ *   output -> xb_grad_norm -> clip = (float)min(1, 2.0 / ((double)norm + 1e-6)) (clip_grad_norm_(max_norm = 2.0)) ->
+ *   xb_adamw_step on W, then on b, at step t = steps taken + 1 -> xb_head_repack.
+ *   *loss = (float)(the chunks' losses summed in double in index order / n), before the step; *grad_norm before clipping.
+ *   A gradient whose norm is not finite leaves the weights unchanged (XB_ERR_DEVICE).
+ * xb_head_get_weights reads the master weights back; xb_head_train_end frees the trainer's state -- the context goes on
+ * computing with the trained head until weights are loaded again.  Calls outside begin .. end: XB_ERR_STATE.
+ */
+XB_API int xb_head_train_begin(xb_ctx *ctx, const float *w, const float *b);
+XB_API int xb_head_train_step(xb_ctx *ctx, const float *signal, int n, const uint8_t *targets, int Lt, const int32_t *lengths, float lr,
+                              float *loss, float *grad_norm);
+XB_API int xb_head_get_weights(xb_ctx *ctx, float *w, float *b);
+XB_API int xb_head_train_end(xb_ctx *ctx);
+
 /* compute_scores (crf/basecall.py:27-82), viterbi branch: encode + decode without materialising
  * the blank column or copying scores off the device. */
 XB_API int xb_basecall_chunks(xb_ctx *ctx, const float *signal, int n, const char *alphabet,

@@ -4,11 +4,13 @@
 `src/tools/analyze_paf.py -p`; `... splice DNA_CTC XNA_CTC OUT --ubs XY --prop-ubs P` == the XNA spliced augmentation of
 `bonito train -m per_kmer` (bonito/stitch_chunks.py) written out as ctc-data; `... spike CTC OUT -r KMER.model --ubs XY
 --prop-ubs P` == the synthetic spiking of `bonito train --spike` (bonito/spike_chunks.py), likewise; `... synth CTC OUT -r
-KMER.model --ubs XY --prop-ubs P` == the fully synthetic chunks of `bonito train --spike --fully_synth`, likewise."""
+KMER.model --ubs XY --prop-ubs P` == the fully synthetic chunks of `bonito train --spike --fully_synth`, likewise; `... train
+TRAINING_DIR --pretrained MODEL_DIR --directory CTC_DATA -F` == `bonito train -F` at its default --num-unfreeze-top 1: the CRF
+head fine-tuned with everything below it frozen."""
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 
 from . import __version__
-from .cli import analyze, basecaller, evaluate, segment, spike, splice, synth
+from .cli import analyze, basecaller, evaluate, segment, spike, splice, synth, train
 
 
 def main():
@@ -31,6 +33,8 @@ def main():
     p.set_defaults(func=spike.main)
     p = sub.add_parser("synth", parents=[synth.argparser()])
     p.set_defaults(func=synth.main)
+    p = sub.add_parser("train", parents=[train.argparser()])
+    p.set_defaults(func=train.main)
     args = parser.parse_args()
     args.func(args)
 

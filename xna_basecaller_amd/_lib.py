@@ -35,6 +35,8 @@ EXPORTS = [
     "xb_splice_library", "xb_splice_chunks", "xb_splice_chunks_dev",
     "xb_spike_model", "xb_spike_chunks", "xb_spike_chunks_dev", "xb_synth_chunks", "xb_synth_chunks_dev",
     "xb_ctc_loss", "xb_ctc_loss_dev", "xb_validate_chunks", "xb_ctc_loss_grad", "xb_ctc_loss_grad_dev",
+    "xb_head_grad", "xb_head_grad_dev", "xb_grad_norm_dev", "xb_adamw_step_dev", "xb_head_repack_dev",
+    "xb_head_train_begin", "xb_head_train_step", "xb_head_get_weights", "xb_head_train_end",
 ]
 XB_COMM_ID_BYTES = 128
 # xb_status (include/xna_basecaller.h)
@@ -152,6 +154,19 @@ def load():
     lib.xb_validate_chunks.argtypes = [vp, vp, ip, C.c_char_p, vp, ip, vp, vp, vp, vp]
     lib.xb_ctc_loss_grad.argtypes = [vp, vp, ip, ip, ip, vp, ip, vp, C.c_float, ip, vp, vp]
     lib.xb_ctc_loss_grad_dev.argtypes = lib.xb_ctc_loss_grad.argtypes
+    lib.xb_head_grad.argtypes = [vp, vp, vp, vp, vp, C.c_int64, vp, vp]
+    lib.xb_head_grad_dev.argtypes = lib.xb_head_grad.argtypes
+    lib.xb_grad_norm_dev.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp]
+    lib.xb_adamw_step_dev.argtypes = [vp, vp, vp, vp, vp, C.c_int64, fl, fl, fl, fl]
+    lib.xb_head_repack_dev.argtypes = [vp, vp, vp]
+    lib.xb_internal_head_image.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
+    lib.xb_internal_head_state.argtypes = [vp] + [C.POINTER(vp)] * 4 + [C.POINTER(C.c_int64)]
+    lib.xb_internal_head_plan.argtypes = [C.c_int64, ip, ip, ip, C.c_char_p, vp]
+    lib.xb_internal_head_plan.restype = None
+    lib.xb_head_train_begin.argtypes = [vp, vp, vp]
+    lib.xb_head_train_step.argtypes = [vp, vp, ip, vp, ip, vp, fl, fp, fp]
+    lib.xb_head_get_weights.argtypes = [vp, vp, vp]
+    lib.xb_head_train_end.argtypes = [vp]
     lib.xb_result_stream.argtypes = [vp]
     lib.xb_result_stream.restype = C.c_void_p
     lib.xb_set_profiling.argtypes = [vp, ip]
@@ -456,6 +471,85 @@ class Context:
         self._check(self.lib.xb_ctc_loss_grad_dev(self.h, _ptr(d_scores), int(T), int(n), int(bool(has_blank)), _ptr(d_targets),
                                                   int(Lt), _ptr(d_lengths), float(loss_clip or 0.0), _mean_flag(reduction),
                                                   _ptr(d_loss), _ptr(d_grad)))
+
+    # ---- the head's gradient and trainer (csrc/xb_head.hip) ------------------------------
+    def head_grad(self, y, dy, x_hi=None, x_lo=None):
+        """xb_head_grad: RAW blank-less scores y and their gradient dy, both (M, C_noblank) fp32, and X (M, features) as fp16 bit
+        patterns x_hi + x_lo (both None: the last LSTM layer's output of the last encode, M = T n) -> (dW (C_noblank, features),
+        db (C_noblank,)) fp32, the gradient of the head's weight and bias."""
+        O, F = self.C_noblank, self.cfg.features
+        y = np.ascontiguousarray(y, dtype=np.float32).reshape(-1, O)
+        dy = np.ascontiguousarray(dy, dtype=np.float32).reshape(-1, O)
+        M = y.shape[0]
+        if dy.shape != y.shape:
+            raise ValueError("head_grad: y and dy of one shape (M, %d) expected" % O)
+        if x_hi is not None:
+            x_hi = np.ascontiguousarray(x_hi, dtype=np.uint16).reshape(-1, F)
+            x_lo = np.ascontiguousarray(x_lo, dtype=np.uint16).reshape(-1, F)
+            if x_hi.shape != (M, F) or x_lo.shape != (M, F):
+                raise ValueError("head_grad: x_hi, x_lo (M, %d) expected" % F)
+        dw, db = np.empty((O, F), np.float32), np.empty((O,), np.float32)
+        self._check(self.lib.xb_head_grad(self.h, y.ctypes.data, dy.ctypes.data, _ptr(x_hi), _ptr(x_lo), M, dw.ctypes.data,
+                                          db.ctypes.data))
+        return dw, db
+
+    def head_grad_dev(self, d_y, d_dy, d_x_hi, d_x_lo, rows, d_dw, d_db):
+        self._check(self.lib.xb_head_grad_dev(self.h, _ptr(d_y), _ptr(d_dy), _ptr(d_x_hi), _ptr(d_x_lo), int(rows), _ptr(d_dw),
+                                              _ptr(d_db)))
+
+    def grad_norm_dev(self, d_dw, len_w, d_db, len_b, d_norm):
+        self._check(self.lib.xb_grad_norm_dev(self.h, _ptr(d_dw), int(len_w), _ptr(d_db), int(len_b), _ptr(d_norm)))
+
+    def adamw_step_dev(self, d_p, d_g, d_m, d_v, length, clip, decay, step_size, bc2_sqrt):
+        self._check(self.lib.xb_adamw_step_dev(self.h, _ptr(d_p), _ptr(d_g), _ptr(d_m), _ptr(d_v), int(length), float(clip),
+                                               float(decay), float(step_size), float(bc2_sqrt)))
+
+    def head_repack_dev(self, d_w, d_b):
+        self._check(self.lib.xb_head_repack_dev(self.h, _ptr(d_w), _ptr(d_b)))
+
+    def head_image(self):
+        """The head's weights as the forward reads them: (hi, lo (C_noblank, features) uint16, the fragment-major image (bytes),
+        bias (C_noblank,) fp32)."""
+        O, F = self.C_noblank, self.cfg.features
+        hi, lo = np.empty((O, F), np.uint16), np.empty((O, F), np.uint16)
+        f4 = np.empty(((F // 32) * (((O + 255) & ~255) // 32) * 4 * 1024,), np.uint8)
+        bias = np.empty((O,), np.float32)
+        self._check(self.lib.xb_internal_head_image(self.h, hi.ctypes.data, lo.ctypes.data, f4.ctypes.data, f4.size, bias.ctypes.data))
+        return hi, lo, f4, bias
+
+    def head_train_begin(self, w, b):
+        O, F = self.C_noblank, self.cfg.features
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        if w.shape != (O, F) or b.shape != (O,):
+            raise ValueError("head_train_begin: weight (%d, %d) and bias (%d,) expected" % (O, F, O))
+        self._check(self.lib.xb_head_train_begin(self.h, w.ctypes.data, b.ctypes.data))
+
+    def head_train_step(self, signal, targets, target_lengths, lr):
+        """xb_head_train_step: one AdamW step of the head on n chunks -> (mean loss before the step, gradient norm before clipping)."""
+        signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1, self.chunk_len)
+        n = signal.shape[0]
+        targets, tl = self._labels(targets, target_lengths, n)
+        loss, norm = C.c_float(), C.c_float()
+        self._check(self.lib.xb_head_train_step(self.h, signal.ctypes.data, n, targets.ctypes.data, targets.shape[1], tl.ctypes.data,
+                                                float(lr), C.byref(loss), C.byref(norm)))
+        return loss.value, norm.value
+
+    def head_state_dev(self):
+        """Device pointers of an open trainer's (p, m, v, g), each (W | b) fp32, and the steps taken (tests)."""
+        ptrs = [C.c_void_p() for _ in range(4)]
+        step = C.c_int64()
+        self._check(self.lib.xb_internal_head_state(self.h, *[C.byref(p) for p in ptrs], C.byref(step)))
+        return tuple(p.value for p in ptrs) + (step.value,)
+
+    def head_get_weights(self):
+        O, F = self.C_noblank, self.cfg.features
+        w, b = np.empty((O, F), np.float32), np.empty((O,), np.float32)
+        self._check(self.lib.xb_head_get_weights(self.h, w.ctypes.data, b.ctypes.data))
+        return w, b
+
+    def head_train_end(self):
+        self._check(self.lib.xb_head_train_end(self.h))
 
     def validate_chunks(self, signal, alphabet, targets, target_lengths):
         """xb_validate_chunks: signal (n, chunk_len), targets (n, Lt), target_lengths (n) -> (seq (n, T) int8 left-packed ASCII,

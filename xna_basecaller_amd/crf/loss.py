@@ -2,7 +2,8 @@
 The training criterion as a torch autograd function: CTC_CRF.ctc_loss on scores that are a torch tensor on the model's device
 (training.py:82 takes model.seqdist.ctc_loss as Trainer's criterion; the reference's is seqdist's, CUDA-only).  The forward runs
 xb_ctc_loss_grad_dev on the tensors' own memory -- loss and d loss / d scores in one device call -- and saves the gradient; the
-backward is a product.  No optimiser, no backward through the encoder: torch's own layers provide that.
+backward is a product.  No backward through the encoder: torch's own layers provide that (the head alone is trained without
+torch: crf/trainer.py).
 """
 import torch
 

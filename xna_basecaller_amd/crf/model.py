@@ -424,6 +424,14 @@ class Model(torch.nn.Module):
         ctx = self.context(sig.shape[1], sig.shape[0])
         return ctx.validate_chunks(sig, self.alphabet, targets, lengths)
 
+    def head_trainer(self, chunk_len=None, batch=None):
+        """A HeadTrainer (crf/trainer.py) on this model's context for chunks of chunk_len samples, up to `batch` per step
+        (defaults: the [basecaller] chunksize / batchsize): step(batch, targets, lengths, lr) -> (loss, grad_norm) trains
+        encoder.9.linear.{weight,bias} with everything below frozen, state_dict() is the model's with those two replaced."""
+        from .trainer import HeadTrainer
+        run = self.config.get("basecaller", {})
+        return HeadTrainer(self, chunk_len or run.get("chunksize", 4000), batch or run.get("batchsize", 64))
+
     def _decode_rows(self, scores, op):
         if hasattr(scores, "detach"):
             scores = scores.detach().to(torch.float32).cpu().numpy()

@@ -406,6 +406,7 @@ int run_encoder(xb_ctx *ctx, const float *d_signal, int n, int expand, float *sc
     const int F = c.features, T = ctx->T;
     const int nsplit = ctx->ns_conv;
     ctx->dep_next = 0;
+    ctx->enc_n = n;
     {
         StageScope sc(ctx, XB_STAGE_CONV, 2);
         xb::ConvFrontParams cf{};
@@ -439,6 +440,13 @@ int run_encoder(xb_ctx *ctx, const float *d_signal, int n, int expand, float *sc
     }
     return XB_OK;
 }
+
+}  // namespace
+
+// the encoder of n chunks into blank-less scores (T, n, ldc), for xb_head.hip (the trainer's forward pass)
+int encoder_run(xb_ctx *ctx, const float *d_signal, int n, float *d_scores, int ldc) { return run_encoder(ctx, d_signal, n, 0, d_scores, ldc); }
+
+namespace {
 
 // optional outputs of the Log scans (xb_crf_logz / xb_crf_scans)
 struct ScanOut {
@@ -756,7 +764,8 @@ XB_API void xb_ctx_destroy(xb_ctx *ctx)
     for (auto &ev : ctx->events) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto &b : ctx->bufs) (void)hipFree(b.p);
     for (auto &b : ctx->wsbufs) (void)hipFree(b.p);
-    for (DevBuf *b : {&ctx->staging, &ctx->map.image, &ctx->map.partial, &ctx->map.scratch, &ctx->dtw.scratch, &ctx->ctcgrad.stash, &ctx->ctcgrad.w, &ctx->splice.pool,
+    for (DevBuf *b : {&ctx->staging, &ctx->map.image, &ctx->map.partial, &ctx->map.scratch, &ctx->dtw.scratch, &ctx->ctcgrad.stash, &ctx->ctcgrad.w, &ctx->head.part, &ctx->head.small,
+                      &ctx->head.stage, &ctx->head.train, &ctx->head.grad, &ctx->head.labels, &ctx->splice.pool,
                       &ctx->splice.rows, &ctx->splice.table, &ctx->spike.model})
         if (b->p) (void)hipFree(b->p);
     for (auto &o : ctx->dtw.off) {
@@ -777,6 +786,7 @@ XB_API int xb_load_weights(xb_ctx *ctx, const char *name, const float *host, int
     const int64_t want = expected_size(ctx, name);
     if (want < 0) return fail(ctx, XB_ERR_INVALID, "unknown state-dict key '%s'", name);
     if (want != n) return fail(ctx, XB_ERR_INVALID, "'%s': got %lld elements, config implies %lld", name, (long long)n, (long long)want);
+    if (ctx->head.open) return fail(ctx, XB_ERR_STATE, "xb_load_weights: a head trainer is open on this context; call xb_head_train_end first");
     // a held-back basecall belongs to the weights it was called with (loading clears weights_ready, the launch needs it)
     if (ctx->holding) {
         XB_HIP(ctx, hipSetDevice(ctx->device));

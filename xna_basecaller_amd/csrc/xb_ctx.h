@@ -223,6 +223,17 @@ struct xb_ctx {
         DevBuf stash, w;
     } ctcgrad;
 
+    // The head's gradient and trainer (xb_head.hip).  part: the slabs' partial sums of one launch of xb_head_grad (bounded by
+    // XB_HEAD_SCRATCH_MB); small: max |dY| word, the norm's partial sums and result; stage: the host forms' staging.  While a
+    // trainer is open (xb_head_train_begin .. _end): the fp32 master weights, AdamW's moments and the gradient in one buffer
+    // (W, b, mW, mb, vW, vb, dW, db), the batch's score gradient, labels and losses, and the step count.  Freed by xb_ctx_destroy.
+    struct HeadState {
+        DevBuf part, small, stage, train, grad, labels;
+        bool open = false;
+        long step = 0;
+    } head;
+    int enc_n = 0;                              // chunks of the most recent encoder pass (whose layer outputs lie in x_hi / x_lo)
+
     bool profiling = false;
     std::vector<StageEvent> events;
     float stage_ms[XB_STAGE_COUNT] = {};
@@ -262,6 +273,7 @@ int ctc_loss_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int
                  int Lt, const int32_t *d_len, float *d_loss, float *d_logz);
 int ctc_grad_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int n, int has_blank, int ld, const uint8_t *d_targets,
                  int Lt, const int32_t *d_len, float loss_clip, int mean, float *d_loss, float *d_grad);
+int encoder_run(xb_ctx *ctx, const float *d_signal, int n, float *d_scores, int ldc);   // blank-less scores (T, n, ldc), main stream
 // ... and two from inside its extern "C" block, beside the pairing logic: flush_held launches a held-back asynchronous basecall;
 // basecall_async makes one of n chunks at d_signal into device outputs (seq, len, out), of pipeline slot `slot` or none
 extern "C" int flush_held(xb_ctx *ctx);
