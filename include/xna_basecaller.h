@@ -402,6 +402,43 @@ XB_API int xb_head_train_step(xb_ctx *ctx, const float *signal, int n, const uin
 XB_API int xb_head_get_weights(xb_ctx *ctx, float *w, float *b);
 XB_API int xb_head_train_end(xb_ctx *ctx);
 
+/*
+ * One LSTM layer's recurrence for training: the forward that keeps what the backward needs, and the backward through time --
+ * the step that `bonito train -F` above --num-unfreeze-top 1 needs from the top LSTM layer on.  One unidirectional layer with
+ * torch.nn.LSTM's semantics: gate order i, f, g, o, h_-1 = c_-1 = 0; reverse != 0 processes the time axis from T-1 down to 0
+ * and stores every output at its own t (nn.py:189-193: flip, rnn, flip).  F is independent of the context's model: the context
+ * gives the stream, the error message and the workspace.  All tensors fp32, dense, on the device, 16-byte aligned.
+ *   gin     (T, n, 4F): gin[t] = x_t W_ih^T + b_ih + b_hh, an INPUT (a non-recurrent product: the caller's).
+ *   w_hh    (4F, F) row-major: torch's weight_hh_l0.
+ * xb_lstm_train_forward_dev, per step in processing order (p = the step processed before t):
+ *   pre = gin[t] + y[p] W_hh^T (at the first step: gin[t]);  (i, f, o) = sigma(pre), g = tanh(pre);
+ *   gates[t] (n, 4F) = i | f | g | o after the activation;  c[t] (n, F) = fma(f, c[p], i * g);  y[t] (n, F) = o * tanh(c[t]).
+ * xb_lstm_train_backward_dev, per step in the opposite order (s = the step processed after t in the forward), from dy (T, n, F)
+ * and the forward's gates and c:
+ *   dh = dy[t] + dgin[s] W_hh (at the last processed step: dy[t]);  th = tanh(c[t]);  do = dh * th;
+ *   dc = fma(dh * o, (1 - th)(1 + th), carry);  di = dc * g;  df = dc * c[p];  dg = dc * i;  carry = dc * f;
+ *   dgin[t] (n, 4F) = di * (i (1 - i)) | df * (f (1 - f)) | dg * ((1 - g)(1 + g)) | do * (o (1 - o)),  zeros written as +0.
+ *   dgin is d loss / d gin: d loss / d W_hh = sum_t dgin[t]^T y[p(t)] and the gradients of x, W_ih and the bias follow from it by
+ *   products without a recurrence, which are the caller's (crf/lstm.py leaves them to torch).
+ * Arithmetic: fp32 throughout.  The recurrent products run on the f32-input MFMA (v_mfma_f32_16x16x4_f32: exact f32 operands,
+ *   one rounding per product, a fixed k order per output element -- gradients of 1e-9 need no scaling); the forward's sum runs
+ *   over K = F, the backward's over K = 4F as four gate-wise partial sums added in gate order.  sigma(x) = 1 / (1 + exp(-x))
+ *   and tanh (an odd polynomial below 0.625, 1 - 2 / (exp(2|x|) + 1) above) use the decode's exp, whose argument is clamped:
+ *   finite and monotone for every finite x, saturated gates included.  One launch per time step; no workgroup waits for another
+ *   inside a kernel; no floating-point atomics: a row's results do not depend on which other rows are in the call, and a call
+ *   repeated gives the same bytes.  Measured error against float64: DESIGN.md 4.2.6.
+ * The stash is the caller's: y, gates and c are T * n * 6F floats, of which the backward reads gates and c, T * n * 5F floats --
+ *   0.71 GB at T = 720, n = 64, F = 768 and 4.2 GB at n = 384.  The workspace (the (n, F) carry and W_hh transposed) belongs to
+ *   the context and grows with the calls.
+ * Accepted: T >= 1, n >= 1, F a multiple of 16 in 16 .. 1024; anything else, a null pointer or one that is not 16-byte aligned
+ *   is XB_ERR_INVALID with the figures.  No weights need to be loaded.  The calls return without waiting; the outputs are
+ *   ordered on xb_result_stream.  No counterpart in the reference (autograd through torch.nn.LSTM, cuDNN).
+ */
+XB_API int xb_lstm_train_forward_dev(xb_ctx *ctx, const float *d_gin, const float *d_w_hh, int T, int n, int F, int reverse,
+                                     float *d_y, float *d_gates, float *d_c);
+XB_API int xb_lstm_train_backward_dev(xb_ctx *ctx, const float *d_dy, const float *d_w_hh, const float *d_gates, const float *d_c,
+                                      int T, int n, int F, int reverse, float *d_dgin);
+
 /* compute_scores (crf/basecall.py:27-82), viterbi branch: encode + decode without materialising
  * the blank column or copying scores off the device. */
 XB_API int xb_basecall_chunks(xb_ctx *ctx, const float *signal, int n, const char *alphabet,

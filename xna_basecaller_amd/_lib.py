@@ -37,6 +37,7 @@ EXPORTS = [
     "xb_ctc_loss", "xb_ctc_loss_dev", "xb_validate_chunks", "xb_ctc_loss_grad", "xb_ctc_loss_grad_dev",
     "xb_head_grad", "xb_head_grad_dev", "xb_grad_norm_dev", "xb_adamw_step_dev", "xb_head_repack_dev",
     "xb_head_train_begin", "xb_head_train_step", "xb_head_get_weights", "xb_head_train_end",
+    "xb_lstm_train_forward_dev", "xb_lstm_train_backward_dev",
 ]
 XB_COMM_ID_BYTES = 128
 # xb_status (include/xna_basecaller.h)
@@ -167,6 +168,8 @@ def load():
     lib.xb_head_train_step.argtypes = [vp, vp, ip, vp, ip, vp, fl, fp, fp]
     lib.xb_head_get_weights.argtypes = [vp, vp, vp]
     lib.xb_head_train_end.argtypes = [vp]
+    lib.xb_lstm_train_forward_dev.argtypes = [vp, vp, vp, ip, ip, ip, ip, vp, vp, vp]
+    lib.xb_lstm_train_backward_dev.argtypes = [vp, vp, vp, vp, vp, ip, ip, ip, ip, vp]
     lib.xb_result_stream.argtypes = [vp]
     lib.xb_result_stream.restype = C.c_void_p
     lib.xb_set_profiling.argtypes = [vp, ip]
@@ -506,6 +509,16 @@ class Context:
 
     def head_repack_dev(self, d_w, d_b):
         self._check(self.lib.xb_head_repack_dev(self.h, _ptr(d_w), _ptr(d_b)))
+
+    def lstm_train_forward_dev(self, d_gin, d_w_hh, T, n, F, reverse, d_y, d_gates, d_c):
+        """xb_lstm_train_forward_dev: gin (T, n, 4F), W_hh (4F, F) -> y (T, n, F), gates (T, n, 4F), c (T, n, F), all fp32 on the device."""
+        self._check(self.lib.xb_lstm_train_forward_dev(self.h, _ptr(d_gin), _ptr(d_w_hh), int(T), int(n), int(F), int(bool(reverse)),
+                                                       _ptr(d_y), _ptr(d_gates), _ptr(d_c)))
+
+    def lstm_train_backward_dev(self, d_dy, d_w_hh, d_gates, d_c, T, n, F, reverse, d_dgin):
+        """xb_lstm_train_backward_dev: dy (T, n, F) and the forward's gates and c -> dgin (T, n, 4F)."""
+        self._check(self.lib.xb_lstm_train_backward_dev(self.h, _ptr(d_dy), _ptr(d_w_hh), _ptr(d_gates), _ptr(d_c), int(T), int(n), int(F),
+                                                        int(bool(reverse)), _ptr(d_dgin)))
 
     def head_image(self):
         """The head's weights as the forward reads them: (hi, lo (C_noblank, features) uint16, the fragment-major image (bytes),

@@ -174,7 +174,9 @@ class Permute(torch.nn.Module):
 
 
 class LSTM(torch.nn.Module):
-    """Parameter holder for nn.py:176-235 (keys rnn.{weight_ih_l0,weight_hh_l0,bias_ih_l0,bias_hh_l0})."""
+    """Parameter holder for nn.py:176-235 (keys rnn.{weight_ih_l0,weight_hh_l0,bias_ih_l0,bias_hh_l0}).  The model's own
+    forward never calls it (the encoder is one device call on the packed weights); called on its own, as model.encoder[i](x),
+    it is the layer with a backward (crf/lstm.py)."""
 
     def __init__(self, size, insize, bias=True, reverse=False):
         super().__init__()
@@ -183,6 +185,13 @@ class LSTM(torch.nn.Module):
         with torch.no_grad():
             self.rnn.bias_hh_l0.zero_()
         self.rnn.bias_hh_l0.requires_grad = False
+
+    def forward(self, x):
+        """(T, N, insize) float32, contiguous, on the model's device -> (T, N, size) with a grad_fn: nn.py:189-193 (flip, rnn,
+        flip when reverse) from this layer's float32 parameters, which must be on that device too (model.encoder[i].to(device)).
+        The recurrence and its backward through time run in xb_lstm_train_forward_dev / _backward_dev."""
+        from .lstm import lstm_forward
+        return lstm_forward(self, x)
 
 
 class LinearCRFEncoder(torch.nn.Module):
@@ -282,6 +291,8 @@ class Model(torch.nn.Module):
             enc = {k: v for k, v in config["encoder"].items()}
             self.encoder = rnn_encoder(self.seqdist.n_base, self.seqdist.state_len,
                                        insize=config["input"]["features"], **enc)
+        for layer in self.encoder:                # a layer called on its own (LSTM.forward) runs on this model's device context
+            layer._model = weakref.ref(self)
         self.stride = enc.get("stride", 5)
         self.alphabet = self.seqdist.alphabet
         self.config = config

@@ -766,7 +766,7 @@ XB_API void xb_ctx_destroy(xb_ctx *ctx)
     for (auto &b : ctx->wsbufs) (void)hipFree(b.p);
     for (DevBuf *b : {&ctx->staging, &ctx->map.image, &ctx->map.partial, &ctx->map.scratch, &ctx->dtw.scratch, &ctx->ctcgrad.stash, &ctx->ctcgrad.w, &ctx->head.part, &ctx->head.small,
                       &ctx->head.stage, &ctx->head.train, &ctx->head.grad, &ctx->head.labels, &ctx->splice.pool,
-                      &ctx->splice.rows, &ctx->splice.table, &ctx->spike.model})
+                      &ctx->splice.rows, &ctx->splice.table, &ctx->spike.model, &ctx->lstmtrain.carry, &ctx->lstmtrain.wt})
         if (b->p) (void)hipFree(b->p);
     for (auto &o : ctx->dtw.off) {
         if (o.h) (void)hipHostFree(o.h);

@@ -232,6 +232,11 @@ struct xb_ctx {
         bool open = false;
         long step = 0;
     } head;
+    // The LSTM layer's training recurrence (xb_lstm_train.hip): the (n, F) cell-gradient carry of the backward's steps and the
+    // transposed recurrent weights (F, 4F) of the call in flight.  Grow with the calls; freed by xb_ctx_destroy.
+    struct LstmTrainState {
+        DevBuf carry, wt;
+    } lstmtrain;
     int enc_n = 0;                              // chunks of the most recent encoder pass (whose layer outputs lie in x_hi / x_lo)
 
     bool profiling = false;
