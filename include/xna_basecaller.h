@@ -439,6 +439,33 @@ XB_API int xb_lstm_train_forward_dev(xb_ctx *ctx, const float *d_gin, const floa
 XB_API int xb_lstm_train_backward_dev(xb_ctx *ctx, const float *d_dy, const float *d_w_hh, const float *d_gates, const float *d_c,
                                       int T, int n, int F, int reverse, float *d_dgin);
 
+/*
+ * The products of training that carry no recurrence, in fp32 (csrc/xb_train_gemm.hip).  All tensors fp32, dense, on the device;
+ * no alignment is asked of them (16-byte aligned operands whose row length is a multiple of 4 are read 16 bytes at a time, others
+ * float by float -- the sums are the same).  Products run on the f32-input MFMA (v_mfma_f32_16x16x4_f32: exact f32 operands, so a
+ * gradient of 1e-9 needs no scaling).  No floating-point atomics; an output element is summed by one wave in an order that its
+ * shape alone decides: a repeated call gives the same bytes.  No weights need to be loaded; the calls return without waiting,
+ * outputs ordered on xb_result_stream.  No counterpart in the reference (torch autograd, cuBLAS).
+ * xb_linear_f32_dev: out (M, N) = act(a (M, K) w (N, K)^T + bias (N) or NULL); act 0 the identity, 1 scale * tanh with the training
+ *   recurrence's tanh.  Both operands k-contiguous; the sum of an element runs over k ascending in groups of four (one MFMA), an
+ *   order that depends on K alone: a row's results do not depend on the rows beside it.  M, N, K >= 1, any value.  It serves
+ *   gin = x W_ih^T + b, the head's scores, and -- given the transposed weight -- dx = dgin W_ih and the head's dX = dZ W.
+ * xb_wgrad_f32_dev: dw (N, K)[o, f] = sum_m a (M, N)[m, o] b (M, K)[m, f], dcol (N)[o] = sum_m a[m, o] (NULL: not wanted).  Both
+ *   operands arrive row-major over the summed dimension and are turned on their way through LDS.  One workgroup per 64 x 64 tile of
+ *   dw walks all of M in ascending order: no partial sums between workgroups, no second kernel, no scratch.  THE BLOCKED FORM
+ *   SHIPPED: an element's running fp32 sum (four rows per MFMA) is closed every 1024 rows and added to its total, blocks in
+ *   ascending order (DESIGN.md 4.2.7 has the measurement that decided it).  dcol is summed in float64 (four interleaved row
+ *   classes, each ascending, added in order) and rounded once.  Zeros are written as +0; M = 0 writes +0 everywhere.  M >= 0,
+ *   N, K >= 1.  It serves dW_ih and db (a = dgin, b = x), dW_hh (a and b offset against each other by one time step: a = dgin + n 4F,
+ *   b = y forward in time, a = dgin, b = y + n F in a reverse layer, M = (T - 1) n) and the head's dW, db (a = dZ, b = y).
+ * xb_head_dz_dev: dz = dy * (((scale - y) * (scale + y)) / scale) over count elements, y the head's output scale * tanh(z): xb_head_grad's
+ *   non-cancelling form without its power-of-two factor, one rounding per operation.  scale > 0.
+ */
+XB_API int xb_linear_f32_dev(xb_ctx *ctx, const float *d_a, const float *d_w, const float *d_bias, int64_t M, int N, int K, int act,
+                             float scale, float *d_out);
+XB_API int xb_wgrad_f32_dev(xb_ctx *ctx, const float *d_a, const float *d_b, int64_t M, int N, int K, float *d_dw, float *d_dcol);
+XB_API int xb_head_dz_dev(xb_ctx *ctx, const float *d_y, const float *d_dy, int64_t count, float scale, float *d_dz);
+
 /* compute_scores (crf/basecall.py:27-82), viterbi branch: encode + decode without materialising
  * the blank column or copying scores off the device. */
 XB_API int xb_basecall_chunks(xb_ctx *ctx, const float *signal, int n, const char *alphabet,

@@ -38,6 +38,7 @@ EXPORTS = [
     "xb_head_grad", "xb_head_grad_dev", "xb_grad_norm_dev", "xb_adamw_step_dev", "xb_head_repack_dev",
     "xb_head_train_begin", "xb_head_train_step", "xb_head_get_weights", "xb_head_train_end",
     "xb_lstm_train_forward_dev", "xb_lstm_train_backward_dev",
+    "xb_linear_f32_dev", "xb_wgrad_f32_dev", "xb_head_dz_dev",
 ]
 XB_COMM_ID_BYTES = 128
 # xb_status (include/xna_basecaller.h)
@@ -170,6 +171,10 @@ def load():
     lib.xb_head_train_end.argtypes = [vp]
     lib.xb_lstm_train_forward_dev.argtypes = [vp, vp, vp, ip, ip, ip, ip, vp, vp, vp]
     lib.xb_lstm_train_backward_dev.argtypes = [vp, vp, vp, vp, vp, ip, ip, ip, ip, vp]
+    lib.xb_linear_f32_dev.argtypes = [vp, vp, vp, vp, C.c_int64, ip, ip, ip, fl, vp]
+    lib.xb_wgrad_f32_dev.argtypes = [vp, vp, vp, C.c_int64, ip, ip, vp, vp]
+    lib.xb_internal_wgrad_blocked.argtypes = [vp, vp, vp, C.c_int64, ip, ip, vp, vp, C.c_int64]
+    lib.xb_head_dz_dev.argtypes = [vp, vp, vp, C.c_int64, fl, vp]
     lib.xb_result_stream.argtypes = [vp]
     lib.xb_result_stream.restype = C.c_void_p
     lib.xb_set_profiling.argtypes = [vp, ip]
@@ -563,6 +568,24 @@ class Context:
 
     def head_train_end(self):
         self._check(self.lib.xb_head_train_end(self.h))
+
+    # ---- the fp32 products of training (csrc/xb_train_gemm.hip) -------------------------------------------------------------------
+    def linear_f32_dev(self, d_a, d_w, d_bias, M, N, K, act, scale, d_out):
+        """xb_linear_f32_dev: out (M, N) = act(a (M, K) w (N, K)^T + bias); act 0 identity, 1 scale * tanh.  fp32 on the device."""
+        self._check(self.lib.xb_linear_f32_dev(self.h, _ptr(d_a), _ptr(d_w), _ptr(d_bias), int(M), int(N), int(K), int(act), float(scale),
+                                               _ptr(d_out)))
+
+    def wgrad_f32_dev(self, d_a, d_b, M, N, K, d_dw, d_dcol, block_rows=None):
+        """xb_wgrad_f32_dev: dw (N, K) = a (M, N)^T b (M, K), dcol (N) = column sums of a (or None).  block_rows: the measurement
+        entry with another length of the row blocks (a multiple of 32)."""
+        if block_rows is None:
+            self._check(self.lib.xb_wgrad_f32_dev(self.h, _ptr(d_a), _ptr(d_b), int(M), int(N), int(K), _ptr(d_dw), _ptr(d_dcol)))
+        else:
+            self._check(self.lib.xb_internal_wgrad_blocked(self.h, _ptr(d_a), _ptr(d_b), int(M), int(N), int(K), _ptr(d_dw), _ptr(d_dcol),
+                                                           int(block_rows)))
+
+    def head_dz_dev(self, d_y, d_dy, count, scale, d_dz):
+        self._check(self.lib.xb_head_dz_dev(self.h, _ptr(d_y), _ptr(d_dy), int(count), float(scale), _ptr(d_dz)))
 
     def validate_chunks(self, signal, alphabet, targets, target_lengths):
         """xb_validate_chunks: signal (n, chunk_len), targets (n, Lt), target_lengths (n) -> (seq (n, T) int8 left-packed ASCII,

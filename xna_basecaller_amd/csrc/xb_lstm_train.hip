@@ -15,27 +15,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int JB = 16;          // hidden units of one workgroup: one MFMA tile of columns (per gate)
 constexpr int LDP = JB + 1;     // floats per LDS row: the element pass reads 16 rows x 16 columns without a bank conflict
 
-// sigma and tanh from xb_expf (which clamps its argument to [-87, 88]: no overflow, so no inf / inf): finite for every finite
-// x, 0 / 1 and -1 / 1 where they saturate
-__device__ __forceinline__ float lt_sigmoid(float x)
-{
-    return 1.0f / (1.0f + xb_expf(-x));
-}
-// below 0.625 the odd polynomial of Cephes' tanhf (x + x^3 P(x^2): no cancellation near 0), above it 1 - 2 / (e^2|x| + 1)
-__device__ __forceinline__ float lt_tanh(float x)
-{
-    const float a = __builtin_fabsf(x);
-    const float z = x * x;
-    float p = -5.70498872745e-3f;
-    p = __builtin_fmaf(p, z, 2.06390887954e-2f);
-    p = __builtin_fmaf(p, z, -5.37397155531e-2f);
-    p = __builtin_fmaf(p, z, 1.33314422036e-1f);
-    p = __builtin_fmaf(p, z, -3.33332819422e-1f);
-    const float small = __builtin_fmaf(p * z, x, x);
-    const float big = __builtin_copysignf(1.0f - 2.0f / (xb_expf(a + a) + 1.0f), x);
-    return a < 0.625f ? small : big;
-}
-
 // One wave's share of a product: for RT tiles of 16 rows, acc[rt] += A[rows, k] * B[16 columns, k]^T over nk chunks of 16 k.
 // Both operands are k-contiguous in memory (16 floats of a row per chunk, a float4 per lane); lane (r = lane & 15, q = lane >> 4)
 // holds k = 16 kc + 4 q + m in its element m, and MFMA m of the chunk sums over the four q -- every k once, in an order that

@@ -67,4 +67,27 @@ __device__ __forceinline__ float xb_logf(float x)
     r = __builtin_fmaf(fe, 0.693359375f, r);
     return r;
 }
+
+// The training kernels' activations (xb_lstm_train.hip, xb_train_gemm.hip).  Their quotients are correctly rounded only in a
+// translation unit built with -fhip-fp32-correctly-rounded-divide-sqrt, as those two are.
+// sigma and tanh from xb_expf (which clamps its argument to [-87, 88]: no overflow, so no inf / inf): finite for every finite
+// x, 0 / 1 and -1 / 1 where they saturate
+__device__ __forceinline__ float lt_sigmoid(float x)
+{
+    return 1.0f / (1.0f + xb_expf(-x));
+}
+// below 0.625 the odd polynomial of Cephes' tanhf (x + x^3 P(x^2): no cancellation near 0), above it 1 - 2 / (e^2|x| + 1)
+__device__ __forceinline__ float lt_tanh(float x)
+{
+    const float a = __builtin_fabsf(x);
+    const float z = x * x;
+    float p = -5.70498872745e-3f;
+    p = __builtin_fmaf(p, z, 2.06390887954e-2f);
+    p = __builtin_fmaf(p, z, -5.37397155531e-2f);
+    p = __builtin_fmaf(p, z, 1.33314422036e-1f);
+    p = __builtin_fmaf(p, z, -3.33332819422e-1f);
+    const float small = __builtin_fmaf(p * z, x, x);
+    const float big = __builtin_copysignf(1.0f - 2.0f / (xb_expf(a + a) + 1.0f), x);
+    return a < 0.625f ? small : big;
+}
 }  // namespace
