@@ -1,6 +1,6 @@
 """ctypes view of libxnacall.so's non-public host-logic exports (xb_internal_*, csrc/xb_api.hip): the encoder's planner
-(csrc/xb_schedule.h) and the weight packer (csrc/xb_pack.h).  None of them touches the device or needs a context, so the
-tests that use this module run without a GPU."""
+(csrc/xb_schedule.h), the weight packer (csrc/xb_pack.h) and the decoder of the device status words (csrc/xb_status.h).  None
+of them touches the device or needs a context, so the tests that use this module run without a GPU."""
 import ctypes as C
 
 import numpy as np
@@ -57,6 +57,7 @@ def lib():
         so.xb_internal_gate_interleave.restype = None
         so.xb_internal_i8_limbs.argtypes = [vp, ip, ip, vp, vp, vp]
         so.xb_internal_i8_limbs.restype = None
+        so.xb_internal_decode_status.argtypes = [C.c_uint, C.c_uint, C.POINTER(C.c_char_p)]
         _cached = so
     return _cached
 
@@ -96,6 +97,14 @@ class Planner:
             return self.p, None
         assert 0 < count <= MAX_LAUNCHES and self.p.error == 0
         return self.p, self.recs[:count]
+
+
+def decode_status(sync_word, data_word):
+    """What a synchronising call reports for a context's two device status words (csrc/xb_status.h): (code, message), the
+    message None with XB_OK."""
+    msg = C.c_char_p()
+    code = lib().xb_internal_decode_status(sync_word, data_word, C.byref(msg))
+    return code, (msg.value.decode() if msg.value is not None else None)
 
 
 def _f32(a):

@@ -1,12 +1,13 @@
-// The encoder's host scheduler (csrc/xb_schedule.h) and weight packer (csrc/xb_pack.h) on their own, for a sanitizer run
-// without a GPU and without Python:
+// The encoder's host scheduler (csrc/xb_schedule.h), the weight packer (csrc/xb_pack.h) and the decoder of the device status
+// words (csrc/xb_status.h) on their own, for a sanitizer run without a GPU and without Python:
 //
 //   clang++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/host_logic_main.cpp -o /tmp/host_logic && /tmp/host_logic
 //
 // The planner walks the grid of tests/test_schedule_host.py (every feature size, CU count, step count, the batch seams, the
 // device facts on and off, the knob sets) and every launch of every plan is checked to lie inside the batch, the steps and
 // the 64 group slots.  The packer runs on exact-size heap blocks, so a read past a tensor or a write past an image is an
-// error the sanitizer reports.  Exit status 0 and "ok" when nothing failed.
+// error the sanitizer reports.  The status decoder walks the eight cases of tests/test_status_host.py.  Exit status 0 and
+// "ok" when nothing failed.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -15,6 +16,7 @@
 
 #include "../xna_basecaller_amd/csrc/xb_pack.h"
 #include "../xna_basecaller_amd/csrc/xb_schedule.h"
+#include "../xna_basecaller_amd/csrc/xb_status.h"
 
 static long failures = 0, plans = 0, launches = 0;
 
@@ -175,10 +177,29 @@ static void walk_packer()
     }
 }
 
+// the two device status words: sync word {0, 1} x data word {0, 2, 4, 6}, as tests/test_status_host.py states them
+static void walk_status()
+{
+    const char *sync_text = "LSTM inter-workgroup sync timed out (persistent kernel was not fully resident?)";
+    const char *loss_text = "xb_ctc_loss: a target length outside [state_len, Lt] or a label above n_base inside it";
+    const char *scan_text = "CTC scan: a target length was outside the lattice";
+    for (unsigned sync = 0; sync <= 1; ++sync)
+        for (unsigned data = 0; data <= 6; data += 2) {
+            const xb::DeviceStatus s = xb::decode_status(sync, data);
+            const char *text = sync ? sync_text : ((data & 4) ? loss_text : (data ? scan_text : nullptr));
+            const int code = sync ? XB_ERR_DEVICE : ((data & 4) ? XB_ERR_INVALID : (data ? XB_ERR_DEVICE : XB_OK));
+            CHECK(s.code == code && (text ? (s.message && strcmp(s.message, text) == 0) : s.message == nullptr));
+            // a report takes one condition out of the words and leaves the others for the next one
+            CHECK(s.sync_left == 0 && s.data_left == (sync ? data : ((data & 4) ? (data & ~4u) : 0u)));
+        }
+    CHECK(xb::SYNC_LOST == 1u && xb::DATA_SCAN_LENGTH == 2u && xb::DATA_LOSS_LABEL == 4u);
+}
+
 int main()
 {
     walk_plans();
     walk_packer();
+    walk_status();
     printf("%ld plans, %ld launches checked\n", plans, launches);
     if (failures) printf("%ld check(s) failed\n", failures);
     else printf("ok\n");

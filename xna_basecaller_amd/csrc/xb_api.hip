@@ -37,6 +37,15 @@ int join_async_decode(xb_ctx *ctx)
     return XB_OK;
 }
 
+// result_stream is named last: launching a held-back call names its own
+int enter(xb_ctx *ctx, bool dev)
+{
+    XB_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = join_async_decode(ctx)) return rc;
+    if (dev) ctx->result_stream = ctx->stream;
+    return XB_OK;
+}
+
 int check_alphabet(xb_ctx *ctx, const char *alphabet)
 {
     if ((int)strlen(alphabet) < ctx->cfg.n_base + 1 || strlen(alphabet) >= sizeof(xb_ctx::Call{}.alphabet))
@@ -54,59 +63,44 @@ bool has_required(const Planes &o, int level) { return o.p[0] && (level < 1 || o
 
 int64_t ipow(int64_t b, int e) { int64_t r = 1; while (e-- > 0) r *= b; return r; }
 
-template <typename Tp>
-int dev_alloc(xb_ctx *ctx, Tp **out, size_t count)
-{
-    void *p = nullptr;
-    const size_t bytes = (count * sizeof(Tp) + 255) & ~(size_t)255;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess)
-        return fail(ctx, XB_ERR_NOMEM, "hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
-    (ctx->alloc_ws ? ctx->wsbufs : ctx->bufs).push_back({p, bytes});
-    *out = reinterpret_cast<Tp *>(p);
-    return XB_OK;
-}
-
 // The workspaces whose size follows the number of chunks in a pass.  A context starts with room for max_batch chunks; the
 // first time two calls are co-scheduled (or on xb_reserve_pairing) they are replaced by twice that.
 int alloc_workspaces(xb_ctx *ctx, int cap)
 {
-    for (auto &b : ctx->wsbufs) (void)hipFree(b.p);
-    ctx->wsbufs.clear();
+    DevPool &ws = ctx->mem_ws;
+    ws.release();
     ctx->cap = 0;
     const xb_config *cfg = &ctx->cfg;
     const int S = ctx->S;
     const size_t N = (size_t)cap, T = ctx->T, F = cfg->features, L = cfg->chunk_len;
     const size_t Cb = (size_t)S * (cfg->n_base + 1);
     const size_t Cmax = Cb > (size_t)ctx->ld_nb ? Cb : (size_t)ctx->ld_nb;
-    ctx->alloc_ws = true;
     int rc = XB_OK;
-    rc = rc ? rc : dev_alloc(ctx, &ctx->d_signal, N * L);
-    rc = rc ? rc : dev_alloc(ctx, &ctx->im_hi, T * N * ctx->kp);
-    rc = rc ? rc : dev_alloc(ctx, &ctx->im_lo, T * N * ctx->kp);
+    rc = rc ? rc : ws.alloc(ctx, &ctx->d_signal, N * L);
+    rc = rc ? rc : ws.alloc(ctx, &ctx->im_hi, T * N * ctx->kp);
+    rc = rc ? rc : ws.alloc(ctx, &ctx->im_lo, T * N * ctx->kp);
     for (int i = 0; i < 2 && !rc; ++i) {
-        rc = rc ? rc : dev_alloc(ctx, &ctx->x_hi[i], T * N * F);
-        rc = rc ? rc : dev_alloc(ctx, &ctx->x_lo[i], T * N * F);
+        rc = rc ? rc : ws.alloc(ctx, &ctx->x_hi[i], T * N * F);
+        rc = rc ? rc : ws.alloc(ctx, &ctx->x_lo[i], T * N * F);
     }
     // + 64 rows: the recurrence's LDS-DMA of a ragged last group reads (and ignores) up to 63 rows past the last chunk
-    rc = rc ? rc : dev_alloc(ctx, &ctx->gin, (T * N + 64) * 4 * F);
-    if (ctx->knobs.overlap) rc = rc ? rc : dev_alloc(ctx, &ctx->gin2, (T * N + 64) * 4 * F);
-    rc = rc ? rc : dev_alloc(ctx, &ctx->c_state, N * F);
-    rc = rc ? rc : dev_alloc(ctx, &ctx->scores, T * N * Cmax);
-    if (ctx->knobs.overlap && ctx->knobs.decode_async) rc = rc ? rc : dev_alloc(ctx, &ctx->scores2, T * N * (size_t)ctx->ld_nb);
-    rc = rc ? rc : dev_alloc(ctx, &ctx->alpha, (T + 1) * N * S);
-    rc = rc ? rc : dev_alloc(ctx, &ctx->beta, (T + 1) * N * S);
-    rc = rc ? rc : dev_alloc(ctx, &ctx->bmax, (T + 1) * N * S);
-    rc = rc ? rc : dev_alloc(ctx, &ctx->logz, N);
-    rc = rc ? rc : dev_alloc(ctx, &ctx->qbuf, T * N * ((Cb + 3) & ~(size_t)3));
-    rc = rc ? rc : dev_alloc(ctx, &ctx->labels, N * T);
-    rc = rc ? rc : dev_alloc(ctx, &ctx->seq, N * T);
-    rc = rc ? rc : dev_alloc(ctx, &ctx->seq_len, N);
+    rc = rc ? rc : ws.alloc(ctx, &ctx->gin, (T * N + 64) * 4 * F);
+    if (ctx->knobs.overlap) rc = rc ? rc : ws.alloc(ctx, &ctx->gin2, (T * N + 64) * 4 * F);
+    rc = rc ? rc : ws.alloc(ctx, &ctx->c_state, N * F);
+    rc = rc ? rc : ws.alloc(ctx, &ctx->scores, T * N * Cmax);
+    if (ctx->knobs.overlap && ctx->knobs.decode_async) rc = rc ? rc : ws.alloc(ctx, &ctx->scores2, T * N * (size_t)ctx->ld_nb);
+    rc = rc ? rc : ws.alloc(ctx, &ctx->alpha, (T + 1) * N * S);
+    rc = rc ? rc : ws.alloc(ctx, &ctx->beta, (T + 1) * N * S);
+    rc = rc ? rc : ws.alloc(ctx, &ctx->bmax, (T + 1) * N * S);
+    rc = rc ? rc : ws.alloc(ctx, &ctx->logz, N);
+    rc = rc ? rc : ws.alloc(ctx, &ctx->qbuf, T * N * ((Cb + 3) & ~(size_t)3));
+    rc = rc ? rc : ws.alloc(ctx, &ctx->labels, N * T);
+    rc = rc ? rc : ws.alloc(ctx, &ctx->seq, N * T);
+    rc = rc ? rc : ws.alloc(ctx, &ctx->seq_len, N);
     if (ctx->fuse_ok) {      // results of a pair before they are split (two short calls can pair inside max_batch chunks)
-        rc = rc ? rc : dev_alloc(ctx, &ctx->fseq, N * T);
-        rc = rc ? rc : dev_alloc(ctx, &ctx->flen, N);
+        rc = rc ? rc : ws.alloc(ctx, &ctx->fseq, N * T);
+        rc = rc ? rc : ws.alloc(ctx, &ctx->flen, N);
     }
-    ctx->alloc_ws = false;
     if (!rc) ctx->cap = cap;
     return rc;
 }
@@ -165,33 +159,28 @@ int64_t expected_size(const xb_ctx *c, const std::string &name)
     return -1;
 }
 
-// weight upload: the allocation belongs to the current weight set (ctx->wbufs), which the next xb_weights_ready releases
+// weight upload: the allocation belongs to the current weight set (ctx->mem_w), which the next xb_weights_ready releases
 template <typename Tp>
 int upload(xb_ctx *ctx, Tp **dst, const std::vector<Tp> &src)
 {
-    void *p = nullptr;
-    const size_t bytes = (src.size() * sizeof(Tp) + 255) & ~(size_t)255;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess)
-        return fail(ctx, XB_ERR_NOMEM, "hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
-    ctx->wbufs.push_back(p);
-    *dst = reinterpret_cast<Tp *>(p);
+    if (int rc = ctx->mem_w.alloc(ctx, dst, src.size())) return rc;
     XB_HIP(ctx, hipMemcpy(*dst, src.data(), src.size() * sizeof(Tp), hipMemcpyHostToDevice));
     return XB_OK;
 }
 
+// What the two status words say once the main stream has drained (xb_status.h): one condition per call, and that one is taken
+// out of its word -- a validation bit beside it is the next synchronising call's to report.
 int check_device_error(xb_ctx *ctx)
 {
-    unsigned e = 0;
-    XB_HIP(ctx, hipMemcpyAsync(&e, ctx->error, sizeof e, hipMemcpyDeviceToHost, ctx->stream));
+    unsigned w[xb_ctx::STATUS_DATA_AT + 1] = {};
+    XB_HIP(ctx, hipMemcpyAsync(w, ctx->error, sizeof w, hipMemcpyDeviceToHost, ctx->stream));
     XB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (e != 0) {
-        (void)hipMemsetAsync(ctx->error, 0, sizeof(unsigned), ctx->stream);
-        if (e == 2u) return fail(ctx, XB_ERR_DEVICE, "CTC scan: a target length was outside the lattice");
-        if (e == 4u) return fail(ctx, XB_ERR_INVALID, "xb_ctc_loss: a target length outside [state_len, Lt] or a label above n_base inside it");
-        return fail(ctx, XB_ERR_DEVICE, "LSTM inter-workgroup sync timed out (persistent kernel was not fully resident?)");
-    }
-    return XB_OK;
+    const unsigned sync_word = w[0], data_word = w[xb_ctx::STATUS_DATA_AT];
+    const xb::DeviceStatus s = xb::decode_status(sync_word, data_word);
+    if (s.code == XB_OK) return XB_OK;
+    if (s.sync_left != sync_word) (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ctx->error), (int)s.sync_left, 1, ctx->stream);
+    if (s.data_left != data_word) (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ctx->error_data), (int)s.data_left, 1, ctx->stream);
+    return fail(ctx, s.code, "%s", s.message);
 }
 
 // ---- encoder orchestration --------------------------------------------------------------
@@ -502,7 +491,7 @@ int run_decode(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, 
 }
 
 template <typename Tp>
-int dev_alloc_once(xb_ctx *ctx, Tp **out, size_t count) { return *out ? XB_OK : dev_alloc(ctx, out, count); }
+int dev_alloc_once(xb_ctx *ctx, Tp **out, size_t count) { return *out ? XB_OK : ctx->mem_ctx.alloc(ctx, out, count); }
 
 // device staging and workspace of an output level (once per context; level 2 includes level 1's).  The pair planes exist
 // only where calls can pair (enqueue_call pairs none of a level while they are missing).
@@ -573,7 +562,7 @@ int ctc_loss_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int
     xb::CtcLossParams p{};
     p.scores = d_scores; p.T = T; p.N = n; p.ld = ld; p.has_blank = has_blank; p.blank = c.blank_score;
     p.nb = c.n_base; p.sl = c.state_len; p.targets = d_targets; p.Lt = Lt; p.tlen = d_len;
-    p.logz_crf = ctx->logz; p.loss = d_loss; p.logz = d_logz; p.error = ctx->error;
+    p.logz_crf = ctx->logz; p.loss = d_loss; p.logz = d_logz; p.error = ctx->error_data;
     if (const char *e = getenv("XB_CTC_LOSS_THREADS")) p.threads = atoi(e);
     StageScope sc(ctx, XB_STAGE_DECODE, 1);
     hipError_t e = xb::launch_ctc_loss(p, ctx->stream);
@@ -603,7 +592,7 @@ int ctc_grad_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int
     xb::CtcLossParams &p = q.l;
     p.scores = d_scores; p.T = T; p.N = n; p.ld = ld; p.has_blank = has_blank; p.blank = c.blank_score;
     p.nb = c.n_base; p.sl = c.state_len; p.targets = d_targets; p.Lt = Lt; p.tlen = d_len;
-    p.logz_crf = ctx->logz; p.loss = d_loss; p.error = ctx->error;
+    p.logz_crf = ctx->logz; p.loss = d_loss; p.error = ctx->error_data;
     if (const char *e = getenv("XB_CTC_LOSS_THREADS")) p.threads = atoi(e);
     q.post = ctx->qbuf; q.ldq = (ctx->S * (c.n_base + 1) + 3) & ~3;
     q.stash = static_cast<float *>(ctx->ctcgrad.stash.p); q.slot = slot;
@@ -706,14 +695,16 @@ XB_API int xb_ctx_create(xb_ctx **out, int device, const xb_config *cfg)
                    cfg->max_batch <= xb::pair_capacity(cfg->features, ctx->cu_count, ctx->knobs.lstm_wide);
     const size_t F = cfg->features;
     int rc = alloc_workspaces(ctx, cfg->max_batch);
-    rc = rc ? rc : dev_alloc(ctx, &ctx->xh, (size_t)64 * 2 * 2 * 64 * F);
-    rc = rc ? rc : dev_alloc(ctx, &ctx->sync, (size_t)SYNC_SLOTS * 32 + 32 + 64);      // group slots, error word, slab arrival counters
+    rc = rc ? rc : ctx->mem_ctx.alloc(ctx, &ctx->xh, (size_t)64 * 2 * 2 * 64 * F);
+    rc = rc ? rc : ctx->mem_ctx.alloc(ctx, &ctx->sync, (size_t)SYNC_SLOTS * 32 + 32 + 64);      // group slots, status words, slab arrival counters
     if (rc) {
         g_create_error = ctx->err;
         xb_ctx_destroy(ctx);
         return rc;
     }
+    static_assert(xb_ctx::STATUS_DATA_AT * sizeof(unsigned) >= 64 && xb_ctx::STATUS_DATA_AT < 32, "the status words: two 64-byte lines of the 32 words");
     ctx->error = ctx->sync + SYNC_SLOTS * 32;
+    ctx->error_data = ctx->error + xb_ctx::STATUS_DATA_AT;
     XB_CREATE_HIP(hipMemset(ctx->sync, 0, sizeof(unsigned) * (SYNC_SLOTS * 32 + 32 + 64)));
     ctx->sig_done = ctx->sync + SYNC_SLOTS * 32 + 32;
     if (ctx->knobs.lstm_signal) {
@@ -721,15 +712,19 @@ XB_API int xb_ctx_create(xb_ctx **out, int device, const xb_config *cfg)
         if (hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, device) != hipSuccess || !can) {
             ctx->knobs.lstm_signal = 0;
         } else {
-            void *fp = nullptr;
-            if (hipExtMallocWithFlags(&fp, 8, hipMallocSignalMemory) != hipSuccess) {
+            // signal memory where the device has it, plain device memory otherwise; owned like everything else of the context
+            DevBuf flag;
+            if (hipExtMallocWithFlags(&flag.p, 8, hipMallocSignalMemory) == hipSuccess) {
+                flag.bytes = 8;
+            } else {
                 (void)hipGetLastError();
-                if (hipMalloc(&fp, 8) != hipSuccess) { (void)hipGetLastError(); fp = nullptr; }
+                flag.p = nullptr;
+                if (flag.alloc(ctx, 8)) (void)hipGetLastError();
             }
-            if (fp) {
-                ctx->bufs.push_back({fp, 8});
-                ctx->sig_flag = static_cast<unsigned *>(fp);
-                XB_CREATE_HIP(hipMemset(fp, 0, 8));
+            if (flag.p) {
+                ctx->sig_flag = static_cast<unsigned *>(flag.p);
+                ctx->mem_ctx.bufs.push_back(std::move(flag));
+                XB_CREATE_HIP(hipMemset(ctx->sig_flag, 0, 8));
             } else {
                 ctx->knobs.lstm_signal = 0;
             }
@@ -762,22 +757,14 @@ XB_API void xb_ctx_destroy(xb_ctx *ctx)
     if (ctx->stream_copy) { (void)hipStreamSynchronize(ctx->stream_copy); (void)hipStreamDestroy(ctx->stream_copy); }
     for (auto &e : ctx->deps) (void)hipEventDestroy(e);
     for (auto &ev : ctx->events) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
-    for (auto &b : ctx->bufs) (void)hipFree(b.p);
-    for (auto &b : ctx->wsbufs) (void)hipFree(b.p);
-    for (DevBuf *b : {&ctx->staging, &ctx->map.image, &ctx->map.partial, &ctx->map.scratch, &ctx->dtw.scratch, &ctx->ctcgrad.stash, &ctx->ctcgrad.w, &ctx->head.part, &ctx->head.small,
-                      &ctx->head.stage, &ctx->head.train, &ctx->head.grad, &ctx->head.labels, &ctx->splice.pool,
-                      &ctx->splice.rows, &ctx->splice.table, &ctx->spike.model, &ctx->lstmtrain.carry, &ctx->lstmtrain.wt})
-        if (b->p) (void)hipFree(b->p);
     for (auto &o : ctx->dtw.off) {
         if (o.h) (void)hipHostFree(o.h);
-        if (o.d) (void)hipFree(o.d);
         if (o.copied) (void)hipEventDestroy(o.copied);
     }
-    for (void *w : ctx->wbufs) (void)hipFree(w);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
     if (ctx->stream3) (void)hipStreamDestroy(ctx->stream3);
-    delete ctx;
+    delete ctx;      // every DevBuf and DevPool of the context frees its device memory here: the device is set, nothing is in flight
 }
 
 XB_API int xb_load_weights(xb_ctx *ctx, const char *name, const float *host, int64_t n)
@@ -816,10 +803,9 @@ XB_API int xb_weights_ready(xb_ctx *ctx)
     for (auto &k : keys)
         if (!need(k)) return fail(ctx, XB_ERR_STATE, "missing tensor '%s'", k.c_str());
     // a second load_state_dict on a live context: nothing may still be reading the previous weight set
-    if (!ctx->wbufs.empty()) {
+    if (!ctx->mem_w.empty()) {
         if (int rcs = sync_all(ctx)) return rcs;
-        for (void *w : ctx->wbufs) (void)hipFree(w);
-        ctx->wbufs.clear();
+        ctx->mem_w.release();
     }
 
     int rc;
@@ -908,7 +894,7 @@ extern "C" __attribute__((visibility("default"))) int xb_internal_defer_after(xb
 }
 
 // The host logic on its own, for the CPU tests (tests/host_logic.py): the planner and the knobs of xb_schedule.h, the packer
-// of xb_pack.h.  None touches the device or needs a context.  Not part of the public header.
+// of xb_pack.h, the decoder of xb_status.h.  None touches the device or needs a context.  Not part of the public header.
 #define XB_INTERNAL extern "C" __attribute__((visibility("default")))
 XB_INTERNAL void xb_internal_knobs_from_env(xb::Knobs *out) { *out = xb::knobs_from_env(); }
 XB_INTERNAL int xb_internal_pair_capacity(int F, int cu_count, int lstm_wide) { return xb::pair_capacity(F, cu_count, lstm_wide); }
@@ -922,6 +908,13 @@ XB_INTERNAL int xb_internal_plan_layer(const xb::PlanQuery *q, xb::LayerPlan *pl
     for (int i = 0, r = 0; i < nts; ++i)
         for (int j = 0; j < slabs && r < max_launches; ++j) launches[r++] = plan->launch(i, j);
     return nts * slabs;
+}
+// -> the status a synchronising call returns for the two device status words; *message its text, null with XB_OK
+XB_INTERNAL int xb_internal_decode_status(unsigned sync_word, unsigned data_word, const char **message)
+{
+    const xb::DeviceStatus s = xb::decode_status(sync_word, data_word);
+    if (message) *message = s.message;
+    return s.code;
 }
 XB_INTERNAL int xb_internal_f32_to_e4m3(float x) { return xb::f32_to_e4m3(x); }
 // hi, lo: (rows, ld) fp16; q8_exp as xb::split_rows takes it
@@ -979,9 +972,7 @@ XB_API int xb_encode_dev(xb_ctx *ctx, const float *d_signal, int n, int expand_b
     int rc = check_ready(ctx, n);
     if (rc) return rc;
     if (!d_signal || !d_scores) return fail(ctx, XB_ERR_INVALID, "null device pointer");
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->result_stream = ctx->stream;
-    if ((rc = join_async_decode(ctx))) return rc;
+    if ((rc = enter(ctx, true))) return rc;
     const int ldc = expand_blanks ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
     return run_encoder(ctx, d_signal, n, expand_blanks ? 1 : 0, d_scores, ldc);
 }
@@ -991,8 +982,7 @@ XB_API int xb_encode(xb_ctx *ctx, const float *signal, int n, int expand_blanks,
     int rc = check_ready(ctx, n);
     if (rc) return rc;
     if (!signal || !scores) return fail(ctx, XB_ERR_INVALID, "null host pointer");
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = join_async_decode(ctx))) return rc;
+    if ((rc = enter(ctx, false))) return rc;
     XB_HIP(ctx, hipMemcpyAsync(ctx->d_signal, signal, sizeof(float) * (size_t)n * ctx->cfg.chunk_len,
                                hipMemcpyHostToDevice, ctx->stream));
     const int ldc = expand_blanks ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
@@ -1012,11 +1002,9 @@ static int decode_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_
     if (o.level == 0 && !d_scores) return fail(ctx, XB_ERR_INVALID, "null device pointer");
     if (o.level >= 1 && (!d_scores || !has_required(planes(d_seq, d_seq_len, o), o.level) || !alphabet))
         return fail(ctx, XB_ERR_INVALID, "null argument");
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
+    if (int rc = enter(ctx, true)) return rc;
     if (o.level == 2)                                 // the letter mass workspace
         if (int rc = ensure_staging(ctx, 2)) return rc;
-    ctx->result_stream = ctx->stream;
     const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
     return run_decode(ctx, d_scores, T, n, has_blank ? 1 : 0, ld, alphabet, d_labels, d_seq, d_seq_len, nullptr, nullptr, &o);
 }
@@ -1031,8 +1019,7 @@ static int decode_host(xb_ctx *ctx, const float *scores, int T, int n, int has_b
     if (o.level == 0 && !scores) return fail(ctx, XB_ERR_INVALID, "null host pointer");
     if (o.level >= 1 && (!scores || !has_required(dst, o.level) || !alphabet)) return fail(ctx, XB_ERR_INVALID, "null argument");
     if (T < 1 || T > ctx->T) return fail(ctx, XB_ERR_INVALID, "T=%d outside [1, %d]", T, ctx->T);
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rcj = join_async_decode(ctx)) return rcj;
+    if (int rcj = enter(ctx, false)) return rcj;
     if (o.level)
         if (int rcs = ensure_staging(ctx, o.level)) return rcs;
     const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
@@ -1092,12 +1079,10 @@ XB_API int xb_crf_scans_dev(xb_ctx *ctx, const float *d_scores, int T, int n, in
     if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
     if (!d_scores) return fail(ctx, XB_ERR_INVALID, "null device pointer");
     if (!d_alpha && !d_beta && !d_logz && !d_post) return fail(ctx, XB_ERR_INVALID, "no output requested");
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
+    if (int rc = enter(ctx, true)) return rc;       // the scans run on the main stream (not on the async decode stream)
     const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
     ScanOut so;
     so.alpha = d_alpha; so.beta = d_beta; so.logz = d_logz; so.post = d_post;
-    ctx->result_stream = ctx->stream;       // the scans run on the main stream (not on the async decode stream)
     return run_decode(ctx, d_scores, T, n, has_blank ? 1 : 0, ld, nullptr, nullptr, nullptr, nullptr, nullptr, &so);
 }
 
@@ -1109,8 +1094,7 @@ XB_API int xb_crf_scans(xb_ctx *ctx, const float *scores, int T, int n, int has_
     if (!scores) return fail(ctx, XB_ERR_INVALID, "null host pointer");
     if (!alpha && !beta && !logz && !post) return fail(ctx, XB_ERR_INVALID, "no output requested");
     if (T < 1 || T > ctx->T) return fail(ctx, XB_ERR_INVALID, "T=%d outside [1, %d]", T, ctx->T);
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rcj = join_async_decode(ctx)) return rcj;
+    if (int rcj = enter(ctx, false)) return rcj;
     const int S = ctx->S, E = ctx->cfg.n_base + 1;
     const int ld = has_blank ? S * E : ctx->O;
     XB_HIP(ctx, hipMemcpyAsync(ctx->scores, scores, sizeof(float) * (size_t)T * n * ld, hipMemcpyHostToDevice, ctx->stream));
@@ -1181,54 +1165,39 @@ static int run_ctc(xb_ctx *ctx, const float *scores, int T, int n, const int32_t
             if (targets[(size_t)b * Lt + l] < 0 || targets[(size_t)b * Lt + l] > nb)
                 return fail(ctx, XB_ERR_INVALID, "targets[%d][%d] = %d outside [0, n_base = %d]", b, l, targets[(size_t)b * Lt + l], nb);
     }
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rcj = join_async_decode(ctx)) return rcj;
+    if (int rcj = enter(ctx, true)) return rcj;             // (a host form that has always named the main stream)
     std::vector<int32_t> stay, move;
     ctc_indices(targets, n, Lt, nb, sl, stay, move);
     const size_t nm = np > 1 ? np - 1 : 1;
-    // per-call device scratch (a training-side operator: sizes follow the targets, not the context)
-    int32_t *d_stay = nullptr, *d_move = nullptr, *d_len = nullptr;
-    float *d_alpha = nullptr, *d_gs = nullptr, *d_gm = nullptr;
-    int rc = XB_OK;
-    auto cleanup = [&]() {
-        (void)hipFree(d_stay); (void)hipFree(d_move); (void)hipFree(d_len); (void)hipFree(d_alpha); (void)hipFree(d_gs); (void)hipFree(d_gm);
-    };
-#define XB_CTC_HIP(call)                                                                       \
-    do {                                                                                      \
-        hipError_t e_ = (call);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            rc = fail(ctx, e_ == hipErrorOutOfMemory ? XB_ERR_NOMEM : XB_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-            cleanup();                                                                        \
-            return rc;                                                                        \
-        }                                                                                     \
-    } while (0)
+    // per-call device scratch (a training-side operator: sizes follow the targets, not the context), freed on every return
+    DevBuf b_stay, b_move, b_len, b_alpha, b_gs, b_gm;
     const bool grads = gstay || gmove;
-    XB_CTC_HIP(hipMalloc(reinterpret_cast<void **>(&d_stay), sizeof(int32_t) * stay.size()));
-    XB_CTC_HIP(hipMalloc(reinterpret_cast<void **>(&d_move), sizeof(int32_t) * move.size()));
-    XB_CTC_HIP(hipMalloc(reinterpret_cast<void **>(&d_len), sizeof(int32_t) * (size_t)n));
+    if (int rc = b_stay.alloc(ctx, sizeof(int32_t) * stay.size())) return rc;
+    if (int rc = b_move.alloc(ctx, sizeof(int32_t) * move.size())) return rc;
+    if (int rc = b_len.alloc(ctx, sizeof(int32_t) * (size_t)n)) return rc;
     if (grads) {
-        XB_CTC_HIP(hipMalloc(reinterpret_cast<void **>(&d_alpha), sizeof(float) * (size_t)n * (T + 1) * np));
-        XB_CTC_HIP(hipMalloc(reinterpret_cast<void **>(&d_gs), sizeof(float) * (size_t)T * n * np));
-        if (gmove) XB_CTC_HIP(hipMalloc(reinterpret_cast<void **>(&d_gm), sizeof(float) * (size_t)T * n * nm));
+        if (int rc = b_alpha.alloc(ctx, sizeof(float) * (size_t)n * (T + 1) * np)) return rc;
+        if (int rc = b_gs.alloc(ctx, sizeof(float) * (size_t)T * n * np)) return rc;
+        if (gmove)
+            if (int rc = b_gm.alloc(ctx, sizeof(float) * (size_t)T * n * nm)) return rc;
     }
+    int32_t *d_stay = static_cast<int32_t *>(b_stay.p), *d_move = static_cast<int32_t *>(b_move.p), *d_len = static_cast<int32_t *>(b_len.p);
+    float *d_alpha = static_cast<float *>(b_alpha.p), *d_gs = static_cast<float *>(b_gs.p), *d_gm = static_cast<float *>(b_gm.p);
     hipStream_t st = ctx->stream;
-    ctx->result_stream = st;
-    XB_CTC_HIP(hipMemcpyAsync(d_stay, stay.data(), sizeof(int32_t) * stay.size(), hipMemcpyHostToDevice, st));
-    XB_CTC_HIP(hipMemcpyAsync(d_move, move.data(), sizeof(int32_t) * move.size(), hipMemcpyHostToDevice, st));
-    XB_CTC_HIP(hipMemcpyAsync(d_len, tlen, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
-    XB_CTC_HIP(hipMemcpyAsync(ctx->scores, scores, sizeof(float) * (size_t)T * n * C, hipMemcpyHostToDevice, st));
-    if (d_gs) XB_CTC_HIP(hipMemsetAsync(d_gs, 0, sizeof(float) * (size_t)T * n * np, st));
-    if (d_gm) XB_CTC_HIP(hipMemsetAsync(d_gm, 0, sizeof(float) * (size_t)T * n * nm, st));
+    XB_HIP(ctx, hipMemcpyAsync(d_stay, stay.data(), sizeof(int32_t) * stay.size(), hipMemcpyHostToDevice, st));
+    XB_HIP(ctx, hipMemcpyAsync(d_move, move.data(), sizeof(int32_t) * move.size(), hipMemcpyHostToDevice, st));
+    XB_HIP(ctx, hipMemcpyAsync(d_len, tlen, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    XB_HIP(ctx, hipMemcpyAsync(ctx->scores, scores, sizeof(float) * (size_t)T * n * C, hipMemcpyHostToDevice, st));
+    if (d_gs) XB_HIP(ctx, hipMemsetAsync(d_gs, 0, sizeof(float) * (size_t)T * n * np, st));
+    if (d_gm) XB_HIP(ctx, hipMemsetAsync(d_gm, 0, sizeof(float) * (size_t)T * n * nm, st));
     xb::CtcParams p{};
     p.scores = ctx->scores; p.T = T; p.N = n; p.C = C; p.stay_idx = d_stay; p.move_idx = d_move; p.n = np; p.tlen = d_len;
-    p.sl = sl; p.semiring = semiring; p.alpha = d_alpha; p.logz = ctx->logz; p.gstay = d_gs; p.gmove = d_gm; p.error = ctx->error;
-    XB_CTC_HIP(xb::launch_ctc_scan(p, st));
-    if (logz) XB_CTC_HIP(hipMemcpyAsync(logz, ctx->logz, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, st));
-    if (gstay) XB_CTC_HIP(hipMemcpyAsync(gstay, d_gs, sizeof(float) * (size_t)T * n * np, hipMemcpyDeviceToHost, st));
-    if (gmove && np > 1) XB_CTC_HIP(hipMemcpyAsync(gmove, d_gm, sizeof(float) * (size_t)T * n * nm, hipMemcpyDeviceToHost, st));
-    XB_CTC_HIP(hipStreamSynchronize(st));
-#undef XB_CTC_HIP
-    cleanup();
+    p.sl = sl; p.semiring = semiring; p.alpha = d_alpha; p.logz = ctx->logz; p.gstay = d_gs; p.gmove = d_gm; p.error = ctx->error_data;
+    XB_HIP(ctx, xb::launch_ctc_scan(p, st));
+    if (logz) XB_HIP(ctx, hipMemcpyAsync(logz, ctx->logz, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (gstay) XB_HIP(ctx, hipMemcpyAsync(gstay, d_gs, sizeof(float) * (size_t)T * n * np, hipMemcpyDeviceToHost, st));
+    if (gmove && np > 1) XB_HIP(ctx, hipMemcpyAsync(gmove, d_gm, sizeof(float) * (size_t)T * n * nm, hipMemcpyDeviceToHost, st));
+    XB_HIP(ctx, hipStreamSynchronize(st));
     return check_device_error(ctx);
 }
 
@@ -1256,13 +1225,14 @@ static int run_beam(xb_ctx *ctx, const float *d_scores, int T, int n, int has_bl
     if (!alphabet || (int)strlen(alphabet) < c.n_base + 1) return fail(ctx, XB_ERR_INVALID, "alphabet needs %d symbols", c.n_base + 1);
     if (!ctx->beam_hist) {
         const size_t N = (size_t)c.max_batch, Tm = (size_t)ctx->T;
-        int rc = dev_alloc(ctx, &ctx->beam_hist, N * (Tm + 1) * xb::BEAM_MAX_WIDTH);
-        rc = rc ? rc : dev_alloc(ctx, &ctx->beam_path, N * Tm);
-        rc = rc ? rc : dev_alloc(ctx, &ctx->beam_prob, N * Tm);
-        rc = rc ? rc : dev_alloc(ctx, &ctx->beam_score, N);
-        rc = rc ? rc : dev_alloc(ctx, &ctx->beam_seq, N * Tm);
-        rc = rc ? rc : dev_alloc(ctx, &ctx->beam_q, N * Tm);
-        rc = rc ? rc : dev_alloc(ctx, &ctx->beam_moves, N * Tm);
+        DevPool &mem = ctx->mem_ctx;
+        int rc = mem.alloc(ctx, &ctx->beam_hist, N * (Tm + 1) * xb::BEAM_MAX_WIDTH);
+        rc = rc ? rc : mem.alloc(ctx, &ctx->beam_path, N * Tm);
+        rc = rc ? rc : mem.alloc(ctx, &ctx->beam_prob, N * Tm);
+        rc = rc ? rc : mem.alloc(ctx, &ctx->beam_score, N);
+        rc = rc ? rc : mem.alloc(ctx, &ctx->beam_seq, N * Tm);
+        rc = rc ? rc : mem.alloc(ctx, &ctx->beam_q, N * Tm);
+        rc = rc ? rc : mem.alloc(ctx, &ctx->beam_moves, N * Tm);
         if (rc) { ctx->beam_hist = nullptr; return rc; }
     }
     ScanOut so;
@@ -1295,9 +1265,7 @@ XB_API int xb_beam_search_dev(xb_ctx *ctx, const float *d_scores, int T, int n, 
     if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
     if (!d_scores || !d_sequence || !d_qstring || !d_moves) return fail(ctx, XB_ERR_INVALID, "null device pointer");
     if (T < 1 || T > ctx->T) return fail(ctx, XB_ERR_INVALID, "T=%d outside [1, %d]", T, ctx->T);
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
-    ctx->result_stream = ctx->stream;
+    if (int rc = enter(ctx, true)) return rc;
     const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
     return run_beam(ctx, d_scores, T, n, has_blank ? 1 : 0, ld, alphabet, beam_width, beam_cut, qscale, qoffset, d_sequence,
                     d_qstring, d_moves, d_score);
@@ -1322,9 +1290,7 @@ XB_API int xb_beam_search(xb_ctx *ctx, const float *scores, int T, int n, int ha
     if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
     if (!scores || !sequence || !qstring || !moves) return fail(ctx, XB_ERR_INVALID, "null host pointer");
     if (T < 1 || T > ctx->T) return fail(ctx, XB_ERR_INVALID, "T=%d outside [1, %d]", T, ctx->T);
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rcj = join_async_decode(ctx)) return rcj;
-    ctx->result_stream = ctx->stream;
+    if (int rcj = enter(ctx, true)) return rcj;             // (a host form that has always named the main stream)
     const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
     XB_HIP(ctx, hipMemcpyAsync(ctx->scores, scores, sizeof(float) * (size_t)T * n * ld, hipMemcpyHostToDevice, ctx->stream));
     // the first call allocates the staging planes inside run_beam; pass them after the allocation
@@ -1341,9 +1307,7 @@ XB_API int xb_basecall_chunks_beam(xb_ctx *ctx, const float *signal, int n, cons
     int rc = check_ready(ctx, n);
     if (rc) return rc;
     if (!signal || !sequence || !qstring || !moves || !alphabet) return fail(ctx, XB_ERR_INVALID, "null argument");
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = join_async_decode(ctx))) return rc;
-    ctx->result_stream = ctx->stream;
+    if ((rc = enter(ctx, true))) return rc;                 // (a host form that has always named the main stream)
     XB_HIP(ctx, hipMemcpyAsync(ctx->d_signal, signal, sizeof(float) * (size_t)n * ctx->cfg.chunk_len, hipMemcpyHostToDevice,
                                ctx->stream));
     rc = run_encoder(ctx, ctx->d_signal, n, 0, ctx->scores, ctx->ld_nb);
@@ -1390,7 +1354,7 @@ static int call_post_actions(xb_ctx *ctx, const xb_ctx::Call &c, hipStream_t rs)
     if (c.slot >= 0) {
         xb_ctx::Slot &sl = ctx->slots[c.slot];
         if (int rc = copy_planes(ctx, c.out.level, sl.h, sl.d, 0, c.n, ctx->T, hipMemcpyDeviceToHost, rs)) return rc;
-        // the error word as THIS batch left it (stream order: behind its recurrences and its decode), not as whatever batch
+        // the sync word as THIS batch left it (stream order: behind its recurrences and its decode), not as whatever batch
         // happens to be running when the slot is collected finds it
         XB_HIP(ctx, hipMemcpyAsync(sl.h_err, ctx->error, sizeof(unsigned), hipMemcpyDeviceToHost, rs));
         XB_HIP(ctx, hipEventRecord(sl.done, rs));
@@ -1579,7 +1543,7 @@ static int ensure_slot(xb_ctx *ctx, int slot, int level)
         if (!ctx->stream_copy) XB_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream_copy, hipStreamNonBlocking));
         XB_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&sl.h_signal), sizeof(float) * N * L, hipHostMallocDefault));
         XB_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&sl.h_err), sizeof(unsigned), hipHostMallocDefault));
-        if (int rc = dev_alloc(ctx, &sl.d_signal, N * L)) return rc;
+        if (int rc = ctx->mem_ctx.alloc(ctx, &sl.d_signal, N * L)) return rc;
         XB_HIP(ctx, hipEventCreateWithFlags(&sl.h2d, hipEventDisableTiming));
         XB_HIP(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
     }
@@ -1588,7 +1552,7 @@ static int ensure_slot(xb_ctx *ctx, int slot, int level)
         if (!sl.h.p[i]) XB_HIP(ctx, hipHostMalloc(&sl.h.p[i], bytes, hipHostMallocDefault));
         if (!sl.d.p[i]) {
             uint8_t *p = nullptr;
-            if (int rc = dev_alloc(ctx, &p, bytes)) return rc;
+            if (int rc = ctx->mem_ctx.alloc(ctx, &p, bytes)) return rc;
             sl.d.p[i] = p;
         }
     }
@@ -1654,9 +1618,10 @@ static int collect_chunks(xb_ctx *ctx, int slot, int level, const Planes &dst)
     sl.busy = false;
     for (int i = 0; i < plane_count(level); ++i)
         if (dst.p[i]) memcpy(dst.p[i], sl.h.p[i], (size_t)sl.n * plane_bytes(ctx->T, ctx->cfg.n_base, i));
-    // the persistent recurrence reports a lost rendezvous through the error word (snapshot taken behind this batch):
+    // the persistent recurrence reports a lost rendezvous through the sync word (snapshot taken behind this batch):
     // results would be garbage.  The word is not cleared while another batch is in flight -- that batch fails too (it ran
-    // on a device in an unknown state) -- and is reset once the pipeline has drained.
+    // on a device in an unknown state) -- and is reset once the pipeline has drained.  The data word is not looked at: a
+    // refused label of some loss call says nothing about this batch, and the next synchronising call reports it.
     if (*sl.h_err != 0) ctx->pipeline_failed = true;
     if (ctx->pipeline_failed) {
         bool any_busy = false;
@@ -1666,7 +1631,8 @@ static int collect_chunks(xb_ctx *ctx, int slot, int level, const Planes &dst)
             (void)hipMemset(ctx->error, 0, sizeof(unsigned));
             ctx->pipeline_failed = false;
         }
-        return fail(ctx, XB_ERR_DEVICE, "LSTM inter-workgroup sync timed out (persistent kernel was not fully resident?)");
+        const xb::DeviceStatus lost = xb::decode_status(xb::SYNC_LOST, 0u);
+        return fail(ctx, lost.code, "%s", lost.message);
     }
     return XB_OK;
 }
@@ -1737,8 +1703,7 @@ XB_API int xb_debug_layer_output(xb_ctx *ctx, int which, int n, uint16_t *hi, ui
 {
     if (!ctx || !hi || !second || which < 0 || which > 1) return XB_ERR_INVALID;
     if (n < 1 || n > ctx->cap) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, %d]", n, ctx->cap);
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
+    if (int rc = enter(ctx, false)) return rc;
     if (int rc = sync_all(ctx)) return rc;
     const size_t bytes = sizeof(uint16_t) * (size_t)ctx->T * n * ctx->cfg.features;
     XB_HIP(ctx, hipMemcpy(hi, ctx->x_hi[which], bytes, hipMemcpyDeviceToHost));

@@ -5,16 +5,6 @@
 
 namespace {
 
-// The entry of every call here, after its own checks: the context's device, nothing held back, the main stream behind decodes
-// in flight beside it.  A _dev form leaves its results to the main stream.
-int enter(xb_ctx *ctx, bool dev)
-{
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
-    if (dev) ctx->result_stream = ctx->stream;
-    return XB_OK;
-}
-
 // The device staging of a host-pointer form: typed pieces of xb_ctx::staging in the order they are taken, each 256-byte
 // aligned.  `used` is their total; once ready() has grown the buffer to it, a piece converts to its device pointer.
 struct Staging {
@@ -594,19 +584,19 @@ int dtw_run(xb_ctx *ctx, const float *d_signal, int n, int N, const double *d_le
     if (slot.count < (size_t)n + 1) {
         XB_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (slot.h) (void)hipHostFree(slot.h);
-        if (slot.d) (void)hipFree(slot.d);
-        slot.h = slot.d = nullptr;
+        slot.h = nullptr;
+        slot.d.release();
         slot.count = 0;
         const size_t count = ((size_t)n + 1 + 1023) & ~(size_t)1023;
         XB_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&slot.h), count * sizeof(int32_t), hipHostMallocDefault));
-        XB_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&slot.d), count * sizeof(int32_t)));
+        if (int rc = slot.d.alloc(ctx, count * sizeof(int32_t))) return rc;
         slot.count = count;
     }
     memcpy(slot.h, offsets, sizeof(int32_t) * ((size_t)n + 1));
-    XB_HIP(ctx, hipMemcpyAsync(slot.d, slot.h, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(slot.d.p, slot.h, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
     XB_HIP(ctx, hipEventRecord(slot.copied, ctx->stream));
     xb::DtwParams p{};
-    p.signal = d_signal; p.levels = d_levels; p.off = slot.d; p.window = band ? d_window : nullptr;
+    p.signal = d_signal; p.levels = d_levels; p.off = static_cast<const int32_t *>(slot.d.p); p.window = band ? d_window : nullptr;
     p.N = N; p.rep = ref_rep; p.Kmax = Kmax;
     p.scratch = static_cast<unsigned long long *>(s.scratch.p);
     p.choice_words = choice; p.slot_words = slot_words;

@@ -1,7 +1,10 @@
-// xb_ctx.h -- the context behind the C ABI, shared by its two translation units: xb_api.hip (context lifetime, weight upload,
-// the execution of the encoder's plans, decode, pairing, the host pipeline) and xb_api_data.hip (the ctc-data tools).  The host
-// arithmetic xb_api.hip acts on lives in two headers without HIP that are checked on their own: xb_schedule.h (the knobs and the
-// planner of the encoder schedule) and xb_pack.h (the forms a weight tensor is uploaded in).  Private to csrc/.
+// xb_ctx.h -- the context behind the C ABI, shared by the translation units that implement it: xb_api.hip (context lifetime, weight
+// upload, the execution of the encoder's plans, decode, pairing, the host pipeline, and the housekeeping every entry point
+// shares: the call prologue `enter`, the status words), xb_api_data.hip (the ctc-data tools), xb_head.hip (the head's gradient
+// and trainer), xb_lstm_train.hip (the training recurrence) and xb_train_gemm.hip (the fp32 products of training); xb_comm.hip
+// reaches a context through the C ABI and xb_internal_defer_after only.  The host arithmetic xb_api.hip acts on lives in three headers without HIP that are
+// checked on their own: xb_schedule.h (the knobs and the planner of the encoder schedule), xb_pack.h (the forms a weight
+// tensor is uploaded in) and xb_status.h (the device status words).  Private to csrc/.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,12 +22,71 @@
 #include "xb_internal.h"
 #include "xb_pack.h"
 #include "xb_schedule.h"
+#include "xb_status.h"
 
 using xb::half_t;
 
+struct xb_ctx;
+int fail(const xb_ctx *ctx, int code, const char *fmt, ...);     // sets the context's (or, without one, the thread's) last error
+
+// Device memory that belongs to whoever holds the DevBuf: freed by release(), by the assignment of another buffer, or with
+// its holder -- for the context's members that is xb_ctx_destroy's `delete`, with the context's device set and its streams
+// drained.  Movable, not copyable.
 struct DevBuf {
     void *p = nullptr;
     size_t bytes = 0;
+
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) {
+            release();
+            p = o.p; bytes = o.bytes;
+            o.p = nullptr; o.bytes = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    // fresh memory of at least `want` bytes (a multiple of 256), whatever was held released first: the library's one hipMalloc
+    int alloc(const xb_ctx *ctx, size_t want)
+    {
+        release();
+        want = (want + 255) & ~(size_t)255;
+        hipError_t e = hipMalloc(&p, want);
+        if (e != hipSuccess) {
+            p = nullptr;
+            return fail(ctx, XB_ERR_NOMEM, "hipMalloc of %zu bytes failed: %s", want, hipGetErrorString(e));
+        }
+        bytes = want;
+        return XB_OK;
+    }
+};
+
+// Allocations that live and die together, handed out as typed pointers.  A context has three (xb_ctx: mem_ctx, mem_ws, mem_w).
+struct DevPool {
+    std::vector<DevBuf> bufs;
+
+    template <typename Tp>
+    int alloc(const xb_ctx *ctx, Tp **out, size_t count)
+    {
+        DevBuf b;
+        if (int rc = b.alloc(ctx, count * sizeof(Tp))) return rc;
+        *out = static_cast<Tp *>(b.p);
+        bufs.push_back(std::move(b));
+        return XB_OK;
+    }
+    bool empty() const { return bufs.empty(); }
+    void release() { bufs.clear(); }
 };
 
 struct StageEvent {
@@ -67,7 +129,7 @@ struct xb_ctx {
         // pinned + device outputs of max_batch chunks, plane by plane: those of an output level are allocated by the slot's
         // first submission at that level
         Planes h{}, d{};
-        unsigned *h_err = nullptr;             // snapshot of the device error word taken on the result stream behind this batch
+        unsigned *h_err = nullptr;             // snapshot of the device sync word taken on the result stream behind this batch
         hipEvent_t h2d = nullptr, done = nullptr;
         int n = 0;
         bool busy = false;
@@ -88,9 +150,10 @@ struct xb_ctx {
     int T = 0, S = 0, hi = 0, O = 0, kp = 0, ld_nb = 0;
     bool weights_ready = false;
     std::map<std::string, std::vector<float>> host_w;
-    std::vector<DevBuf> bufs;
-    std::vector<DevBuf> wsbufs;                // the batch-sized workspaces (alloc_workspaces)
-    bool alloc_ws = false;
+    // Who owns the device memory behind the typed pointers below:
+    DevPool mem_ctx;                           // what lives as long as the context (and what a call allocates lazily, once)
+    DevPool mem_ws;                            // the batch-sized workspaces, replaced as a whole by alloc_workspaces
+    DevPool mem_w;                             // the weight set of the last xb_weights_ready, released by the next one
 
     // weights on device
     float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *b3 = nullptr;
@@ -104,7 +167,6 @@ struct xb_ctx {
     // projections also as hi-only images for XB_PREC_F16F8_IN1
     unsigned char *w3_f4 = nullptr, *wih_f4[5] = {}, *wih_f4h[5] = {}, *wl_f4 = nullptr;
     size_t w3_ks = 0, wih_ks = 0, wih_ksh = 0, wl_ks = 0;
-    std::vector<void *> wbufs;                 // weight allocations of the current xb_weights_ready (freed by the next one)
     int8_t *whh_q1[5] = {}, *whh_q0[5] = {};   // int8-limb recurrence (knobs.lstm_i8): balanced digits of W_hh, gate-interleaved rows
     float *whh_sc[5] = {};                     // ... and the factor that turns the integer sum into the recurrent term
 
@@ -130,8 +192,12 @@ struct xb_ctx {
     uint8_t *q_moves = nullptr, *q_fmoves = nullptr;
     uint8_t *u_probs = nullptr, *u_fprobs = nullptr;
     float *u_buf = nullptr;
-    unsigned *sync = nullptr;    // [64 groups * 32] counters + error word at the end
-    unsigned *error = nullptr;
+    // [64 groups * 32] arrival counters, then 32 words that hold the two status words (xb_status.h), then the slab counters.
+    // error: the sync word, which the recurrence polls and stores (LstmParams::error); error_data: the data word of the
+    // validating kernels (CtcParams::error, CtcLossParams::error), STATUS_DATA_AT words on: another 64-byte line
+    unsigned *sync = nullptr;
+    unsigned *error = nullptr, *error_data = nullptr;
+    static constexpr int STATUS_DATA_AT = 16;
     // workgroups of the persistent kernel admitted per CU, by recurrence arithmetic (nsplit 1..5) and one / two groups per
     // workgroup (occupancy query, lazily; -1 = not asked yet)
     int lstm_resident[6][2] = {{-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}};
@@ -169,12 +235,12 @@ struct xb_ctx {
     int last_n = 0;                             // next encoder run (xb_validate_chunks reads them where they lie)
 
     // The device staging of the ctc-data tools' host-pointer forms (xb_api_data.hip, Staging): one buffer for all of them --
-    // each returns synchronised, so no two are ever live at once.  Grows with the calls; freed by xb_ctx_destroy.
+    // each returns synchronised, so no two are ever live at once.  Grows with the calls; lives as long as the context.
     DevBuf staging;
 
     // template mapper (xb_map_templates): the library last passed in (host copy and its device image: codes, offsets, the
     // chunks of the score pass) and buffers that grow with the calls -- the score pass's records, the trace pass's direction
-    // scratch.  Owned here, freed by xb_ctx_destroy.
+    // scratch.  Live as long as the context.
     struct MapState {
         std::vector<char> lib;
         std::vector<int32_t> off;
@@ -191,11 +257,12 @@ struct xb_ctx {
 
     // DTW segmentation (xb_dtw_segment): the choice-bit scratch of the launches in flight and the chunks' level offsets on
     // their way to the device -- two pinned slots in rotation, so that a call returns without waiting for its own device
-    // work.  Owned here, freed by xb_ctx_destroy.
+    // work.  The device side lives as long as the context; xb_ctx_destroy frees the pinned side and the events.
     struct DtwState {
         DevBuf scratch;
         struct Slot {
-            int32_t *h = nullptr, *d = nullptr;
+            int32_t *h = nullptr;
+            DevBuf d;                                   // `count` int32
             size_t count = 0;
             hipEvent_t copied = nullptr;
         } off[2];
@@ -204,21 +271,21 @@ struct xb_ctx {
     } dtw;
 
     // XNA spliced augmentation (xb_splice_library / xb_splice_chunks): the library's device image, kept until the next
-    // xb_splice_library.  Owned here, freed by xb_ctx_destroy.
+    // xb_splice_library.  Lives as long as the context.
     struct SpliceState {
         DevBuf pool, rows, table;
         bool loaded = false;
     } splice;
 
-    // XNA synthetic spiking (xb_spike_model / xb_spike_chunks / xb_synth_chunks): the k-mer table, kept until the next xb_spike_model.  Owned
-    // here, freed by xb_ctx_destroy.
+    // XNA synthetic spiking (xb_spike_model / xb_spike_chunks / xb_synth_chunks): the k-mer table, kept until the next xb_spike_model.  Lives
+    // as long as the context.
     struct SpikeState {
         DevBuf model;
         bool loaded = false;
     } spike;
 
     // The loss gradient (xb_ctc_loss_grad): the alpha stash of one launch of the lattice kernel (bounded by XB_CTC_SCRATCH_MB)
-    // and the chunks' weights; the posteriors lie in the decode's qbuf.  Grow with the calls; freed by xb_ctx_destroy.
+    // and the chunks' weights; the posteriors lie in the decode's qbuf.  Grow with the calls; live as long as the context.
     struct CtcGradState {
         DevBuf stash, w;
     } ctcgrad;
@@ -226,14 +293,21 @@ struct xb_ctx {
     // The head's gradient and trainer (xb_head.hip).  part: the slabs' partial sums of one launch of xb_head_grad (bounded by
     // XB_HEAD_SCRATCH_MB); small: max |dY| word, the norm's partial sums and result; stage: the host forms' staging.  While a
     // trainer is open (xb_head_train_begin .. _end): the fp32 master weights, AdamW's moments and the gradient in one buffer
-    // (W, b, mW, mb, vW, vb, dW, db), the batch's score gradient, labels and losses, and the step count.  Freed by xb_ctx_destroy.
+    // (W, b, mW, mb, vW, vb, dW, db), the batch's score gradient, labels and losses, and the step count.  part, small and stage
+    // live as long as the context; the trainer's three from xb_head_train_begin / _step to close() (xb_head_train_end).
     struct HeadState {
         DevBuf part, small, stage, train, grad, labels;
         bool open = false;
         long step = 0;
+        void close()
+        {
+            train.release(); grad.release(); labels.release();
+            open = false;
+            step = 0;
+        }
     } head;
     // The LSTM layer's training recurrence (xb_lstm_train.hip): the (n, F) cell-gradient carry of the backward's steps and the
-    // transposed recurrent weights (F, 4F) of the call in flight.  Grow with the calls; freed by xb_ctx_destroy.
+    // transposed recurrent weights (F, 4F) of the call in flight.  Grow with the calls; live as long as the context.
     struct LstmTrainState {
         DevBuf carry, wt;
     } lstmtrain;
@@ -244,8 +318,6 @@ struct xb_ctx {
     float stage_ms[XB_STAGE_COUNT] = {};
     int64_t stage_launches[XB_STAGE_COUNT] = {};
 };
-
-int fail(const xb_ctx *ctx, int code, const char *fmt, ...);     // sets the context's (or, without one, the thread's) last error
 
 #define XB_HIP(ctx, call)                                                                     \
     do {                                                                                      \
@@ -260,13 +332,14 @@ inline int grow(xb_ctx *ctx, DevBuf *b, size_t bytes)
 {
     if (bytes <= b->bytes) return XB_OK;
     XB_HIP(ctx, hipStreamSynchronize(ctx->stream));                     // nothing in flight reads the old buffer
-    if (b->p) (void)hipFree(b->p);
-    b->p = nullptr;
-    b->bytes = 0;
-    bytes = (bytes + 255) & ~(size_t)255;
-    hipError_t e = hipMalloc(&b->p, bytes);
-    if (e != hipSuccess) return fail(ctx, XB_ERR_NOMEM, "hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
-    b->bytes = bytes;
+    return b->alloc(ctx, bytes);
+}
+
+// what follows the launches of an entry point `who`: a launch the runtime refused
+inline int launched(const xb_ctx *ctx, const char *who)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ctx, XB_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
     return XB_OK;
 }
 
@@ -274,6 +347,9 @@ inline int grow(xb_ctx *ctx, DevBuf *b, size_t bytes)
 int check_ready(xb_ctx *ctx, int n);     // a context with weights and room for a batch of n
 int check_alphabet(xb_ctx *ctx, const char *alphabet);
 int join_async_decode(xb_ctx *ctx);      // flush_held, then the main stream waits for decodes in flight on the third stream
+// The entry of a call, after its own checks: the context's device, nothing held back, the main stream behind decodes in flight
+// beside it.  dev: the call leaves its results to the main stream (every _dev form), named after a held call was launched.
+int enter(xb_ctx *ctx, bool dev);
 int ctc_loss_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int n, int has_blank, int ld, const uint8_t *d_targets,
                  int Lt, const int32_t *d_len, float *d_loss, float *d_logz);
 int ctc_grad_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int n, int has_blank, int ld, const uint8_t *d_targets,

@@ -250,20 +250,6 @@ __global__ __launch_bounds__(256) void head_repack_kernel(const float *w, int O,
     *reinterpret_cast<half8 *>(blk + (2 + c) * 1024) = q;
 }
 
-#define XB_LAUNCHED(ctx, who)                                                                                                   \
-    do {                                                                                                                        \
-        hipError_t e_ = hipGetLastError();                                                                                      \
-        if (e_ != hipSuccess) return fail(ctx, XB_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e_));               \
-    } while (0)
-
-int enter(xb_ctx *ctx, bool dev)
-{
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
-    if (dev) ctx->result_stream = ctx->stream;
-    return XB_OK;
-}
-
 // layout of xb_ctx::head.small: the max |dY| word, the norm, the norm's partial sums
 unsigned *small_amax(xb_ctx *ctx) { return static_cast<unsigned *>(ctx->head.small.p); }
 float *small_norm(xb_ctx *ctx) { return reinterpret_cast<float *>(static_cast<char *>(ctx->head.small.p) + 64); }
@@ -306,7 +292,7 @@ int head_grad_run(xb_ctx *ctx, const char *who, const float *d_y, const float *d
     const size_t cells = (size_t)M * O;
     XB_HIP(ctx, hipMemsetAsync(amax, 0, sizeof(unsigned), ctx->stream));
     head_absmax_kernel<<<(unsigned)std::min<size_t>(1024, (cells + 255) / 256), 256, 0, ctx->stream>>>(d_dy, cells, amax);
-    XB_LAUNCHED(ctx, who);
+    if (int rc = launched(ctx, who)) return rc;
     HeadGradArgs a{};
     a.y = d_y; a.dy = d_dy; a.x_hi = d_xh; a.x_lo = d_xl; a.M = (long)M; a.O = O; a.F = F; a.scale = ctx->cfg.scale; a.amax = amax;
     a.o_tiles_launch = plan.o_tiles_per_launch; a.nslabs = plan.nslabs; a.ksteps = plan.ksteps;
@@ -317,12 +303,12 @@ int head_grad_run(xb_ctx *ctx, const char *who, const float *d_y, const float *d
         const int tiles = std::min(plan.o_tiles_per_launch, plan.o_tiles - t0);
         a.o_tile0 = t0;
         head_grad_kernel<<<dim3(plan.f_tiles, tiles, plan.nslabs), 256, 0, ctx->stream>>>(a);
-        XB_LAUNCHED(ctx, who);
+        if (int rc = launched(ctx, who)) return rc;
         const int o_begin = t0 * TO, rows = std::min(tiles * TO, O - o_begin);
         const size_t work = (size_t)rows * F + rows;
         head_reduce_kernel<<<(unsigned)((work + 255) / 256), 256, 0, ctx->stream>>>(a.part_w, a.part_b, plan.nslabs, rows_l, o_begin, rows, F, amax,
                                                                                   a.scale, d_dw, d_db);
-        XB_LAUNCHED(ctx, who);
+        if (int rc = launched(ctx, who)) return rc;
     }
     return XB_OK;
 }
@@ -331,17 +317,16 @@ int grad_norm_run(xb_ctx *ctx, const float *d_a, size_t na, const float *d_b, si
 {
     if (int rc = small_ready(ctx)) return rc;
     head_norm_partial_kernel<<<NORM_BLOCKS, 256, 0, ctx->stream>>>(d_a, na, d_b, nb, small_part(ctx));
-    XB_LAUNCHED(ctx, "xb_grad_norm");
+    if (int rc = launched(ctx, "xb_grad_norm")) return rc;
     head_norm_final_kernel<<<1, 256, 0, ctx->stream>>>(small_part(ctx), d_norm);
-    XB_LAUNCHED(ctx, "xb_grad_norm");
+    if (int rc = launched(ctx, "xb_grad_norm")) return rc;
     return XB_OK;
 }
 
 int adamw_run(xb_ctx *ctx, float *p, float *g, float *m, float *v, size_t len, float clip, float decay, float step_size, float bc2_sqrt)
 {
     adamw_kernel<<<(unsigned)((len + 255) / 256), 256, 0, ctx->stream>>>(p, g, m, v, len, clip, decay, step_size, bc2_sqrt);
-    XB_LAUNCHED(ctx, "xb_adamw_step");
-    return XB_OK;
+    return launched(ctx, "xb_adamw_step");
 }
 
 int repack_run(xb_ctx *ctx, const float *d_w, const float *d_b)
@@ -349,7 +334,7 @@ int repack_run(xb_ctx *ctx, const float *d_w, const float *d_b)
     const int O = ctx->O, F = ctx->cfg.features;
     const size_t threads = (size_t)(F / 32) * (((O + 255) & ~255) / 32) * 128;
     head_repack_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, ctx->stream>>>(d_w, O, F, ctx->wl_hi, ctx->wl_lo, ctx->wl_f4, ctx->wl_ks);
-    XB_LAUNCHED(ctx, "xb_head_repack");
+    if (int rc = launched(ctx, "xb_head_repack")) return rc;
     XB_HIP(ctx, hipMemcpyAsync(ctx->bl, d_b, sizeof(float) * (size_t)O, hipMemcpyDeviceToDevice, ctx->stream));
     return XB_OK;
 }
@@ -580,13 +565,7 @@ XB_API int xb_head_train_end(xb_ctx *ctx)
     if (!ctx->head.open) return fail(ctx, XB_ERR_STATE, "xb_head_train_end: no trainer is open");
     if (int rc = enter(ctx, false)) return rc;
     if (int rc = xb_synchronize(ctx)) return rc;
-    for (DevBuf *d : {&ctx->head.train, &ctx->head.grad, &ctx->head.labels}) {
-        if (d->p) (void)hipFree(d->p);
-        d->p = nullptr;
-        d->bytes = 0;
-    }
-    ctx->head.open = false;
-    ctx->head.step = 0;
+    ctx->head.close();
     return XB_OK;
 }
 

@@ -57,7 +57,7 @@ struct CtcParams {
     float *logz;                 // (N) or nullptr
     float *gstay;                // (T, N, n) or nullptr: Log: d logZ / d stay; Max: the one-hot alignment (zeroed by the caller)
     float *gmove;                // (T, N, n - 1) or nullptr (Log only)
-    unsigned *error;             // bit 1 set when a target length is out of range
+    unsigned *error;             // the context's data word: xb::DATA_SCAN_LENGTH (xb_status.h) ORed in when a target length is out of range
 };
 hipError_t launch_ctc_scan(const CtcParams &p, hipStream_t stream);
 int ctc_max_positions();
@@ -77,7 +77,7 @@ struct CtcLossParams {
     const float *logz_crf;       // (N) the CRF's log partition function of the same scores
     float *loss;                 // (N) -logz_ctc / tlen
     float *logz;                 // (N) or nullptr: logz_ctc
-    unsigned *error;             // bit 2 set when a target length or a label inside it is out of range
+    unsigned *error;             // the context's data word: xb::DATA_LOSS_LABEL (xb_status.h) ORed in when a target length or a label inside it is out of range
     int threads;                 // 0 = the rule ctc_loss_threads; 64, 128, 256 (experiments: XB_CTC_LOSS_THREADS)
 };
 int ctc_loss_threads(int positions);       // threads per chunk for a label row that gives `positions` lattice positions
@@ -211,7 +211,7 @@ struct LstmParams {
     int persistent;              // 1: all steps in one launch with inter-workgroup sync
     unsigned *sync;              // per-group monotonic arrival counters, 64 words per 64-chunk group slot (zeroed once per layer and chunk slab)
     unsigned sync_base;          // arrivals per member already counted by earlier launches of this layer (time slabs)
-    unsigned *error;             // set non-zero when a sync wait timed out
+    unsigned *error;             // the context's sync word: xb::SYNC_LOST (xb_status.h) stored when a sync wait timed out; polled by the waits
     int nsplit;                  // as GemmParams::nsplit (2: w_lo, y_lo and the exchange "lo" part are q8 images, h exponent 8);
                                  // 4: int8-limb recurrence (wq1, wq0, wscale below; y stays hi + q8 image for the next GEMM);
                                  // 5: the same without the d0 x d0 product

@@ -187,14 +187,6 @@ __global__ __launch_bounds__(256) void lstm_train_transpose_kernel(const float *
     wt[((size_t)blockIdx.x * 16 + ty) * R + blockIdx.y * 16 + tx] = tile[tx][ty];
 }
 
-int enter_dev(xb_ctx *ctx)
-{
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
-    ctx->result_stream = ctx->stream;
-    return XB_OK;
-}
-
 int check_shape(xb_ctx *ctx, const char *who, int T, int n, int F, std::initializer_list<const void *> ptrs)
 {
     for (const void *p : ptrs) {
@@ -219,7 +211,7 @@ XB_API int xb_lstm_train_forward_dev(xb_ctx *ctx, const float *d_gin, const floa
 {
     if (!ctx) return XB_ERR_INVALID;
     if (int rc = check_shape(ctx, "xb_lstm_train_forward", T, n, F, {d_gin, d_w_hh, d_y, d_gates, d_c})) return rc;
-    if (int rc = enter_dev(ctx)) return rc;
+    if (int rc = enter(ctx, true)) return rc;
     const size_t nF = (size_t)n * F;
     const int rt = row_tiles(n);
     const dim3 grid((unsigned)((n + rt * 16 - 1) / (rt * 16)), (unsigned)(F / JB));
@@ -233,8 +225,7 @@ XB_API int xb_lstm_train_forward_dev(xb_ctx *ctx, const float *d_gin, const floa
         if (rt == 1) hipLaunchKernelGGL(lstm_train_fwd_kernel<1>, grid, dim3(256), 0, ctx->stream, a);
         else hipLaunchKernelGGL(lstm_train_fwd_kernel<4>, grid, dim3(256), 0, ctx->stream, a);
     }
-    XB_HIP(ctx, hipGetLastError());
-    return XB_OK;
+    return launched(ctx, "xb_lstm_train_forward");
 }
 
 XB_API int xb_lstm_train_backward_dev(xb_ctx *ctx, const float *d_dy, const float *d_w_hh, const float *d_gates, const float *d_c, int T,
@@ -242,7 +233,7 @@ XB_API int xb_lstm_train_backward_dev(xb_ctx *ctx, const float *d_dy, const floa
 {
     if (!ctx) return XB_ERR_INVALID;
     if (int rc = check_shape(ctx, "xb_lstm_train_backward", T, n, F, {d_dy, d_w_hh, d_gates, d_c, d_dgin})) return rc;
-    if (int rc = enter_dev(ctx)) return rc;
+    if (int rc = enter(ctx, true)) return rc;
     const size_t nF = (size_t)n * F;
     if (int rc = grow(ctx, &ctx->lstmtrain.carry, nF * sizeof(float))) return rc;
     if (int rc = grow(ctx, &ctx->lstmtrain.wt, (size_t)4 * F * F * sizeof(float))) return rc;
@@ -262,8 +253,7 @@ XB_API int xb_lstm_train_backward_dev(xb_ctx *ctx, const float *d_dy, const floa
         if (rt == 1) hipLaunchKernelGGL(lstm_train_bwd_kernel<1>, grid, dim3(256), 0, ctx->stream, a);
         else hipLaunchKernelGGL(lstm_train_bwd_kernel<4>, grid, dim3(256), 0, ctx->stream, a);
     }
-    XB_HIP(ctx, hipGetLastError());
-    return XB_OK;
+    return launched(ctx, "xb_lstm_train_backward");
 }
 
 }  // extern "C"

@@ -241,21 +241,6 @@ __global__ __launch_bounds__(256) void head_dz_kernel(const float *y, const floa
     dz[i] = dy[i] * gv;
 }
 
-int launched(xb_ctx *ctx, const char *who)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ctx, XB_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
-    return XB_OK;
-}
-
-int enter_dev(xb_ctx *ctx)
-{
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = join_async_decode(ctx)) return rc;
-    ctx->result_stream = ctx->stream;
-    return XB_OK;
-}
-
 bool vec_ok(const float *p, int ld) { return (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // the grid's y dimension holds 65535 blocks: M up to 64 * 65535 rows per launch, more in several
@@ -306,7 +291,7 @@ XB_API int xb_linear_f32_dev(xb_ctx *ctx, const float *d_a, const float *d_w, co
     if (M < 1 || N < 1 || K < 1 || M > ((int64_t)1 << 40) || (act != 0 && act != 1))
         return fail(ctx, XB_ERR_INVALID, "xb_linear_f32: M = %lld, N = %d, K = %d, act = %d; accepted: each size >= 1, act 0 or 1", (long long)M, N, K, act);
     if (act == 1 && !std::isfinite(scale)) return fail(ctx, XB_ERR_INVALID, "xb_linear_f32: scale %g", (double)scale);
-    if (int rc = enter_dev(ctx)) return rc;
+    if (int rc = enter(ctx, true)) return rc;
     return xb::linear_f32_run(ctx, d_a, d_w, d_bias, M, N, K, act, scale, d_out);
 }
 
@@ -316,7 +301,7 @@ XB_API int xb_wgrad_f32_dev(xb_ctx *ctx, const float *d_a, const float *d_b, int
     if (!d_dw || (M > 0 && (!d_a || !d_b))) return fail(ctx, XB_ERR_INVALID, "xb_wgrad_f32: null device pointer");
     if (M < 0 || N < 1 || K < 1 || M > ((int64_t)1 << 40) || (N + TM - 1) / TM > 65535)
         return fail(ctx, XB_ERR_INVALID, "xb_wgrad_f32: M = %lld, N = %d, K = %d; accepted: M >= 0, N in 1 .. %d, K >= 1", (long long)M, N, K, TM * 65535);
-    if (int rc = enter_dev(ctx)) return rc;
+    if (int rc = enter(ctx, true)) return rc;
     return xb::wgrad_f32_run(ctx, d_a, d_b, M, N, K, d_dw, d_dcol, xb::WGRAD_BLOCK_ROWS);
 }
 
@@ -326,7 +311,7 @@ extern "C" __attribute__((visibility("default"))) int xb_internal_wgrad_blocked(
                                                                                 int K, float *d_dw, float *d_dcol, int64_t block_rows)
 {
     if (!ctx || !d_dw || M < 0 || N < 1 || K < 1 || block_rows < 32 || block_rows % 32) return XB_ERR_INVALID;
-    if (int rc = enter_dev(ctx)) return rc;
+    if (int rc = enter(ctx, true)) return rc;
     return xb::wgrad_f32_run(ctx, d_a, d_b, M, N, K, d_dw, d_dcol, (long)block_rows);
 }
 
@@ -336,7 +321,7 @@ XB_API int xb_head_dz_dev(xb_ctx *ctx, const float *d_y, const float *d_dy, int6
     if (!d_y || !d_dy || !d_dz) return fail(ctx, XB_ERR_INVALID, "xb_head_dz: null device pointer");
     if (count < 1 || count > ((int64_t)1 << 40)) return fail(ctx, XB_ERR_INVALID, "xb_head_dz: %lld elements", (long long)count);
     if (!(scale > 0.0f) || !std::isfinite(scale)) return fail(ctx, XB_ERR_INVALID, "xb_head_dz: scale %g, a positive number is needed", (double)scale);
-    if (int rc = enter_dev(ctx)) return rc;
+    if (int rc = enter(ctx, true)) return rc;
     return xb::head_dz_run(ctx, d_y, d_dy, count, scale, d_dz);
 }
 
