@@ -11,9 +11,18 @@ size of y's own is what torch's y carries too).  The backward is fed the DEVICE'
 Every test prints both errors.
 
   kernels    T in {1, 2, 5} x n in {1, 17, 65} (a lone row, a ragged row tile, one past a workgroup's 64 rows: the launch with
-             four row tiles per workgroup) x F in {16, 48, 96}, and T = 3, n = 5, F = 768 (the real K = 3072 of the backward); both
-             directions
+             four row tiles per workgroup) x F in {16, 48, 96}, T = 3, n = 5, F = 768 (the real K = 3072 of the backward), and
+             T = 64, n = 65, F = 48 (a long chain in the four-tile launch); both directions
+  widths     every F the entry points accept (16, 32, .. 1024: nk = F / 16 chunks of k, 1 .. 64), T = 3 (the middle step has a
+             recurrent product, a c_prev and a carry at once), both directions: n = 100 (four row tiles per workgroup, k in groups
+             of 4 chunks and a tail) against the restatement, and its rows 0..16 against the bytes of an n = 17 call (one row
+             tile, groups of 8 and a tail) -- every nk through both variants' grouped and tail loops, and "a row's bytes do not
+             depend on the rows beside it" at every width
+  row tiles  F in {48, 144, 768}, T = 2, n in {16, 64, 100, 129, 200} (64: the last size with one tile per workgroup; 129: a
+             third workgroup with one row; 200: four workgroups, the last with a full, a ragged and two skipped tiles) against the
+             restatement, rows 0..15 of each the bytes of the n = 16 call
   bytes      rows 0..16 of an n = 65 call equal an n = 17 call; a repeated call; dy = 0 gives zero bytes; gin of +-1e4 stays finite
+  workspace  one context through (n = 100, F = 1024), (n = 17, F = 16) and the first again: each the bytes of a fresh context's
   refusals   F = 24, F = 1040, T = 0, a null pointer: XB_ERR_INVALID, and the context still works
   layer      encoder[7](x) and encoder[8](x) of a small Model, a scalar loss, .backward(): y, x.grad and the three parameter
              gradients against the reference; ten AdamW steps on top LSTM + head bring the loss down"""
@@ -30,7 +39,10 @@ from xna_basecaller_amd import _lib
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
 MARGIN = 8.0
-SHAPES = [(T, n, F) for T in (1, 2, 5) for n in (1, 17, 65) for F in (16, 48, 96)] + [(3, 5, 768)]
+SHAPES = [(T, n, F) for T in (1, 2, 5) for n in (1, 17, 65) for F in (16, 48, 96)] + [(3, 5, 768), (64, 65, 48)]
+WIDTHS = list(range(16, 1025, 16))                                  # every F check_shape accepts
+TILING = [(F, rev, n) for F in (48, 144, 768) for rev in (False, True) for n in (16, 64, 100, 129, 200)]
+RATIOS = []
 
 
 @pytest.fixture(scope="module")
@@ -38,10 +50,11 @@ def ctx():
     c = _lib.Context(0, 4, 2, 32, 19, 5, 5.0, 2.0, 100, 1)        # the recurrence uses the context's stream and workspace only
     yield c
     c.close()
+    if RATIOS:
+        print("largest ratio to torch float32: %.2f (%s)" % max(RATIOS))
 
 
-@functools.lru_cache(maxsize=None)
-def case(T, n, F, reverse):
+def draw(T, n, F, reverse):
     """float32 inputs (gin, W_hh, dy), the float64 reference of both entry points and the yardstick: torch.nn.LSTM in float32 on
     the CPU, fed gin through an identity input projection (exact), whose x.grad is dgin.  Computed once, never modified."""
     rng = np.random.default_rng(100000 * T + 1000 * n + F + (7 if reverse else 0))
@@ -55,7 +68,11 @@ def case(T, n, F, reverse):
     yard = dict(y=R.rel(t32["y"], y), dgin=R.rel(t32["dx"], dgin))
     for a in (gin, w_hh, dy, y, gates, c, dgin):
         a.setflags(write=False)
-    return dict(gin=gin, w_hh=w_hh, dy=dy, y=y, gates=gates, c=c, dgin=dgin, yard=yard)
+    return dict(gin=gin, w_hh=w_hh, dy=dy, y=y, gates=gates, c=c, dgin=dgin, yard=yard, t32=dict(y=t32["y"], dgin=t32["dx"]))
+
+
+case = functools.lru_cache(maxsize=None)(draw)
+wide_case = functools.lru_cache(maxsize=2)(draw)                    # up to 50 MB a case: used by the test that asks, then dropped
 
 
 def _dev(a):
@@ -85,7 +102,8 @@ def dev_backward(ctx, dy, w_hh, gates, c, reverse):
 
 def held(what, got, ref, yard):
     err = R.rel(got, ref)
-    print("%-28s device %.3g  torch float32 %.3g  ratio %.2f" % (what, err, yard, err / yard if yard else float("inf")))
+    RATIOS.append((err / yard if yard else (0.0 if err == 0.0 else float("inf")), what))
+    print("%-28s device %.3g  torch float32 %.3g  ratio %.2f" % (what, err, yard, RATIOS[-1][0]))
     assert np.isfinite(got).all(), what
     assert err <= MARGIN * yard, (what, err, yard)
 
@@ -114,6 +132,73 @@ def test_rows_do_not_depend_on_the_batch(ctx, reverse):
         assert np.ascontiguousarray(whole[:, :17]).tobytes() == part.tobytes(), name
     dsub = dev_backward(ctx, k["dy"][:, :17], k["w_hh"], sub[1], sub[2], reverse)
     assert np.ascontiguousarray(dgin[:, :17]).tobytes() == dsub.tobytes()
+
+
+def _rows_equal(whole, part, what):
+    """The first rows of every step of `whole` (T, n, ..) are the bytes of `part` (T, m, ..)."""
+    assert np.ascontiguousarray(whole[:, :part.shape[1]]).tobytes() == part.tobytes(), what
+
+
+@pytest.mark.parametrize("reverse", [False, True])
+@pytest.mark.parametrize("F", WIDTHS)
+def test_every_width_in_both_launches(ctx, F, reverse):
+    k = wide_case(3, 100, F, reverse)
+    tag = "sweep F%d %s" % (F, "rev" if reverse else "fwd")
+    y, gates, c = dev_forward(ctx, k["gin"], k["w_hh"], reverse)
+    held(tag + " y", y, k["y"], k["yard"]["y"])
+    held(tag + " gates", gates, k["gates"], k["yard"]["y"])
+    held(tag + " c", c, k["c"], k["yard"]["y"])
+    dgin = dev_backward(ctx, k["dy"], k["w_hh"], gates, c, reverse)
+    held(tag + " dgin", dgin, R.backward(k["dy"], k["w_hh"], gates, c, reverse), k["yard"]["dgin"])
+    sub = dev_forward(ctx, k["gin"][:, :17], k["w_hh"], reverse)                # one row tile a workgroup, k in groups of 8
+    for name, whole, part in zip(("y", "gates", "c"), (y, gates, c), sub):
+        _rows_equal(whole, part, tag + " " + name)
+    _rows_equal(dgin, dev_backward(ctx, k["dy"][:, :17], k["w_hh"], sub[1], sub[2], reverse), tag + " dgin")
+
+
+@pytest.mark.parametrize("F,reverse,n", TILING)
+def test_row_tiling(ctx, F, reverse, n):
+    k = wide_case(2, 200, F, reverse)                                   # n rows of the case are its first n
+    tag = "tiles n%d F%d %s" % (n, F, "rev" if reverse else "fwd")
+    gin, dy = k["gin"][:, :n], k["dy"][:, :n]
+    y, gates, c = dev_forward(ctx, gin, k["w_hh"], reverse)
+    yard = R.rel(k["t32"]["y"][:, :n], k["y"][:, :n])
+    held(tag + " y", y, k["y"][:, :n], yard)
+    held(tag + " gates", gates, k["gates"][:, :n], yard)
+    held(tag + " c", c, k["c"][:, :n], yard)
+    dgin = dev_backward(ctx, dy, k["w_hh"], gates, c, reverse)
+    held(tag + " dgin", dgin, R.backward(dy, k["w_hh"], gates, c, reverse), R.rel(k["t32"]["dgin"][:, :n], k["dgin"][:, :n]))
+    first = dev_forward(ctx, gin[:, :16], k["w_hh"], reverse)
+    for name, whole, part in zip(("y", "gates", "c"), (y, gates, c), first):
+        _rows_equal(whole, part, tag + " " + name)
+    _rows_equal(dgin, dev_backward(ctx, dy[:, :16], k["w_hh"], first[1], first[2], reverse), tag + " dgin")
+
+
+def test_the_workspace_serves_calls_of_any_size_in_any_order():
+    """The carry and the transposed W_hh lie in the context and grow with the calls: a large call, a small one in the large
+    one's buffers and the large one again each give the bytes of the same call on a context of its own."""
+    big, small = wide_case(3, 100, 1024, False), wide_case(3, 17, 16, True)
+    calls = [(big, False), (small, True), (big, False)]
+
+    def run(c, k, reverse):                                             # the backward takes any stash: the reference's, in float32
+        return dev_backward(c, k["dy"], k["w_hh"], k["gates"], k["c"], reverse)
+
+    shared = _lib.Context(0, 4, 2, 32, 19, 5, 5.0, 2.0, 100, 1)
+    try:
+        got = [run(shared, k, reverse) for k, reverse in calls]
+    finally:
+        shared.close()
+    for i, (k, reverse) in enumerate(calls[:2]):
+        fresh = _lib.Context(0, 4, 2, 32, 19, 5, 5.0, 2.0, 100, 1)
+        try:
+            alone = run(fresh, k, reverse)
+        finally:
+            fresh.close()
+        own = R.backward(k["dy"], k["w_hh"], k["gates"].astype(np.float32), k["c"].astype(np.float32), reverse)
+        held("workspace, call %d dgin" % i, alone, own, k["yard"]["dgin"])      # the right call, not only the same one
+        assert got[i].tobytes() == alone.tobytes(), i
+        if i == 0:
+            assert got[2].tobytes() == alone.tobytes()
 
 
 @pytest.mark.parametrize("n", [17, 65])

@@ -7,10 +7,15 @@ tensor's maximum -- the device must stay within MARGIN = 8 times that.  Every co
   linear   M in {1, 17, 65} x N in {16, 48, 125} x K in {16, 125, 200} (a lone row, a ragged row tile, one past a workgroup's 64
            rows; one column tile, a ragged one, two; k of one chunk, ragged with rows that are not 16-byte aligned, several
            staging rounds), both activations, with and without bias; rows 0..16 of M = 65 are the bytes of M = 17; a repeated
-           call; +-1e4 under tanh
+           call; +-1e4 under tanh.  The widths of a real step at M = 17, with bias, both activations: (N, K) = (3072, 768) gin,
+           (768, 3072) dx, (1296, 768) the scores, (768, 1296) the head's dX, (768, 625) the same at C = 625, whose rows are not
+           16-byte aligned -- column tiles up to 47, up to 96 staging rounds.  The launch seam: M = 64 * 65535 + 65 rows are two
+           launches; all of it against float64, and the last 129 rows (the last tile before the seam, the second launch) are
+           the bytes of a call on those rows alone
   wgrad    M in {0, 1, 5, 130, 20000} x (N, K) in {(16, 16), (125, 48), (200, 125)} (20000 rows: 19 blocks of the blocked sum and
            a ragged one; not at (200, 125)), dcol included; M = 0 and a gradient of zeros give zero bytes; a repeated call; the
-           shifted operands of dW_hh in both directions
+           shifted operands of dW_hh in both directions.  The widths of a real step at M = 130, dcol included: (N, K) =
+           (3072, 768) dW_ih and dW_hh, (1296, 768) the head, (625, 768) the head at C = 625 (rows of a not 16-byte aligned)
   dz       bit-equal to numpy operation by operation, |y| = scale included"""
 import functools
 
@@ -27,6 +32,9 @@ MARGIN = 8.0
 SCALE = 5.0
 LINEAR = [(M, N, K) for M in (1, 17, 65) for N in (16, 48, 125) for K in (16, 125, 200)]
 WGRAD = [(M, N, K) for M in (0, 1, 5, 130, 20000) for N, K in ((16, 16), (125, 48), (200, 125)) if not (M == 20000 and N == 200)]
+LINEAR_REAL = [(3072, 768), (768, 3072), (1296, 768), (768, 1296), (768, 625)]
+WGRAD_REAL = [(3072, 768), (1296, 768), (625, 768)]
+SEAM_ROWS = 64 * 65535                 # rows of one launch of xb_linear_f32: 65535 blocks of 64 in the grid's y dimension
 RATIOS = []
 
 
@@ -90,6 +98,29 @@ def test_linear_against_float64(ctx, M, N, K):
         held("linear M%d N%d K%d act%d bias%d" % (M, N, K, act, bias), got, ref[:M], R.rel(t32[:M], ref[:M]))
 
 
+@pytest.mark.parametrize("N,K", LINEAR_REAL)
+def test_linear_at_the_widths_of_a_real_step(ctx, N, K):
+    a, w, b, out = linear_case(N, K)
+    for act in (0, 1):
+        ref, t32 = out[act, True]
+        got = dev_linear(ctx, a[:17], w, b, act)
+        held("linear M17 N%d K%d act%d bias1" % (N, K, act), got, ref[:17], R.rel(t32[:17], ref[:17]))
+
+
+def test_linear_across_the_launch_seam(ctx):
+    M, N, K = SEAM_ROWS + 65, 8, 8
+    rng = np.random.default_rng(65535)
+    a = rng.standard_normal((M, K), dtype=np.float32)
+    w = rng.uniform(-2.0 / np.sqrt(K), 2.0 / np.sqrt(K), (N, K)).astype(np.float32)
+    b = (0.5 * rng.standard_normal(N)).astype(np.float32)
+    ref = a.astype(np.float64) @ w.astype(np.float64).T + b.astype(np.float64)
+    t32 = torch.nn.functional.linear(torch.from_numpy(a), torch.from_numpy(w), torch.from_numpy(b)).numpy()
+    got = dev_linear(ctx, a, w, b, 0)
+    held("linear M%d N%d K%d act0 bias1" % (M, N, K), got, ref, R.rel(t32, ref))
+    assert SEAM_ROWS - 64 <= M - 129 < SEAM_ROWS < M                   # the rows compared lie on both sides of the seam
+    assert got[M - 129:].tobytes() == dev_linear(ctx, a[M - 129:], w, b, 0).tobytes()
+
+
 @pytest.mark.parametrize("N,K", [(48, 125), (125, 200)])
 def test_linear_rows_do_not_depend_on_the_batch_and_repeat(ctx, N, K):
     a, w, b, _ = linear_case(N, K)
@@ -147,6 +178,14 @@ def test_wgrad_against_float64(ctx, M, N, K):
     assert again[0].tobytes() == dw.tobytes() and again[1].tobytes() == dcol.tobytes()
     only = dev_wgrad(ctx, a, b, N, K, want_col=False)
     assert only[0].tobytes() == dw.tobytes() and np.isnan(only[1]).all()
+
+
+@pytest.mark.parametrize("N,K", WGRAD_REAL)
+def test_wgrad_at_the_widths_of_a_real_step(ctx, N, K):
+    a, b, ref, t32 = wgrad_case(130, N, K)
+    dw, dcol = dev_wgrad(ctx, a, b, N, K)
+    held("wgrad M130 N%d K%d dw" % (N, K), dw, ref[0], R.rel(t32[0], ref[0]))
+    held("wgrad M130 N%d K%d dcol" % (N, K), dcol, ref[1], R.rel(t32[1], ref[1]))
 
 
 @pytest.mark.parametrize("M", [5, 130])

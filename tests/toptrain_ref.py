@@ -9,12 +9,46 @@ dscores are inputs: the bottom and the loss have their own references.
   torch_run(x0, tensors, scale, dscores, dtype) -> the same from torch.nn.LSTM / Linear and torch.autograd on the CPU: in float64
                                                what the restatement is held to, in float32 the yardstick of the device tests
   table(L, F, C, rows)                      -> csrc/xb_top_plan.h restated: offsets, lengths, floats of a buffer, its stride, bytes
+  CASES, draw(case)                         -> the steps the device's kernels are composed at (tests/test_gpu_toptrain.py) and their
+                                               float32 numpy stand-in is run at (tests/test_toptrain_host.py), and their inputs
 
 tensors: per unfrozen layer weight_ih_l0 (4F, F), weight_hh_l0 (4F, F), bias_ih_l0 (4F), bias_hh_l0 (4F), lowest layer first; then
 the head's weight (C, F) and bias (C) -- 4 L + 2 arrays, the order of csrc/xb_top_plan.h."""
+import collections
+
 import numpy as np
 
 import lstm_train_ref as R
+
+# A composed step: L unfrozen layers, (T, n, F) activations, C score columns; d loss / d scores is N(0, 1), times 10^U(-9, -4)
+# per element where `small` (a mean loss's gradients), or None: the test supplies it (the device's own loss).
+Case = collections.namedtuple("Case", "L T n F C small")
+CASES = [Case(1, 7, 5, 48, 125, False),       # a ragged last column tile, score rows that are not 16-byte aligned
+         Case(2, 7, 17, 48, 125, False),
+         Case(3, 7, 5, 48, 125, True),
+         Case(2, 4, 65, 96, 64, False),       # the recurrence's launch with four row tiles a workgroup
+         Case(1, 3, 5, 768, 125, False),      # the real K
+         Case(5, 6, 5, 32, 64, True),         # every layer csrc/xb_top_plan.h lays out
+         Case(2, 1, 5, 48, 125, False)]       # one time step: dW_hh sums over no rows
+LOSS_CASE = Case(2, 40, 6, 48, 125, None)     # d loss / d scores from xb_ctc_loss_grad on the device's scores (n_base 5, state_len 2)
+
+
+def case_id(c):
+    return "L%d-T%d-n%d-F%d-C%d%s" % (c[:5] + ({False: "", True: "-small", None: "-loss"}[c.small],))
+
+
+def draw(c):
+    """(x0, tensors, dscores) of a case in float32, drawn as tests/test_toptrain_host.py draws them; dscores None for LOSS_CASE."""
+    rng = np.random.default_rng(1000 * c.L + c.T + c.n + c.F + c.C)
+    k = 2.0 / np.sqrt(c.F)
+    tensors = []
+    for _ in range(c.L):
+        tensors += [rng.uniform(-k, k, (4 * c.F, c.F)), rng.uniform(-k, k, (4 * c.F, c.F)), rng.uniform(-k, k, 4 * c.F), rng.uniform(-k, k, 4 * c.F)]
+    tensors += [rng.uniform(-k, k, (c.C, c.F)), rng.uniform(-k, k, c.C)]
+    x0, dscores = rng.standard_normal((c.T, c.n, c.F)), rng.standard_normal((c.T, c.n, c.C))
+    if c.small:
+        dscores = dscores * 10.0 ** rng.uniform(-9, -4, dscores.shape)
+    return x0.astype(np.float32), [a.astype(np.float32) for a in tensors], None if c.small is None else dscores.astype(np.float32)
 
 
 def reverse_of(L, i):
