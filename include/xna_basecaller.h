@@ -466,6 +466,65 @@ XB_API int xb_linear_f32_dev(xb_ctx *ctx, const float *d_a, const float *d_w, co
 XB_API int xb_wgrad_f32_dev(xb_ctx *ctx, const float *d_a, const float *d_b, int64_t M, int N, int K, float *d_dw, float *d_dcol);
 XB_API int xb_head_dz_dev(xb_ctx *ctx, const float *d_y, const float *d_dy, int64_t count, float scale, float *d_dz);
 
+/*
+ * Training the head together with the top L LSTM layers, everything below them frozen: `bonito train -F --no-amp` at
+ * --num-unfreeze-top K = L + 1 in 2 .. 6 (cli/train.py:134-158; the unfreeze loop sets requires_grad on every named parameter of
+ * an unfrozen layer, so both biases of an LSTM layer train).  fp32 throughout from the frozen bottom's output on: the reference's
+ * --no-amp.  F = features, C = S * n_base blank-less columns, T the context's time steps.
+ *
+ * xb_encode_bottom_dev: the frozen bottom.  It runs the convolutions and the first `layers` (0 .. 5) LSTM layers of the inference
+ *   encoder -- the launches of xb_encode, the last layer without a consumer -- and writes that layer's output as x0 (T, n, F) fp32,
+ *   16-byte aligned: x0 = (float)hi + (float)lo, one fp32 addition of the two fp16 planes the pass leaves (layers = 4 / 5: what
+ *   xb_debug_layer_output(0 / 1) reads after a full pass).  It needs the fp16 residual as second part: any precision but
+ *   XB_PREC_MIXED and XB_PREC_F16X3 is XB_ERR_INVALID with a message (the rule of xb_head_grad), as are layers outside 0 .. 5.
+ *   Returns without waiting; x0 is ordered on xb_result_stream.
+ * xb_transpose_f32_dev: out (cols, rows) = in (rows, cols)^T, fp32, exact (a copy through an LDS tile); rows, cols >= 1, any
+ *   value (rows up to 2097120); in and out distinct.  It turns W_ih into (F, 4F) and the head's W into (F, C), the weight
+ *   operands of xb_linear_f32_dev's dx products.  No weights need to be loaded.
+ *
+ * The trainer.  xb_top_train_begin(layers = L in 1 .. 5, params) takes the fp32 master weights from the host as ONE flat array in
+ *   state-dict order: for each of encoder.(9 - L) .. encoder.8 the tensors rnn.weight_ih_l0 (4F, F), rnn.weight_hh_l0 (4F, F),
+ *   rnn.bias_ih_l0 (4F), rnn.bias_hh_l0 (4F), then encoder.9.linear.weight (C, F) and .bias (C) -- 4 L + 2 tensors, one behind
+ *   the other (csrc/xb_top_plan.h).  It allocates four such buffers (p, the gradient g, AdamW's m and v), zeroes m, v and the
+ *   step count.  The activations of a step (T n (L 6F + 9F + 3C) floats) are allocated by the first step and grow with the
+ *   batch.  An allocation that fails is XB_ERR_NOMEM, with the gigabytes a step needs and the advice to lower the batch.
+ *   Refused: L outside 1 .. 5 (the convolutions stay frozen), a precision other than mixed / f16x3, a scale that is not positive
+ *   (XB_ERR_INVALID); a second begin, or a head trainer open on the context (XB_ERR_STATE) -- and xb_head_train_begin is refused
+ *   while this trainer is open.
+ * xb_top_train_grad: the gradient of one batch of n chunks (signal (n, chunk_len), targets (n, Lt) uint8 labels, lengths (n),
+ *   validated as xb_head_train_step validates them), in one call, nothing score-sized leaving the device:
+ *     xb_encode_bottom with 5 - L layers -> x0;  per unfrozen layer, upwards: b = b_ih + b_hh (fp32, one rounding),
+ *     gin = xb_linear_f32(x, W_ih, b), xb_lstm_train_forward (reverse where the LSTM layer's index encoder.N - 4 is even, as in
+ *     the inference encoder);  scores = xb_linear_f32(y, W, b, act 1, scale);  xb_ctc_loss_grad (blank-less, ld = C, reduction
+ *     mean, no loss_clip);  xb_head_dz;  the head's dW, db = xb_wgrad_f32(dz, y);  dy = xb_linear_f32(dz, W^T);  per layer,
+ *     downwards: xb_lstm_train_backward, dW_ih and db = xb_wgrad_f32(dgin, x) with db written to both bias gradients,
+ *     dW_hh = xb_wgrad_f32 on the operands shifted by one time step, and for all but the lowest unfrozen layer
+ *     dy = xb_linear_f32(dgin, W_ih^T);  xb_grad_norm over the whole flat g.
+ *   Every stage is the named entry point's arithmetic on the same operands: the scores and all gradients are, byte for byte, what
+ *   those entry points give when a caller chains them (tests/toptrain_dev.py), and a repeated call gives the same bytes.  The
+ *   forward reads the fp32 masters: nothing is re-packed per step.  g is left UNCLIPPED.  *loss = (float)(the chunks' losses summed
+ *   in double in index order / n); *grad_norm the norm of g.  Returns synchronised.
+ * xb_top_train_step: xb_top_train_grad, then clip = (float)min(1, 2.0 / ((double)norm + 1e-6)) and ONE xb_adamw_step over all
+ *   the parameters at step t = steps taken + 1 (g keeps the clipped gradient).  *loss is the loss before the step, *grad_norm the
+ *   norm before clipping.  A norm that is not finite leaves everything unchanged (XB_ERR_DEVICE).
+ * xb_top_get_weights reads the masters back, flat as xb_top_train_begin took them; xb_top_train_end frees the trainer's state.
+ *   Calls outside begin .. end: XB_ERR_STATE.
+ * The inference forms are NOT the trainer's: xb_encode, xb_basecall_chunks, xb_validate_chunks go on computing with the weights
+ *   last loaded.  xb_load_weights and xb_weights_ready stay allowed while this trainer is open; they replace the inference forms
+ *   only, the masters remain the trainer's.  That is how trained layers reach the inference path: read the masters, load them
+ *   (once per epoch, before validation; crf/trainer.py's TopTrainer.publish).
+ * No counterpart in the reference (torch autograd, cuDNN, cuBLAS, torch.optim.AdamW).
+ */
+XB_API int xb_encode_bottom_dev(xb_ctx *ctx, const float *d_signal, int n, int layers, float *d_x0);
+XB_API int xb_transpose_f32_dev(xb_ctx *ctx, const float *d_in, int rows, int cols, float *d_out);
+XB_API int xb_top_train_begin(xb_ctx *ctx, int layers, const float *params);
+XB_API int xb_top_train_grad(xb_ctx *ctx, const float *signal, int n, const uint8_t *targets, int Lt, const int32_t *lengths, float *loss,
+                             float *grad_norm);
+XB_API int xb_top_train_step(xb_ctx *ctx, const float *signal, int n, const uint8_t *targets, int Lt, const int32_t *lengths, float lr,
+                             float *loss, float *grad_norm);
+XB_API int xb_top_get_weights(xb_ctx *ctx, float *params);
+XB_API int xb_top_train_end(xb_ctx *ctx);
+
 /* compute_scores (crf/basecall.py:27-82), viterbi branch: encode + decode without materialising
  * the blank column or copying scores off the device. */
 XB_API int xb_basecall_chunks(xb_ctx *ctx, const float *signal, int n, const char *alphabet,

@@ -6,7 +6,8 @@
 --prop-ubs P` == the synthetic spiking of `bonito train --spike` (bonito/spike_chunks.py), likewise; `... synth CTC OUT -r
 KMER.model --ubs XY --prop-ubs P` == the fully synthetic chunks of `bonito train --spike --fully_synth`, likewise; `... train
 TRAINING_DIR --pretrained MODEL_DIR --directory CTC_DATA -F` == `bonito train -F` at its default --num-unfreeze-top 1: the CRF
-head fine-tuned with everything below it frozen."""
+head fine-tuned with everything below it frozen; with `--num-unfreeze-top K --no-amp`, K in 2 .. 6, the top K - 1 LSTM layers
+are trained with it, in float32."""
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 
 from . import __version__

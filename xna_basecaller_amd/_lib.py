@@ -39,6 +39,8 @@ EXPORTS = [
     "xb_head_train_begin", "xb_head_train_step", "xb_head_get_weights", "xb_head_train_end",
     "xb_lstm_train_forward_dev", "xb_lstm_train_backward_dev",
     "xb_linear_f32_dev", "xb_wgrad_f32_dev", "xb_head_dz_dev",
+    "xb_encode_bottom_dev", "xb_transpose_f32_dev",
+    "xb_top_train_begin", "xb_top_train_grad", "xb_top_train_step", "xb_top_get_weights", "xb_top_train_end",
 ]
 XB_COMM_ID_BYTES = 128
 # xb_status (include/xna_basecaller.h)
@@ -175,6 +177,16 @@ def load():
     lib.xb_wgrad_f32_dev.argtypes = [vp, vp, vp, C.c_int64, ip, ip, vp, vp]
     lib.xb_internal_wgrad_blocked.argtypes = [vp, vp, vp, C.c_int64, ip, ip, vp, vp, C.c_int64]
     lib.xb_head_dz_dev.argtypes = [vp, vp, vp, C.c_int64, fl, vp]
+    lib.xb_encode_bottom_dev.argtypes = [vp, vp, ip, ip, vp]
+    lib.xb_transpose_f32_dev.argtypes = [vp, vp, ip, ip, vp]
+    lib.xb_top_train_begin.argtypes = [vp, ip, vp]
+    lib.xb_top_train_grad.argtypes = [vp, vp, ip, vp, ip, vp, fp, fp]
+    lib.xb_top_train_step.argtypes = [vp, vp, ip, vp, ip, vp, fl, fp, fp]
+    lib.xb_top_get_weights.argtypes = [vp, vp]
+    lib.xb_top_train_end.argtypes = [vp]
+    lib.xb_internal_top_state.argtypes = [vp] + [C.POINTER(vp)] * 7 + [C.POINTER(C.c_int64)] * 2
+    lib.xb_internal_peek.argtypes = [vp, vp, vp, C.c_size_t]
+    lib.xb_internal_bottom_part.argtypes = [vp, vp, ip, ip, vp, ip]
     lib.xb_result_stream.argtypes = [vp]
     lib.xb_result_stream.restype = C.c_void_p
     lib.xb_set_profiling.argtypes = [vp, ip]
@@ -586,6 +598,78 @@ class Context:
 
     def head_dz_dev(self, d_y, d_dy, count, scale, d_dz):
         self._check(self.lib.xb_head_dz_dev(self.h, _ptr(d_y), _ptr(d_dy), int(count), float(scale), _ptr(d_dz)))
+
+    # ---- the trainer of the head and the top LSTM layers (csrc/xb_top.hip) ----------------------------------------------------------
+    def encode_bottom_dev(self, d_signal, n, layers, d_x0):
+        """xb_encode_bottom_dev: signal (n, chunk_len) on the device -> x0 (T, n, features) fp32 on the device, the output of the
+        convolutions (layers = 0) or of LSTM layer layers - 1."""
+        self._check(self.lib.xb_encode_bottom_dev(self.h, _ptr(d_signal), int(n), int(layers), _ptr(d_x0)))
+
+    def bottom_part_dev(self, d_signal, n, layers, d_x0, what):
+        """encode_bottom_dev in halves (tools/toptrain_time.py): what = 1 the pass alone, 2 the join of the planes it left."""
+        self._check(self.lib.xb_internal_bottom_part(self.h, _ptr(d_signal), int(n), int(layers), _ptr(d_x0), int(what)))
+
+    def transpose_f32_dev(self, d_in, rows, cols, d_out):
+        """xb_transpose_f32_dev: out (cols, rows) = in (rows, cols)^T, fp32 on the device."""
+        self._check(self.lib.xb_transpose_f32_dev(self.h, _ptr(d_in), int(rows), int(cols), _ptr(d_out)))
+
+    def top_params(self, layers):
+        """Floats of the flat parameter buffer of a trainer of the head and the top `layers` LSTM layers (csrc/xb_top_plan.h)."""
+        F, O = self.cfg.features, self.C_noblank
+        return layers * (8 * F * F + 8 * F) + O * F + O
+
+    def top_train_begin(self, layers, params):
+        """xb_top_train_begin: params, the 4 layers + 2 tensors flat in state-dict order (top_params(layers) floats)."""
+        params = np.ascontiguousarray(params, dtype=np.float32)
+        if 1 <= layers <= 5 and params.shape != (self.top_params(layers),):
+            raise ValueError("top_train_begin: %d floats expected for %d layers, got %r" % (self.top_params(layers), layers, params.shape))
+        self._check(self.lib.xb_top_train_begin(self.h, int(layers), params.ctypes.data))
+        self._top_layers = int(layers)
+
+    def _top_call(self, signal, targets, target_lengths, lr):
+        signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1, self.chunk_len)
+        n = signal.shape[0]
+        targets, tl = self._labels(targets, target_lengths, n)
+        loss, norm = C.c_float(), C.c_float()
+        head = (self.h, signal.ctypes.data, n, targets.ctypes.data, targets.shape[1], tl.ctypes.data)
+        if lr is None:
+            self._check(self.lib.xb_top_train_grad(*head, C.byref(loss), C.byref(norm)))
+        else:
+            self._check(self.lib.xb_top_train_step(*head, float(lr), C.byref(loss), C.byref(norm)))
+        return loss.value, norm.value
+
+    def top_train_grad(self, signal, targets, target_lengths):
+        """xb_top_train_grad: the gradient of one batch, left unclipped on the device -> (mean loss, gradient norm)."""
+        return self._top_call(signal, targets, target_lengths, None)
+
+    def top_train_step(self, signal, targets, target_lengths, lr):
+        """xb_top_train_step: one clipped AdamW step on n chunks -> (mean loss before the step, gradient norm before clipping)."""
+        return self._top_call(signal, targets, target_lengths, lr)
+
+    def top_state_dev(self):
+        """Device pointers of an open trainer: dict(p, g, m, v: the flat buffers; x0, scores, dscores of the last step (None
+        before the first); rows = T n of that step; step: the steps taken) (tests)."""
+        ptrs = [C.c_void_p() for _ in range(7)]
+        rows, step = C.c_int64(), C.c_int64()
+        self._check(self.lib.xb_internal_top_state(self.h, *[C.byref(p) for p in ptrs], C.byref(rows), C.byref(step)))
+        out = dict(zip(("p", "g", "m", "v", "x0", "scores", "dscores"), (p.value for p in ptrs)))
+        out.update(rows=rows.value, step=step.value)
+        return out
+
+    def peek(self, d_ptr, shape, dtype=np.float32):
+        """Device memory at a raw pointer as a host array, behind everything the context has enqueued (tests)."""
+        out = np.empty(shape, dtype)
+        self._check(self.lib.xb_internal_peek(self.h, int(d_ptr), out.ctypes.data, out.nbytes))
+        return out
+
+    def top_get_weights(self):
+        """xb_top_get_weights: the fp32 master weights, flat, as top_train_begin took them."""
+        params = np.empty((self.top_params(getattr(self, "_top_layers", 1)),), np.float32)
+        self._check(self.lib.xb_top_get_weights(self.h, params.ctypes.data))
+        return params
+
+    def top_train_end(self):
+        self._check(self.lib.xb_top_train_end(self.h))
 
     def validate_chunks(self, signal, alphabet, targets, target_lengths):
         """xb_validate_chunks: signal (n, chunk_len), targets (n, Lt), target_lengths (n) -> (seq (n, T) int8 left-packed ASCII,

@@ -1,8 +1,11 @@
 """
 `bonito train TRAINING_DIR --pretrained MODEL_DIR --directory CTC_DATA -F` (ub-bonito/bonito/cli/train.py, training.py): fine-tune
 a pretrained model with its bottom layers frozen and the top layer with parameters -- the CRF head, encoder.9.linear -- trainable
-(--num-unfreeze-top 1, the reference's default).  That recipe needs no backward pass through the recurrence, and it is the
-one this package implements: a step is one device call (Model.head_trainer, xb_head_train_step).
+(--num-unfreeze-top 1, the reference's default).  That recipe needs no backward pass through the recurrence: a step is one
+device call (Model.head_trainer, xb_head_train_step).  --num-unfreeze-top K for K in 2 .. 6 together with --no-amp trains the
+head and the top K - 1 LSTM layers, float32 throughout above the frozen bottom (the reference's --no-amp; its default, autocast
+with a GradScaler, is not implemented): again one device call per step (Model.top_trainer, xb_top_train_step).  The trained
+layers are loaded into the inference path before each epoch's validation and checkpoint (TopTrainer.publish).
 
 Per epoch, as Trainer.fit: losses_N.csv (chunks, time, grad_norm, lr, loss per step), weights_N.tar (torch.save of the state
 dict), the validation pass (evaluate --loss's path, xb_validate_chunks, with the new weights), a training.csv row and the
@@ -11,7 +14,8 @@ with -f continues after the highest weights_N.tar (load_state); AdamW's moments 
 without --restore-optim.  The schedule is linear_warmup_cosine_decay (schedule.py); the shuffle is a numpy permutation seeded
 with --seed, drawn once per epoch.
 
-Refused, each with the alternative: training without -F, --num-unfreeze-top other than 1, --config (training from scratch),
+Refused, each with the alternative: training without -F, --num-unfreeze-top 2 .. 6 without --no-amp, --num-unfreeze-top below 1
+or above 6 (the convolutions stay frozen), --config (training from scratch),
 --grad-accum-split other than 1, --restore-optim, a nonzero drop rate, --skip-top, and the --spike / --stitch-mode family
 (run `spike`, `synth` or `splice` beforehand: the augmentation is then fixed per data set, not redrawn per epoch).
 """
@@ -35,7 +39,8 @@ TRAINING_COLUMNS = ("time", "duration", "epoch", "train_loss", "validation_loss"
 
 
 def refusals(args):
-    """The first thing main does, before any file or device is touched: every recipe outside `-F --num-unfreeze-top 1`."""
+    """The first thing main does, before any file or device is touched: every recipe outside `-F --num-unfreeze-top 1` and
+    `-F --num-unfreeze-top 2 .. 6 --no-amp`."""
     def no(msg):
         raise SystemExit("> error: " + msg)
 
@@ -45,11 +50,16 @@ def refusals(args):
     if not args.pretrained:
         no("--pretrained MODEL_DIR is required: only fine-tuning of a pretrained model's head is implemented")
     if not args.freeze_bottom:
-        no("training every layer needs backward passes through the LSTM layers, which this package does not have; "
-           "use -F (--freeze-bottom) to train the CRF head alone")
-    if args.num_unfreeze_top != 1:
-        no("--num-unfreeze-top %d would unfreeze LSTM layers; only the top layer (--num-unfreeze-top 1) can be trained here"
-           % args.num_unfreeze_top)
+        no("training every layer needs a backward pass through the convolutions, which this package does not have; "
+           "use -F (--freeze-bottom) to train the CRF head alone, or with --num-unfreeze-top 2 .. 6 --no-amp the top LSTM layers too")
+    if args.num_unfreeze_top < 1:
+        no("--num-unfreeze-top %d: at least the top layer is trained; use --num-unfreeze-top 1 .. 6" % args.num_unfreeze_top)
+    if args.num_unfreeze_top > 6:
+        no("--num-unfreeze-top %d would unfreeze convolutions, which have no backward pass here; the most is --num-unfreeze-top 6 "
+           "--no-amp (the head and all five LSTM layers)" % args.num_unfreeze_top)
+    if args.num_unfreeze_top > 1 and not args.no_amp:
+        no("--num-unfreeze-top %d unfreezes LSTM layers, whose backward pass is float32 here (no autocast, no GradScaler): add "
+           "--no-amp, or train the head alone with --num-unfreeze-top 1" % args.num_unfreeze_top)
     if args.grad_accum_split != 1:
         no("--grad-accum-split %d: a step is one device pass over the whole batch; lower --batch instead" % args.grad_accum_split)
     if args.restore_optim:
@@ -155,13 +165,17 @@ def main(args):
     for t, l in ((train[1], train[2]), (valid[1], valid[2])):
         check_loss_inputs(t, l, model.seqdist.state_len)
     print("[WARNING: freezing bottom layers]")
-    print("> > Unfreezing top/last 1 layer(s):\n> > linearcrfencoder")
+    top_layers = args.num_unfreeze_top - 1                      # LSTM layers trained beside the head
+    print("> > Unfreezing top/last %d layer(s):\n> > %s" % (args.num_unfreeze_top, ", ".join(["linearcrfencoder"] + ["lstm"] * top_layers)))
     print("> batch_size: {} | epochs: {} | lr: {}".format(args.batch, args.epochs, args.lr))
 
     n = len(train[0])
     steps_per_epoch = -(-n // args.batch)
     total_steps = args.epochs * steps_per_epoch
-    trainer = model.head_trainer(train[0].shape[1], args.batch)
+    if top_layers:
+        trainer = model.top_trainer(top_layers, train[0].shape[1], args.batch)
+    else:
+        trainer = model.head_trainer(train[0].shape[1], args.batch)
     import torch  # the checkpoint container only
     rng = np.random.default_rng(args.seed)
     step = 0
@@ -181,6 +195,8 @@ def main(args):
             smoothed = loss if smoothed is None else 0.01 * loss + 0.99 * smoothed
             append_row(log, LOSS_COLUMNS, [seen, time.perf_counter() - t0, grad_norm, lr, loss])
         duration = time.perf_counter() - t0
+        if top_layers:
+            trainer.publish()                                   # the validation below and the checkpoint see the trained layers
         torch.save(trainer.state_dict(), os.path.join(workdir, "weights_%d.tar" % epoch))
         val_loss, val_mean, val_median = validate(model, valid, args.batch)
         print("[epoch {}] directory={} loss={:.4f} mean_acc={:.3f}% median_acc={:.3f}%".format(
@@ -204,6 +220,7 @@ def argparser():
     parser.add_argument("--batch", default=128, type=int)
     parser.add_argument("--chunks", default=0, type=int)
     parser.add_argument("--valid-chunks", default=0, type=int)
+    parser.add_argument("--no-amp", action="store_true", default=False)
     parser.add_argument("-f", "--force", action="store_true", default=False)
     parser.add_argument("--restore-optim", action="store_true", default=False)
     parser.add_argument("--grad-accum-split", default=1, type=int)

@@ -443,6 +443,14 @@ class Model(torch.nn.Module):
         run = self.config.get("basecaller", {})
         return HeadTrainer(self, chunk_len or run.get("chunksize", 4000), batch or run.get("batchsize", 64))
 
+    def top_trainer(self, layers, chunk_len=None, batch=None):
+        """A TopTrainer (crf/trainer.py) on this model's context: step / grad as head_trainer's, on encoder.9.linear and the top
+        `layers` (1 .. 5) LSTM layers, float32 above the frozen bottom; publish() loads the trained tensors into this model's
+        parameters and its live context."""
+        from .trainer import TopTrainer
+        run = self.config.get("basecaller", {})
+        return TopTrainer(self, layers, chunk_len or run.get("chunksize", 4000), batch or run.get("batchsize", 64))
+
     def _decode_rows(self, scores, op):
         if hasattr(scores, "detach"):
             scores = scores.detach().to(torch.float32).cpu().numpy()

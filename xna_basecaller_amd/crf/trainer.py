@@ -5,9 +5,16 @@ Fine-tuning of the CRF head with the encoder below it frozen -- `bonito train -F
 state of such a run on the model's context (xb_head_train_begin .. xb_head_train_end): fp32 master weights, AdamW's moments,
 the step count.  A step is one device call (xb_head_train_step): encoder, loss gradient, head gradient, norm, clipping at 2.0,
 AdamW with torch's defaults, re-pack; nothing score-sized leaves the device.
+
+TopTrainer is the same run with the top L = K - 1 LSTM layers unfrozen beside the head (--num-unfreeze-top K in 2 .. 6 with
+--no-amp: float32 throughout above the frozen bottom).  Its step is one device call too (xb_top_train_step): the inference
+encoder's bottom pass, the training recurrences and fp32 products forwards and backwards, the loss gradient, one norm, one
+clipped AdamW update over all 4 L + 2 tensors.  The step reads fp32 master weights that only the trainer holds; the packed
+forms the inference path reads change when publish() loads the masters into the live context (once per epoch).
 """
 from collections import OrderedDict
 
+import numpy as np
 import torch
 
 W_KEY, B_KEY = "encoder.9.linear.weight", "encoder.9.linear.bias"
@@ -66,4 +73,91 @@ class HeadTrainer:
         with torch.no_grad():
             last.linear.weight.copy_(torch.from_numpy(w))
             last.linear.bias.copy_(torch.from_numpy(b))
+        self.ctx = None
+
+
+LSTM_KEYS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+
+
+def top_keys(layers):
+    """The state-dict keys a TopTrainer of `layers` LSTM layers trains, in the order of csrc/xb_top_plan.h."""
+    return ["encoder.%d.rnn.%s" % (n, k) for n in range(9 - layers, 9) for k in LSTM_KEYS] + [W_KEY, B_KEY]
+
+
+class TopTrainer:
+
+    def __init__(self, model, layers, chunk_len, batch):
+        last = model.encoder[-1]
+        if getattr(last, "scale", None) is None or not float(last.scale) > 0:
+            raise NotImplementedError("the trainer needs the head's scale (scores = scale * tanh(Wx + b)); this model has none")
+        if not 1 <= int(layers) <= 5:
+            raise ValueError("%d unfrozen LSTM layers: 1 .. 5 can be trained (the convolutions stay frozen)" % layers)
+        self.model, self.layers = model, int(layers)
+        self.keys = top_keys(self.layers)
+        self.ctx = model.context(chunk_len, batch)
+        self.chunk_len, self.max_batch = int(chunk_len), self.ctx.max_batch
+        sd = model.state_dict()
+        self.shapes = [tuple(sd[k].shape) for k in self.keys]
+        flat = np.concatenate([sd[k].detach().to(torch.float32).cpu().numpy().ravel() for k in self.keys])
+        self.ctx.top_train_begin(self.layers, flat)
+        self.steps = 0
+
+    def _live(self):
+        if self.ctx is None or self.model._ctx is not self.ctx:
+            raise RuntimeError("the trainer's device context is gone (the model was moved, reloaded or asked for another "
+                               "chunk length or a larger batch): create a new trainer")
+
+    def _signal(self, batch):
+        self._live()
+        sig = self.model._as_signal(batch)
+        if sig.shape[1] != self.chunk_len or sig.shape[0] > self.max_batch:
+            raise ValueError("batch of %d chunks of %d samples: this trainer takes up to %d chunks of %d"
+                             % (sig.shape[0], sig.shape[1], self.max_batch, self.chunk_len))
+        return sig
+
+    def grad(self, batch, targets, lengths):
+        """The gradient of a (N,1,L) batch, left unclipped on the device -> (mean loss, gradient norm); no update."""
+        return self.ctx.top_train_grad(self._signal(batch), targets, lengths)
+
+    def step(self, batch, targets, lengths, lr):
+        """One optimiser step at learning rate lr -> (mean loss before the step, gradient norm before clipping)."""
+        out = self.ctx.top_train_step(self._signal(batch), targets, lengths, lr)
+        self.steps += 1
+        return out
+
+    def weights(self):
+        """The master weights: key -> float32 array in the tensor's own shape."""
+        self._live()
+        flat = self.ctx.top_get_weights()
+        out, at = OrderedDict(), 0
+        for k, shape in zip(self.keys, self.shapes):
+            size = int(np.prod(shape))
+            out[k] = flat[at:at + size].reshape(shape).copy()
+            at += size
+        return out
+
+    def state_dict(self):
+        """The model's state dict with the trained tensors replaced by the masters."""
+        sd = OrderedDict((k, v.detach().clone()) for k, v in self.model.state_dict().items())
+        for k, a in self.weights().items():
+            sd[k] = torch.from_numpy(a).to(sd[k].dtype)
+        return sd
+
+    def publish(self):
+        """The masters go into the model's own parameters, in place, and into the live context's inference forms: from here on
+        validate_chunks, basecall_chunks and the model's forward compute with the trained layers."""
+        trained = self.weights()
+        own = self.model.state_dict(keep_vars=True)
+        with torch.no_grad():
+            for k, a in trained.items():
+                own[k].copy_(torch.from_numpy(a))
+        # the live context, not Model.load_state_dict (which would drop it, and the trainer's state with it)
+        self.ctx.load_state_dict({k: v.detach().to(torch.float32).cpu().numpy() for k, v in self.model.state_dict().items()})
+
+    def close(self):
+        """End the run: publish, then free the trainer's device state."""
+        if self.ctx is None:
+            return
+        self.publish()
+        self.ctx.top_train_end()
         self.ctx = None

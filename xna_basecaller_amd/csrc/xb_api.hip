@@ -435,6 +435,50 @@ int run_encoder(xb_ctx *ctx, const float *d_signal, int n, int expand, float *sc
 // the encoder of n chunks into blank-less scores (T, n, ldc), for xb_head.hip (the trainer's forward pass)
 int encoder_run(xb_ctx *ctx, const float *d_signal, int n, float *d_scores, int ldc) { return run_encoder(ctx, d_signal, n, 0, d_scores, ldc); }
 
+// The frozen bottom of a training step (xb_top.hip): run_encoder's launches up to and including LSTM layer `layers` - 1, the
+// last of them without a consumer (next = nullptr: run_lstm_layer then plans no slab GEMM and issues none afterwards).  The
+// output, fp16 hi + fp16 residual, lies in x_hi / x_lo [layers & 1], as the full pass leaves it there on its way up.
+int encoder_bottom_run(xb_ctx *ctx, const float *d_signal, int n, int layers)
+{
+    const xb_config &c = ctx->cfg;
+    const int F = c.features, T = ctx->T;
+    const int nsplit = ctx->ns_conv;
+    if (layers < 0 || layers > 5) return fail(ctx, XB_ERR_INVALID, "the bottom pass runs 0 .. 5 LSTM layers, got %d", layers);
+    if ((layers < 5 ? ctx->ns_in[layers] : ctx->ns_lin) != 3)
+        return fail(ctx, XB_ERR_INVALID, "the bottom pass needs the fp16 residual of layer output %d, which this context's stage arithmetic does not write", layers);
+    ctx->dep_next = 0;
+    ctx->enc_n = layers == 5 ? n : 0;           // below the top, x_hi[1] / x_lo[1] do not hold the last layer's output
+    {
+        StageScope sc(ctx, XB_STAGE_CONV, 2);
+        xb::ConvFrontParams cf{};
+        cf.signal = d_signal; cf.signal2 = nullptr; cf.split = n; cf.N = n; cf.L = c.chunk_len; cf.T = T; cf.winlen = c.winlen; cf.stride = c.stride;
+        cf.kp = ctx->kp; cf.w1 = ctx->w1; cf.b1 = ctx->b1; cf.w2 = ctx->w2; cf.b2 = ctx->b2;
+        cf.a_hi = ctx->im_hi; cf.a_lo = ctx->im_lo; cf.q8 = nsplit == 2;
+        XB_HIP(ctx, xb::launch_conv_front(cf, ctx->stream));
+        xb::GemmParams g{};
+        g.a_hi = ctx->im_hi; g.a_lo = ctx->im_lo; g.b_hi = ctx->w3_hi; g.b_lo = ctx->w3_lo;
+        g.M = T * n; g.Nn = F; g.K = ctx->kp; g.lda = ctx->kp; g.ldb = ctx->kp;
+        g.bias = ctx->b3; g.out_hi = ctx->x_hi[0]; g.out_lo = ctx->x_lo[0]; g.ldc = F; g.nsplit = nsplit;
+        g.a_exp = 0; g.b_exp = ctx->w3_exp; g.out_exp = 0;
+        g.out_fmt = second_part(ctx->ns_in[0]);
+        if (ctx->knobs.gemm4) { g.b4 = ctx->w3_f4; g.b4_kstride = ctx->w3_ks; }
+        XB_HIP(ctx, xb::launch_gemm(g, xb::EPI_SILU_SPLIT, ctx->stream));
+    }
+    if (layers == 0) return XB_OK;
+    float *gin[2] = {ctx->gin, ctx->gin2 ? ctx->gin2 : ctx->gin};
+    int cur = 0;
+    {
+        const NextGemm first{0, ctx->x_hi[0], ctx->x_lo[0], gin[0], 4 * F, 0};
+        if (int rc = launch_row_gemm(ctx, first, n, 0, T, ctx->stream)) return rc;
+    }
+    for (int l = 0; l < layers; ++l) {
+        const NextGemm next{l + 1, ctx->x_hi[cur ^ 1], ctx->x_lo[cur ^ 1], gin[(l + 1) & 1], 4 * F, 0};
+        if (int rc = run_lstm_layer(ctx, l, n, gin[l & 1], ctx->x_hi[cur ^ 1], ctx->x_lo[cur ^ 1], l + 1 < layers ? &next : nullptr)) return rc;
+        cur ^= 1;
+    }
+    return XB_OK;
+}
+
 namespace {
 
 // optional outputs of the Log scans (xb_crf_logz / xb_crf_scans)

@@ -1,7 +1,8 @@
 // xb_ctx.h -- the context behind the C ABI, shared by the translation units that implement it: xb_api.hip (context lifetime, weight
 // upload, the execution of the encoder's plans, decode, pairing, the host pipeline, and the housekeeping every entry point
 // shares: the call prologue `enter`, the status words), xb_api_data.hip (the ctc-data tools), xb_head.hip (the head's gradient
-// and trainer), xb_lstm_train.hip (the training recurrence) and xb_train_gemm.hip (the fp32 products of training); xb_comm.hip
+// and trainer), xb_lstm_train.hip (the training recurrence), xb_train_gemm.hip (the fp32 products of training) and xb_top.hip (the
+// trainer of the head and the top LSTM layers); xb_comm.hip
 // reaches a context through the C ABI and xb_internal_defer_after only.  The host arithmetic xb_api.hip acts on lives in three headers without HIP that are
 // checked on their own: xb_schedule.h (the knobs and the planner of the encoder schedule), xb_pack.h (the forms a weight
 // tensor is uploaded in) and xb_status.h (the device status words).  Private to csrc/.
@@ -311,7 +312,24 @@ struct xb_ctx {
     struct LstmTrainState {
         DevBuf carry, wt;
     } lstmtrain;
-    int enc_n = 0;                              // chunks of the most recent encoder pass (whose layer outputs lie in x_hi / x_lo)
+    // The trainer of the head and the top L LSTM layers (xb_top.hip), open from xb_top_train_begin to _end.  train: p, g, m, v in
+    // the layout of xb::top_plan, four strides; small: the norm word (64 floats), the layers' summed biases, one transposed
+    // weight; act: the activations of a step of `rows` = T n rows, allocated by the first step and grown with the batch; labels:
+    // the batch's labels, lengths and losses.
+    struct TopState {
+        DevBuf train, small, act, labels;
+        bool open = false;
+        int L = 0;
+        long step = 0;
+        size_t rows = 0;                        // rows the activations were last laid out for (0: no step yet)
+        void close()
+        {
+            train.release(); small.release(); act.release(); labels.release();
+            open = false;
+            L = 0; step = 0; rows = 0;
+        }
+    } top;
+    int enc_n = 0;                              // chunks of the most recent full encoder pass (whose layer outputs lie in x_hi / x_lo)
 
     bool profiling = false;
     std::vector<StageEvent> events;
@@ -355,6 +373,8 @@ int ctc_loss_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int
 int ctc_grad_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int n, int has_blank, int ld, const uint8_t *d_targets,
                  int Lt, const int32_t *d_len, float loss_clip, int mean, float *d_loss, float *d_grad);
 int encoder_run(xb_ctx *ctx, const float *d_signal, int n, float *d_scores, int ldc);   // blank-less scores (T, n, ldc), main stream
+// the convolutions and the first `layers` (0 .. 5) LSTM layers of the same pass; the output lies in x_hi / x_lo [layers & 1]
+int encoder_bottom_run(xb_ctx *ctx, const float *d_signal, int n, int layers);
 // ... and two from inside its extern "C" block, beside the pairing logic: flush_held launches a held-back asynchronous basecall;
 // basecall_async makes one of n chunks at d_signal into device outputs (seq, len, out), of pipeline slot `slot` or none
 extern "C" int flush_held(xb_ctx *ctx);

@@ -6,6 +6,7 @@
 #include "xb_ctx.h"
 #include "xb_ctc_check.h"
 #include "xb_head_split.h"
+#include "xb_head_train.h"
 
 namespace {
 
@@ -256,6 +257,8 @@ float *small_norm(xb_ctx *ctx) { return reinterpret_cast<float *>(static_cast<ch
 double *small_part(xb_ctx *ctx) { return reinterpret_cast<double *>(static_cast<char *>(ctx->head.small.p) + 256); }
 int small_ready(xb_ctx *ctx) { return grow(ctx, &ctx->head.small, 256 + sizeof(double) * NORM_BLOCKS); }
 
+}  // namespace
+
 int head_usable(xb_ctx *ctx, const char *who)
 {
     if (ctx->ns_lin != 3)
@@ -265,6 +268,8 @@ int head_usable(xb_ctx *ctx, const char *who)
         return fail(ctx, XB_ERR_INVALID, "%s: the head needs its tanh with a positive scale, the context has scale %g", who, (double)ctx->cfg.scale);
     return XB_OK;
 }
+
+namespace {
 
 // X of a call: the caller's planes, or (both null) the last LSTM layer's output of the most recent encoder pass, whose rows the
 // call must then cover
@@ -313,6 +318,8 @@ int head_grad_run(xb_ctx *ctx, const char *who, const float *d_y, const float *d
     return XB_OK;
 }
 
+}  // namespace
+
 int grad_norm_run(xb_ctx *ctx, const float *d_a, size_t na, const float *d_b, size_t nb, float *d_norm)
 {
     if (int rc = small_ready(ctx)) return rc;
@@ -328,6 +335,8 @@ int adamw_run(xb_ctx *ctx, float *p, float *g, float *m, float *v, size_t len, f
     adamw_kernel<<<(unsigned)((len + 255) / 256), 256, 0, ctx->stream>>>(p, g, m, v, len, clip, decay, step_size, bc2_sqrt);
     return launched(ctx, "xb_adamw_step");
 }
+
+namespace {
 
 int repack_run(xb_ctx *ctx, const float *d_w, const float *d_b)
 {
@@ -350,6 +359,8 @@ struct TrainBuf {
     }
 };
 
+}  // namespace
+
 // AdamW's scalars of step `step` at learning rate lr, computed in double and rounded once (torch's defaults: betas 0.9 / 0.999,
 // weight decay 0.01)
 void adamw_scalars(double lr, long step, float *decay, float *step_size, float *bc2_sqrt)
@@ -358,8 +369,6 @@ void adamw_scalars(double lr, long step, float *decay, float *step_size, float *
     *step_size = (float)(lr / (1.0 - std::pow(0.9, (double)step)));
     *bc2_sqrt = (float)std::sqrt(1.0 - std::pow(0.999, (double)step));
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -465,6 +474,7 @@ XB_API int xb_head_train_begin(xb_ctx *ctx, const float *w, const float *b)
     if (int rc = check_ready(ctx, 1)) return rc;
     if (!w || !b) return fail(ctx, XB_ERR_INVALID, "xb_head_train_begin: null host pointer");
     if (ctx->head.open) return fail(ctx, XB_ERR_STATE, "xb_head_train_begin: a trainer is already open on this context");
+    if (ctx->top.open) return fail(ctx, XB_ERR_STATE, "xb_head_train_begin: a top-layer trainer is open on this context; call xb_top_train_end first");
     if (int rc = head_usable(ctx, "xb_head_train_begin")) return rc;
     if (int rc = enter(ctx, false)) return rc;
     const size_t OF = (size_t)ctx->O * ctx->cfg.features, O = (size_t)ctx->O;

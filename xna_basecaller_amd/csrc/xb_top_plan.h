@@ -1,5 +1,5 @@
-// xb_top_plan.h -- the layout for a trainer of the head and the top L LSTM layers (groundwork: no trainer uses it yet; the
-// products it would chain are xb_train_gemm.hip's): where each unfrozen tensor lies in the flat parameter buffers, and where a step of (T, n, F, C, L) keeps its activations.  Tensors in state-dict order: for each unfrozen LSTM layer
+// xb_top_plan.h -- the layout of the trainer of the head and the top L LSTM layers (xb_top.hip: xb_top_train_begin .. _end): where
+// each unfrozen tensor lies in the flat parameter buffers, and where a step of (T, n, F, C, L) keeps its activations.  Tensors in state-dict order: for each unfrozen LSTM layer
 // encoder.(9 - L) .. encoder.8 weight_ih_l0 (4F, F), weight_hh_l0 (4F, F), bias_ih_l0 (4F), bias_hh_l0 (4F), then
 // encoder.9.linear.weight (C, F) and .bias (C).  Four buffers of that layout follow one another, each starting on a 16-byte boundary: p, g, m, v.  The activations of
 // a step, in floats per (t, chunk) row: x0 F | gin 4F (dy lies in its first F floats once the forward is done) | dgin 4F | per
