@@ -525,6 +525,55 @@ XB_API int xb_top_train_step(xb_ctx *ctx, const float *signal, int n, const uint
 XB_API int xb_top_get_weights(xb_ctx *ctx, float *params);
 XB_API int xb_top_train_end(xb_ctx *ctx);
 
+/*
+ * Training the convolutions (csrc/xb_conv_train.hip), and with them every layer: `bonito train --no-amp` without -f, the
+ * reference's headline recipes.  One layer is the `Convolution` of rnn_encoder: Conv1d(Cin, Cout, K, stride, padding = K / 2,
+ * bias) followed by swish.  Everything fp32, dense, on the device, 16-byte aligned; generic in (Cin, Cout, K, stride).
+ *   x (n, Cin, Lin), w (Cout, Cin, K), b (Cout): torch's layouts.  Lout = (Lin + 2 (K / 2) - K) / stride + 1.
+ *   z, y and dy: (n, Cout, Lout) with tnc = 0, (Lout, n, Cout) otherwise -- the encoder's Permute([2, 0, 1]) fused into conv3.
+ * xb_conv_train_forward_dev: z[b, co, t] = sum_ci sum_k x[b, ci, t stride + k - K / 2] w[co, ci, k] + b[co] (x is 0 outside
+ *   0 .. Lin - 1), the pre-activation and the only stash beside x; y = z sigma(z) with the training recurrence's sigma.
+ * xb_conv_train_backward_dev: dz = dy (sigma(z) (1 + z (1 - sigma(z)))); db[co] = sum dz; dw[co, ci, k] = sum dz[b, co, t]
+ *   x[b, ci, t stride + k - K / 2]; dx[b, ci, s] = sum_co sum_k dz[b, co, t] w[co, ci, k] over t stride + k - K / 2 = s.
+ *   d_dx = NULL: not wanted (conv1); dw and db are the same bytes either way.
+ * Two routes, and THE RULE that chooses reads the shape alone (csrc/xb_conv_plan.h): stride 1, at most 16 channels on either
+ *   side and Cin K <= 64 is narrow, everything else wide.
+ *   Narrow (conv1 1 -> 4, conv2 4 -> 16, K = 5): direct kernels.  A workgroup stages its 256 positions of x with their halo and all
+ *   weights in LDS, a thread produces all Cout channels of its position, accesses run along L.  A sum of z runs over ci
+ *   ascending, k ascending (one fma each), the bias last; dx is a gather over co ascending, k ascending.  dw and db: every
+ *   workgroup sums its own 256 positions in float64 -- four runs of 64 in ascending order, added as (0 + 1) + (2 + 3) -- and
+ *   writes one partial per element to scratch; a second kernel adds the workgroups' partials in ascending order in float64 and
+ *   rounds once.  The number of workgroups is n ceil(max(Lin, Lout) / 256).
+ *   Wide (conv3 16 -> F, K = 19, stride 5): an im2col writes col (Lout n, Cin K), row t n + b, column ci K + k, so that w as
+ *   (Cout, Cin K) is xb_linear_f32's weight operand as it lies.  z = xb_linear_f32(col, w, b), then the swish.  Backward: dz,
+ *   then dw, db = xb_wgrad_f32(dz, col), dcol = xb_linear_f32(dz, w^T) with w^T from xb_transpose_f32, and a gather col2im: a dx
+ *   element adds its at most ceil(K / stride) terms of dcol in ascending k.  The backward recomputes col from x.  dz, col, dcol
+ *   and w^T (Lout n (Cout + 2 Cin K) + Cin K Cout floats) live in a workspace of the context that grows with the calls.
+ * No floating-point atomics; a repeated call gives the same bytes; a chunk's z, y and dx do not depend on which other chunks are
+ *   in the call; zeros are written as +0.  Accepted: n, Cin, Cout, K, stride, Lin >= 1 with Cin K <= 4096 (Lout >= 1 follows),
+ *   every tensor of the call, col included, below 2^38 elements; anything else, a null pointer (but d_dx) or one that is not
+ *   16-byte aligned is XB_ERR_INVALID with the figures, before anything is launched.  No weights need to be loaded.  The calls
+ *   return without waiting; the outputs are ordered on xb_result_stream.  Measured error and time: DESIGN.md 4.2.9.
+ *
+ * xb_full_train_begin(params): the trainer of xb_top_train_begin at L = 5 with the three convolutions trained as well.  params is
+ *   ONE flat array in state-dict order: encoder.0.conv.weight (4, 1, 5), .bias (4), encoder.1.conv.weight (16, 4, 5), .bias (16),
+ *   encoder.2.conv.weight (F, 16, W), .bias (F) -- 360 + F (16 W + 1) floats (csrc/xb_conv_plan.h) -- then the 4 * 5 + 2 tensors
+ *   of xb_top_train_begin.  xb_top_train_grad, xb_top_train_step, xb_top_get_weights and xb_top_train_end serve this trainer too,
+ *   on the whole flat array.  A gradient is the chain of xb_top_train_grad with
+ *     the three xb_conv_train_forward in place of xb_encode_bottom -- conv1 on the signal as (n, 1, chunk_len), conv3 with tnc = 1
+ *     writing x0 -- and, behind the lowest LSTM layer's backward, dy = xb_linear_f32(dgin, W_ih^T) for that layer too, then the
+ *     three xb_conv_train_backward (conv3 with tnc = 1, conv1 with dx = NULL);  ONE xb_grad_norm over the whole flat g,
+ *   byte for byte what the public entry points give when chained (tests/test_gpu_fulltrain.py), and the step ONE AdamW over all
+ *   28 tensors.  The inference bottom never runs, so the context's precision is free; the other refusals are those of
+ *   xb_top_train_begin (XB_ERR_STATE while any trainer is open on the context).
+ */
+XB_API int xb_conv_train_forward_dev(xb_ctx *ctx, const float *d_x, const float *d_w, const float *d_b, int n, int Cin, int Lin, int Cout,
+                                     int K, int stride, int tnc, float *d_z, float *d_y);
+XB_API int xb_conv_train_backward_dev(xb_ctx *ctx, const float *d_dy, const float *d_x, const float *d_z, const float *d_w, int n, int Cin,
+                                      int Lin, int Cout, int K, int stride, int tnc, float *d_dx /* NULL: not wanted */, float *d_dw,
+                                      float *d_db);
+XB_API int xb_full_train_begin(xb_ctx *ctx, const float *params);
+
 /* compute_scores (crf/basecall.py:27-82), viterbi branch: encode + decode without materialising
  * the blank column or copying scores off the device. */
 XB_API int xb_basecall_chunks(xb_ctx *ctx, const float *signal, int n, const char *alphabet,

@@ -41,6 +41,7 @@ EXPORTS = [
     "xb_linear_f32_dev", "xb_wgrad_f32_dev", "xb_head_dz_dev",
     "xb_encode_bottom_dev", "xb_transpose_f32_dev",
     "xb_top_train_begin", "xb_top_train_grad", "xb_top_train_step", "xb_top_get_weights", "xb_top_train_end",
+    "xb_conv_train_forward_dev", "xb_conv_train_backward_dev", "xb_full_train_begin",
 ]
 XB_COMM_ID_BYTES = 128
 # xb_status (include/xna_basecaller.h)
@@ -184,6 +185,9 @@ def load():
     lib.xb_top_train_step.argtypes = [vp, vp, ip, vp, ip, vp, fl, fp, fp]
     lib.xb_top_get_weights.argtypes = [vp, vp]
     lib.xb_top_train_end.argtypes = [vp]
+    lib.xb_conv_train_forward_dev.argtypes = [vp, vp, vp, vp] + [ip] * 7 + [vp, vp]
+    lib.xb_conv_train_backward_dev.argtypes = [vp, vp, vp, vp, vp] + [ip] * 7 + [vp, vp, vp]
+    lib.xb_full_train_begin.argtypes = [vp, vp]
     lib.xb_internal_top_state.argtypes = [vp] + [C.POINTER(vp)] * 7 + [C.POINTER(C.c_int64)] * 2
     lib.xb_internal_peek.argtypes = [vp, vp, vp, C.c_size_t]
     lib.xb_internal_bottom_part.argtypes = [vp, vp, ip, ip, vp, ip]
@@ -626,6 +630,32 @@ class Context:
         self._check(self.lib.xb_top_train_begin(self.h, int(layers), params.ctypes.data))
         self._top_layers = int(layers)
 
+    # ---- the convolutions' training, and the trainer of every layer (csrc/xb_conv_train.hip, xb_top.hip) --------------------------
+    def conv_train_forward_dev(self, d_x, d_w, d_b, n, Cin, Lin, Cout, K, stride, tnc, d_z, d_y):
+        """xb_conv_train_forward_dev: x (n, Cin, Lin), w (Cout, Cin, K), b (Cout) -> the pre-activation z and y = swish(z), both
+        (n, Cout, Lout), or (Lout, n, Cout) with tnc; fp32 on the device."""
+        self._check(self.lib.xb_conv_train_forward_dev(self.h, _ptr(d_x), _ptr(d_w), _ptr(d_b), int(n), int(Cin), int(Lin), int(Cout), int(K),
+                                                       int(stride), int(bool(tnc)), _ptr(d_z), _ptr(d_y)))
+
+    def conv_train_backward_dev(self, d_dy, d_x, d_z, d_w, n, Cin, Lin, Cout, K, stride, tnc, d_dx, d_dw, d_db):
+        """xb_conv_train_backward_dev: dy and the forward's x, z, w -> dx (n, Cin, Lin) (None: not wanted), dw (Cout, Cin, K), db (Cout)."""
+        self._check(self.lib.xb_conv_train_backward_dev(self.h, _ptr(d_dy), _ptr(d_x), _ptr(d_z), _ptr(d_w), int(n), int(Cin), int(Lin), int(Cout),
+                                                        int(K), int(stride), int(bool(tnc)), _ptr(d_dx), _ptr(d_dw), _ptr(d_db)))
+
+    def full_params(self):
+        """Floats of the flat parameter buffer of a trainer of every layer: the conv section of csrc/xb_conv_plan.h, then top_params(5)."""
+        F = self.cfg.features
+        return 360 + F * (16 * self.cfg.winlen + 1) + self.top_params(5)
+
+    def full_train_begin(self, params):
+        """xb_full_train_begin: params, all 28 tensors flat in state-dict order (full_params() floats).  top_train_grad / _step,
+        top_get_weights and top_train_end serve this trainer too."""
+        params = np.ascontiguousarray(params, dtype=np.float32)
+        if params.shape != (self.full_params(),):
+            raise ValueError("full_train_begin: %d floats expected, got %r" % (self.full_params(), params.shape))
+        self._check(self.lib.xb_full_train_begin(self.h, params.ctypes.data))
+        self._top_layers = "full"
+
     def _top_call(self, signal, targets, target_lengths, lr):
         signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1, self.chunk_len)
         n = signal.shape[0]
@@ -664,7 +694,8 @@ class Context:
 
     def top_get_weights(self):
         """xb_top_get_weights: the fp32 master weights, flat, as top_train_begin took them."""
-        params = np.empty((self.top_params(getattr(self, "_top_layers", 1)),), np.float32)
+        layers = getattr(self, "_top_layers", 1)
+        params = np.empty((self.full_params() if layers == "full" else self.top_params(layers),), np.float32)
         self._check(self.lib.xb_top_get_weights(self.h, params.ctypes.data))
         return params
 

@@ -5,7 +5,9 @@ a pretrained model with its bottom layers frozen and the top layer with paramete
 device call (Model.head_trainer, xb_head_train_step).  --num-unfreeze-top K for K in 2 .. 6 together with --no-amp trains the
 head and the top K - 1 LSTM layers, float32 throughout above the frozen bottom (the reference's --no-amp; its default, autocast
 with a GradScaler, is not implemented): again one device call per step (Model.top_trainer, xb_top_train_step).  The trained
-layers are loaded into the inference path before each epoch's validation and checkpoint (TopTrainer.publish).
+layers are loaded into the inference path before each epoch's validation and checkpoint (TopTrainer.publish).  Without -F and
+with --no-amp EVERY layer trains -- the reference's headline recipes, which never pass -f: the convolutions too have their
+float32 forward and backward on the device (Model.full_trainer, xb_full_train_begin), one device call per step as before.
 
 Per epoch, as Trainer.fit: losses_N.csv (chunks, time, grad_norm, lr, loss per step), weights_N.tar (torch.save of the state
 dict), the validation pass (evaluate --loss's path, xb_validate_chunks, with the new weights), a training.csv row and the
@@ -14,8 +16,9 @@ with -f continues after the highest weights_N.tar (load_state); AdamW's moments 
 without --restore-optim.  The schedule is linear_warmup_cosine_decay (schedule.py); the shuffle is a numpy permutation seeded
 with --seed, drawn once per epoch.
 
-Refused, each with the alternative: training without -F, --num-unfreeze-top 2 .. 6 without --no-amp, --num-unfreeze-top below 1
-or above 6 (the convolutions stay frozen), --config (training from scratch),
+Refused, each with the alternative: training without -F and without --no-amp, or without -F with a --num-unfreeze-top (which the
+reference would silently ignore), --num-unfreeze-top 2 .. 6 without --no-amp, --num-unfreeze-top below 1 or above 6 (a partial
+unfreeze of the conv stack; drop -F to train every layer), --config (training from scratch),
 --grad-accum-split other than 1, --restore-optim, a nonzero drop rate, --skip-top, and the --spike / --stitch-mode family
 (run `spike`, `synth` or `splice` beforehand: the augmentation is then fixed per data set, not redrawn per epoch).
 """
@@ -39,8 +42,8 @@ TRAINING_COLUMNS = ("time", "duration", "epoch", "train_loss", "validation_loss"
 
 
 def refusals(args):
-    """The first thing main does, before any file or device is touched: every recipe outside `-F --num-unfreeze-top 1` and
-    `-F --num-unfreeze-top 2 .. 6 --no-amp`."""
+    """The first thing main does, before any file or device is touched: every recipe outside `-F --num-unfreeze-top 1`,
+    `-F --num-unfreeze-top 2 .. 6 --no-amp` and `--no-amp` without -F (every layer)."""
     def no(msg):
         raise SystemExit("> error: " + msg)
 
@@ -49,14 +52,18 @@ def refusals(args):
            "the head of a pretrained model: use --pretrained MODEL_DIR -F")
     if not args.pretrained:
         no("--pretrained MODEL_DIR is required: only fine-tuning of a pretrained model's head is implemented")
-    if not args.freeze_bottom:
-        no("training every layer needs a backward pass through the convolutions, which this package does not have; "
+    if not args.freeze_bottom and not args.no_amp:
+        no("training every layer is float32 here (no autocast, no GradScaler): add --no-amp to train every layer, or "
            "use -F (--freeze-bottom) to train the CRF head alone, or with --num-unfreeze-top 2 .. 6 --no-amp the top LSTM layers too")
+    if not args.freeze_bottom and args.num_unfreeze_top != 1:
+        no("--num-unfreeze-top %d without -F: every layer trains when the bottom is not frozen, and the reference would silently "
+           "ignore the flag; drop it, or use -F (--freeze-bottom) with it" % args.num_unfreeze_top)
     if args.num_unfreeze_top < 1:
         no("--num-unfreeze-top %d: at least the top layer is trained; use --num-unfreeze-top 1 .. 6" % args.num_unfreeze_top)
     if args.num_unfreeze_top > 6:
-        no("--num-unfreeze-top %d would unfreeze convolutions, which have no backward pass here; the most is --num-unfreeze-top 6 "
-           "--no-amp (the head and all five LSTM layers)" % args.num_unfreeze_top)
+        no("--num-unfreeze-top %d would unfreeze some of the convolutions, and a partial unfreeze of the conv stack is not "
+           "implemented; the most with -F is --num-unfreeze-top 6 --no-amp (the head and all five LSTM layers), or drop -F to train "
+           "every layer (--no-amp)" % args.num_unfreeze_top)
     if args.num_unfreeze_top > 1 and not args.no_amp:
         no("--num-unfreeze-top %d unfreezes LSTM layers, whose backward pass is float32 here (no autocast, no GradScaler): add "
            "--no-amp, or train the head alone with --num-unfreeze-top 1" % args.num_unfreeze_top)
@@ -164,15 +171,19 @@ def main(args):
         model.to(args.device)
     for t, l in ((train[1], train[2]), (valid[1], valid[2])):
         check_loss_inputs(t, l, model.seqdist.state_len)
-    print("[WARNING: freezing bottom layers]")
+    full = not args.freeze_bottom                               # every layer (refusals: --no-amp is set then)
     top_layers = args.num_unfreeze_top - 1                      # LSTM layers trained beside the head
-    print("> > Unfreezing top/last %d layer(s):\n> > %s" % (args.num_unfreeze_top, ", ".join(["linearcrfencoder"] + ["lstm"] * top_layers)))
+    if not full:
+        print("[WARNING: freezing bottom layers]")
+        print("> > Unfreezing top/last %d layer(s):\n> > %s" % (args.num_unfreeze_top, ", ".join(["linearcrfencoder"] + ["lstm"] * top_layers)))
     print("> batch_size: {} | epochs: {} | lr: {}".format(args.batch, args.epochs, args.lr))
 
     n = len(train[0])
     steps_per_epoch = -(-n // args.batch)
     total_steps = args.epochs * steps_per_epoch
-    if top_layers:
+    if full:
+        trainer = model.full_trainer(train[0].shape[1], args.batch)
+    elif top_layers:
         trainer = model.top_trainer(top_layers, train[0].shape[1], args.batch)
     else:
         trainer = model.head_trainer(train[0].shape[1], args.batch)
@@ -195,7 +206,7 @@ def main(args):
             smoothed = loss if smoothed is None else 0.01 * loss + 0.99 * smoothed
             append_row(log, LOSS_COLUMNS, [seen, time.perf_counter() - t0, grad_norm, lr, loss])
         duration = time.perf_counter() - t0
-        if top_layers:
+        if full or top_layers:
             trainer.publish()                                   # the validation below and the checkpoint see the trained layers
         torch.save(trainer.state_dict(), os.path.join(workdir, "weights_%d.tar" % epoch))
         val_loss, val_mean, val_median = validate(model, valid, args.batch)

@@ -451,6 +451,13 @@ class Model(torch.nn.Module):
         run = self.config.get("basecaller", {})
         return TopTrainer(self, layers, chunk_len or run.get("chunksize", 4000), batch or run.get("batchsize", 64))
 
+    def full_trainer(self, chunk_len=None, batch=None):
+        """A FullTrainer (crf/trainer.py) on this model's context: top_trainer's step / grad / publish on every tensor of the
+        state dict -- the convolutions, the five LSTM layers and the head, float32 throughout."""
+        from .trainer import FullTrainer
+        run = self.config.get("basecaller", {})
+        return FullTrainer(self, chunk_len or run.get("chunksize", 4000), batch or run.get("batchsize", 64))
+
     def _decode_rows(self, scores, op):
         if hasattr(scores, "detach"):
             scores = scores.detach().to(torch.float32).cpu().numpy()

@@ -11,6 +11,10 @@ TopTrainer is the same run with the top L = K - 1 LSTM layers unfrozen beside th
 encoder's bottom pass, the training recurrences and fp32 products forwards and backwards, the loss gradient, one norm, one
 clipped AdamW update over all 4 L + 2 tensors.  The step reads fp32 master weights that only the trainer holds; the packed
 forms the inference path reads change when publish() loads the masters into the live context (once per epoch).
+
+FullTrainer is TopTrainer with every key of the state dict: `train --no-amp` without -F, the reference's recipe that freezes
+nothing.  The step (xb_full_train_begin, then the same xb_top_train_step) runs the three convolutions in their float32 training
+form in place of the inference bottom, all five LSTM layers, the head, and the convolutions' backward behind the lowest layer's.
 """
 from collections import OrderedDict
 
@@ -93,14 +97,19 @@ class TopTrainer:
         if not 1 <= int(layers) <= 5:
             raise ValueError("%d unfrozen LSTM layers: 1 .. 5 can be trained (the convolutions stay frozen)" % layers)
         self.model, self.layers = model, int(layers)
-        self.keys = top_keys(self.layers)
-        self.ctx = model.context(chunk_len, batch)
+        self._open(top_keys(self.layers), chunk_len, batch)
+
+    def _open(self, keys, chunk_len, batch):
+        self.keys = list(keys)
+        self.ctx = self.model.context(chunk_len, batch)
         self.chunk_len, self.max_batch = int(chunk_len), self.ctx.max_batch
-        sd = model.state_dict()
+        sd = self.model.state_dict()
         self.shapes = [tuple(sd[k].shape) for k in self.keys]
-        flat = np.concatenate([sd[k].detach().to(torch.float32).cpu().numpy().ravel() for k in self.keys])
-        self.ctx.top_train_begin(self.layers, flat)
+        self._begin(np.concatenate([sd[k].detach().to(torch.float32).cpu().numpy().ravel() for k in self.keys]))
         self.steps = 0
+
+    def _begin(self, flat):
+        self.ctx.top_train_begin(self.layers, flat)
 
     def _live(self):
         if self.ctx is None or self.model._ctx is not self.ctx:
@@ -161,3 +170,28 @@ class TopTrainer:
         self.publish()
         self.ctx.top_train_end()
         self.ctx = None
+
+
+CONV_KEYS = tuple("encoder.%d.conv.%s" % (n, k) for n in range(3) for k in ("weight", "bias"))
+
+
+def full_keys():
+    """The state-dict keys a FullTrainer trains, in the order of csrc/xb_conv_plan.h and xb_top_plan.h: all 28."""
+    return list(CONV_KEYS) + top_keys(5)
+
+
+class FullTrainer(TopTrainer):
+
+    def __init__(self, model, chunk_len, batch):
+        last = model.encoder[-1]
+        if getattr(last, "scale", None) is None or not float(last.scale) > 0:
+            raise NotImplementedError("the trainer needs the head's scale (scores = scale * tanh(Wx + b)); this model has none")
+        keys = list(model.state_dict())
+        if keys != full_keys():
+            raise NotImplementedError("the trainer of every layer takes rnn_encoder's three convolutions, five LSTM layers and head; "
+                                      "this model's state dict has other keys")
+        self.model, self.layers = model, 5
+        self._open(keys, chunk_len, batch)
+
+    def _begin(self, flat):
+        self.ctx.full_train_begin(flat)

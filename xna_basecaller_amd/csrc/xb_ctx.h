@@ -1,8 +1,8 @@
 // xb_ctx.h -- the context behind the C ABI, shared by the translation units that implement it: xb_api.hip (context lifetime, weight
 // upload, the execution of the encoder's plans, decode, pairing, the host pipeline, and the housekeeping every entry point
 // shares: the call prologue `enter`, the status words), xb_api_data.hip (the ctc-data tools), xb_head.hip (the head's gradient
-// and trainer), xb_lstm_train.hip (the training recurrence), xb_train_gemm.hip (the fp32 products of training) and xb_top.hip (the
-// trainer of the head and the top LSTM layers); xb_comm.hip
+// and trainer), xb_lstm_train.hip (the training recurrence), xb_train_gemm.hip (the fp32 products of training), xb_conv_train.hip (the convolutions' training) and xb_top.hip (the
+// trainers of the head with the top LSTM layers, and of every layer); xb_comm.hip
 // reaches a context through the C ABI and xb_internal_defer_after only.  The host arithmetic xb_api.hip acts on lives in three headers without HIP that are
 // checked on their own: xb_schedule.h (the knobs and the planner of the encoder schedule), xb_pack.h (the forms a weight
 // tensor is uploaded in) and xb_status.h (the device status words).  Private to csrc/.
@@ -312,20 +312,26 @@ struct xb_ctx {
     struct LstmTrainState {
         DevBuf carry, wt;
     } lstmtrain;
+    // The convolutions' training (xb_conv_train.hip): the wide route's workspace of the call in flight (dz | col | dcol | wt,
+    // xb_conv_plan.h) and the narrow route's float64 partials of dw and db.  Grow with the calls; live as long as the context.
+    struct ConvTrainState {
+        DevBuf ws, part;
+    } convtrain;
     // The trainer of the head and the top L LSTM layers (xb_top.hip), open from xb_top_train_begin to _end.  train: p, g, m, v in
     // the layout of xb::top_plan, four strides; small: the norm word (64 floats), the layers' summed biases, one transposed
     // weight; act: the activations of a step of `rows` = T n rows, allocated by the first step and grown with the batch; labels:
-    // the batch's labels, lengths and losses.
+    // the batch's labels, lengths and losses.  full (xb_full_train_begin, L = 5): the six conv tensors lie in front of the LSTM
+    // section in each of p, g, m, v, and the conv stack's activations (xb_conv_plan.h) behind the others in act.
     struct TopState {
         DevBuf train, small, act, labels;
-        bool open = false;
+        bool open = false, full = false;
         int L = 0;
         long step = 0;
         size_t rows = 0;                        // rows the activations were last laid out for (0: no step yet)
         void close()
         {
             train.release(); small.release(); act.release(); labels.release();
-            open = false;
+            open = full = false;
             L = 0; step = 0; rows = 0;
         }
     } top;

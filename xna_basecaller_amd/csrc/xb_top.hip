@@ -3,13 +3,18 @@
 // layers (encoder_bottom_run, xb_api.hip) and joined into fp32; from there on a step is the chain tests/toptrain_dev.py
 // composes -- the fp32 products of xb_train_gemm.hip, the training recurrence of xb_lstm_train.hip, xb_ctc_loss_grad, the norm and
 // AdamW of xb_head.hip -- on the buffers csrc/xb_top_plan.h lays out, in one call.  Three small kernels of its own: the join of
-// the two fp16 planes, an exact transpose, the sum of a layer's two biases.  The contracts are in the public header.  Built
-// without contraction, as the translation units it chains.
+// the two fp16 planes, an exact transpose, the sum of a layer's two biases.  xb_full_train_begin opens the same trainer at L = 5
+// with the three convolutions trained as well (`bonito train --no-amp` without -f): their training forwards (xb_conv_train.hip)
+// stand in for the frozen bottom, their backwards follow the lowest LSTM layer's, on the buffers csrc/xb_conv_plan.h adds in
+// front of and behind the plan's.  The contracts are in the public header.  Built without contraction, as the translation
+// units it chains.
 #include "xb_ctx.h"
 #include "xb_ctc_check.h"
 #include "xb_head_train.h"
 #include "xb_top_plan.h"
 #include "xb_train_gemm.h"
+#include "xb_conv_plan.h"
+#include "xb_conv_train.h"
 
 namespace {
 
@@ -70,11 +75,17 @@ int join_run(xb_ctx *ctx, const half_t *hi, const half_t *lo, size_t count, floa
     return launched(ctx, "xb_encode_bottom");
 }
 
-int transpose_run(xb_ctx *ctx, const float *in, int rows, int cols, float *out)
+}  // namespace
+
+int xb::transpose_run(xb_ctx *ctx, const float *in, int rows, int cols, float *out)
 {
     top_transpose_kernel<<<dim3((unsigned)((cols + TT - 1) / TT), (unsigned)((rows + TT - 1) / TT)), 256, 0, ctx->stream>>>(in, rows, cols, out);
     return launched(ctx, "xb_transpose_f32");
 }
+
+namespace {
+
+using xb::transpose_run;
 
 int bias_sum_run(xb_ctx *ctx, const float *b_ih, const float *b_hh, int len, float *b)
 {
@@ -98,14 +109,23 @@ int bottom_run(xb_ctx *ctx, const float *d_signal, int n, int layers, float *d_x
 }
 
 xb::TopPlan plan_of(const xb_ctx *ctx) { return xb::top_plan(ctx->top.L, ctx->cfg.features, ctx->O); }
+xb::ConvPlan conv_plan_of(const xb_ctx *ctx) { return xb::conv_plan(ctx->cfg.chunk_len, ctx->cfg.features, ctx->cfg.winlen, ctx->cfg.stride); }
 
-// the trainer's buffers: four strides of the plan's layout, and the small buffer: the norm | the summed biases | a turned weight
+// floats of one flat buffer and from one buffer to the next; conv: the floats of the conv section in front (0: none)
+size_t flat_stride(size_t conv, const xb::TopPlan &pl) { return (conv + pl.params + 3) & ~(size_t)3; }
+
+// the trainer's buffers: four strides of the flat layout -- the conv section of a full trainer, then the plan's -- and the small
+// buffer: the norm | the summed biases | a turned weight.  tp, tg: where the plan's section starts in p and g.
 struct TopBuf {
-    float *p, *g, *m, *v, *norm, *bias, *turned, *act;
+    float *p, *g, *m, *v, *tp, *tg, *norm, *bias, *turned, *act;
+    size_t params;
     TopBuf(xb_ctx *ctx, const xb::TopPlan &pl)
     {
+        const size_t conv = ctx->top.full ? conv_plan_of(ctx).params : 0, stride = flat_stride(conv, pl);
+        params = conv + pl.params;
         p = static_cast<float *>(ctx->top.train.p);
-        g = p + pl.stride; m = g + pl.stride; v = m + pl.stride;
+        g = p + stride; m = g + stride; v = m + stride;
+        tp = p + conv; tg = g + conv;
         norm = static_cast<float *>(ctx->top.small.p);
         bias = norm + 64; turned = bias + pl.bias_sum;
         act = static_cast<float *>(ctx->top.act.p);
@@ -114,8 +134,20 @@ struct TopBuf {
 
 int top_nomem(xb_ctx *ctx, const char *who, const xb::TopPlan &pl, size_t rows)
 {
-    return fail(ctx, XB_ERR_NOMEM, "%s: a step of %zu rows with %d unfrozen LSTM layers needs %.2f GB on the device beside the context's "
-                "workspaces, and an allocation failed; lower the batch", who, rows, pl.L, (double)pl.step_bytes(rows) / 1e9);
+    double bytes = (double)pl.step_bytes(rows);
+    if (ctx->top.full) {
+        const xb::ConvPlan cp = conv_plan_of(ctx);
+        bytes += sizeof(float) * (double)(cp.act(rows / (size_t)ctx->T).floats + 4 * cp.params);
+    }
+    return fail(ctx, XB_ERR_NOMEM, "%s: a step of %zu rows with %d unfrozen LSTM layers%s needs %.2f GB on the device beside the context's "
+                "workspaces, and an allocation failed; lower the batch", who, rows, pl.L, ctx->top.full ? " and the convolutions" : "", bytes / 1e9);
+}
+
+// floats of a step's activations: the plan's, and behind them (from a 16-byte boundary) a full trainer's conv activations
+size_t conv_act_at(const xb::TopPlan &pl, size_t rows) { return xb::conv_round4(pl.act_floats(rows)); }
+size_t act_floats(const xb_ctx *ctx, const xb::TopPlan &pl, size_t rows)
+{
+    return ctx->top.full ? conv_act_at(pl, rows) + conv_plan_of(ctx).act(rows / (size_t)ctx->T).floats : pl.act_floats(rows);
 }
 
 // One gradient of the step: everything up to the norm.  The caller has validated, entered and staged the batch.
@@ -130,39 +162,53 @@ int top_grad_run(xb_ctx *ctx, const char *who, int n, const uint8_t *d_targets, 
     float *scores = b.act + pl.scores(rows), *dscores = b.act + pl.dscores(rows), *dz = b.act + pl.dz(rows);
     auto rev_of = [&](int i) { return (pl.layer_index(i) - 4) % 2 == 0 ? 1 : 0; };      // LSTM layer index even: backwards in time
 
-    if (int rc = bottom_run(ctx, ctx->d_signal, n, pl.bottom_layers(), x0)) return rc;
+    // a full trainer: the three conv forwards in place of the frozen bottom, conv3 writing x0 as (T, n, F)
+    const xb::ConvPlan cp = conv_plan_of(ctx);
+    const xb::ConvAct ca = cp.act((size_t)n);
+    float *cv = ctx->top.full ? b.act + conv_act_at(pl, rows) : nullptr;
+    const int L1 = (int)cp.L1, L2 = (int)cp.L2, C1 = xb::CONV_C1, C2 = xb::CONV_C2, K12 = xb::CONV_K12;
+    if (ctx->top.full) {
+        if (int rc = xb::conv_forward_run(ctx, ctx->d_signal, b.p + cp.off[0], b.p + cp.off[1], n, 1, cp.chunk, C1, K12, 1, 0, cv + ca.z1, cv + ca.y1, nullptr)) return rc;
+        if (int rc = xb::conv_forward_run(ctx, cv + ca.y1, b.p + cp.off[2], b.p + cp.off[3], n, C1, L1, C2, K12, 1, 0, cv + ca.z2, cv + ca.y2, nullptr)) return rc;
+        if (int rc = xb::conv_forward_run(ctx, cv + ca.y2, b.p + cp.off[4], b.p + cp.off[5], n, C2, L2, F, cp.W, cp.S, 1, cv + ca.z3, x0, cv + ca.col)) return rc;
+    } else if (int rc = bottom_run(ctx, ctx->d_signal, n, pl.bottom_layers(), x0)) return rc;
     const float *x = x0;
     for (int i = 0; i < L; ++i) {
         const size_t *o = pl.layer(i);
         float *bias = b.bias + (size_t)i * 4 * F;
-        if (int rc = bias_sum_run(ctx, b.p + o[2], b.p + o[3], 4 * F, bias)) return rc;
-        if (int rc = xb::linear_f32_run(ctx, x, b.p + o[0], bias, (int64_t)rows, 4 * F, F, 0, 1.0f, gin)) return rc;
+        if (int rc = bias_sum_run(ctx, b.tp + o[2], b.tp + o[3], 4 * F, bias)) return rc;
+        if (int rc = xb::linear_f32_run(ctx, x, b.tp + o[0], bias, (int64_t)rows, 4 * F, F, 0, 1.0f, gin)) return rc;
         float *y = b.act + pl.y(rows, i);
-        if (int rc = xb_lstm_train_forward_dev(ctx, gin, b.p + o[1], T, n, F, rev_of(i), y, b.act + pl.gates(rows, i), b.act + pl.c(rows, i))) return rc;
+        if (int rc = xb_lstm_train_forward_dev(ctx, gin, b.tp + o[1], T, n, F, rev_of(i), y, b.act + pl.gates(rows, i), b.act + pl.c(rows, i))) return rc;
         x = y;
     }
-    if (int rc = xb::linear_f32_run(ctx, x, b.p + pl.head_w(), b.p + pl.head_b(), (int64_t)rows, C, F, 1, scale, scores)) return rc;
+    if (int rc = xb::linear_f32_run(ctx, x, b.tp + pl.head_w(), b.tp + pl.head_b(), (int64_t)rows, C, F, 1, scale, scores)) return rc;
     if (int rc = ctc_grad_run(ctx, who, scores, T, n, 0, C, d_targets, Lt, d_len, 0.0f, 1, d_loss, dscores)) return rc;
     if (int rc = xb::head_dz_run(ctx, scores, dscores, (int64_t)(rows * C), scale, dz)) return rc;
-    if (int rc = xb::wgrad_f32_run(ctx, dz, x, (int64_t)rows, C, F, b.g + pl.head_w(), b.g + pl.head_b())) return rc;
-    if (int rc = transpose_run(ctx, b.p + pl.head_w(), C, F, b.turned)) return rc;
+    if (int rc = xb::wgrad_f32_run(ctx, dz, x, (int64_t)rows, C, F, b.tg + pl.head_w(), b.tg + pl.head_b())) return rc;
+    if (int rc = transpose_run(ctx, b.tp + pl.head_w(), C, F, b.turned)) return rc;
     if (int rc = xb::linear_f32_run(ctx, dz, b.turned, nullptr, (int64_t)rows, F, C, 0, 1.0f, dy)) return rc;      // the head's dX = dZ W
     for (int i = L - 1; i >= 0; --i) {
         const size_t *o = pl.layer(i);
         const int rev = rev_of(i);
         const float *y = b.act + pl.y(rows, i), *xin = i ? b.act + pl.y(rows, i - 1) : x0;
-        if (int rc = xb_lstm_train_backward_dev(ctx, dy, b.p + o[1], b.act + pl.gates(rows, i), b.act + pl.c(rows, i), T, n, F, rev, dgin)) return rc;
-        if (int rc = xb::wgrad_f32_run(ctx, dgin, xin, (int64_t)rows, 4 * F, F, b.g + o[0], b.g + o[2])) return rc;       // dW_ih and db
-        XB_HIP(ctx, hipMemcpyAsync(b.g + o[3], b.g + o[2], sizeof(float) * 4 * F, hipMemcpyDeviceToDevice, ctx->stream));  // both biases receive it
+        if (int rc = xb_lstm_train_backward_dev(ctx, dy, b.tp + o[1], b.act + pl.gates(rows, i), b.act + pl.c(rows, i), T, n, F, rev, dgin)) return rc;
+        if (int rc = xb::wgrad_f32_run(ctx, dgin, xin, (int64_t)rows, 4 * F, F, b.tg + o[0], b.tg + o[2])) return rc;       // dW_ih and db
+        XB_HIP(ctx, hipMemcpyAsync(b.tg + o[3], b.tg + o[2], sizeof(float) * 4 * F, hipMemcpyDeviceToDevice, ctx->stream));  // both biases receive it
         // dW_hh = sum_t dgin[t]^T y[the step processed before t]: the operands shifted against each other by one time step
         const float *wa = dgin + (rev ? (size_t)0 : (size_t)n * 4 * F), *wb = y + (rev ? (size_t)n * F : (size_t)0);
-        if (int rc = xb::wgrad_f32_run(ctx, wa, wb, (int64_t)(T - 1) * n, 4 * F, F, b.g + o[1], nullptr)) return rc;
-        if (i) {                                                                                                            // dx = dgin W_ih: the dy of the layer below
-            if (int rc = transpose_run(ctx, b.p + o[0], 4 * F, F, b.turned)) return rc;
+        if (int rc = xb::wgrad_f32_run(ctx, wa, wb, (int64_t)(T - 1) * n, 4 * F, F, b.tg + o[1], nullptr)) return rc;
+        if (i || ctx->top.full) {                                                                                           // dx = dgin W_ih: the dy of the layer below
+            if (int rc = transpose_run(ctx, b.tp + o[0], 4 * F, F, b.turned)) return rc;
             if (int rc = xb::linear_f32_run(ctx, dgin, b.turned, nullptr, (int64_t)rows, F, 4 * F, 0, 1.0f, dy)) return rc;
         }
     }
-    return grad_norm_run(ctx, b.g, pl.params, nullptr, 0, b.norm);
+    if (ctx->top.full) {                                    // dy is d loss / d x0 in conv3's (T, n, F) layout; conv1's input has no gradient
+        if (int rc = xb::conv_backward_run(ctx, dy, cv + ca.y2, cv + ca.z3, b.p + cp.off[4], n, C2, L2, F, cp.W, cp.S, 1, cv + ca.dy2, b.g + cp.off[4], b.g + cp.off[5], cv + ca.col)) return rc;
+        if (int rc = xb::conv_backward_run(ctx, cv + ca.dy2, cv + ca.y1, cv + ca.z2, b.p + cp.off[2], n, C1, L1, C2, K12, 1, 0, cv + ca.dy1, b.g + cp.off[2], b.g + cp.off[3], nullptr)) return rc;
+        if (int rc = xb::conv_backward_run(ctx, cv + ca.dy1, ctx->d_signal, cv + ca.z1, b.p + cp.off[0], n, 1, cp.chunk, C1, K12, 1, 0, nullptr, b.g + cp.off[0], b.g + cp.off[1], nullptr)) return rc;
+    }
+    return grad_norm_run(ctx, b.g, b.params, nullptr, 0, b.norm);
 }
 
 // xb_top_train_grad, and with `step` the update behind it
@@ -184,7 +230,7 @@ int top_call(xb_ctx *ctx, const char *who, const float *signal, int n, const uin
     const xb::TopPlan pl = plan_of(ctx);
     const size_t N = (size_t)n, rows = (size_t)ctx->T * N;
     const size_t lab = (N * Lt + 255) & ~(size_t)255, len = (N * 4 + 255) & ~(size_t)255;
-    if (grow(ctx, &ctx->top.act, pl.act_floats(rows) * sizeof(float))) {
+    if (grow(ctx, &ctx->top.act, act_floats(ctx, pl, rows) * sizeof(float))) {
         ctx->top.rows = 0;                      // the old activations went with the failed allocation
         return top_nomem(ctx, who, pl, rows);
     }
@@ -211,7 +257,7 @@ int top_call(xb_ctx *ctx, const char *who, const float *signal, int n, const uin
         const float clip = (float)std::min(1.0, 2.0 / ((double)norm + 1e-6));
         float decay, step_size, bc2_sqrt;
         adamw_scalars((double)lr, ctx->top.step + 1, &decay, &step_size, &bc2_sqrt);
-        if (int rc = adamw_run(ctx, b.p, b.g, b.m, b.v, pl.params, clip, decay, step_size, bc2_sqrt)) return rc;
+        if (int rc = adamw_run(ctx, b.p, b.g, b.m, b.v, b.params, clip, decay, step_size, bc2_sqrt)) return rc;
         ++ctx->top.step;
         if (int rc = xb_synchronize(ctx)) return rc;
     }
@@ -246,34 +292,61 @@ XB_API int xb_transpose_f32_dev(xb_ctx *ctx, const float *d_in, int rows, int co
     return transpose_run(ctx, d_in, rows, cols, d_out);
 }
 
-XB_API int xb_top_train_begin(xb_ctx *ctx, int layers, const float *params)
+// xb_top_train_begin, and with `full` xb_full_train_begin: the checks, the four flat buffers, the masters
+static int train_begin(xb_ctx *ctx, const char *who, int layers, bool full, const float *params)
 {
     if (!ctx) return XB_ERR_INVALID;
     if (int rc = check_ready(ctx, 1)) return rc;
-    if (!params) return fail(ctx, XB_ERR_INVALID, "xb_top_train_begin: null host pointer");
-    if (ctx->top.open) return fail(ctx, XB_ERR_STATE, "xb_top_train_begin: a trainer is already open on this context");
-    if (ctx->head.open) return fail(ctx, XB_ERR_STATE, "xb_top_train_begin: a head trainer is open on this context; call xb_head_train_end first");
+    if (!params) return fail(ctx, XB_ERR_INVALID, "%s: null host pointer", who);
+    if (ctx->top.open) return fail(ctx, XB_ERR_STATE, "%s: a trainer is already open on this context", who);
+    if (ctx->head.open) return fail(ctx, XB_ERR_STATE, "%s: a head trainer is open on this context; call xb_head_train_end first", who);
     const int F = ctx->cfg.features;
     const xb::TopPlan pl = xb::top_plan(layers, F, ctx->O);
-    if (pl.error) return fail(ctx, XB_ERR_INVALID, "xb_top_train_begin: %d unfrozen LSTM layers, accepted: 1 .. %d (the convolutions stay frozen)", layers, xb::TOP_MAX_LAYERS);
-    if (F % 16 || F > 1024) return fail(ctx, XB_ERR_INVALID, "xb_top_train_begin: the training recurrence takes features that are a multiple of 16 up to 1024, got %d", F);
-    if (int rc = head_usable(ctx, "xb_top_train_begin")) return rc;
-    if (int rc = bottom_usable(ctx, "xb_top_train_begin")) return rc;
+    if (pl.error) return fail(ctx, XB_ERR_INVALID, "%s: %d unfrozen LSTM layers, accepted: 1 .. %d (the convolutions stay frozen)", who, layers, xb::TOP_MAX_LAYERS);
+    if (F % 16 || F > 1024) return fail(ctx, XB_ERR_INVALID, "%s: the training recurrence takes features that are a multiple of 16 up to 1024, got %d", who, F);
+    size_t conv = 0;
+    if (full) {
+        // the inference bottom never runs: no rule about its precision; the head's tanh needs its scale, as everywhere
+        if (!(ctx->cfg.scale > 0.0f) || !std::isfinite(ctx->cfg.scale))
+            return fail(ctx, XB_ERR_INVALID, "%s: the head needs its tanh with a positive scale, the context has scale %g", who, (double)ctx->cfg.scale);
+        const xb::ConvPlan cp = conv_plan_of(ctx);
+        if (cp.error || cp.T != ctx->T)
+            return fail(ctx, XB_ERR_INVALID, "%s: a window of %d at stride %d on chunks of %d samples cannot be laid out (16 * window <= %d)", who,
+                        ctx->cfg.winlen, ctx->cfg.stride, ctx->cfg.chunk_len, xb::CONV_MAX_CK);
+        if (cp.params % 4)          // cannot happen while F % 16 == 0; the LSTM section's kernels read 16 bytes at a time
+            return fail(ctx, XB_ERR_INVALID, "%s: the conv section of %zu floats leaves the LSTM section off a 16-byte boundary", who, cp.params);
+        conv = cp.params;
+    } else {
+        if (int rc = head_usable(ctx, who)) return rc;
+        if (int rc = bottom_usable(ctx, who)) return rc;
+    }
     if (int rc = enter(ctx, false)) return rc;
-    const size_t max_rows = (size_t)ctx->T * ctx->cfg.max_batch;
-    if (grow(ctx, &ctx->top.train, 4 * pl.stride * sizeof(float)) || grow(ctx, &ctx->top.small, (64 + pl.small_floats()) * sizeof(float))) {
+    const size_t max_rows = (size_t)ctx->T * ctx->cfg.max_batch, stride = flat_stride(conv, pl);
+    ctx->top.full = full;
+    if (grow(ctx, &ctx->top.train, 4 * stride * sizeof(float)) || grow(ctx, &ctx->top.small, (64 + pl.small_floats()) * sizeof(float))) {
+        const int rc = top_nomem(ctx, who, pl, max_rows);
         ctx->top.close();
-        return top_nomem(ctx, "xb_top_train_begin", pl, max_rows);
+        return rc;
     }
     ctx->top.L = layers;
     const TopBuf b(ctx, pl);
-    XB_HIP(ctx, hipMemsetAsync(b.p, 0, 4 * pl.stride * sizeof(float), ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(b.p, params, pl.params * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    XB_HIP(ctx, hipMemsetAsync(b.p, 0, 4 * stride * sizeof(float), ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(b.p, params, b.params * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     if (int rc = xb_synchronize(ctx)) { ctx->top.close(); return rc; }
     ctx->top.step = 0;
     ctx->top.rows = 0;
     ctx->top.open = true;
     return XB_OK;
+}
+
+XB_API int xb_top_train_begin(xb_ctx *ctx, int layers, const float *params)
+{
+    return train_begin(ctx, "xb_top_train_begin", layers, false, params);
+}
+
+XB_API int xb_full_train_begin(xb_ctx *ctx, const float *params)
+{
+    return train_begin(ctx, "xb_full_train_begin", xb::TOP_MAX_LAYERS, true, params);
 }
 
 XB_API int xb_top_train_grad(xb_ctx *ctx, const float *signal, int n, const uint8_t *targets, int Lt, const int32_t *lengths, float *loss,
@@ -294,8 +367,8 @@ XB_API int xb_top_get_weights(xb_ctx *ctx, float *params)
     if (!ctx->top.open) return fail(ctx, XB_ERR_STATE, "xb_top_get_weights: no trainer is open");
     if (!params) return fail(ctx, XB_ERR_INVALID, "xb_top_get_weights: null host pointer");
     if (int rc = enter(ctx, false)) return rc;
-    const xb::TopPlan pl = plan_of(ctx);
-    XB_HIP(ctx, hipMemcpyAsync(params, ctx->top.train.p, pl.params * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    const TopBuf b(ctx, plan_of(ctx));
+    XB_HIP(ctx, hipMemcpyAsync(params, b.p, b.params * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     return xb_synchronize(ctx);
 }
 
