@@ -117,6 +117,69 @@ def test_bad_lengths_and_labels_are_refused_and_the_context_carries_on():
     ctx.close()
 
 
+def test_every_host_form_refuses_a_bad_label_batch_alike_and_carries_on():
+    """The five host forms that take label rows -- xb_ctc_loss, xb_ctc_loss_grad, xb_validate_chunks, xb_head_train_step and
+    xb_top_train_step -- hold one contract on them: a width one short of a single position, a length one above the width and a
+    label above n_base are each refused with XB_ERR_INVALID and one text behind the entry point's own name, and the good
+    batch right after each refusal gives the bytes of the same calls on a context that never saw a bad one.  One context, the
+    first four under an open head trainer, the last under a top trainer of one layer."""
+    from xna_basecaller_amd.crf.trainer import B_KEY, W_KEY, top_keys
+    nb, sl, F, L, B, Lt = 6, 3, 32, 200, 2, 12
+    keys, shapes = encoder_shapes(F, nb)
+    sd = seeded_state_dict(keys, shapes, seed=5)
+    rng = np.random.default_rng(17)
+    x = rng.standard_normal((B, L)).astype(np.float32)
+    sc = random_scores(L // 5, B, nb, sl=sl, seed=4, with_blank=False)
+    targets, lens = _targets(rng, B, Lt, nb, sl)
+    long_l, high_t = lens.copy(), targets.copy()
+    long_l[1] = Lt + 1
+    high_t[0, 0] = nb + 1
+    bad = [(np.ones((B, sl - 1), np.uint8), lens, "target width %d gives 0 positions" % (sl - 1)),
+           (targets, long_l, "target_lengths[1] = %d" % (Lt + 1)),
+           (high_t, lens, "targets[0][0] = %d" % (nb + 1))]
+    calls = {
+        "xb_ctc_loss": lambda c, t, l: (c.ctc_loss(sc, t, l, has_blank=False),),
+        "xb_ctc_loss_grad": lambda c, t, l: c.ctc_loss_grad(sc, t, l, has_blank=False),
+        "xb_validate_chunks": lambda c, t, l: c.validate_chunks(x, "NACGTXY", t, l),
+        "xb_head_train_step": lambda c, t, l: c.head_train_step(x, t, l, 2e-3) + c.head_get_weights() + c.head_image(),
+        "xb_top_train_step": lambda c, t, l: c.top_train_step(x, t, l, 2e-3) + (c.top_get_weights(),),
+    }
+    texts = [set() for _ in bad]
+
+    def walk(with_bad):
+        ctx = _lib.Context(0, nb, sl, F, 19, 5, 5.0, BLANK, L, B, precision=_lib.XB_PREC_MIXED)
+        assert ctx.T == 40
+        ctx.load_state_dict(sd)
+        out = []
+
+        def go(name):
+            for k, (t, l, what) in enumerate(bad):
+                if with_bad:
+                    with pytest.raises(_lib.XbError) as e:
+                        calls[name](ctx, t, l)
+                    front, _, text = str(e.value).partition(name + ": ")
+                    assert e.value.code == _lib.XB_ERR_INVALID and front == "libxnacall error %d: " % _lib.XB_ERR_INVALID, (name, str(e.value))
+                    assert text.startswith(what), (name, text)
+                    texts[k].add(text)
+                out.append((name, k, [np.array(a) for a in calls[name](ctx, targets, lens)]))
+
+        ctx.head_train_begin(sd[W_KEY], sd[B_KEY])
+        for name in list(calls)[:4]:
+            go(name)
+        ctx.head_train_end()
+        ctx.top_train_begin(1, np.concatenate([sd[k].ravel() for k in top_keys(1)]))
+        go("xb_top_train_step")
+        ctx.top_train_end()
+        ctx.close()
+        return out
+
+    got, want = walk(True), walk(False)
+    assert [len(t) for t in texts] == [1, 1, 1], texts          # five entry points, one text each
+    assert len(got) == len(want) == 15
+    for (name, k, a), (_, _, b) in zip(got, want):
+        assert len(a) == len(b) and all(p.dtype == q.dtype and p.tobytes() == q.tobytes() for p, q in zip(a, b)), (name, k)
+
+
 def test_device_form_validates_on_the_device():
     """xb_ctc_loss_dev has nothing on the host to check: the kernel flags a bad length or label in the context's error word,
     writes no loss for that chunk, and the next xb_synchronize reports XB_ERR_INVALID; the context works afterwards."""

@@ -2,7 +2,12 @@
 """GPU tool: two builds of libxnacall.so against each other, BYTE for byte -- scores (fp32), called sequences and lengths -- over
 the shapes that exercise the recurrence's variants (one / two groups per workgroup, ragged groups, chunk slabs, small feature
 sizes, every precision), each build loaded in its own process (XNA_LIBXNACALL).  Used in round 5 to show that the recurrence's
-lean-issue rewrite (same arithmetic, fewer instructions) changes no bit:  python tools/lib_ab.py OLD.so NEW.so"""
+lean-issue rewrite (same arithmetic, fewer instructions) changes no bit:  python tools/lib_ab.py OLD.so NEW.so
+
+TRAIN_CASES are the loss and training families on small contexts (chunks of 200 samples, at most 8): three steps each of a head
+trainer, a top trainer at L = 1 and L = 2 and a full trainer with a validate_chunks between the first two, top_train_grad,
+ctc_loss, ctc_loss_grad, validate_chunks, head_grad with and without X.  Their digests cover every returned float, the weights
+after each step and the head's image.  --train runs these alone."""
 import hashlib
 import json
 import os
@@ -25,16 +30,86 @@ CASES = [  # features, nb, chunk_len, n, precision, paired calls, env
     (96, 5, 1000, 70, "f16x3", 1, {}),
     (64, 6, 1000, 40, "mixed", 1, {}),
 ]
+TRAIN_CASES = [(F, Lt) for F in (32, 64) for Lt in (12, 24)]       # features, label row width
 
 
-def worker():
+def train_digest(F, Lt):
+    import numpy as np
+    from xna_basecaller_amd import _lib
+    from xna_basecaller_amd.crf.trainer import B_KEY, W_KEY, full_keys, top_keys
+    from xna_basecaller_amd.synthetic import seeded_weights
+    nb, sl, L, N, alphabet = 6, 3, 200, 8, "NACGTXY"
+    sd = seeded_weights(F, nb)
+    rng = np.random.default_rng(F + Lt)
+    h = hashlib.sha1()
+
+    def add(*arrays):
+        for a in arrays:
+            h.update(np.ascontiguousarray(a).tobytes())
+
+    def batch(n):
+        lens = rng.integers(sl, Lt + 1, n).astype(np.int32)
+        targets = np.zeros((n, Lt), np.uint8)
+        for i in range(n):
+            targets[i, :lens[i]] = rng.integers(1, nb + 1, lens[i])
+        return rng.standard_normal((n, L)).astype(np.float32), targets, lens
+
+    def context():
+        ctx = _lib.Context(0, nb, sl, F, 19, 5, 5.0, 2.0, L, N, precision=_lib.XB_PREC_MIXED)
+        ctx.load_state_dict(sd)
+        return ctx
+
+    flat = lambda keys: np.concatenate([sd[k].ravel() for k in keys])                          # noqa: E731
+    batches = [batch(n) for n in (8, 3, 8)]
+    for kind in ("head", 1, 2, "full"):
+        ctx = context()
+        if kind == "head":
+            ctx.head_train_begin(sd[W_KEY], sd[B_KEY])
+        elif kind == "full":
+            ctx.full_train_begin(flat(full_keys()))
+        else:
+            ctx.top_train_begin(kind, flat(top_keys(kind)))
+        for i, (x, t, l) in enumerate(batches):
+            if kind == "head":
+                add(np.array(ctx.head_train_step(x, t, l, 2e-3), np.float32), *ctx.head_get_weights())
+                add(*ctx.head_image())
+            else:
+                add(np.array(ctx.top_train_step(x, t, l, 2e-3), np.float32), ctx.top_get_weights())
+            if i == 0:
+                add(*ctx.validate_chunks(x, alphabet, t, l))
+        if kind == "head":
+            ctx.head_train_end()
+        else:
+            add(np.array(ctx.top_train_grad(*batches[1]), np.float32))
+            ctx.top_train_end()
+        ctx.close()
+
+    ctx = context()
+    x, t, l = batches[0]
+    y = ctx.encode(x, expand_blanks=False)
+    for sc in (y, ctx.encode(x, expand_blanks=True)):
+        add(*ctx.ctc_loss(sc, t, l, has_blank=None if sc is y else True, want_logz=True))
+        add(*ctx.ctc_loss_grad(sc, t, l))
+    add(*ctx.validate_chunks(x, alphabet, t, l))
+    loss, dy = ctx.ctc_loss_grad(y, t, l)
+    ctx.encode(x, expand_blanks=False)                          # X = None: the last encoder pass
+    add(*ctx.head_grad(y, dy))
+    M = y.shape[0] * y.shape[1]
+    x_hi = rng.standard_normal((M, F)).astype(np.float16)
+    x_lo = (rng.standard_normal((M, F)) * 2.0 ** -11).astype(np.float16)
+    add(*ctx.head_grad(y, dy, x_hi.view(np.uint16), x_lo.view(np.uint16)))
+    ctx.close()
+    return h.hexdigest()
+
+
+def worker(train_only=False):
     import numpy as np
     import torch
     sys.path.insert(0, ROOT)
     from xna_basecaller_amd import _lib
     from xna_basecaller_amd.synthetic import peaky_weights, seeded_weights
     out = []
-    for F, nb, L, n, prec, calls, env in CASES:
+    for F, nb, L, n, prec, calls, env in ([] if train_only else CASES):
         os.environ.update(env)
         ctx = _lib.Context(0, nb, 3, F, 19, 5, 5.0, 2.0, L, n, precision=_lib.PRECISIONS[prec])
         for k in env:
@@ -58,17 +133,22 @@ def worker():
         h.update(np.ascontiguousarray(scores).tobytes())
         out.append(h.hexdigest())
         ctx.close()
+    out += [train_digest(F, Lt) for F, Lt in TRAIN_CASES]
     print("DIGESTS " + json.dumps(out))
 
 
 def main():
-    if len(sys.argv) == 2 and sys.argv[1] == "--worker":
-        return worker()
-    libs = sys.argv[1:3]
+    train_only = "--train" in sys.argv[1:]
+    argv = [a for a in sys.argv[1:] if a != "--train"]
+    if argv == ["--worker"]:
+        return worker(train_only)
+    libs = argv[:2]
+    cases = ([] if train_only else CASES) + [("train", "features %d" % F, "label rows %d wide" % Lt) for F, Lt in TRAIN_CASES]
     res = []
     for lib in libs:
         env = dict(os.environ, XNA_LIBXNACALL=os.path.abspath(lib))
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker"] + ["--train"] * train_only, env=env,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE)
         line = [l for l in r.stdout.decode().splitlines() if l.startswith("DIGESTS ")]
         if r.returncode or not line:
             print(r.stderr.decode()[-2000:])
@@ -76,7 +156,7 @@ def main():
             return 1
         res.append(json.loads(line[0][8:]))
     bad = 0
-    for case, a, b in zip(CASES, res[0], res[1]):
+    for case, a, b in zip(cases, res[0], res[1]):
         same = a == b
         bad += not same
         print("%-60s %s" % (str(case), "identical" if same else "DIFFERENT  %s vs %s" % (a[:10], b[:10])))

@@ -461,6 +461,19 @@ class Context:
             raise ValueError("target_lengths: (n) expected")
         return np.ascontiguousarray(t, dtype=np.uint8), tl
 
+    def _chunk_batch(self, signal, targets, target_lengths):
+        """What the calls on labelled chunks pass: signal as contiguous (n, chunk_len) fp32, and its _labels."""
+        signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1, self.chunk_len)
+        return (signal,) + self._labels(targets, target_lengths, signal.shape[0])
+
+    def _train_call(self, fn, signal, targets, target_lengths, *lr):
+        """A trainer's call fn on labelled chunks, at a learning rate or without one -> (mean loss, gradient norm)."""
+        signal, targets, tl = self._chunk_batch(signal, targets, target_lengths)
+        loss, norm = C.c_float(), C.c_float()
+        self._check(fn(self.h, signal.ctypes.data, signal.shape[0], targets.ctypes.data, targets.shape[1], tl.ctypes.data,
+                       *map(float, lr), C.byref(loss), C.byref(norm)))
+        return loss.value, norm.value
+
     def ctc_loss(self, scores, targets, target_lengths, has_blank=True, want_logz=False):
         """xb_ctc_loss: RAW scores (T, n, C) in either layout, targets (n, Lt) CTC labels, target_lengths (n) -> loss (n,) fp32 =
         CTC_CRF.ctc_loss(..., normalise_scores=True, reduction='none'); with want_logz (loss, logz_ctc)."""
@@ -561,13 +574,7 @@ class Context:
 
     def head_train_step(self, signal, targets, target_lengths, lr):
         """xb_head_train_step: one AdamW step of the head on n chunks -> (mean loss before the step, gradient norm before clipping)."""
-        signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1, self.chunk_len)
-        n = signal.shape[0]
-        targets, tl = self._labels(targets, target_lengths, n)
-        loss, norm = C.c_float(), C.c_float()
-        self._check(self.lib.xb_head_train_step(self.h, signal.ctypes.data, n, targets.ctypes.data, targets.shape[1], tl.ctypes.data,
-                                                float(lr), C.byref(loss), C.byref(norm)))
-        return loss.value, norm.value
+        return self._train_call(self.lib.xb_head_train_step, signal, targets, target_lengths, lr)
 
     def head_state_dev(self):
         """Device pointers of an open trainer's (p, m, v, g), each (W | b) fp32, and the steps taken (tests)."""
@@ -656,25 +663,13 @@ class Context:
         self._check(self.lib.xb_full_train_begin(self.h, params.ctypes.data))
         self._top_layers = "full"
 
-    def _top_call(self, signal, targets, target_lengths, lr):
-        signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1, self.chunk_len)
-        n = signal.shape[0]
-        targets, tl = self._labels(targets, target_lengths, n)
-        loss, norm = C.c_float(), C.c_float()
-        head = (self.h, signal.ctypes.data, n, targets.ctypes.data, targets.shape[1], tl.ctypes.data)
-        if lr is None:
-            self._check(self.lib.xb_top_train_grad(*head, C.byref(loss), C.byref(norm)))
-        else:
-            self._check(self.lib.xb_top_train_step(*head, float(lr), C.byref(loss), C.byref(norm)))
-        return loss.value, norm.value
-
     def top_train_grad(self, signal, targets, target_lengths):
         """xb_top_train_grad: the gradient of one batch, left unclipped on the device -> (mean loss, gradient norm)."""
-        return self._top_call(signal, targets, target_lengths, None)
+        return self._train_call(self.lib.xb_top_train_grad, signal, targets, target_lengths)
 
     def top_train_step(self, signal, targets, target_lengths, lr):
         """xb_top_train_step: one clipped AdamW step on n chunks -> (mean loss before the step, gradient norm before clipping)."""
-        return self._top_call(signal, targets, target_lengths, lr)
+        return self._train_call(self.lib.xb_top_train_step, signal, targets, target_lengths, lr)
 
     def top_state_dev(self):
         """Device pointers of an open trainer: dict(p, g, m, v: the flat buffers; x0, scores, dscores of the last step (None
@@ -705,9 +700,8 @@ class Context:
     def validate_chunks(self, signal, alphabet, targets, target_lengths):
         """xb_validate_chunks: signal (n, chunk_len), targets (n, Lt), target_lengths (n) -> (seq (n, T) int8 left-packed ASCII,
         lens (n,), loss (n,) fp32): basecall_chunks' calls and ctc_loss of the same scores, which never leave the device."""
-        signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1, self.chunk_len)
+        signal, targets, tl = self._chunk_batch(signal, targets, target_lengths)
         n = signal.shape[0]
-        targets, tl = self._labels(targets, target_lengths, n)
         seq, lens = self._outputs(0, n, self.T)
         loss = np.empty((n,), np.float32)
         self._check(self.lib.xb_validate_chunks(self.h, signal.ctypes.data, n, "".join(alphabet).encode(), targets.ctypes.data,

@@ -5,7 +5,8 @@ a pretrained model with its bottom layers frozen and the top layer with paramete
 device call (Model.head_trainer, xb_head_train_step).  --num-unfreeze-top K for K in 2 .. 6 together with --no-amp trains the
 head and the top K - 1 LSTM layers, float32 throughout above the frozen bottom (the reference's --no-amp; its default, autocast
 with a GradScaler, is not implemented): again one device call per step (Model.top_trainer, xb_top_train_step).  The trained
-layers are loaded into the inference path before each epoch's validation and checkpoint (TopTrainer.publish).  Without -F and
+layers are loaded into the inference path before each epoch's validation and checkpoint (Trainer.publish; the head recipe's
+step has already put them there, and publish only refreshes the model's parameters).  Without -F and
 with --no-amp EVERY layer trains -- the reference's headline recipes, which never pass -f: the convolutions too have their
 float32 forward and backward on the device (Model.full_trainer, xb_full_train_begin), one device call per step as before.
 
@@ -206,8 +207,7 @@ def main(args):
             smoothed = loss if smoothed is None else 0.01 * loss + 0.99 * smoothed
             append_row(log, LOSS_COLUMNS, [seen, time.perf_counter() - t0, grad_norm, lr, loss])
         duration = time.perf_counter() - t0
-        if full or top_layers:
-            trainer.publish()                                   # the validation below and the checkpoint see the trained layers
+        trainer.publish()                                       # the validation below and the model's parameters see the trained layers
         torch.save(trainer.state_dict(), os.path.join(workdir, "weights_%d.tar" % epoch))
         val_loss, val_mean, val_median = validate(model, valid, args.batch)
         print("[epoch {}] directory={} loss={:.4f} mean_acc={:.3f}% median_acc={:.3f}%".format(

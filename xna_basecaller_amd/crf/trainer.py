@@ -15,6 +15,10 @@ forms the inference path reads change when publish() loads the masters into the 
 FullTrainer is TopTrainer with every key of the state dict: `train --no-amp` without -F, the reference's recipe that freezes
 nothing.  The step (xb_full_train_begin, then the same xb_top_train_step) runs the three convolutions in their float32 training
 form in place of the inference bottom, all five LSTM layers, the head, and the convolutions' backward behind the lowest layer's.
+
+What the three share is Trainer: the run's life on the model's context, the step, the checkpoint, publish() and close().  A
+trainer says which keys it trains (_keys), how the device run begins and ends (_begin, _end), what a step calls (_step) and how
+the masters come back (_masters).
 """
 from collections import OrderedDict
 
@@ -22,65 +26,8 @@ import numpy as np
 import torch
 
 W_KEY, B_KEY = "encoder.9.linear.weight", "encoder.9.linear.bias"
-
-
-class HeadTrainer:
-
-    def __init__(self, model, chunk_len, batch):
-        last = model.encoder[-1]
-        if getattr(last, "scale", None) is None or not float(last.scale) > 0:
-            raise NotImplementedError("the head trainer needs the head's scale (scores = scale * tanh(Wx + b)); this model has none")
-        self.model = model
-        self.ctx = model.context(chunk_len, batch)
-        self.chunk_len, self.max_batch = int(chunk_len), self.ctx.max_batch
-        self.ctx.head_train_begin(last.linear.weight.detach().to(torch.float32).cpu().numpy(),
-                                  last.linear.bias.detach().to(torch.float32).cpu().numpy())
-        self.steps = 0
-
-    def _live(self):
-        if self.ctx is None or self.model._ctx is not self.ctx:
-            raise RuntimeError("the head trainer's device context is gone (the model was moved, reloaded or asked for another "
-                               "chunk length or a larger batch): create a new trainer")
-
-    def step(self, batch, targets, lengths, lr):
-        """One optimiser step on a (N,1,L) batch with its (N,Lt) label rows and (N,) lengths at learning rate lr ->
-        (mean loss before the step, gradient norm before clipping)."""
-        self._live()
-        sig = self.model._as_signal(batch)
-        if sig.shape[1] != self.chunk_len or sig.shape[0] > self.max_batch:
-            raise ValueError("batch of %d chunks of %d samples: this trainer takes up to %d chunks of %d"
-                             % (sig.shape[0], sig.shape[1], self.max_batch, self.chunk_len))
-        out = self.ctx.head_train_step(sig, targets, lengths, lr)
-        self.steps += 1
-        return out
-
-    def weights(self):
-        self._live()
-        return self.ctx.head_get_weights()
-
-    def state_dict(self):
-        """The model's state dict with the two head tensors replaced by the trained ones."""
-        w, b = self.weights()
-        sd = OrderedDict((k, v.detach().clone()) for k, v in self.model.state_dict().items())
-        sd[W_KEY] = torch.from_numpy(w).to(sd[W_KEY].dtype)
-        sd[B_KEY] = torch.from_numpy(b).to(sd[B_KEY].dtype)
-        return sd
-
-    def close(self):
-        """End the run: the trained floats go into the model's own parameters (its live context already computes with them)."""
-        if self.ctx is None:
-            return
-        self._live()
-        w, b = self.ctx.head_get_weights()
-        self.ctx.head_train_end()
-        last = self.model.encoder[-1]
-        with torch.no_grad():
-            last.linear.weight.copy_(torch.from_numpy(w))
-            last.linear.bias.copy_(torch.from_numpy(b))
-        self.ctx = None
-
-
 LSTM_KEYS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+CONV_KEYS = tuple("encoder.%d.conv.%s" % (n, k) for n in range(3) for k in ("weight", "bias"))
 
 
 def top_keys(layers):
@@ -88,28 +35,27 @@ def top_keys(layers):
     return ["encoder.%d.rnn.%s" % (n, k) for n in range(9 - layers, 9) for k in LSTM_KEYS] + [W_KEY, B_KEY]
 
 
-class TopTrainer:
+def full_keys():
+    """The state-dict keys a FullTrainer trains, in the order of csrc/xb_conv_plan.h and xb_top_plan.h: all 28."""
+    return list(CONV_KEYS) + top_keys(5)
 
-    def __init__(self, model, layers, chunk_len, batch):
+
+class Trainer:
+    # the step leaves the inference forms of the live context as they were: publish() has to load the masters into them
+    reloads = True
+
+    def __init__(self, model, chunk_len, batch):
         last = model.encoder[-1]
         if getattr(last, "scale", None) is None or not float(last.scale) > 0:
             raise NotImplementedError("the trainer needs the head's scale (scores = scale * tanh(Wx + b)); this model has none")
-        if not 1 <= int(layers) <= 5:
-            raise ValueError("%d unfrozen LSTM layers: 1 .. 5 can be trained (the convolutions stay frozen)" % layers)
-        self.model, self.layers = model, int(layers)
-        self._open(top_keys(self.layers), chunk_len, batch)
-
-    def _open(self, keys, chunk_len, batch):
-        self.keys = list(keys)
-        self.ctx = self.model.context(chunk_len, batch)
+        self.model = model
+        self.keys = list(self._keys())
+        self.ctx = model.context(chunk_len, batch)
         self.chunk_len, self.max_batch = int(chunk_len), self.ctx.max_batch
-        sd = self.model.state_dict()
+        sd = model.state_dict()
         self.shapes = [tuple(sd[k].shape) for k in self.keys]
-        self._begin(np.concatenate([sd[k].detach().to(torch.float32).cpu().numpy().ravel() for k in self.keys]))
+        self._begin([sd[k].detach().to(torch.float32).cpu().numpy() for k in self.keys])
         self.steps = 0
-
-    def _begin(self, flat):
-        self.ctx.top_train_begin(self.layers, flat)
 
     def _live(self):
         if self.ctx is None or self.model._ctx is not self.ctx:
@@ -124,26 +70,17 @@ class TopTrainer:
                              % (sig.shape[0], sig.shape[1], self.max_batch, self.chunk_len))
         return sig
 
-    def grad(self, batch, targets, lengths):
-        """The gradient of a (N,1,L) batch, left unclipped on the device -> (mean loss, gradient norm); no update."""
-        return self.ctx.top_train_grad(self._signal(batch), targets, lengths)
-
     def step(self, batch, targets, lengths, lr):
-        """One optimiser step at learning rate lr -> (mean loss before the step, gradient norm before clipping)."""
-        out = self.ctx.top_train_step(self._signal(batch), targets, lengths, lr)
+        """One optimiser step on a (N,1,L) batch with its (N,Lt) label rows and (N,) lengths at learning rate lr ->
+        (mean loss before the step, gradient norm before clipping)."""
+        out = self._step(self._signal(batch), targets, lengths, lr)
         self.steps += 1
         return out
 
     def weights(self):
         """The master weights: key -> float32 array in the tensor's own shape."""
         self._live()
-        flat = self.ctx.top_get_weights()
-        out, at = OrderedDict(), 0
-        for k, shape in zip(self.keys, self.shapes):
-            size = int(np.prod(shape))
-            out[k] = flat[at:at + size].reshape(shape).copy()
-            at += size
-        return out
+        return OrderedDict((k, np.array(a).reshape(shape)) for k, a, shape in zip(self.keys, self._masters(), self.shapes))
 
     def state_dict(self):
         """The model's state dict with the trained tensors replaced by the masters."""
@@ -153,45 +90,87 @@ class TopTrainer:
         return sd
 
     def publish(self):
-        """The masters go into the model's own parameters, in place, and into the live context's inference forms: from here on
-        validate_chunks, basecall_chunks and the model's forward compute with the trained layers."""
+        """The masters go into the model's own parameters, in place, and -- where the step has not put them there already --
+        into the live context's inference forms: from here on validate_chunks, basecall_chunks and the model's forward
+        compute with the trained layers."""
         trained = self.weights()
         own = self.model.state_dict(keep_vars=True)
         with torch.no_grad():
             for k, a in trained.items():
                 own[k].copy_(torch.from_numpy(a))
-        # the live context, not Model.load_state_dict (which would drop it, and the trainer's state with it)
-        self.ctx.load_state_dict({k: v.detach().to(torch.float32).cpu().numpy() for k, v in self.model.state_dict().items()})
+        if self.reloads:
+            # the live context, not Model.load_state_dict (which would drop it, and the trainer's state with it)
+            self.ctx.load_state_dict({k: v.detach().to(torch.float32).cpu().numpy() for k, v in self.model.state_dict().items()})
 
     def close(self):
         """End the run: publish, then free the trainer's device state."""
         if self.ctx is None:
             return
         self.publish()
-        self.ctx.top_train_end()
+        self._end()
         self.ctx = None
 
 
-CONV_KEYS = tuple("encoder.%d.conv.%s" % (n, k) for n in range(3) for k in ("weight", "bias"))
+class HeadTrainer(Trainer):
+    # the step re-packs the head on the device: the live context already computes with the masters
+    reloads = False
+
+    def _keys(self):
+        return [W_KEY, B_KEY]
+
+    def _begin(self, arrays):
+        self.ctx.head_train_begin(*arrays)
+
+    def _step(self, sig, targets, lengths, lr):
+        return self.ctx.head_train_step(sig, targets, lengths, lr)
+
+    def _end(self):
+        self.ctx.head_train_end()
+
+    def _masters(self):
+        return self.ctx.head_get_weights()
 
 
-def full_keys():
-    """The state-dict keys a FullTrainer trains, in the order of csrc/xb_conv_plan.h and xb_top_plan.h: all 28."""
-    return list(CONV_KEYS) + top_keys(5)
+class TopTrainer(Trainer):
+
+    def __init__(self, model, layers, chunk_len, batch):
+        self.layers = int(layers)
+        super().__init__(model, chunk_len, batch)
+
+    def _keys(self):
+        if not 1 <= self.layers <= 5:
+            raise ValueError("%d unfrozen LSTM layers: 1 .. 5 can be trained (the convolutions stay frozen)" % self.layers)
+        return top_keys(self.layers)
+
+    def _begin(self, arrays):
+        self.ctx.top_train_begin(self.layers, np.concatenate([a.ravel() for a in arrays]))
+
+    def _step(self, sig, targets, lengths, lr):
+        return self.ctx.top_train_step(sig, targets, lengths, lr)
+
+    def _end(self):
+        self.ctx.top_train_end()
+
+    def grad(self, batch, targets, lengths):
+        """The gradient of a (N,1,L) batch, left unclipped on the device -> (mean loss, gradient norm); no update."""
+        return self.ctx.top_train_grad(self._signal(batch), targets, lengths)
+
+    def _masters(self):
+        sizes = [int(np.prod(shape)) for shape in self.shapes]
+        return np.split(self.ctx.top_get_weights(), np.cumsum(sizes)[:-1])
 
 
 class FullTrainer(TopTrainer):
 
     def __init__(self, model, chunk_len, batch):
-        last = model.encoder[-1]
-        if getattr(last, "scale", None) is None or not float(last.scale) > 0:
-            raise NotImplementedError("the trainer needs the head's scale (scores = scale * tanh(Wx + b)); this model has none")
-        keys = list(model.state_dict())
+        super().__init__(model, 5, chunk_len, batch)
+
+    def _keys(self):
+        keys = list(self.model.state_dict())
         if keys != full_keys():
             raise NotImplementedError("the trainer of every layer takes rnn_encoder's three convolutions, five LSTM layers and head; "
                                       "this model's state dict has other keys")
-        self.model, self.layers = model, 5
-        self._open(keys, chunk_len, batch)
+        return keys
 
-    def _begin(self, flat):
-        self.ctx.full_train_begin(flat)
+    def _begin(self, arrays):
+        self.ctx.full_train_begin(np.concatenate([a.ravel() for a in arrays]))

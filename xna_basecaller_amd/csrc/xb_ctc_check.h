@@ -1,5 +1,5 @@
-// xb_ctc_check.h -- what the host-pointer forms of the validation loss (xb_ctc_loss, xb_validate_chunks) check of the labels
-// before anything is staged: plain host code without a HIP dependency (tools/ctc_check_main.cpp runs it on its own).
+// xb_ctc_check.h -- what every host form that takes label rows checks of them before anything is staged (label_batch_check,
+// xb_ctx.h): plain host code without a HIP dependency (tools/ctc_check_main.cpp runs it on its own).
 #pragma once
 #include <stdint.h>
 #include <stdio.h>

@@ -1,11 +1,12 @@
 // xb_ctx.h -- the context behind the C ABI, shared by the translation units that implement it: xb_api.hip (context lifetime, weight
 // upload, the execution of the encoder's plans, decode, pairing, the host pipeline, and the housekeeping every entry point
-// shares: the call prologue `enter`, the status words), xb_api_data.hip (the ctc-data tools), xb_head.hip (the head's gradient
-// and trainer), xb_lstm_train.hip (the training recurrence), xb_train_gemm.hip (the fp32 products of training), xb_conv_train.hip (the convolutions' training) and xb_top.hip (the
+// shares: the call prologue `enter`, the status words), xb_api_data.hip (the ctc-data tools and the losses), xb_head.hip (the
+// head's gradient and trainer, and the step tail every trainer ends in), xb_lstm_train.hip (the training recurrence), xb_train_gemm.hip (the fp32 products of training), xb_conv_train.hip (the convolutions' training) and xb_top.hip (the
 // trainers of the head with the top LSTM layers, and of every layer); xb_comm.hip
 // reaches a context through the C ABI and xb_internal_defer_after only.  The host arithmetic xb_api.hip acts on lives in three headers without HIP that are
 // checked on their own: xb_schedule.h (the knobs and the planner of the encoder schedule), xb_pack.h (the forms a weight
-// tensor is uploaded in) and xb_status.h (the device status words).  Private to csrc/.
+// tensor is uploaded in) and xb_status.h (the device status words).  Below the context: `grow`, the view of its one staging
+// buffer (Staging) and the label batch every loss and training call takes (label_batch_check, LabelBatch).  Private to csrc/.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,6 +21,7 @@
 #include <vector>
 
 #include "../../include/xna_basecaller.h"
+#include "xb_ctc_check.h"
 #include "xb_internal.h"
 #include "xb_pack.h"
 #include "xb_schedule.h"
@@ -235,8 +237,9 @@ struct xb_ctx {
     const float *last_scores = nullptr;         // the blank-less scores (T, last_n, ld_nb) of the most recent basecall pass, until the
     int last_n = 0;                             // next encoder run (xb_validate_chunks reads them where they lie)
 
-    // The device staging of the ctc-data tools' host-pointer forms (xb_api_data.hip, Staging): one buffer for all of them --
-    // each returns synchronised, so no two are ever live at once.  Grows with the calls; lives as long as the context.
+    // The device staging of every host-pointer form that needs some (Staging, below): the ctc-data tools, the losses,
+    // xb_head_grad, and the label batch of the trainers' steps.  One buffer for all of them -- each returns synchronised, so no
+    // two are ever live at once.  Grows with the calls; lives as long as the context.
     DevBuf staging;
 
     // template mapper (xb_map_templates): the library last passed in (host copy and its device image: codes, offsets, the
@@ -292,17 +295,17 @@ struct xb_ctx {
     } ctcgrad;
 
     // The head's gradient and trainer (xb_head.hip).  part: the slabs' partial sums of one launch of xb_head_grad (bounded by
-    // XB_HEAD_SCRATCH_MB); small: max |dY| word, the norm's partial sums and result; stage: the host forms' staging.  While a
-    // trainer is open (xb_head_train_begin .. _end): the fp32 master weights, AdamW's moments and the gradient in one buffer
-    // (W, b, mW, mb, vW, vb, dW, db), the batch's score gradient, labels and losses, and the step count.  part, small and stage
-    // live as long as the context; the trainer's three from xb_head_train_begin / _step to close() (xb_head_train_end).
+    // XB_HEAD_SCRATCH_MB); small: max |dY| word, the norm's partial sums and result.  While a trainer is open
+    // (xb_head_train_begin .. _end): the fp32 master weights, AdamW's moments and the gradient in one buffer (W, b, mW, mb, vW,
+    // vb, dW, db), the batch's score gradient, and the step count; a step's labels and losses lie in `staging`.  part and small
+    // live as long as the context; the trainer's two from xb_head_train_begin / _step to close() (xb_head_train_end).
     struct HeadState {
-        DevBuf part, small, stage, train, grad, labels;
+        DevBuf part, small, train, grad;
         bool open = false;
         long step = 0;
         void close()
         {
-            train.release(); grad.release(); labels.release();
+            train.release(); grad.release();
             open = false;
             step = 0;
         }
@@ -319,18 +322,18 @@ struct xb_ctx {
     } convtrain;
     // The trainer of the head and the top L LSTM layers (xb_top.hip), open from xb_top_train_begin to _end.  train: p, g, m, v in
     // the layout of xb::top_plan, four strides; small: the norm word (64 floats), the layers' summed biases, one transposed
-    // weight; act: the activations of a step of `rows` = T n rows, allocated by the first step and grown with the batch; labels:
-    // the batch's labels, lengths and losses.  full (xb_full_train_begin, L = 5): the six conv tensors lie in front of the LSTM
+    // weight; act: the activations of a step of `rows` = T n rows, allocated by the first step and grown with the batch; a
+    // step's labels and losses lie in `staging`.  full (xb_full_train_begin, L = 5): the six conv tensors lie in front of the LSTM
     // section in each of p, g, m, v, and the conv stack's activations (xb_conv_plan.h) behind the others in act.
     struct TopState {
-        DevBuf train, small, act, labels;
+        DevBuf train, small, act;
         bool open = false, full = false;
         int L = 0;
         long step = 0;
         size_t rows = 0;                        // rows the activations were last laid out for (0: no step yet)
         void close()
         {
-            train.release(); small.release(); act.release(); labels.release();
+            train.release(); small.release(); act.release();
             open = full = false;
             L = 0; step = 0; rows = 0;
         }
@@ -358,6 +361,57 @@ inline int grow(xb_ctx *ctx, DevBuf *b, size_t bytes)
     XB_HIP(ctx, hipStreamSynchronize(ctx->stream));                     // nothing in flight reads the old buffer
     return b->alloc(ctx, bytes);
 }
+
+// The device staging of a host-pointer form: typed pieces of xb_ctx::staging in the order they are taken, each 256-byte
+// aligned.  `used` is their total; once ready() has grown the buffer to it, a piece converts to its device pointer.  The buffer
+// is the context's only one, so it relies on this: whoever takes pieces returns synchronised (xb_synchronize) -- no two uses
+// are ever live at once, and nothing in flight reads the buffer when the next call lays it out anew.
+struct Staging {
+    xb_ctx *ctx;
+    size_t used = 0;
+    template <typename Tp> struct Piece {
+        const DevBuf *buf; size_t at;
+        operator Tp *() const { return reinterpret_cast<Tp *>(static_cast<uint8_t *>(buf->p) + at); }
+    };
+    template <typename Tp> Piece<Tp> take(size_t count)
+    {
+        const size_t at = used;
+        used += (count * sizeof(Tp) + 255) & ~(size_t)255;
+        return {&ctx->staging, at};
+    }
+    int ready() { return grow(ctx, &ctx->staging, used); }
+};
+
+// What every loss and training call refuses of a label batch (n rows of Lt labels, their lengths) before any device work: a
+// width whose positions the lattice kernels do not hold, then -- where the rows are on the host (targets != null) -- the first
+// length or label out of range.  The _dev forms pass null: their rows are validated by the kernel, on the device.
+inline int label_batch_check(xb_ctx *ctx, const char *who, const uint8_t *targets, int n, int Lt, const int32_t *lengths)
+{
+    const int np = Lt - (ctx->cfg.state_len - 1);
+    if (np < 1 || np > xb::ctc_max_positions())
+        return fail(ctx, XB_ERR_INVALID, "%s: target width %d gives %d positions, supported: 1..%d", who, Lt, np, xb::ctc_max_positions());
+    char msg[160];
+    if (targets && xb::ctc_labels_check(targets, n, Lt, lengths, ctx->cfg.state_len, ctx->cfg.n_base, msg, sizeof msg))
+        return fail(ctx, XB_ERR_INVALID, "%s: %s", who, msg);
+    return XB_OK;
+}
+
+// A label batch on the device: the targets, the lengths and the chunks' losses as three pieces of a Staging, taken in this
+// order.  upload() follows the Staging's ready().
+struct LabelBatch {
+    size_t n, Lt;
+    Staging::Piece<uint8_t> targets;
+    Staging::Piece<int32_t> len;
+    Staging::Piece<float> loss;
+    LabelBatch(Staging &st, int n_, int Lt_)
+        : n((size_t)n_), Lt((size_t)Lt_), targets(st.take<uint8_t>(n * Lt)), len(st.take<int32_t>(n)), loss(st.take<float>(n)) {}
+    int upload(xb_ctx *ctx, const uint8_t *h_targets, const int32_t *h_lengths) const
+    {
+        XB_HIP(ctx, hipMemcpyAsync(targets, h_targets, n * Lt, hipMemcpyHostToDevice, ctx->stream));
+        XB_HIP(ctx, hipMemcpyAsync(len, h_lengths, n * 4, hipMemcpyHostToDevice, ctx->stream));
+        return XB_OK;
+    }
+};
 
 // what follows the launches of an entry point `who`: a launch the runtime refused
 inline int launched(const xb_ctx *ctx, const char *who)

@@ -4,7 +4,6 @@
 // xb_ctc_loss_grad.  The contracts are in the public header.  This translation unit is built without contraction: AdamW and the
 // operand arithmetic of xb_head_grad are restated operation by operation in tests/adamw_ref.py and tests/headgrad_ref.py.
 #include "xb_ctx.h"
-#include "xb_ctc_check.h"
 #include "xb_head_split.h"
 #include "xb_head_train.h"
 
@@ -370,6 +369,40 @@ void adamw_scalars(double lr, long step, float *decay, float *step_size, float *
     *bc2_sqrt = (float)std::sqrt(1.0 - std::pow(0.999, (double)step));
 }
 
+// ---- the tail every trainer's step shares (xb_head_train.h) ----
+
+int train_call_enter(xb_ctx *ctx, const char *who, const float *signal, int n, const uint8_t *targets, int Lt, const int32_t *lengths,
+                     bool step, float lr, const float *loss, const float *grad_norm)
+{
+    if (int rc = check_ready(ctx, n)) return rc;
+    if (!signal || !targets || !lengths || !loss || !grad_norm) return fail(ctx, XB_ERR_INVALID, "%s: null argument", who);
+    if (step && (!(lr >= 0.0f) || !std::isfinite(lr))) return fail(ctx, XB_ERR_INVALID, "%s: learning rate %g", who, (double)lr);
+    if (int rc = label_batch_check(ctx, who, targets, n, Lt, lengths)) return rc;
+    return enter(ctx, false);
+}
+
+int train_read_back(xb_ctx *ctx, const float *d_norm, const float *d_loss, int n, float *norm, float *mean_loss)
+{
+    std::vector<float> losses((size_t)n);
+    XB_HIP(ctx, hipMemcpyAsync(norm, d_norm, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    XB_HIP(ctx, hipMemcpyAsync(losses.data(), d_loss, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = xb_synchronize(ctx)) return rc;
+    double sum = 0.0;
+    for (float l : losses) sum += (double)l;
+    *mean_loss = (float)(sum / (double)n);
+    return XB_OK;
+}
+
+int train_update(xb_ctx *ctx, const char *who, float norm, float lr, long step, float *p, float *g, float *m, float *v, size_t len)
+{
+    if (!std::isfinite(norm)) return fail(ctx, XB_ERR_DEVICE, "%s: the gradient's norm is not finite; the weights are unchanged", who);
+    // clip_grad_norm_(max_norm = 2.0): the factor in double from the fp32 norm, rounded once
+    const float clip = (float)std::min(1.0, 2.0 / ((double)norm + 1e-6));
+    float decay, step_size, bc2_sqrt;
+    adamw_scalars((double)lr, step, &decay, &step_size, &bc2_sqrt);
+    return adamw_run(ctx, p, g, m, v, len, clip, decay, step_size, bc2_sqrt);
+}
+
 extern "C" {
 
 XB_API int xb_head_grad_dev(xb_ctx *ctx, const float *d_y, const float *d_dy, const uint16_t *d_x_hi, const uint16_t *d_x_lo, int64_t rows,
@@ -395,13 +428,12 @@ XB_API int xb_head_grad(xb_ctx *ctx, const float *y, const float *dy, const uint
     if (int rc = head_operand(ctx, "xb_head_grad", x_hi, x_lo, rows)) return rc;
     if (int rc = enter(ctx, false)) return rc;
     const size_t O = (size_t)ctx->O, F = (size_t)ctx->cfg.features, M = (size_t)rows;
-    const size_t yb = (M * O * sizeof(float) + 255) & ~(size_t)255, xb_ = x_hi ? (M * F * 2 + 255) & ~(size_t)255 : 0;
-    const size_t wb = (O * F * sizeof(float) + 255) & ~(size_t)255, bb = (O * sizeof(float) + 255) & ~(size_t)255;
-    if (int rc = grow(ctx, &ctx->head.stage, 2 * yb + 2 * xb_ + wb + bb)) return rc;
-    char *base = static_cast<char *>(ctx->head.stage.p);
-    float *d_y = reinterpret_cast<float *>(base), *d_dy = reinterpret_cast<float *>(base + yb);
-    half_t *d_xh = x_hi ? reinterpret_cast<half_t *>(base + 2 * yb) : nullptr, *d_xl = x_hi ? reinterpret_cast<half_t *>(base + 2 * yb + xb_) : nullptr;
-    float *d_dw = reinterpret_cast<float *>(base + 2 * yb + 2 * xb_), *d_db = reinterpret_cast<float *>(base + 2 * yb + 2 * xb_ + wb);
+    Staging st{ctx};
+    const auto d_y = st.take<float>(M * O), d_dy = st.take<float>(M * O);
+    const auto s_xh = st.take<half_t>(x_hi ? M * F : 0), s_xl = st.take<half_t>(x_hi ? M * F : 0);      // without X: two empty pieces
+    const auto d_dw = st.take<float>(O * F), d_db = st.take<float>(O);
+    if (int rc = st.ready()) return rc;
+    half_t *d_xh = x_hi ? (half_t *)s_xh : nullptr, *d_xl = x_hi ? (half_t *)s_xl : nullptr;
     XB_HIP(ctx, hipMemcpyAsync(d_y, y, M * O * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     XB_HIP(ctx, hipMemcpyAsync(d_dy, dy, M * O * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     if (x_hi) {
@@ -496,49 +528,28 @@ XB_API int xb_head_train_step(xb_ctx *ctx, const float *signal, int n, const uin
 {
     if (!ctx) return XB_ERR_INVALID;
     if (!ctx->head.open) return fail(ctx, XB_ERR_STATE, "xb_head_train_step: no trainer is open; call xb_head_train_begin first");
-    if (int rc = check_ready(ctx, n)) return rc;
-    if (!signal || !targets || !lengths || !loss || !grad_norm) return fail(ctx, XB_ERR_INVALID, "xb_head_train_step: null argument");
-    if (!(lr >= 0.0f) || !std::isfinite(lr)) return fail(ctx, XB_ERR_INVALID, "xb_head_train_step: learning rate %g", (double)lr);
-    const int np = Lt - (ctx->cfg.state_len - 1);
-    if (np < 1 || np > xb::ctc_max_positions())
-        return fail(ctx, XB_ERR_INVALID, "xb_head_train_step: target width %d gives %d positions, supported: 1..%d", Lt, np, xb::ctc_max_positions());
-    char msg[160];
-    if (xb::ctc_labels_check(targets, n, Lt, lengths, ctx->cfg.state_len, ctx->cfg.n_base, msg, sizeof msg))
-        return fail(ctx, XB_ERR_INVALID, "xb_head_train_step: %s", msg);
-    if (int rc = enter(ctx, false)) return rc;
+    if (int rc = train_call_enter(ctx, "xb_head_train_step", signal, n, targets, Lt, lengths, true, lr, loss, grad_norm)) return rc;
     const size_t N = (size_t)n, O = (size_t)ctx->O, OF = O * ctx->cfg.features, T = (size_t)ctx->T;
-    const size_t lab = (N * Lt + 255) & ~(size_t)255, len = (N * 4 + 255) & ~(size_t)255;
     if (int rc = grow(ctx, &ctx->head.grad, T * N * O * sizeof(float))) return rc;
-    if (int rc = grow(ctx, &ctx->head.labels, lab + 2 * len)) return rc;
+    Staging st{ctx};
+    const LabelBatch lb(st, n, Lt);
+    if (int rc = st.ready()) return rc;
     if (int rc = small_ready(ctx)) return rc;
-    uint8_t *d_targets = static_cast<uint8_t *>(ctx->head.labels.p);
-    int32_t *d_len = reinterpret_cast<int32_t *>(d_targets + lab);
-    float *d_loss = reinterpret_cast<float *>(d_targets + lab + len), *d_grad = static_cast<float *>(ctx->head.grad.p);
+    float *d_grad = static_cast<float *>(ctx->head.grad.p);
     const TrainBuf t(ctx);
     XB_HIP(ctx, hipMemcpyAsync(ctx->d_signal, signal, sizeof(float) * N * ctx->cfg.chunk_len, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(d_targets, targets, N * Lt, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(d_len, lengths, N * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = lb.upload(ctx, targets, lengths)) return rc;
     if (int rc = encoder_run(ctx, ctx->d_signal, n, ctx->scores, ctx->O)) return rc;
-    if (int rc = ctc_grad_run(ctx, "xb_head_train_step", ctx->scores, ctx->T, n, 0, ctx->O, d_targets, Lt, d_len, 0.0f, 1, d_loss, d_grad)) return rc;
+    if (int rc = ctc_grad_run(ctx, "xb_head_train_step", ctx->scores, ctx->T, n, 0, ctx->O, lb.targets, Lt, lb.len, 0.0f, 1, lb.loss, d_grad)) return rc;
     if (int rc = head_grad_run(ctx, "xb_head_train_step", ctx->scores, d_grad, nullptr, nullptr, (int64_t)(T * N), t.g, t.g + OF)) return rc;
     if (int rc = grad_norm_run(ctx, t.g, OF, t.g + OF, O, small_norm(ctx))) return rc;
-    std::vector<float> losses(N);
-    float norm = 0.0f;
-    XB_HIP(ctx, hipMemcpyAsync(&norm, small_norm(ctx), sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(losses.data(), d_loss, N * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (int rc = xb_synchronize(ctx)) return rc;
-    if (!std::isfinite(norm)) return fail(ctx, XB_ERR_DEVICE, "xb_head_train_step: the gradient's norm is not finite; the weights are unchanged");
-    // clip_grad_norm_(max_norm = 2.0): the factor in double from the fp32 norm, rounded once
-    const float clip = (float)std::min(1.0, 2.0 / ((double)norm + 1e-6));
-    float decay, step_size, bc2_sqrt;
-    adamw_scalars((double)lr, ctx->head.step + 1, &decay, &step_size, &bc2_sqrt);
-    if (int rc = adamw_run(ctx, t.p, t.g, t.m, t.v, OF, clip, decay, step_size, bc2_sqrt)) return rc;
-    if (int rc = adamw_run(ctx, t.p + OF, t.g + OF, t.m + OF, t.v + OF, O, clip, decay, step_size, bc2_sqrt)) return rc;
+    float norm = 0.0f, mean = 0.0f;
+    if (int rc = train_read_back(ctx, small_norm(ctx), lb.loss, n, &norm, &mean)) return rc;
+    // (W | b) are contiguous in each of p, g, m, v and the update is elementwise: one launch over both
+    if (int rc = train_update(ctx, "xb_head_train_step", norm, lr, ctx->head.step + 1, t.p, t.g, t.m, t.v, t.len)) return rc;
     if (int rc = repack_run(ctx, t.p, t.p + OF)) return rc;
     ++ctx->head.step;
-    double sum = 0.0;
-    for (size_t i = 0; i < N; ++i) sum += (double)losses[i];
-    *loss = (float)(sum / (double)N);
+    *loss = mean;
     *grad_norm = norm;
     return xb_synchronize(ctx);
 }

@@ -9,7 +9,6 @@
 // front of and behind the plan's.  The contracts are in the public header.  Built without contraction, as the translation
 // units it chains.
 #include "xb_ctx.h"
-#include "xb_ctc_check.h"
 #include "xb_head_train.h"
 #include "xb_top_plan.h"
 #include "xb_train_gemm.h"
@@ -217,51 +216,29 @@ int top_call(xb_ctx *ctx, const char *who, const float *signal, int n, const uin
 {
     if (!ctx) return XB_ERR_INVALID;
     if (!ctx->top.open) return fail(ctx, XB_ERR_STATE, "%s: no trainer is open; call xb_top_train_begin first", who);
-    if (int rc = check_ready(ctx, n)) return rc;
-    if (!signal || !targets || !lengths || !loss || !grad_norm) return fail(ctx, XB_ERR_INVALID, "%s: null argument", who);
-    if (step && (!(lr >= 0.0f) || !std::isfinite(lr))) return fail(ctx, XB_ERR_INVALID, "%s: learning rate %g", who, (double)lr);
-    const int np = Lt - (ctx->cfg.state_len - 1);
-    if (np < 1 || np > xb::ctc_max_positions())
-        return fail(ctx, XB_ERR_INVALID, "%s: target width %d gives %d positions, supported: 1..%d", who, Lt, np, xb::ctc_max_positions());
-    char msg[160];
-    if (xb::ctc_labels_check(targets, n, Lt, lengths, ctx->cfg.state_len, ctx->cfg.n_base, msg, sizeof msg))
-        return fail(ctx, XB_ERR_INVALID, "%s: %s", who, msg);
-    if (int rc = enter(ctx, false)) return rc;
+    if (int rc = train_call_enter(ctx, who, signal, n, targets, Lt, lengths, step, lr, loss, grad_norm)) return rc;
     const xb::TopPlan pl = plan_of(ctx);
     const size_t N = (size_t)n, rows = (size_t)ctx->T * N;
-    const size_t lab = (N * Lt + 255) & ~(size_t)255, len = (N * 4 + 255) & ~(size_t)255;
     if (grow(ctx, &ctx->top.act, act_floats(ctx, pl, rows) * sizeof(float))) {
         ctx->top.rows = 0;                      // the old activations went with the failed allocation
         return top_nomem(ctx, who, pl, rows);
     }
-    if (int rc = grow(ctx, &ctx->top.labels, lab + 2 * len)) return rc;
+    Staging st{ctx};
+    const LabelBatch lb(st, n, Lt);
+    if (int rc = st.ready()) return rc;
     ctx->top.rows = rows;
-    uint8_t *d_targets = static_cast<uint8_t *>(ctx->top.labels.p);
-    int32_t *d_len = reinterpret_cast<int32_t *>(d_targets + lab);
-    float *d_loss = reinterpret_cast<float *>(d_targets + lab + len);
     const TopBuf b(ctx, pl);
     XB_HIP(ctx, hipMemcpyAsync(ctx->d_signal, signal, sizeof(float) * N * ctx->cfg.chunk_len, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(d_targets, targets, N * Lt, hipMemcpyHostToDevice, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(d_len, lengths, N * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = top_grad_run(ctx, who, n, d_targets, Lt, d_len, d_loss)) return rc;
-    std::vector<float> losses(N);
-    float norm = 0.0f;
-    XB_HIP(ctx, hipMemcpyAsync(&norm, b.norm, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(losses.data(), d_loss, N * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (int rc = xb_synchronize(ctx)) return rc;
-    double sum = 0.0;
-    for (size_t i = 0; i < N; ++i) sum += (double)losses[i];
+    if (int rc = lb.upload(ctx, targets, lengths)) return rc;
+    if (int rc = top_grad_run(ctx, who, n, lb.targets, Lt, lb.len, lb.loss)) return rc;
+    float norm = 0.0f, mean = 0.0f;
+    if (int rc = train_read_back(ctx, b.norm, lb.loss, n, &norm, &mean)) return rc;
     if (step) {
-        if (!std::isfinite(norm)) return fail(ctx, XB_ERR_DEVICE, "%s: the gradient's norm is not finite; the weights are unchanged", who);
-        // clip_grad_norm_(max_norm = 2.0): the factor in double from the fp32 norm, rounded once
-        const float clip = (float)std::min(1.0, 2.0 / ((double)norm + 1e-6));
-        float decay, step_size, bc2_sqrt;
-        adamw_scalars((double)lr, ctx->top.step + 1, &decay, &step_size, &bc2_sqrt);
-        if (int rc = adamw_run(ctx, b.p, b.g, b.m, b.v, b.params, clip, decay, step_size, bc2_sqrt)) return rc;
+        if (int rc = train_update(ctx, who, norm, lr, ctx->top.step + 1, b.p, b.g, b.m, b.v, b.params)) return rc;
         ++ctx->top.step;
         if (int rc = xb_synchronize(ctx)) return rc;
     }
-    *loss = (float)(sum / (double)N);
+    *loss = mean;
     *grad_norm = norm;
     return XB_OK;
 }
