@@ -24,7 +24,18 @@ CASES = [Case(1, 1, 4, 5, 1, 23, False), Case(3, 4, 16, 5, 1, 23, False),       
          Case(5, 16, 80, 9, 3, 50, False),                                           # another window and stride, a ragged Cout
          Case(2, 16, 768, 19, 5, 40, False),                                         # the real Cout
          Case(6, 16, 32, 19, 5, 1000, False), Case(3, 16, 32, 19, 5, 1001, False),   # 1200 rows: past xb_wgrad_f32's 1024-row block
-         Case(3, 4, 16, 5, 1, 23, True)]                                             # gradients of 1e-9 .. 1e-4
+         Case(3, 4, 16, 5, 1, 23, True),                                             # gradients of 1e-9 .. 1e-4
+         # appended (the tests that index this list keep their cases) -- the narrow route's three templates (CO = 4, 8, 16) and a
+         # Cout below its template's CO: 8 of 8, 5 of 8, 1 of 4, 12 of 16 at window 1
+         Case(2, 4, 8, 5, 1, 300, False), Case(3, 3, 5, 3, 1, 23, False), Case(2, 1, 1, 7, 1, 40, False), Case(2, 8, 12, 1, 1, 300, False),
+         # the narrow route at even windows, Lout = Lin + 1: the backward's tile count comes from Lout (257: 2 tiles a chunk where
+         # Lin gives 1; 513: 3 against 2)
+         Case(2, 2, 6, 6, 1, 256, False), Case(2, 4, 16, 4, 1, 512, False),
+         Case(2, 16, 32, 8, 2, 41, False),                                           # the wide route at an even window
+         Case(2, 16, 32, 3, 8, 50, False), Case(3, 16, 32, 1, 3, 40, False),         # stride above the window: 60 % and 65 % of dx are exact zeros
+         Case(2, 16, 32, 31, 8, 100, False), Case(2, 16, 32, 31, 8, 8, False),       # the widest window; Lout 1
+         Case(2, 16, 32, 31, 1, 33, False), Case(2, 16, 32, 1, 1, 40, False),        # window 31 and window 1 at stride 1 (16 channels in: wide)
+         Case(2, 16, 32, 9, 6, 383, False)]
 
 
 def case_id(c):

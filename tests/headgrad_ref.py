@@ -14,7 +14,12 @@ K_BOUND is 4 x the largest ratio measured on the MI355X over tests/test_gpu_head
 import numpy as np
 
 # MI355X, tests/test_gpu_headgrad.py: the largest |device - float64| / bound over all its cases is 7.94 (features 384, 64 columns,
-# one row -- with a single row nothing averages, the ratio is the fp32 rounding of dZ and of the result); 4099 rows give 0.6 - 0.8
+# one row -- with a single row nothing averages, the ratio is the fp32 rounding of dZ and of the result); 4099 rows give 0.6 - 0.8.
+# That was measured at 64, 125 and 1296 columns, and K_MEASURED and K_BOUND stay what it gave.  The widths added since (216, 625,
+# 1024, 3125, 4096 columns) reach 5.8 - 8.2, but for 16.3 at one row, 1024 columns, features 96: head_grad_kernel above, whose sums
+# are float64, gives 15.7 there, so it is the operands, not the accumulation -- one of that row's 1024 dZ values lies 2^18.4 below the call's
+# largest, its lo part (4.2e-7 after the prescale) falls among fp16's subnormals and leaves 14.7 x 2^-24 of dZ behind, and with one
+# row no other term covers it: all 96 elements of that output row, and no other, exceed 8.
 K_MEASURED = 7.94
 K_BOUND = 4 * K_MEASURED
 

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import convtrain_ref as CR
+import train_geometry_cases as G
 from lstm_train_ref import rel
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,6 +36,20 @@ def test_restatement_against_torch_float64(case):
         assert got.shape == ref[name].shape and np.abs(ref[name]).max() > 0, name
         assert rel(got, ref[name]) <= 1e-12, (name, rel(got, ref[name]))
     assert np.array_equal(CR.untnc(CR.tnc(z)), z) and CR.tnc(z).shape == (z.shape[2], case.n, case.Cout)
+
+
+@pytest.mark.parametrize("case,zeros", [(CR.Case(2, 16, 32, 3, 8, 50, False), 0.60), (CR.Case(3, 16, 32, 1, 3, 40, False), 0.65)], ids=lambda v: CR.case_id(v) if isinstance(v, tuple) else None)
+def test_a_stride_above_the_window_leaves_exact_zeros_in_dx(case, zeros):
+    """The positions no window covers: what the device test's check of dx's zeros (tests/test_gpu_convtrain.py: held) acts on."""
+    assert case in CR.CASES and case.stride > case.K
+    x, w, b, dy = CR.draw(case)
+    z, _ = CR.forward(x, w, b, case.stride)
+    dx = CR.backward(dy, x, z, w, case.stride)[0]
+    t = np.arange(z.shape[2])[:, None] * case.stride + np.arange(case.K)[None, :] - case.K // 2
+    covered = np.zeros(case.Lin, bool)
+    covered[t[(t >= 0) & (t < case.Lin)]] = True
+    assert (dx[:, :, ~covered] == 0).all() and (dx[:, :, covered] != 0).all() and abs((dx == 0).mean() - zeros) < 1e-12
+    assert (CR.torch_run(x, w, b, dy, case.stride, torch.float64)["dx"][:, :, ~covered] == 0).all()
 
 
 def run32(x, w, b, dy, stride):
@@ -92,7 +107,8 @@ def test_plan_check_program_passes_under_the_sanitizers(plan_check):
     assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout + out.stderr
 
 
-@pytest.mark.parametrize("chunk,F,W,S,n", [(200, 32, 19, 5, 6), (1000, 32, 19, 5, 16), (3600, 768, 19, 5, 98), (4000, 96, 9, 3, 384), (23, 48, 19, 5, 3)])
+@pytest.mark.parametrize("chunk,F,W,S,n", [(200, 32, 19, 5, 6), (1000, 32, 19, 5, 16), (3600, 768, 19, 5, 98), (4000, 96, 9, 3, 384), (23, 48, 19, 5, 3)]
+                         + [(c.chunk, c.F, c.W, c.S, c.n) for c in G.CASES])        # the geometries the trainers run at on the device
 def test_plan_against_its_restatement(plan_check, chunk, F, W, S, n):
     out = subprocess.run([plan_check] + [str(v) for v in (chunk, F, W, S, n)], capture_output=True, text=True, check=True).stdout.split("\n")
     want = CR.table(chunk, F, W, S, n)

@@ -71,7 +71,8 @@ def test_oracle_ctc_rejects_bad_lengths():
 
 # ---------------------------------------------------------------------------------------------------------------------
 GPU_CASES = [(4, 37, 3, 9, 3), (5, 120, 5, 40, 3), (6, 200, 7, 130, 3), (6, 64, 2, 3, 3), (5, 90, 4, 300, 3),
-             (4, 64, 3, 12, 5), (5, 65, 3, 11, 4), (6, 63, 3, 9, 2), (4, 40, 3, 7, 2)]
+             (4, 64, 3, 12, 5), (5, 65, 3, 11, 4), (6, 63, 3, 9, 2), (4, 40, 3, 7, 2),
+             (4, 33, 3, 10, 4), (5, 41, 3, 8, 2)]                # with these, every (n_base, state_len) pair of tests/pairs.py
 
 
 @pytest.mark.gpu

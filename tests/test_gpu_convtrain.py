@@ -6,7 +6,9 @@ runs a float32 numpy stand-in through the same cases and the same rule on the CP
 
   cases      convtrain_ref.CASES: both routes, edges, Lin < K, a stride that does not divide Lin, a ragged and the real Cout, dw over
              several workgroups' partials (narrow) and past xb_wgrad_f32's 1024-row block (wide), gradients of 1e-9 .. 1e-4; the
-             wide cases with tnc = 0 and 1
+             narrow kernels' three templates with Cout at and below the template's width; even windows on both routes (narrow:
+             the backward's tile count comes from Lout = Lin + 1); strides above the window (dx holds exact zeros, written as +0);
+             windows 1 and 31, Lout 1; the wide cases with tnc = 0 and 1
   bytes      dx = NULL leaves dw and db as they are; a chunk's z, y and dx are the same alone and inside a batch; a repeated call
              gives the same bytes
   refusals   every malformed argument is XB_ERR_INVALID, and nothing is written
@@ -80,6 +82,8 @@ def held(tag, got, ref, yards):
             failed.append((name, err, yard))
         if np.signbit(g[g == 0]).any():
             failed.append((name, "a zero written as -0"))
+        if name == "dx" and (g[r == 0] != 0).any():                     # a stride above the window: positions no window covers
+            failed.append((name, "a position no window covers is not zero"))
     assert not failed, failed
 
 

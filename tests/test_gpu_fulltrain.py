@@ -19,7 +19,7 @@ import torch
 
 import convtrain_dev as CD
 import toptrain_dev as D
-import toptrain_ref as TR
+import train_geometry_cases as G
 from conftest import encoder_shapes, seeded_state_dict
 from ctc_wide_cases import label_rows
 from lstm_train_ref import rel
@@ -82,23 +82,8 @@ def state(ctx, sd, n):
 
 
 def torch_chain(signal, tensors, dscores, dtype):
-    """The whole encoder from the signal to the scores and the gradients of all 28 tensors for a given d loss / d scores, from
-    torch.nn.functional.conv1d + silu, torch.nn.LSTM and Linear with autograd on the CPU."""
-    params = [torch.from_numpy(np.asarray(a)).to(dtype).clone().requires_grad_(True) for a in tensors]
-    x = torch.from_numpy(np.asarray(signal)).to(dtype)[:, None, :]
-    for i, stride in enumerate((1, 1, 5)):
-        w, b = params[2 * i], params[2 * i + 1]
-        x = torch.nn.functional.silu(torch.nn.functional.conv1d(x, w, b, stride=stride, padding=w.shape[2] // 2))
-    x = x.permute(2, 0, 1)
-    for i in range(5):
-        rnn = torch.nn.LSTM(F, F).to(dtype)
-        named = dict(zip(("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"), params[6 + 4 * i:10 + 4 * i]))
-        rev = TR.reverse_of(5, i)
-        y = torch.func.functional_call(rnn, named, (x.flip(0) if rev else x,))[0]
-        x = y.flip(0) if rev else y
-    scores = SCALE * torch.tanh(torch.nn.functional.linear(x, params[-2], params[-1]))
-    (scores * torch.from_numpy(np.asarray(dscores)).to(dtype)).sum().backward()
-    return dict(scores=scores.detach().numpy(), grads=[p.grad.numpy() for p in params])
+    """train_geometry_cases.torch_chain, the whole encoder in torch on the CPU, at this file's stride and scale."""
+    return G.torch_chain(signal, tensors, dscores, dtype, stride=5, scale=SCALE)
 
 
 @pytest.fixture(scope="module")

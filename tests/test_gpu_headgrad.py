@@ -5,10 +5,13 @@ against tests/headgrad_ref.py's float64 form.  K_BOUND = 4 x the largest ratio m
 file (headgrad_ref.K_MEASURED; every test prints its ratios), and tests/test_headgrad_host.py shows that a single fp16 product
 exceeds it on the CPU.  Shapes: features 32 / 96 / 384 (one, three, twelve k-tiles of the forward; a quarter, three quarters and
 three whole feature tiles here), heads of 64, 125 (ragged in both MFMA tile dimensions) and 1296 columns, rows 1, 21, 255, 256,
-257 (one k-tile short of, at and past two slabs) and 4099 (17 slabs); gradients of the magnitude a mean loss gives (1e-6 .. 1e-3),
+257 (one k-tile short of, at and past two slabs) and 4099 (17 slabs); the heads of the other (n_base, state_len) pairs -- 216, 625,
+1024, 3125 and 4096 columns -- at features 32 and 96 and rows 1, 21, 257 and 1000 (four slabs), under the same K_BOUND; gradients of the magnitude a mean loss gives (1e-6 .. 1e-3),
 one case with every |dY| < 2^-20, which fails without the prescale.  Also: columns of zeros in dY give exact zeros, two calls give
 the same bytes, a workspace bound that splits the call over output rows gives the same bytes and one that shortens the slab list
 stays within the bound, the context's own X is the explicit one bit for bit, and the refusals."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -20,6 +23,12 @@ pytestmark = pytest.mark.gpu
 SCALE = 5.0
 HEADS = {64: (4, 2), 125: (5, 2), 1296: (6, 3)}            # columns -> (n_base, state_len)
 ROWS = (1, 21, 255, 256, 257, 4099)
+# the widths of the other pairs a context takes: 4, 10, 16, 49 and 64 blocks of 64 output rows (3125: a ragged last block, and
+# rows of Y and dY that are not 16-byte aligned); at 1000 rows head_plan cuts the sum into four slabs at every width
+NEW_HEADS = {216: (6, 2), 625: (5, 3), 1024: (4, 4), 3125: (5, 4), 4096: (4, 5)}
+HEADS.update(NEW_HEADS)
+NEW_ROWS = (1, 21, 257, 1000)
+SHAPES = [(F, O) for O in (64, 125, 1296) for F in (32, 96, 384)] + [(F, O) for O in sorted(NEW_HEADS) for F in (32, 96)]
 
 
 def _context(F, O, chunk_len=100, n=1, precision=_lib.XB_PREC_MIXED, seed=3):
@@ -40,12 +49,21 @@ def _measure(ctx, a, what):
     return got, max(r)
 
 
-@pytest.mark.parametrize("O", sorted(HEADS))
-@pytest.mark.parametrize("F", [32, 96, 384])
+def _slabs(M, O, F, cu=256):
+    """nslabs of xb::head_plan (csrc/xb_head_split.h) under the default workspace bound."""
+    out = (ctypes.c_int64 * 10)()
+    _lib.load().xb_internal_head_plan(M, O, F, cu, None, out)
+    assert out[0] == 0
+    return out[2]
+
+
+@pytest.mark.parametrize("F,O", SHAPES, ids=["%d-%d" % s for s in SHAPES])
 def test_gradient_within_the_bound(F, O):
     ctx = _context(F, O)
     worst = {}
-    for M in ROWS:
+    if O in NEW_HEADS:                                                  # several slabs from 32 CUs up: 1000 rows are 32 k-tiles
+        assert _slabs(1000, O, F, cu=32) == _slabs(1000, O, F) == 4 and _slabs(257, O, F) == 2
+    for M in NEW_ROWS if O in NEW_HEADS else ROWS:
         a = H.inputs(M, O, F, seed=M + O + F, zero_cols=(0, O - 1) if M > 1 else ())
         (dw, db), worst["M=%d" % M] = _measure(ctx, a, "F=%d O=%d M=%d" % (F, O, M))
         if M > 1:

@@ -4,9 +4,11 @@
                        below 1 and a gradient of zeros among them
   xb_grad_norm_dev     1e-6 relative against float64
   xb_head_repack_dev   the three images and the bias equal xb::split_rows / xb::fragment_major (tests/host_logic.py) of the same
-                       floats byte for byte, at heads of 64, 125 and 1296 columns and features 32 and 768
+                       floats byte for byte, at heads of 64, 125, 216, 625, 1024, 1296, 3125 and 4096 columns and features 32
+                       and 768
   xb_head_train_step   bit-equal, in loss, norm, weights and images, to the step composed from the public entry points on a
-                       second context; a fresh context loaded with the trained floats encodes the same bytes; 30 steps on 32
+                       second context, at 256 columns and features 96, and two steps each at 3125 and 4096 columns and features 32;
+                       a fresh context loaded with the trained floats encodes the same bytes; 30 steps on 32
                        chunks with fixed label rows bring the loss down; the refusals"""
 import numpy as np
 import pytest
@@ -19,7 +21,7 @@ from xna_basecaller_amd import _lib
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
-HEADS = {64: (4, 2), 125: (5, 2), 256: (4, 3), 1296: (6, 3)}
+HEADS = {64: (4, 2), 125: (5, 2), 256: (4, 3), 1296: (6, 3), 216: (6, 2), 625: (5, 3), 1024: (4, 4), 3125: (5, 4), 4096: (4, 5)}
 W_KEY, B_KEY = "encoder.9.linear.weight", "encoder.9.linear.bias"
 
 
@@ -91,7 +93,7 @@ def _same_image(got, want, what):
         assert g.tobytes() == np.ascontiguousarray(w).tobytes(), (what, name)
 
 
-@pytest.mark.parametrize("O", [64, 125, 1296])
+@pytest.mark.parametrize("O", [64, 125, 1296, 216, 625, 1024, 3125, 4096])
 @pytest.mark.parametrize("F", [32, 768])
 def test_repack_is_the_host_packer_byte_for_byte(F, O):
     ctx, sd = _context(F, O)
@@ -112,10 +114,10 @@ def test_repack_is_the_host_packer_byte_for_byte(F, O):
 F_T, O_T, L_T, LT = 96, 256, 500, 24
 
 
-def _batch(n, seed):
+def _batch(n, seed, O=O_T, chunk_len=L_T):
     rng = np.random.default_rng(seed)
-    nb, sl = HEADS[O_T]
-    signal = rng.standard_normal((n, L_T)).astype(np.float32)
+    nb, sl = HEADS[O]
+    signal = rng.standard_normal((n, chunk_len)).astype(np.float32)
     lens = rng.integers(sl + 5, LT + 1, n).astype(np.int32)
     lens[0] = LT
     targets = np.zeros((n, LT), np.uint8)
@@ -149,26 +151,34 @@ def _composed_step(ctx, state, batch, lr, t):
     return np.float32(total / n), norm
 
 
-def test_step_is_its_parts_and_the_trained_floats_reload():
-    n = 8
-    a, sd = _context(F_T, O_T, chunk_len=L_T, n=n)
-    b, _ = _context(F_T, O_T, chunk_len=L_T, n=n, sd=sd)
+def _steps_are_their_parts(F, O, chunk_len, n, steps):
+    """`steps` xb_head_train_step calls on context a against the composed step on context b; both left open, the trainer too."""
+    a, sd = _context(F, O, chunk_len=chunk_len, n=n)
+    b, _ = _context(F, O, chunk_len=chunk_len, n=n, sd=sd)
+    assert a.T >= LT - HEADS[O][1]                                       # every label row has a path
     a.head_train_begin(sd[W_KEY], sd[B_KEY])
     state = {"w": [_dev(sd[W_KEY]), _dev(np.zeros_like(sd[W_KEY])), _dev(np.zeros_like(sd[W_KEY]))],
              "b": [_dev(sd[B_KEY]), _dev(np.zeros_like(sd[B_KEY])), _dev(np.zeros_like(sd[B_KEY]))]}
     torch.cuda.synchronize()
     lr = 2e-3
-    for t in range(1, 4):
-        batch = _batch(n, seed=t)
+    for t in range(1, steps + 1):
+        batch = _batch(n, seed=t, O=O, chunk_len=chunk_len)
         loss, norm = a.head_train_step(*batch, lr)
         ref_loss, ref_norm = _composed_step(b, state, batch, lr, t)
         print("step %d: loss %.6f norm %.6g" % (t, loss, norm))
+        assert np.isfinite(loss) and np.isfinite(norm) and norm > 0
         assert np.float32(loss).tobytes() == ref_loss.tobytes() and np.float32(norm).tobytes() == ref_norm.tobytes(), (t, loss, ref_loss)
         w, bias = a.head_get_weights()
         assert w.tobytes() == state["w"][0].cpu().numpy().tobytes() and bias.tobytes() == state["b"][0].cpu().numpy().tobytes(), t
         assert not np.array_equal(w, sd[W_KEY]) and not np.array_equal(bias, sd[B_KEY])
         _same_image(a.head_image(), b.head_image(), "step %d" % t)
         _same_image(a.head_image(), _expected_image(w, bias), "step %d, master weights" % t)
+    return a, b, sd
+
+
+def test_step_is_its_parts_and_the_trained_floats_reload():
+    n = 8
+    a, b, sd = _steps_are_their_parts(F_T, O_T, L_T, n, 3)
     signal = _batch(n, seed=9)[0]
     trained = a.encode(signal, expand_blanks=False)
     w, bias = a.head_get_weights()
@@ -177,6 +187,16 @@ def test_step_is_its_parts_and_the_trained_floats_reload():
     a.head_train_end()
     assert a.encode(signal, expand_blanks=False).tobytes() == trained.tobytes()        # the trained head stays until weights are loaded
     for c in (a, b, fresh):
+        c.close()
+
+
+@pytest.mark.parametrize("O", [3125, 4096])
+def test_step_is_its_parts_at_the_widest_heads(O):
+    """Features 32, chunks of 200 samples (T = 40), three chunks, two steps: 49 column tiles with rows that are not 16-byte aligned,
+    and 64 tiles."""
+    a, b, _ = _steps_are_their_parts(32, O, 200, 3, 2)
+    a.head_train_end()
+    for c in (a, b):
         c.close()
 
 

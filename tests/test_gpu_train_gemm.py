@@ -9,13 +9,14 @@ tensor's maximum -- the device must stay within MARGIN = 8 times that.  Every co
            staging rounds), both activations, with and without bias; rows 0..16 of M = 65 are the bytes of M = 17; a repeated
            call; +-1e4 under tanh.  The widths of a real step at M = 17, with bias, both activations: (N, K) = (3072, 768) gin,
            (768, 3072) dx, (1296, 768) the scores, (768, 1296) the head's dX, (768, 625) the same at C = 625, whose rows are not
-           16-byte aligned -- column tiles up to 47, up to 96 staging rounds.  The launch seam: M = 64 * 65535 + 65 rows are two
+           16-byte aligned -- column tiles up to 47, up to 96 staging rounds; and the scores and the head's dX at the other
+           head widths a context takes, 216, 1024, 3125 (rows not 16-byte aligned) and 4096.  The launch seam: M = 64 * 65535 + 65 rows are two
            launches; all of it against float64, and the last 129 rows (the last tile before the seam, the second launch) are
            the bytes of a call on those rows alone
   wgrad    M in {0, 1, 5, 130, 20000} x (N, K) in {(16, 16), (125, 48), (200, 125)} (20000 rows: 19 blocks of the blocked sum and
            a ragged one; not at (200, 125)), dcol included; M = 0 and a gradient of zeros give zero bytes; a repeated call; the
            shifted operands of dW_hh in both directions.  The widths of a real step at M = 130, dcol included: (N, K) =
-           (3072, 768) dW_ih and dW_hh, (1296, 768) the head, (625, 768) the head at C = 625 (rows of a not 16-byte aligned)
+           (3072, 768) dW_ih and dW_hh, (1296, 768) the head, (625, 768) the head at C = 625 (rows of a not 16-byte aligned), and at C = 216, 3125 and 4096
   dz       bit-equal to numpy operation by operation, |y| = scale included"""
 import functools
 
@@ -34,6 +35,9 @@ LINEAR = [(M, N, K) for M in (1, 17, 65) for N in (16, 48, 125) for K in (16, 12
 WGRAD = [(M, N, K) for M in (0, 1, 5, 130, 20000) for N, K in ((16, 16), (125, 48), (200, 125)) if not (M == 20000 and N == 200)]
 LINEAR_REAL = [(3072, 768), (768, 3072), (1296, 768), (768, 1296), (768, 625)]
 WGRAD_REAL = [(3072, 768), (1296, 768), (625, 768)]
+# the head widths of the other (n_base, state_len) pairs: 216 (6, 2), 1024 (4, 4), 3125 (5, 4), 4096 (4, 5)
+LINEAR_REAL += [(216, 768), (768, 216), (1024, 768), (3125, 768), (768, 3125), (4096, 768), (768, 4096)]
+WGRAD_REAL += [(216, 768), (3125, 768), (4096, 768)]
 SEAM_ROWS = 64 * 65535                 # rows of one launch of xb_linear_f32: 65535 blocks of 64 in the grid's y dimension
 RATIOS = []
 

@@ -14,12 +14,11 @@ import torch
 import oracle
 from conftest import encoder_shapes, make_config, random_scores, seeded_state_dict
 from ctc_wide_cases import BLANK, ctc_logz_f64 as _ctc_logz_f64, label_rows, loss_reference as _reference
+from test_ctc import GPU_CASES
 from xna_basecaller_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
-GPU_CASES = [(4, 37, 3, 9, 3), (5, 120, 5, 40, 3), (6, 200, 7, 130, 3), (6, 64, 2, 3, 3), (5, 90, 4, 300, 3),
-             (4, 64, 3, 12, 5), (5, 65, 3, 11, 4), (6, 63, 3, 9, 2), (4, 40, 3, 7, 2)]
 # (nb, T, N, Lt, sl, T of the context): the shapes above on a context of their own T, then the two added cases
 CASES = [c + (c[1],) for c in GPU_CASES] + [(5, 3, 3, 9, 3, 64), (6, 50, 1, 20, 3, 50)]
 IDS = ["%d-%d-%d-%d-sl%d-ctx%d" % c for c in CASES]

@@ -17,6 +17,7 @@ import torch
 
 import lstm_train_ref as R
 import toptrain_ref as TR
+import train_geometry_cases as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -153,7 +154,8 @@ def test_plan_check_program_passes_under_the_sanitizers(plan_check):
     assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout + out.stderr
 
 
-@pytest.mark.parametrize("L,F,C,rows", [(1, 16, 25, 15), (2, 32, 125, 120), (5, 96, 1296, 120), (2, 768, 1296, 720 * 98), (5, 768, 625, 720 * 384)])
+@pytest.mark.parametrize("L,F,C,rows", [(1, 16, 25, 15), (2, 32, 125, 120), (5, 96, 1296, 120), (2, 768, 1296, 720 * 98), (5, 768, 625, 720 * 384)]
+                         + [(L, c.F, G.columns(c), G.steps(c)[2] * c.n) for c in G.CASES for L in (2, 5)])      # the trainers' geometries on the device
 def test_plan_against_its_restatement(plan_check, L, F, C, rows):
     out = subprocess.run([plan_check, str(L), str(F), str(C), str(rows)], capture_output=True, text=True, check=True).stdout.split("\n")
     want = TR.table(L, F, C, rows)

@@ -5,7 +5,8 @@ scores = scale * tanh(y W^T + b), and the gradients of every tensor from a given
 dscores are inputs: the bottom and the loss have their own references.
 
   reverse_of(L, i)                          -> whether unfrozen layer i (0 = lowest, encoder.(9 - L + i)) runs backwards in time
-  run(x0, tensors, scale, dscores)          -> dict(scores (T, n, C), grads: one array per tensor, in the tensors' order)
+  run(x0, tensors, scale, dscores)          -> dict(scores (T, n, C), grads: one array per tensor, in the tensors' order, dx0:
+                                               d loss / d x0 (T, n, F), what the layers below the unfrozen ones receive)
   torch_run(x0, tensors, scale, dscores, dtype) -> the same from torch.nn.LSTM / Linear and torch.autograd on the CPU: in float64
                                                what the restatement is held to, in float32 the yardstick of the device tests
   table(L, F, C, rows)                      -> csrc/xb_top_plan.h restated: offsets, lengths, floats of a buffer, its stride, bytes
@@ -29,7 +30,13 @@ CASES = [Case(1, 7, 5, 48, 125, False),       # a ragged last column tile, score
          Case(2, 4, 65, 96, 64, False),       # the recurrence's launch with four row tiles a workgroup
          Case(1, 3, 5, 768, 125, False),      # the real K
          Case(5, 6, 5, 32, 64, True),         # every layer csrc/xb_top_plan.h lays out
-         Case(2, 1, 5, 48, 125, False)]       # one time step: dW_hh sums over no rows
+         Case(2, 1, 5, 48, 125, False),       # one time step: dW_hh sums over no rows
+         # appended (TR.CASES[1] stays what it was): the head widths of the other (n_base, state_len) pairs a context takes
+         Case(1, 7, 5, 48, 216, False),       # (6, 2)
+         Case(1, 7, 5, 48, 625, True),        # (5, 3): score rows that are not 16-byte aligned
+         Case(2, 5, 17, 32, 1024, False),     # (4, 4)
+         Case(1, 7, 5, 48, 3125, False),      # (5, 4): not 16-byte aligned, 49 column tiles
+         Case(2, 5, 5, 32, 4096, False)]      # (4, 5)
 LOSS_CASE = Case(2, 40, 6, 48, 125, None)     # d loss / d scores from xb_ctc_loss_grad on the device's scores (n_base 5, state_len 2)
 
 
@@ -83,7 +90,7 @@ def run(x0, tensors, scale, dscores):
         db = g2.sum(axis=0)
         grads[4 * i:4 * i + 4] = [g2.T @ xin.reshape(rows, F), g2.T @ R.h_prev(y, rev).reshape(rows, F), db, db.copy()]
         dy = dgin @ w_ih
-    return dict(scores=scores, grads=grads)
+    return dict(scores=scores, grads=grads, dx0=dy)
 
 
 def torch_run(x0, tensors, scale, dscores, dtype):
