@@ -62,7 +62,7 @@ def to_e4m3(a):
 
 
 def split_rows_exp(w):
-    """The tensor-wide e4m3 exponent of split_rows (csrc/xb_api.hip): the largest |value| lands near 224."""
+    """The tensor-wide e4m3 exponent of split_rows (csrc/xb_pack.h): the largest |value| lands near 224."""
     amax = float(np.abs(np.asarray(w, np.float32)).max())
     e = int(np.floor(np.log2(np.float32(448.0) / np.float32(amax)))) - 1 if amax > 0 and np.isfinite(amax) else 0
     return min(max(e, -16), 32)

@@ -1,6 +1,6 @@
 """
 Python restatement of the encoder's host scheduler (plan_layer, xna_basecaller_amd/csrc/xb_schedule.h, as run_encoder /
-run_lstm_layer of xb_api.hip execute it) and the table of schedules that tests/test_gpu_schedules.py runs.
+run_lstm_layer of xb_run_encoder.hip execute it) and the table of schedules that tests/test_gpu_schedules.py runs.
 tests/test_schedule_host.py holds the C++ planner to this restatement, case by case, without a GPU.
 
 plan(F, n, T, cu_count, env) predicts, for one encoder pass over n chunks of T steps, which plan every LSTM layer takes and

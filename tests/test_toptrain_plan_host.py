@@ -1,4 +1,4 @@
-"""CPU: the bottom pass of the top-layer trainer (encoder_bottom_run, csrc/xb_api.hip) runs its last LSTM layer without a
+"""CPU: the bottom pass of the top-layer trainer (encoder_bottom_run, csrc/xb_run_encoder.hip) runs its last LSTM layer without a
 consumer: run_lstm_layer is called with next = nullptr.  That function dereferences `next` only where the plan issues slab
 GEMMs beside the recurrence (the orderings `events` and `signal`) and, guarded, after it.  The planner must therefore never plan
 a slab GEMM for a query with has_next = 0 -- whatever the batch, the width, the device and the knobs."""

@@ -7,7 +7,13 @@ lean-issue rewrite (same arithmetic, fewer instructions) changes no bit:  python
 TRAIN_CASES are the loss and training families on small contexts (chunks of 200 samples, at most 8): three steps each of a head
 trainer, a top trainer at L = 1 and L = 2 and a full trainer with a validate_chunks between the first two, top_train_grad,
 ctc_loss, ctc_loss_grad, validate_chunks, head_grad with and without X.  Their digests cover every returned float, the weights
-after each step and the head's image.  --train runs these alone."""
+after each step and the head's image.  --train runs these alone.
+
+API_CASES are the inference calls on the same small contexts: decode with labels, decode_q and decode_ub in both layouts, crf_scans
+with all four outputs, ctc_logz with gradients, ctc_alignments, beam_search, basecall_chunks_beam, basecall_chunks at the three
+levels, two rounds of submit_chunks / collect_chunks over the four slots at each level, and one paired couple of
+basecall_chunks_dev.  After each of them the digest takes every returned array and the `launches` of xb_get_stage_times: a call
+launches exactly what it launched in the other build.  --api runs these alone."""
 import hashlib
 import json
 import os
@@ -31,6 +37,57 @@ CASES = [  # features, nb, chunk_len, n, precision, paired calls, env
     (64, 6, 1000, 40, "mixed", 1, {}),
 ]
 TRAIN_CASES = [(F, Lt) for F in (32, 64) for Lt in (12, 24)]       # features, label row width
+API_CASES = [32, 64]                                               # features
+
+
+def api_digest(F):
+    import numpy as np
+    import torch
+    from xna_basecaller_amd import _lib
+    from xna_basecaller_amd.synthetic import peaky_weights
+    nb, sl, L, N, Lt, alphabet = 6, 3, 200, 8, 12, "NACGTXY"
+    rng = np.random.default_rng(F)
+    ctx = _lib.Context(0, nb, sl, F, 19, 5, 5.0, 2.0, L, N, precision=_lib.XB_PREC_MIXED)
+    ctx.load_state_dict(peaky_weights(F, nb))
+    h = hashlib.sha1()
+
+    def add(out):
+        """a case's arrays, then what the context has launched so far"""
+        for a in (out.values() if isinstance(out, dict) else out):
+            h.update(np.ascontiguousarray(a).tobytes())
+        h.update(np.array([v[1] for v in ctx.stage_times().values()], np.int64).tobytes())
+
+    x = rng.standard_normal((N, L)).astype(np.float32)
+    lens = rng.integers(sl, Lt + 1, N).astype(np.int32)
+    targets = rng.integers(1, nb + 1, (N, Lt)).astype(np.int32)
+    with_blank, without = ctx.encode(x, expand_blanks=True), ctx.encode(x, expand_blanks=False)
+    add(ctx.decode(with_blank, alphabet, want_labels=True))
+    add(ctx.decode(without, alphabet, want_labels=True))
+    for sc in (with_blank, without):
+        add(ctx.decode_q(sc, alphabet, 1.5, 0.25))
+        add(ctx.decode_ub(sc, alphabet, 1.5, 0.25))
+        add(ctx.beam_search(sc[:, :5], alphabet, beam_width=8))
+    add(ctx.crf_scans(with_blank))
+    add(ctx.ctc_logz(with_blank, targets, lens, want_grads=True))
+    add(ctx.ctc_alignments(with_blank, targets, lens))
+    add(ctx.basecall_chunks_beam(x[:5], alphabet, beam_width=8))
+    for level in (0, 1, 2):
+        add(ctx.basecall_chunks(x, alphabet, 1.5, 0.25, level=level))
+    for level in (0, 1, 2):
+        for _ in range(2):
+            for slot in range(_lib.XB_PIPELINE_SLOTS):
+                ctx.submit_chunks(slot, x[slot:], alphabet, 1.5, 0.25, level=level)
+            for slot in range(_lib.XB_PIPELINE_SLOTS):
+                add(ctx.collect_chunks(slot, N - slot, level=level))
+    ctx.reserve_pairing()
+    dx = torch.from_numpy(x).cuda()
+    bufs = [(torch.zeros((n, ctx.T), dtype=torch.int8, device="cuda"), torch.zeros((n,), dtype=torch.int32, device="cuda")) for n in (N, 3)]
+    for s, l in bufs:
+        ctx.basecall_chunks_dev(dx.data_ptr(), s.shape[0], alphabet, s.data_ptr(), l.data_ptr())
+    ctx.synchronize()
+    add([a.cpu().numpy() for pair in bufs for a in pair])
+    ctx.close()
+    return h.hexdigest()
 
 
 def train_digest(F, Lt):
@@ -102,14 +159,14 @@ def train_digest(F, Lt):
     return h.hexdigest()
 
 
-def worker(train_only=False):
+def worker(only=None):
     import numpy as np
     import torch
     sys.path.insert(0, ROOT)
     from xna_basecaller_amd import _lib
     from xna_basecaller_amd.synthetic import peaky_weights, seeded_weights
     out = []
-    for F, nb, L, n, prec, calls, env in ([] if train_only else CASES):
+    for F, nb, L, n, prec, calls, env in ([] if only else CASES):
         os.environ.update(env)
         ctx = _lib.Context(0, nb, 3, F, 19, 5, 5.0, 2.0, L, n, precision=_lib.PRECISIONS[prec])
         for k in env:
@@ -133,21 +190,24 @@ def worker(train_only=False):
         h.update(np.ascontiguousarray(scores).tobytes())
         out.append(h.hexdigest())
         ctx.close()
-    out += [train_digest(F, Lt) for F, Lt in TRAIN_CASES]
+    out += [train_digest(F, Lt) for F, Lt in TRAIN_CASES] if only != "--api" else []
+    out += [api_digest(F) for F in API_CASES] if only != "--train" else []
     print("DIGESTS " + json.dumps(out))
 
 
 def main():
-    train_only = "--train" in sys.argv[1:]
-    argv = [a for a in sys.argv[1:] if a != "--train"]
+    only = ([a for a in sys.argv[1:] if a in ("--train", "--api")] or [None])[0]
+    argv = [a for a in sys.argv[1:] if a != only]
     if argv == ["--worker"]:
-        return worker(train_only)
+        return worker(only)
     libs = argv[:2]
-    cases = ([] if train_only else CASES) + [("train", "features %d" % F, "label rows %d wide" % Lt) for F, Lt in TRAIN_CASES]
+    cases = [] if only else list(CASES)
+    cases += [("train", "features %d" % F, "label rows %d wide" % Lt) for F, Lt in TRAIN_CASES] if only != "--api" else []
+    cases += [("api", "features %d" % F) for F in API_CASES] if only != "--train" else []
     res = []
     for lib in libs:
         env = dict(os.environ, XNA_LIBXNACALL=os.path.abspath(lib))
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker"] + ["--train"] * train_only, env=env,
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker"] + [only] * bool(only), env=env,
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE)
         line = [l for l in r.stdout.decode().splitlines() if l.startswith("DIGESTS ")]
         if r.returncode or not line:

@@ -1,6 +1,8 @@
-// xb_api.hip -- C ABI of libxnacall.so (see include/xna_basecaller.h for the contract and the
-// reference call sites each entry point replaces).
-#include "xb_ctx.h"
+// xb_api.hip -- the context core of the C ABI of libxnacall.so (see include/xna_basecaller.h for the contract and the reference
+// call sites each entry point replaces): a context's lifetime and weights, what every entry point shares (fail, check_ready,
+// enter, the status words, the workspaces), profiling, the debug calls and the host-logic exports.  The calls themselves live in
+// xb_run_encoder.hip, xb_api_scores.hip, xb_api_basecall.hip and xb_api_data.hip.
+#include "xb_api_priv.h"
 
 namespace { thread_local std::string g_create_error; }
 
@@ -53,16 +55,6 @@ int check_alphabet(xb_ctx *ctx, const char *alphabet)
     return XB_OK;
 }
 
-namespace {
-
-Planes planes(void *seq, void *len, const DecodeOut &o) { return {{seq, len, o.qstr, o.moves, o.probs}}; }
-int plane_count(int level) { return level == 0 ? 2 : (level == 1 ? 4 : 5); }
-size_t plane_bytes(int T, int nb, int i) { return i == 1 ? sizeof(int32_t) : (i == 4 ? (size_t)nb * T : (size_t)T); }
-// seq, and by level qstring and probs: the planes an entry point requires (xb_decode alone may leave seq out)
-bool has_required(const Planes &o, int level) { return o.p[0] && (level < 1 || o.p[2]) && (level < 2 || o.p[4]); }
-
-int64_t ipow(int64_t b, int e) { int64_t r = 1; while (e-- > 0) r *= b; return r; }
-
 // The workspaces whose size follows the number of chunks in a pass.  A context starts with room for max_batch chunks; the
 // first time two calls are co-scheduled (or on xb_reserve_pairing) they are replaced by twice that.
 int alloc_workspaces(xb_ctx *ctx, int cap)
@@ -109,26 +101,7 @@ int alloc_workspaces(xb_ctx *ctx, int cap)
     return rc;
 }
 
-struct StageScope {
-    xb_ctx *c;
-    int stage;
-    hipEvent_t a = nullptr, b = nullptr;
-    hipStream_t st_;
-    StageScope(xb_ctx *ctx, int st, int launches, hipStream_t stream = nullptr)
-        : c(ctx), stage(st), st_(stream ? stream : ctx->stream)
-    {
-        c->stage_launches[st] += launches;
-        if (c->profiling && hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess)
-            (void)hipEventRecord(a, st_);
-    }
-    ~StageScope()
-    {
-        if (a && b) {
-            (void)hipEventRecord(b, st_);
-            c->events.push_back({stage, a, b});
-        }
-    }
-};
+namespace {
 
 int collect_events(xb_ctx *ctx)
 {
@@ -172,6 +145,8 @@ int upload(xb_ctx *ctx, Tp **dst, const std::vector<Tp> &src)
     return XB_OK;
 }
 
+}  // namespace
+
 // What the two status words say once the main stream has drained (xb_status.h): one condition per call, and that one is taken
 // out of its word -- a validation bit beside it is the next synchronising call's to report.
 int check_device_error(xb_ctx *ctx)
@@ -187,80 +162,6 @@ int check_device_error(xb_ctx *ctx)
     return fail(ctx, s.code, "%s", s.message);
 }
 
-// ---- encoder orchestration --------------------------------------------------------------
-int precision_nsplit(int pr)
-{
-    return pr == XB_PREC_F16 ? 1 : ((pr == XB_PREC_F16F8 || pr == XB_PREC_F16F8_IN1 || pr == XB_PREC_MIXED) ? 2 : 3);
-}
-
-// Stage mask of the three-product arithmetic inside an f16f8 context: bits 0-4 = input projection of LSTM layer l, bits 5-9 =
-// recurrence of layer l, bit 10 = CRF linear layer, bit 11 = conv3.  XB_PREC_MIXED: every feed-forward projection.  Measured on the
-// peaky model (profiles/r04_x3_attribution.txt): the error variance of plain f16f8 splits as input projections 65 %,
-// linear 18 %, recurrences 13 %, conv3 5 %; per ms of step time the recurrences buy the least, and they are the critical path.
-constexpr int X3_MIXED_STAGES = 0x1f | (1 << 10) | (1 << 11);
-void set_stage_arithmetic(xb_ctx *ctx, int x3_mask)
-{
-    const int base = precision_nsplit(ctx->cfg.precision);
-    const bool mix = base == 2;
-    for (int l = 0; l < 5; ++l) {
-        ctx->ns_in[l] = mix && ((x3_mask >> l) & 1) ? 3 : base;
-        ctx->ns_rec[l] = mix && ((x3_mask >> (5 + l)) & 1) ? 3 : base;
-    }
-    ctx->ns_lin = mix && ((x3_mask >> 10) & 1) ? 3 : base;
-    ctx->ns_conv = mix && ((x3_mask >> 11) & 1) ? 3 : base;
-}
-// second part an activation tensor needs for a consumer of arithmetic ns: 2 = q8 image, 1 = fp16 residual, 0 = none read
-int second_part(int ns) { return ns == 2 ? 2 : (ns == 3 ? 1 : 0); }
-
-// the GEMM that consumes a layer's output rows of time steps [ta, tb): the input projection of LSTM layer `layer`
-// (layer < 5, into `gin_out`) or the CRF linear layer (layer == 5, into the scores)
-struct NextGemm {
-    int layer;
-    const half_t *x_hi, *x_lo;
-    float *out;
-    int ldc, expand;
-};
-
-int launch_row_gemm(xb_ctx *ctx, const NextGemm &ng, int n, int ta, int tb, hipStream_t st, bool shadow = false)
-{
-    const xb_config &c = ctx->cfg;
-    const int F = c.features;
-    xb::GemmParams g{};
-    const size_t r0 = (size_t)ta * n;
-    g.a_hi = ng.x_hi + r0 * F; g.a_lo = ng.x_lo + r0 * F;
-    g.M = (tb - ta) * n; g.K = F; g.lda = F; g.ldb = F; g.nsplit = ng.layer < 5 ? ctx->ns_in[ng.layer] : ctx->ns_lin;
-    g.ldc = ng.ldc; g.out_f32 = ng.out + r0 * ng.ldc;
-    g.one_per_cu = shadow && ctx->knobs.gemm_shadow_wgs == 1;
-    g.sn = ctx->knobs.gemm_sn;
-    // which kernel: gemm4p_kernel, except for the slabs that run beside the two-groups-per-workgroup recurrence of a batch
-    // above 1024 chunks, where the one-workgroup-per-CU gemm8r_kernel disturbs the recurrence less (same box, ms per step at
-    // batch 2048: 477 vs 488 (gemm4p, one workgroup per CU) vs 499; batch 1024: 240 vs 246 vs 235; batch 512: 126.7 vs 129.7 vs
-    // 123.0 -- profiles/r03_gemm_kernel_by_batch.txt).  XB_GEMM_SHADOW=4 / 8 forces one of them.
-    const bool use4 = ctx->knobs.gemm4 && !(shadow && (ctx->knobs.gemm_shadow_kernel == 8 || (ctx->knobs.gemm_shadow_kernel == 0 && n > 1024)));
-    if (ng.layer < 5) {
-        StageScope sc(ctx, XB_STAGE_LSTM_IN, 1, st);
-        g.b_hi = ctx->wih_hi[ng.layer]; g.b_lo = ctx->wih_lo[ng.layer]; g.Nn = 4 * F; g.bias = ctx->lbias[ng.layer];
-        // main product only (the q8 images stay unused) -- in1_layers: bit l = input projection of layer l (diagnostic
-        // XB_IN1_LAYERS, default all five)
-        if (use4) { g.b4 = ctx->wih_f4[ng.layer]; g.b4_kstride = ctx->wih_ks; }
-        if (ctx->cfg.precision == XB_PREC_F16F8_IN1 && ((ctx->knobs.in1_layers >> ng.layer) & 1)) {
-            g.nsplit = 1;
-            if (use4) { g.b4 = ctx->wih_f4h[ng.layer]; g.b4_kstride = ctx->wih_ksh; }
-        }
-        g.a_exp = ng.layer == 0 ? 0 : 8; g.b_exp = ctx->wih_exp[ng.layer];     // conv3 output / LSTM output
-        g.gin_n = n;                                                           // member-major gin (xb_internal.h)
-        XB_HIP(ctx, xb::launch_gemm(g, xb::EPI_BIAS_F32, st));
-    } else {
-        StageScope sc(ctx, XB_STAGE_LINEAR, 1, st);
-        g.b_hi = ctx->wl_hi; g.b_lo = ctx->wl_lo; g.Nn = ctx->O; g.bias = ctx->bl;
-        g.scale = c.scale; g.nb = c.n_base; g.expand = ng.expand; g.blank = c.blank_score;
-        g.a_exp = 8; g.b_exp = ctx->wl_exp;
-        if (use4) { g.b4 = ctx->wl_f4; g.b4_kstride = ctx->wl_ks; }
-        XB_HIP(ctx, xb::launch_gemm(g, xb::EPI_TANH_SCALE, st));
-    }
-    return XB_OK;
-}
-
 int next_dep(xb_ctx *ctx, hipEvent_t *ev)
 {
     if (ctx->dep_next == ctx->deps.size()) {
@@ -269,317 +170,6 @@ int next_dep(xb_ctx *ctx, hipEvent_t *ev)
         ctx->deps.push_back(e);
     }
     *ev = ctx->deps[ctx->dep_next++];
-    return XB_OK;
-}
-
-int sync_all(xb_ctx *ctx);
-
-// Recurrence of one layer from `gin` into (xout_hi, xout_lo).  With `next` set, the GEMM that consumes this layer's output
-// is issued as well: either afterwards on the main stream, or -- overlapped mode -- slab by slab on the second stream while
-// the recurrence (192 of the 256 CUs, latency bound) is still running; the main stream then waits for the last slab.
-// Which launches, over which chunks and steps, in which order: xb::plan_layer (xb_schedule.h); this function executes its plan.
-// the arrival counters: SYNC_SLOTS x 32 words, i.e. the 64 group slots of 64 chunks at 64 words each (lstm_kernel LG_SYNC)
-constexpr int SYNC_SLOTS = 128;
-static_assert(xb::PLAN_ERR_INVALID == XB_ERR_INVALID, "a refused plan is an invalid argument");
-
-void set_launch(xb::LstmParams &p, const xb::PlanLaunch &l)
-{
-    p.n0 = l.n0; p.nslab = l.nslab; p.s_begin = l.s_begin; p.s_end = l.s_end; p.dual = l.dual;
-    p.grp0 = l.grp0; p.slab = l.slab; p.xcd_local = l.xcd_local; p.sync_base = l.sync_base;
-}
-
-// the main stream waits for what the second stream has been given so far
-int join_stream2(xb_ctx *ctx)
-{
-    hipEvent_t ev;
-    if (int rc = next_dep(ctx, &ev)) return rc;
-    XB_HIP(ctx, hipEventRecord(ev, ctx->stream2));
-    XB_HIP(ctx, hipStreamWaitEvent(ctx->stream, ev, 0));
-    return XB_OK;
-}
-
-int run_lstm_layer(xb_ctx *ctx, int layer, int n, const float *gin, half_t *xout_hi, half_t *xout_lo, const NextGemm *next)
-{
-    const int F = ctx->cfg.features, T = ctx->T;
-    // what the GEMM that reads this layer's output needs as the second part; the int8-limb recurrence writes hi + q8 only
-    const int y_need = second_part(layer < 4 ? ctx->ns_in[layer + 1] : ctx->ns_lin);
-    const bool i8 = ctx->knobs.lstm_i8 && ctx->whh_q1[layer] && ctx->ns_rec[layer] == 2 && y_need != 1;
-    const int rec_nsplit = i8 ? (ctx->knobs.lstm_i8 == 2 ? 5 : 4) : ctx->ns_rec[layer];
-    // the occupancy calculator's word on the persistent kernel, asked once per context and arithmetic
-    int (&res)[2] = ctx->lstm_resident[rec_nsplit];
-    if (res[0] < 0) res[0] = xb::lstm_resident_per_cu(F, rec_nsplit, 0);
-    if (res[1] < 0) res[1] = xb::lstm_resident_per_cu(F, rec_nsplit, 1);
-    xb::PlanQuery q{};
-    q.F = F; q.n = n; q.T = T; q.cu_count = ctx->cu_count; q.knobs = ctx->knobs;
-    if (const char *e = getenv("XB_LSTM_SPREAD")) q.spread = atoi(e) != 0;
-    q.has_next = next && ctx->stream2;
-    q.resident1 = res[0] >= 1; q.resident2 = res[1] >= 1; q.signal_ok = ctx->sig_flag != nullptr;
-    const xb::LayerPlan plan = xb::plan_layer(q);
-    if (plan.error) return fail(ctx, plan.error, "%s", plan.message);
-
-    XB_HIP(ctx, hipMemsetAsync(ctx->c_state, 0, sizeof(float) * (size_t)n * F, ctx->stream));
-    xb::LstmParams p{};
-    p.gin = gin; p.w_hi = ctx->whh_hi[layer]; p.w_lo = ctx->whh_lo[layer];
-    p.y_hi = xout_hi; p.y_lo = xout_lo; p.c_state = ctx->c_state; p.xh = ctx->xh;
-    p.T = T; p.N = n; p.F = F; p.reverse = (layer % 2) == 0;
-    p.sync = ctx->sync; p.error = ctx->error; p.nsplit = ctx->ns_rec[layer]; p.w_exp = ctx->whh_exp[layer];
-    p.y_alt = (p.nsplit == 2 || p.nsplit == 3) && y_need != 0 && y_need != second_part(p.nsplit);
-    if (i8) {
-        p.nsplit = rec_nsplit; p.wq1 = ctx->whh_q1[layer]; p.wq0 = ctx->whh_q0[layer]; p.wscale = ctx->whh_sc[layer];
-    }
-    p.spread = plan.spread;
-    p.persistent = plan.mode == 2;
-    // the GEMM of time slab i beside the recurrence, on the second stream
-    auto slab_gemm = [&](int i) {
-        int ta, tb;
-        plan.gemm_rows(i, p.reverse != 0, &ta, &tb);
-        return launch_row_gemm(ctx, *next, n, ta, tb, ctx->stream2, true);
-    };
-    if (!p.persistent) {
-        StageScope sc(ctx, XB_STAGE_LSTM_REC, plan.rec_launches);
-        set_launch(p, plan.launch(0, 0));
-        for (int s = 0; s < T; ++s) {
-            p.s_begin = s; p.s_end = s + 1;
-            XB_HIP(ctx, xb::launch_lstm(p, ctx->stream));
-        }
-    } else {
-        if (plan.global_groups) XB_HIP(ctx, hipMemsetAsync(ctx->sync, 0, sizeof(unsigned) * SYNC_SLOTS * 32, ctx->stream));
-        if (plan.ordering == xb::PLAN_SIGNAL) {
-            if (ctx->sig_seq > (1u << 30)) {           // keep the 32-bit flag monotonic: start over from an idle device
-                int rc = sync_all(ctx);
-                if (rc) return rc;
-                XB_HIP(ctx, hipMemset(ctx->sig_flag, 0, 4));
-                ctx->sig_seq = 0;
-            }
-            XB_HIP(ctx, hipMemsetAsync(ctx->sig_done, 0, sizeof(unsigned) * 64, ctx->stream));
-            {
-                StageScope sc(ctx, XB_STAGE_LSTM_REC, plan.rec_launches);
-                set_launch(p, plan.launch(0, 0));
-                p.sig_flag = ctx->sig_flag; p.sig_done = ctx->sig_done; p.sig_base = ctx->sig_seq; p.sig_nts = plan.nts;
-                XB_HIP(ctx, xb::launch_lstm(p, ctx->stream));
-            }
-            for (int i = 0; i < plan.nts; ++i) {
-                XB_HIP(ctx, hipStreamWaitValue32(ctx->stream2, ctx->sig_flag, ctx->sig_seq + (unsigned)i + 1u, hipStreamWaitValueGte,
-                                                 0xffffffffu));
-                if (int rc = slab_gemm(i)) return rc;
-            }
-            ctx->sig_seq += (unsigned)plan.nts;
-            return join_stream2(ctx);
-        }
-        for (int i = 0; i < plan.nts; ++i) {
-            {
-                StageScope sc(ctx, XB_STAGE_LSTM_REC, i == 0 ? plan.rec_launches : 0);
-                for (int j = 0; j < plan.chunk_slabs; ++j) {
-                    set_launch(p, plan.launch(i, j));
-                    if (!plan.global_groups) XB_HIP(ctx, hipMemsetAsync(ctx->sync, 0, sizeof(unsigned) * SYNC_SLOTS * 32, ctx->stream));
-                    XB_HIP(ctx, xb::launch_lstm(p, ctx->stream));
-                }
-            }
-            if (plan.ordering == xb::PLAN_EVENTS) {
-                hipEvent_t ev;
-                int rc = next_dep(ctx, &ev);
-                if (rc) return rc;
-                XB_HIP(ctx, hipEventRecord(ev, ctx->stream));
-                XB_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ev, 0));
-                if ((rc = slab_gemm(i))) return rc;
-            }
-        }
-        if (plan.ordering == xb::PLAN_EVENTS) return join_stream2(ctx);
-    }
-    // PLAN_SERIAL, PLAN_SLABS_SERIAL_GEMM: the GEMM follows on the main stream
-    if (next) return launch_row_gemm(ctx, *next, n, 0, T, ctx->stream);
-    return XB_OK;
-}
-
-// scores_out: (T, n, ldc) with ldc given; expand selects the blank-column layout
-int run_encoder(xb_ctx *ctx, const float *d_signal, int n, int expand, float *scores_out, int ldc,
-                const float *d_signal2 = nullptr, int split = 0)
-{
-    const xb_config &c = ctx->cfg;
-    const int F = c.features, T = ctx->T;
-    const int nsplit = ctx->ns_conv;
-    ctx->dep_next = 0;
-    ctx->enc_n = n;
-    {
-        StageScope sc(ctx, XB_STAGE_CONV, 2);
-        xb::ConvFrontParams cf{};
-        cf.signal = d_signal; cf.signal2 = d_signal2; cf.split = d_signal2 ? split : n; cf.N = n; cf.L = c.chunk_len; cf.T = T; cf.winlen = c.winlen; cf.stride = c.stride;
-        cf.kp = ctx->kp; cf.w1 = ctx->w1; cf.b1 = ctx->b1; cf.w2 = ctx->w2; cf.b2 = ctx->b2;
-        cf.a_hi = ctx->im_hi; cf.a_lo = ctx->im_lo; cf.q8 = nsplit == 2;
-        XB_HIP(ctx, xb::launch_conv_front(cf, ctx->stream));
-        xb::GemmParams g{};
-        g.a_hi = ctx->im_hi; g.a_lo = ctx->im_lo; g.b_hi = ctx->w3_hi; g.b_lo = ctx->w3_lo;
-        g.M = T * n; g.Nn = F; g.K = ctx->kp; g.lda = ctx->kp; g.ldb = ctx->kp;
-        g.bias = ctx->b3; g.out_hi = ctx->x_hi[0]; g.out_lo = ctx->x_lo[0]; g.ldc = F; g.nsplit = nsplit;
-        g.a_exp = 0; g.b_exp = ctx->w3_exp; g.out_exp = 0;
-        g.out_fmt = second_part(ctx->ns_in[0]);            // (0: hi only is read -- the GEMM's own form)
-        if (ctx->knobs.gemm4) { g.b4 = ctx->w3_f4; g.b4_kstride = ctx->w3_ks; }
-        XB_HIP(ctx, xb::launch_gemm(g, xb::EPI_SILU_SPLIT, ctx->stream));
-    }
-    // layer l reads gin[l & 1] while the next layer's input projection is written into the other buffer
-    float *gin[2] = {ctx->gin, ctx->gin2 ? ctx->gin2 : ctx->gin};
-    int cur = 0;
-    {
-        const NextGemm first{0, ctx->x_hi[0], ctx->x_lo[0], gin[0], 4 * F, 0};
-        int rc = launch_row_gemm(ctx, first, n, 0, T, ctx->stream);
-        if (rc) return rc;
-    }
-    for (int l = 0; l < 5; ++l) {
-        NextGemm next{l + 1, ctx->x_hi[cur ^ 1], ctx->x_lo[cur ^ 1], l < 4 ? gin[(l + 1) & 1] : scores_out,
-                      l < 4 ? 4 * F : ldc, expand};
-        int rc = run_lstm_layer(ctx, l, n, gin[l & 1], ctx->x_hi[cur ^ 1], ctx->x_lo[cur ^ 1], &next);
-        if (rc) return rc;
-        cur ^= 1;
-    }
-    return XB_OK;
-}
-
-}  // namespace
-
-// the encoder of n chunks into blank-less scores (T, n, ldc), for xb_head.hip (the trainer's forward pass)
-int encoder_run(xb_ctx *ctx, const float *d_signal, int n, float *d_scores, int ldc) { return run_encoder(ctx, d_signal, n, 0, d_scores, ldc); }
-
-// The frozen bottom of a training step (xb_top.hip): run_encoder's launches up to and including LSTM layer `layers` - 1, the
-// last of them without a consumer (next = nullptr: run_lstm_layer then plans no slab GEMM and issues none afterwards).  The
-// output, fp16 hi + fp16 residual, lies in x_hi / x_lo [layers & 1], as the full pass leaves it there on its way up.
-int encoder_bottom_run(xb_ctx *ctx, const float *d_signal, int n, int layers)
-{
-    const xb_config &c = ctx->cfg;
-    const int F = c.features, T = ctx->T;
-    const int nsplit = ctx->ns_conv;
-    if (layers < 0 || layers > 5) return fail(ctx, XB_ERR_INVALID, "the bottom pass runs 0 .. 5 LSTM layers, got %d", layers);
-    if ((layers < 5 ? ctx->ns_in[layers] : ctx->ns_lin) != 3)
-        return fail(ctx, XB_ERR_INVALID, "the bottom pass needs the fp16 residual of layer output %d, which this context's stage arithmetic does not write", layers);
-    ctx->dep_next = 0;
-    ctx->enc_n = layers == 5 ? n : 0;           // below the top, x_hi[1] / x_lo[1] do not hold the last layer's output
-    {
-        StageScope sc(ctx, XB_STAGE_CONV, 2);
-        xb::ConvFrontParams cf{};
-        cf.signal = d_signal; cf.signal2 = nullptr; cf.split = n; cf.N = n; cf.L = c.chunk_len; cf.T = T; cf.winlen = c.winlen; cf.stride = c.stride;
-        cf.kp = ctx->kp; cf.w1 = ctx->w1; cf.b1 = ctx->b1; cf.w2 = ctx->w2; cf.b2 = ctx->b2;
-        cf.a_hi = ctx->im_hi; cf.a_lo = ctx->im_lo; cf.q8 = nsplit == 2;
-        XB_HIP(ctx, xb::launch_conv_front(cf, ctx->stream));
-        xb::GemmParams g{};
-        g.a_hi = ctx->im_hi; g.a_lo = ctx->im_lo; g.b_hi = ctx->w3_hi; g.b_lo = ctx->w3_lo;
-        g.M = T * n; g.Nn = F; g.K = ctx->kp; g.lda = ctx->kp; g.ldb = ctx->kp;
-        g.bias = ctx->b3; g.out_hi = ctx->x_hi[0]; g.out_lo = ctx->x_lo[0]; g.ldc = F; g.nsplit = nsplit;
-        g.a_exp = 0; g.b_exp = ctx->w3_exp; g.out_exp = 0;
-        g.out_fmt = second_part(ctx->ns_in[0]);
-        if (ctx->knobs.gemm4) { g.b4 = ctx->w3_f4; g.b4_kstride = ctx->w3_ks; }
-        XB_HIP(ctx, xb::launch_gemm(g, xb::EPI_SILU_SPLIT, ctx->stream));
-    }
-    if (layers == 0) return XB_OK;
-    float *gin[2] = {ctx->gin, ctx->gin2 ? ctx->gin2 : ctx->gin};
-    int cur = 0;
-    {
-        const NextGemm first{0, ctx->x_hi[0], ctx->x_lo[0], gin[0], 4 * F, 0};
-        if (int rc = launch_row_gemm(ctx, first, n, 0, T, ctx->stream)) return rc;
-    }
-    for (int l = 0; l < layers; ++l) {
-        const NextGemm next{l + 1, ctx->x_hi[cur ^ 1], ctx->x_lo[cur ^ 1], gin[(l + 1) & 1], 4 * F, 0};
-        if (int rc = run_lstm_layer(ctx, l, n, gin[l & 1], ctx->x_hi[cur ^ 1], ctx->x_lo[cur ^ 1], l + 1 < layers ? &next : nullptr)) return rc;
-        cur ^= 1;
-    }
-    return XB_OK;
-}
-
-namespace {
-
-// optional outputs of the Log scans (xb_crf_logz / xb_crf_scans)
-struct ScanOut {
-    float *alpha = nullptr, *beta = nullptr, *logz = nullptr, *post = nullptr;   // device; post has row stride ldq
-};
-
-// out: the outputs of level 1 and 2 (the quality variant writes its beta rows into the beta stash); null for level 0
-int run_decode(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, int ld, const char *alphabet,
-               int8_t *d_labels, int8_t *d_seq, int32_t *d_len, hipStream_t st = nullptr, const ScanOut *scan = nullptr,
-               const DecodeOut *out = nullptr)
-{
-    if (!st) st = ctx->stream;
-    const xb_config &c = ctx->cfg;
-    if (T < 1 || T > ctx->T) return fail(ctx, XB_ERR_INVALID, "T=%d outside [1, %d]", T, ctx->T);
-    xb::DecodeParams p{};
-    p.scores = d_scores; p.T = T; p.N = n; p.S = ctx->S; p.hi = ctx->hi; p.nb = c.n_base;
-    p.cin = has_blank ? ctx->S * (c.n_base + 1) : ctx->S * c.n_base;
-    p.ld = ld; p.has_blank = has_blank; p.blank = c.blank_score;
-    p.alpha = ctx->alpha; p.beta = ctx->beta; p.bmax = ctx->bmax;
-    p.qbuf = ctx->qbuf; p.ldq = (ctx->S * (c.n_base + 1) + 3) & ~3;
-    if (scan) {
-        if (scan->alpha) p.alpha = scan->alpha;
-        p.logz = scan->logz;
-        p.beta_out = scan->beta;
-        if (scan->post) { p.qbuf = scan->post; p.post_mode = 1; }
-        p.stop_after = (scan->beta || scan->post) ? 2 : 1;
-    }
-    p.labels = d_labels; p.seq = d_seq; p.seq_len = d_len;
-    if (out && out->level >= 1) {
-        if (!out->qstr || !d_seq) return fail(ctx, XB_ERR_INVALID, "qualities need the seq and qstring outputs");
-        p.qstr = out->qstr; p.moves = out->moves; p.qscale = out->qscale; p.qoffset = out->qoffset;
-        p.beta_out = ctx->beta;
-        if (out->level == 2) {
-            if (!ctx->u_buf) return fail(ctx, XB_ERR_INVALID, "letter probabilities need their workspace");
-            p.probs = out->probs; p.ubuf = ctx->u_buf;
-        }
-    }
-    memset(p.alphabet, 0, sizeof p.alphabet);
-    if (alphabet) {
-        if ((int)strlen(alphabet) < c.n_base + 1) return fail(ctx, XB_ERR_INVALID, "alphabet needs %d symbols", c.n_base + 1);
-        memcpy(p.alphabet, alphabet, (size_t)c.n_base + 1);
-    } else if (d_seq) {
-        return fail(ctx, XB_ERR_INVALID, "alphabet is required when seq is requested");
-    }
-#ifdef XB_LSTM_STAMPS
-    if (const char *e = getenv("XB_DECODE_STOP")) p.debug_stop = atoi(e);
-    if (const char *e = getenv("XB_DECODE_LINEAR_LDS")) p.debug_lds = atoi(e);
-#endif
-    StageScope sc(ctx, XB_STAGE_DECODE, 1, st);
-    hipError_t e = xb::launch_crf_decode(p, st);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorInvalidValue ? XB_ERR_INVALID : XB_ERR_HIP, "crf decode launch failed: %s", hipGetErrorString(e));
-    return XB_OK;
-}
-
-template <typename Tp>
-int dev_alloc_once(xb_ctx *ctx, Tp **out, size_t count) { return *out ? XB_OK : ctx->mem_ctx.alloc(ctx, out, count); }
-
-// device staging and workspace of an output level (once per context; level 2 includes level 1's).  The pair planes exist
-// only where calls can pair (enqueue_call pairs none of a level while they are missing).
-int ensure_staging(xb_ctx *ctx, int level)
-{
-    const size_t NT = (size_t)ctx->cfg.max_batch * ctx->T, NPT = NT * ctx->cfg.n_base;
-    const bool pairs = ctx->fuse_ok != 0;
-    int rc = XB_OK;
-    if (level >= 1) {
-        rc = rc ? rc : dev_alloc_once(ctx, &ctx->q_seq, NT);
-        rc = rc ? rc : dev_alloc_once(ctx, &ctx->q_moves, NT);
-        if (pairs) rc = rc ? rc : dev_alloc_once(ctx, &ctx->q_fseq, 2 * NT);
-        if (pairs) rc = rc ? rc : dev_alloc_once(ctx, &ctx->q_fmoves, 2 * NT);
-    }
-    if (level == 2) {
-        rc = rc ? rc : dev_alloc_once(ctx, &ctx->u_buf, (pairs ? 2 : 1) * NPT);
-        rc = rc ? rc : dev_alloc_once(ctx, &ctx->u_probs, NPT);
-        if (pairs) rc = rc ? rc : dev_alloc_once(ctx, &ctx->u_fprobs, 2 * NPT);
-    }
-    return rc;
-}
-
-// the device staging of a host-pointer call with outputs o: the same level and calibration, moves only where o has them
-DecodeOut staging_of(const xb_ctx *ctx, const DecodeOut &o)
-{
-    DecodeOut d = o;
-    d.qstr = ctx->q_seq; d.moves = o.moves ? ctx->q_moves : nullptr; d.probs = ctx->u_probs;
-    return d;
-}
-
-// chunks [c0, c0 + n) of the planes of a level from src to chunks [0, n) of dst (rows of T steps); planes null on either
-// side are skipped
-int copy_planes(xb_ctx *ctx, int level, const Planes &dst, const Planes &src, int c0, int n, int T, hipMemcpyKind kind,
-                hipStream_t st)
-{
-    for (int i = 0; i < plane_count(level); ++i) {
-        const size_t b = plane_bytes(T, ctx->cfg.n_base, i);
-        if (dst.p[i] && src.p[i])
-            XB_HIP(ctx, hipMemcpyAsync(dst.p[i], static_cast<const char *>(src.p[i]) + (size_t)c0 * b, (size_t)n * b, kind, st));
-    }
     return XB_OK;
 }
 
@@ -592,72 +182,6 @@ int sync_all(xb_ctx *ctx)
     return XB_OK;
 }
 
-}  // namespace
-
-// The validation loss of n chunks from device-resident RAW scores (T, n, ld), for xb_api_data.hip (xb_ctc_loss, xb_validate_chunks):
-// the Log forward scan leaves logZ_crf in the decode's own (max_batch) buffer, the CTC forward scan of the labels reads it
-// there.  Two launches on the main stream, nothing waited for; the callers have checked n and the pointers.
-int ctc_loss_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int n, int has_blank, int ld, const uint8_t *d_targets,
-                 int Lt, const int32_t *d_len, float *d_loss, float *d_logz)
-{
-    const xb_config &c = ctx->cfg;
-    const int np = Lt - (c.state_len - 1);
-    if (np < 1 || np > xb::ctc_max_positions())
-        return fail(ctx, XB_ERR_INVALID, "%s: target width %d gives %d positions, supported: 1..%d", who, Lt, np, xb::ctc_max_positions());
-    ScanOut so;
-    so.logz = ctx->logz;
-    if (int rc = run_decode(ctx, d_scores, T, n, has_blank, ld, nullptr, nullptr, nullptr, nullptr, nullptr, &so)) return rc;
-    xb::CtcLossParams p{};
-    p.scores = d_scores; p.T = T; p.N = n; p.ld = ld; p.has_blank = has_blank; p.blank = c.blank_score;
-    p.nb = c.n_base; p.sl = c.state_len; p.targets = d_targets; p.Lt = Lt; p.tlen = d_len;
-    p.logz_crf = ctx->logz; p.loss = d_loss; p.logz = d_logz; p.error = ctx->error_data;
-    if (const char *e = getenv("XB_CTC_LOSS_THREADS")) p.threads = atoi(e);
-    StageScope sc(ctx, XB_STAGE_DECODE, 1);
-    hipError_t e = xb::launch_ctc_loss(p, ctx->stream);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorInvalidValue ? XB_ERR_INVALID : XB_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
-    return XB_OK;
-}
-
-// The loss and d loss / d scores of n chunks from device-resident RAW scores (T, n, ld), for xb_api_data.hip (xb_ctc_loss_grad): the
-// Log scans leave logZ_crf and the edge posteriors in the decode's own workspaces (logz, qbuf); the lattice kernel runs over
-// as many chunks per launch as the stash bound holds, then the fill kernel over all.  All on the main stream, nothing waited for
-// unless a workspace grows.
-int ctc_grad_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int n, int has_blank, int ld, const uint8_t *d_targets,
-                 int Lt, const int32_t *d_len, float loss_clip, int mean, float *d_loss, float *d_grad)
-{
-    const xb_config &c = ctx->cfg;
-    const int np = Lt - (c.state_len - 1);
-    if (np < 1 || np > xb::ctc_max_positions())
-        return fail(ctx, XB_ERR_INVALID, "%s: target width %d gives %d positions, supported: 1..%d", who, Lt, np, xb::ctc_max_positions());
-    const size_t slot = xb::ctc_grad_slot_floats(T, np);
-    const size_t per_launch = xb::ctc_grad_chunks_per_launch(T, np, n, xb::ctc_scratch_bound(getenv("XB_CTC_SCRATCH_MB")));
-    if (int rc = grow(ctx, &ctx->ctcgrad.stash, per_launch * slot * sizeof(float))) return rc;
-    if (int rc = grow(ctx, &ctx->ctcgrad.w, sizeof(float) * (size_t)c.max_batch)) return rc;
-    ScanOut so;
-    so.logz = ctx->logz; so.post = ctx->qbuf;
-    if (int rc = run_decode(ctx, d_scores, T, n, has_blank, ld, nullptr, nullptr, nullptr, nullptr, nullptr, &so)) return rc;
-    xb::CtcGradParams q{};
-    xb::CtcLossParams &p = q.l;
-    p.scores = d_scores; p.T = T; p.N = n; p.ld = ld; p.has_blank = has_blank; p.blank = c.blank_score;
-    p.nb = c.n_base; p.sl = c.state_len; p.targets = d_targets; p.Lt = Lt; p.tlen = d_len;
-    p.logz_crf = ctx->logz; p.loss = d_loss; p.error = ctx->error_data;
-    if (const char *e = getenv("XB_CTC_LOSS_THREADS")) p.threads = atoi(e);
-    q.post = ctx->qbuf; q.ldq = (ctx->S * (c.n_base + 1) + 3) & ~3;
-    q.stash = static_cast<float *>(ctx->ctcgrad.stash.p); q.slot = slot;
-    q.loss_clip = loss_clip; q.mean = mean ? 1 : 0;
-    q.w = static_cast<float *>(ctx->ctcgrad.w.p); q.grad = d_grad;
-    for (size_t first = 0; first < (size_t)n; first += per_launch) {
-        q.first = (int)first;
-        q.count = (int)std::min<size_t>(per_launch, (size_t)n - first);
-        hipError_t e = xb::launch_ctc_grad(q, ctx->stream);
-        if (e != hipSuccess) return fail(ctx, e == hipErrorInvalidValue ? XB_ERR_INVALID : XB_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
-    }
-    hipError_t e = xb::launch_ctc_grad_fill(q, ctx->stream);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorInvalidValue ? XB_ERR_INVALID : XB_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
-    return XB_OK;
-}
-
-// ===========================================================================================
 extern "C" {
 
 XB_API const char *xb_version(void) { return "xnacall 0.1.0 (gfx950)"; }
@@ -1013,692 +537,6 @@ XB_API int xb_stream_wait_event(xb_ctx *ctx, void *hip_event)
     XB_HIP(ctx, hipStreamWaitEvent(ctx->stream, ev, 0));
     if (ctx->stream3) XB_HIP(ctx, hipStreamWaitEvent(ctx->stream3, ev, 0));
     return XB_OK;
-}
-
-XB_API int xb_encode_dev(xb_ctx *ctx, const float *d_signal, int n, int expand_blanks, float *d_scores)
-{
-    int rc = check_ready(ctx, n);
-    if (rc) return rc;
-    if (!d_signal || !d_scores) return fail(ctx, XB_ERR_INVALID, "null device pointer");
-    if ((rc = enter(ctx, true))) return rc;
-    const int ldc = expand_blanks ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
-    return run_encoder(ctx, d_signal, n, expand_blanks ? 1 : 0, d_scores, ldc);
-}
-
-XB_API int xb_encode(xb_ctx *ctx, const float *signal, int n, int expand_blanks, float *scores)
-{
-    int rc = check_ready(ctx, n);
-    if (rc) return rc;
-    if (!signal || !scores) return fail(ctx, XB_ERR_INVALID, "null host pointer");
-    if ((rc = enter(ctx, false))) return rc;
-    XB_HIP(ctx, hipMemcpyAsync(ctx->d_signal, signal, sizeof(float) * (size_t)n * ctx->cfg.chunk_len,
-                               hipMemcpyHostToDevice, ctx->stream));
-    const int ldc = expand_blanks ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
-    rc = run_encoder(ctx, ctx->d_signal, n, expand_blanks ? 1 : 0, ctx->scores, ldc);
-    if (rc) return rc;
-    XB_HIP(ctx, hipMemcpyAsync(scores, ctx->scores, sizeof(float) * (size_t)ctx->T * n * ldc, hipMemcpyDeviceToHost,
-                               ctx->stream));
-    return xb_synchronize(ctx);
-}
-
-// the device-pointer decodes: labels (level 0 only), the bases and the outputs of o's level, on the main stream
-static int decode_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const char *alphabet, int8_t *d_labels,
-                      int8_t *d_seq, int32_t *d_seq_len, const DecodeOut &o)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
-    if (o.level == 0 && !d_scores) return fail(ctx, XB_ERR_INVALID, "null device pointer");
-    if (o.level >= 1 && (!d_scores || !has_required(planes(d_seq, d_seq_len, o), o.level) || !alphabet))
-        return fail(ctx, XB_ERR_INVALID, "null argument");
-    if (int rc = enter(ctx, true)) return rc;
-    if (o.level == 2)                                 // the letter mass workspace
-        if (int rc = ensure_staging(ctx, 2)) return rc;
-    const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
-    return run_decode(ctx, d_scores, T, n, has_blank ? 1 : 0, ld, alphabet, d_labels, d_seq, d_seq_len, nullptr, nullptr, &o);
-}
-
-// the host-pointer decodes: through the context's staging; labels and a null seq at level 0 only
-static int decode_host(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, const char *alphabet, int8_t *labels,
-                       int8_t *seq, int32_t *seq_len, const DecodeOut &o)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
-    const Planes dst = planes(seq, seq_len, o);
-    if (o.level == 0 && !scores) return fail(ctx, XB_ERR_INVALID, "null host pointer");
-    if (o.level >= 1 && (!scores || !has_required(dst, o.level) || !alphabet)) return fail(ctx, XB_ERR_INVALID, "null argument");
-    if (T < 1 || T > ctx->T) return fail(ctx, XB_ERR_INVALID, "T=%d outside [1, %d]", T, ctx->T);
-    if (int rcj = enter(ctx, false)) return rcj;
-    if (o.level)
-        if (int rcs = ensure_staging(ctx, o.level)) return rcs;
-    const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
-    XB_HIP(ctx, hipMemcpyAsync(ctx->scores, scores, sizeof(float) * (size_t)T * n * ld, hipMemcpyHostToDevice, ctx->stream));
-    const DecodeOut d = staging_of(ctx, o);
-    int rc = run_decode(ctx, ctx->scores, T, n, has_blank ? 1 : 0, ld, alphabet, o.level ? nullptr : ctx->labels,
-                        seq ? ctx->seq : nullptr, ctx->seq_len, nullptr, nullptr, &d);
-    if (rc) return rc;
-    if (labels) XB_HIP(ctx, hipMemcpyAsync(labels, ctx->labels, (size_t)n * T, hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = copy_planes(ctx, o.level, dst, planes(ctx->seq, ctx->seq_len, d), 0, n, T, hipMemcpyDeviceToHost, ctx->stream)))
-        return rc;
-    return xb_synchronize(ctx);
-}
-
-XB_API int xb_decode_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const char *alphabet,
-                         int8_t *d_labels, int8_t *d_seq, int32_t *d_seq_len)
-{
-    return decode_dev(ctx, d_scores, T, n, has_blank, alphabet, d_labels, d_seq, d_seq_len, {});
-}
-
-XB_API int xb_decode(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, const char *alphabet,
-                     int8_t *labels, int8_t *seq, int32_t *seq_len)
-{
-    return decode_host(ctx, scores, T, n, has_blank, alphabet, labels, seq, seq_len, {});
-}
-
-XB_API int xb_decode_q_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const char *alphabet, float qscale,
-                           float qoffset, int8_t *d_seq, int8_t *d_qstring, uint8_t *d_moves, int32_t *d_seq_len)
-{
-    return decode_dev(ctx, d_scores, T, n, has_blank, alphabet, nullptr, d_seq, d_seq_len, {1, qscale, qoffset, d_qstring, d_moves});
-}
-
-XB_API int xb_decode_q(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, const char *alphabet, float qscale,
-                       float qoffset, int8_t *seq, int8_t *qstring, uint8_t *moves, int32_t *seq_len)
-{
-    return decode_host(ctx, scores, T, n, has_blank, alphabet, nullptr, seq, seq_len, {1, qscale, qoffset, qstring, moves});
-}
-
-XB_API int xb_decode_ub_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const char *alphabet,
-                            float qscale, float qoffset, int8_t *d_seq, int8_t *d_qstring, uint8_t *d_moves, uint8_t *d_probs,
-                            int32_t *d_seq_len)
-{
-    return decode_dev(ctx, d_scores, T, n, has_blank, alphabet, nullptr, d_seq, d_seq_len,
-                      {2, qscale, qoffset, d_qstring, d_moves, d_probs});
-}
-
-XB_API int xb_decode_ub(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, const char *alphabet, float qscale,
-                        float qoffset, int8_t *seq, int8_t *qstring, uint8_t *moves, uint8_t *probs, int32_t *seq_len)
-{
-    return decode_host(ctx, scores, T, n, has_blank, alphabet, nullptr, seq, seq_len, {2, qscale, qoffset, qstring, moves, probs});
-}
-
-XB_API int xb_crf_scans_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, float *d_alpha, float *d_beta,
-                            float *d_logz, float *d_post)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
-    if (!d_scores) return fail(ctx, XB_ERR_INVALID, "null device pointer");
-    if (!d_alpha && !d_beta && !d_logz && !d_post) return fail(ctx, XB_ERR_INVALID, "no output requested");
-    if (int rc = enter(ctx, true)) return rc;       // the scans run on the main stream (not on the async decode stream)
-    const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
-    ScanOut so;
-    so.alpha = d_alpha; so.beta = d_beta; so.logz = d_logz; so.post = d_post;
-    return run_decode(ctx, d_scores, T, n, has_blank ? 1 : 0, ld, nullptr, nullptr, nullptr, nullptr, nullptr, &so);
-}
-
-XB_API int xb_crf_scans(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, float *alpha, float *beta, float *logz,
-                        float *post)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
-    if (!scores) return fail(ctx, XB_ERR_INVALID, "null host pointer");
-    if (!alpha && !beta && !logz && !post) return fail(ctx, XB_ERR_INVALID, "no output requested");
-    if (T < 1 || T > ctx->T) return fail(ctx, XB_ERR_INVALID, "T=%d outside [1, %d]", T, ctx->T);
-    if (int rcj = enter(ctx, false)) return rcj;
-    const int S = ctx->S, E = ctx->cfg.n_base + 1;
-    const int ld = has_blank ? S * E : ctx->O;
-    XB_HIP(ctx, hipMemcpyAsync(ctx->scores, scores, sizeof(float) * (size_t)T * n * ld, hipMemcpyHostToDevice, ctx->stream));
-    // device staging in the decode's own workspaces: alpha -> its stash, beta -> the (otherwise unused) beta stash, P -> the
-    // Q buffer (row stride ldq), logZ -> its own (max_batch) buffer
-    const int ldq = (S * E + 3) & ~3;
-    ScanOut so;
-    so.alpha = ctx->alpha; so.beta = beta ? ctx->beta : nullptr; so.post = post ? ctx->qbuf : nullptr;
-    so.logz = logz ? ctx->logz : nullptr;
-    int rc = run_decode(ctx, ctx->scores, T, n, has_blank ? 1 : 0, ld, nullptr, nullptr, nullptr, nullptr, nullptr, &so);
-    if (rc) return rc;
-    const size_t sv = sizeof(float) * (size_t)(T + 1) * n * S;
-    if (alpha) XB_HIP(ctx, hipMemcpyAsync(alpha, ctx->alpha, sv, hipMemcpyDeviceToHost, ctx->stream));
-    if (beta) XB_HIP(ctx, hipMemcpyAsync(beta, ctx->beta, sv, hipMemcpyDeviceToHost, ctx->stream));
-    if (logz) XB_HIP(ctx, hipMemcpyAsync(logz, so.logz, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (post)
-        XB_HIP(ctx, hipMemcpy2DAsync(post, sizeof(float) * (size_t)S * E, ctx->qbuf, sizeof(float) * (size_t)ldq,
-                                     sizeof(float) * (size_t)S * E, (size_t)T * n, hipMemcpyDeviceToHost, ctx->stream));
-    return xb_synchronize(ctx);
-}
-
-XB_API int xb_crf_logz_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, float *d_logz)
-{
-    return xb_crf_scans_dev(ctx, d_scores, T, n, has_blank, nullptr, nullptr, d_logz, nullptr);
-}
-
-XB_API int xb_crf_logz(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, float *logz)
-{
-    return xb_crf_scans(ctx, scores, T, n, has_blank, nullptr, nullptr, logz, nullptr);
-}
-
-// prepare_ctc_scores' gather columns (crf/model.py:102-116) for n targets of Lt labels: np = Lt - (sl - 1) positions
-static void ctc_indices(const int32_t *targets, int n, int Lt, int nb, int sl, std::vector<int32_t> &stay, std::vector<int32_t> &move)
-{
-    const int np = Lt - (sl - 1), E = nb + 1;
-    stay.assign((size_t)n * np, 0);
-    move.assign((size_t)n * (np > 1 ? np - 1 : 1), 0);
-    for (int b = 0; b < n; ++b) {
-        for (int l = 0; l < np; ++l) {
-            int64_t st = 0;
-            for (int i = 0; i < sl; ++i) {
-                const int v = std::max(targets[(size_t)b * Lt + l + i] - 1, 0);        // torch.clamp(targets - 1, 0)
-                st += (int64_t)v * ipow(nb, sl - i - 1);
-            }
-            stay[(size_t)b * np + l] = (int32_t)(st * E);
-        }
-        for (int l = 0; l + 1 < np; ++l)
-            move[(size_t)b * (np - 1) + l] = stay[(size_t)b * np + l + 1] + std::max(targets[(size_t)b * Lt + l] - 1, 0) + 1;
-    }
-}
-
-static int run_ctc(xb_ctx *ctx, const float *scores, int T, int n, const int32_t *targets, int Lt, const int32_t *tlen,
-                   int semiring, float *logz, float *gstay, float *gmove)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    const int sl = ctx->cfg.state_len, nb = ctx->cfg.n_base, S = ctx->S, C = S * (nb + 1);
-    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
-    if (T < 1 || T > ctx->T) return fail(ctx, XB_ERR_INVALID, "T=%d outside [1, %d]", T, ctx->T);
-    if (!scores || !targets || !tlen) return fail(ctx, XB_ERR_INVALID, "null host pointer");
-    if (!logz && !gstay && !gmove) return fail(ctx, XB_ERR_INVALID, "no output requested");
-    const int np = Lt - (sl - 1);
-    if (np < 1 || np > xb::ctc_max_positions())
-        return fail(ctx, XB_ERR_INVALID, "target width %d gives %d positions, supported: 1..%d", Lt, np, xb::ctc_max_positions());
-    for (int b = 0; b < n; ++b) {
-        if (tlen[b] < sl || tlen[b] > Lt)
-            return fail(ctx, XB_ERR_INVALID, "target_lengths[%d] = %d outside [state_len = %d, %d]", b, tlen[b], sl, Lt);
-        for (int l = 0; l < Lt; ++l)
-            if (targets[(size_t)b * Lt + l] < 0 || targets[(size_t)b * Lt + l] > nb)
-                return fail(ctx, XB_ERR_INVALID, "targets[%d][%d] = %d outside [0, n_base = %d]", b, l, targets[(size_t)b * Lt + l], nb);
-    }
-    if (int rcj = enter(ctx, true)) return rcj;             // (a host form that has always named the main stream)
-    std::vector<int32_t> stay, move;
-    ctc_indices(targets, n, Lt, nb, sl, stay, move);
-    const size_t nm = np > 1 ? np - 1 : 1;
-    // per-call device scratch (a training-side operator: sizes follow the targets, not the context), freed on every return
-    DevBuf b_stay, b_move, b_len, b_alpha, b_gs, b_gm;
-    const bool grads = gstay || gmove;
-    if (int rc = b_stay.alloc(ctx, sizeof(int32_t) * stay.size())) return rc;
-    if (int rc = b_move.alloc(ctx, sizeof(int32_t) * move.size())) return rc;
-    if (int rc = b_len.alloc(ctx, sizeof(int32_t) * (size_t)n)) return rc;
-    if (grads) {
-        if (int rc = b_alpha.alloc(ctx, sizeof(float) * (size_t)n * (T + 1) * np)) return rc;
-        if (int rc = b_gs.alloc(ctx, sizeof(float) * (size_t)T * n * np)) return rc;
-        if (gmove)
-            if (int rc = b_gm.alloc(ctx, sizeof(float) * (size_t)T * n * nm)) return rc;
-    }
-    int32_t *d_stay = static_cast<int32_t *>(b_stay.p), *d_move = static_cast<int32_t *>(b_move.p), *d_len = static_cast<int32_t *>(b_len.p);
-    float *d_alpha = static_cast<float *>(b_alpha.p), *d_gs = static_cast<float *>(b_gs.p), *d_gm = static_cast<float *>(b_gm.p);
-    hipStream_t st = ctx->stream;
-    XB_HIP(ctx, hipMemcpyAsync(d_stay, stay.data(), sizeof(int32_t) * stay.size(), hipMemcpyHostToDevice, st));
-    XB_HIP(ctx, hipMemcpyAsync(d_move, move.data(), sizeof(int32_t) * move.size(), hipMemcpyHostToDevice, st));
-    XB_HIP(ctx, hipMemcpyAsync(d_len, tlen, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
-    XB_HIP(ctx, hipMemcpyAsync(ctx->scores, scores, sizeof(float) * (size_t)T * n * C, hipMemcpyHostToDevice, st));
-    if (d_gs) XB_HIP(ctx, hipMemsetAsync(d_gs, 0, sizeof(float) * (size_t)T * n * np, st));
-    if (d_gm) XB_HIP(ctx, hipMemsetAsync(d_gm, 0, sizeof(float) * (size_t)T * n * nm, st));
-    xb::CtcParams p{};
-    p.scores = ctx->scores; p.T = T; p.N = n; p.C = C; p.stay_idx = d_stay; p.move_idx = d_move; p.n = np; p.tlen = d_len;
-    p.sl = sl; p.semiring = semiring; p.alpha = d_alpha; p.logz = ctx->logz; p.gstay = d_gs; p.gmove = d_gm; p.error = ctx->error_data;
-    XB_HIP(ctx, xb::launch_ctc_scan(p, st));
-    if (logz) XB_HIP(ctx, hipMemcpyAsync(logz, ctx->logz, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, st));
-    if (gstay) XB_HIP(ctx, hipMemcpyAsync(gstay, d_gs, sizeof(float) * (size_t)T * n * np, hipMemcpyDeviceToHost, st));
-    if (gmove && np > 1) XB_HIP(ctx, hipMemcpyAsync(gmove, d_gm, sizeof(float) * (size_t)T * n * nm, hipMemcpyDeviceToHost, st));
-    XB_HIP(ctx, hipStreamSynchronize(st));
-    return check_device_error(ctx);
-}
-
-XB_API int xb_ctc_logz(xb_ctx *ctx, const float *scores, int T, int n, const int32_t *targets, int Lt,
-                       const int32_t *target_lengths, float *logz, float *gstay, float *gmove)
-{
-    return run_ctc(ctx, scores, T, n, targets, Lt, target_lengths, 0, logz, gstay, gmove);
-}
-
-XB_API int xb_ctc_alignments(xb_ctx *ctx, const float *scores, int T, int n, const int32_t *targets, int Lt,
-                             const int32_t *target_lengths, float *alignments, float *max_score)
-{
-    if (!alignments) return fail(ctx, XB_ERR_INVALID, "null host pointer");
-    return run_ctc(ctx, scores, T, n, targets, Lt, target_lengths, 1, max_score, alignments, nullptr);
-}
-
-// beam search over device-resident scores: the Log scans (alpha, beta, logZ) into the decode workspaces, then one wave per chunk
-static int run_beam(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, int ld, const char *alphabet, int beam_width,
-                    float beam_cut, float qscale, float qoffset, int8_t *d_seq, int8_t *d_q, uint8_t *d_moves, float *d_score)
-{
-    const xb_config &c = ctx->cfg;
-    if (beam_width < 1 || beam_width > xb::BEAM_MAX_WIDTH)
-        return fail(ctx, XB_ERR_INVALID, "beam_width %d outside [1, %d]", beam_width, xb::BEAM_MAX_WIDTH);
-    if (ctx->S > xb::BEAM_MAX_STATES) return fail(ctx, XB_ERR_INVALID, "beam search supports at most %d states", xb::BEAM_MAX_STATES);
-    if (!alphabet || (int)strlen(alphabet) < c.n_base + 1) return fail(ctx, XB_ERR_INVALID, "alphabet needs %d symbols", c.n_base + 1);
-    if (!ctx->beam_hist) {
-        const size_t N = (size_t)c.max_batch, Tm = (size_t)ctx->T;
-        DevPool &mem = ctx->mem_ctx;
-        int rc = mem.alloc(ctx, &ctx->beam_hist, N * (Tm + 1) * xb::BEAM_MAX_WIDTH);
-        rc = rc ? rc : mem.alloc(ctx, &ctx->beam_path, N * Tm);
-        rc = rc ? rc : mem.alloc(ctx, &ctx->beam_prob, N * Tm);
-        rc = rc ? rc : mem.alloc(ctx, &ctx->beam_score, N);
-        rc = rc ? rc : mem.alloc(ctx, &ctx->beam_seq, N * Tm);
-        rc = rc ? rc : mem.alloc(ctx, &ctx->beam_q, N * Tm);
-        rc = rc ? rc : mem.alloc(ctx, &ctx->beam_moves, N * Tm);
-        if (rc) { ctx->beam_hist = nullptr; return rc; }
-    }
-    ScanOut so;
-    so.alpha = ctx->alpha; so.beta = ctx->beta; so.logz = ctx->logz;
-    int rc = run_decode(ctx, d_scores, T, n, has_blank, ld, nullptr, nullptr, nullptr, nullptr, nullptr, &so);
-    if (rc) return rc;
-    xb::BeamParams p{};
-    p.scores = d_scores; p.ld = ld; p.has_blank = has_blank; p.blank = c.blank_score;
-    p.alpha = ctx->alpha; p.beta = ctx->beta; p.logz = ctx->logz;
-    p.T = T; p.N = n; p.S = ctx->S; p.nb = c.n_base; p.hi = ctx->hi;
-    p.W = beam_width;
-    p.log_cut = beam_cut > 0.0f ? (float)log((double)beam_cut) : 3.402823466e+38f;
-    p.qscale = qscale; p.qoffset = qoffset;
-    memset(p.base_chars, 0, sizeof p.base_chars);
-    memcpy(p.base_chars, alphabet + 1, (size_t)c.n_base);
-    p.hist = ctx->beam_hist; p.path = ctx->beam_path; p.prob = ctx->beam_prob;
-    p.seq = d_seq ? d_seq : ctx->beam_seq; p.qstr = d_q ? d_q : ctx->beam_q; p.moves = d_moves ? d_moves : ctx->beam_moves;
-    p.score = d_seq ? d_score : ctx->beam_score;
-    StageScope sc(ctx, XB_STAGE_DECODE, 1, ctx->stream);
-    hipError_t e = xb::launch_beam_search(p, ctx->stream);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorInvalidValue ? XB_ERR_INVALID : XB_ERR_HIP, "beam search launch failed: %s", hipGetErrorString(e));
-    return XB_OK;
-}
-
-XB_API int xb_beam_search_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const char *alphabet,
-                              int beam_width, float beam_cut, float qscale, float qoffset, int8_t *d_sequence, int8_t *d_qstring,
-                              uint8_t *d_moves, float *d_score)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
-    if (!d_scores || !d_sequence || !d_qstring || !d_moves) return fail(ctx, XB_ERR_INVALID, "null device pointer");
-    if (T < 1 || T > ctx->T) return fail(ctx, XB_ERR_INVALID, "T=%d outside [1, %d]", T, ctx->T);
-    if (int rc = enter(ctx, true)) return rc;
-    const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
-    return run_beam(ctx, d_scores, T, n, has_blank ? 1 : 0, ld, alphabet, beam_width, beam_cut, qscale, qoffset, d_sequence,
-                    d_qstring, d_moves, d_score);
-}
-
-// the three (n, T) byte planes and the optional path scores back to the host
-static int beam_results_to_host(xb_ctx *ctx, int T, int n, int8_t *sequence, int8_t *qstring, uint8_t *moves, float *score)
-{
-    const size_t nt = (size_t)n * T;
-    XB_HIP(ctx, hipMemcpyAsync(sequence, ctx->beam_seq, nt, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(qstring, ctx->beam_q, nt, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(moves, ctx->beam_moves, nt, hipMemcpyDeviceToHost, ctx->stream));
-    if (score) XB_HIP(ctx, hipMemcpyAsync(score, ctx->beam_score, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    return xb_synchronize(ctx);
-}
-
-XB_API int xb_beam_search(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, const char *alphabet, int beam_width,
-                          float beam_cut, float qscale, float qoffset, int8_t *sequence, int8_t *qstring, uint8_t *moves,
-                          float *score)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "batch %d outside [1, max_batch=%d]", n, ctx->cfg.max_batch);
-    if (!scores || !sequence || !qstring || !moves) return fail(ctx, XB_ERR_INVALID, "null host pointer");
-    if (T < 1 || T > ctx->T) return fail(ctx, XB_ERR_INVALID, "T=%d outside [1, %d]", T, ctx->T);
-    if (int rcj = enter(ctx, true)) return rcj;             // (a host form that has always named the main stream)
-    const int ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
-    XB_HIP(ctx, hipMemcpyAsync(ctx->scores, scores, sizeof(float) * (size_t)T * n * ld, hipMemcpyHostToDevice, ctx->stream));
-    // the first call allocates the staging planes inside run_beam; pass them after the allocation
-    int rc = run_beam(ctx, ctx->scores, T, n, has_blank ? 1 : 0, ld, alphabet, beam_width, beam_cut, qscale, qoffset, nullptr,
-                      nullptr, nullptr, nullptr);
-    if (rc) return rc;
-    return beam_results_to_host(ctx, T, n, sequence, qstring, moves, score);
-}
-
-// signal chunks -> encoder (scores without the blank column, as the reference's beam branch sees them) -> beam search
-XB_API int xb_basecall_chunks_beam(xb_ctx *ctx, const float *signal, int n, const char *alphabet, int beam_width, float beam_cut,
-                                   float qscale, float qoffset, int8_t *sequence, int8_t *qstring, uint8_t *moves, float *score)
-{
-    int rc = check_ready(ctx, n);
-    if (rc) return rc;
-    if (!signal || !sequence || !qstring || !moves || !alphabet) return fail(ctx, XB_ERR_INVALID, "null argument");
-    if ((rc = enter(ctx, true))) return rc;                 // (a host form that has always named the main stream)
-    XB_HIP(ctx, hipMemcpyAsync(ctx->d_signal, signal, sizeof(float) * (size_t)n * ctx->cfg.chunk_len, hipMemcpyHostToDevice,
-                               ctx->stream));
-    rc = run_encoder(ctx, ctx->d_signal, n, 0, ctx->scores, ctx->ld_nb);
-    if (rc) return rc;
-    rc = run_beam(ctx, ctx->scores, ctx->T, n, 0, ctx->ld_nb, alphabet, beam_width, beam_cut, qscale, qoffset, nullptr, nullptr,
-                  nullptr, nullptr);
-    if (rc) return rc;
-    return beam_results_to_host(ctx, ctx->T, n, sequence, qstring, moves, score);
-}
-
-// room for two co-scheduled calls (once per context; everything in flight is waited for, no held call exists here)
-static int reserve_pairing(xb_ctx *ctx)
-{
-    if (!ctx->fuse_ok) return XB_ERR_STATE;
-    if (ctx->cap >= 2 * ctx->cfg.max_batch) return XB_OK;
-    int rc = sync_all(ctx);
-    if (rc) return rc;
-    rc = alloc_workspaces(ctx, 2 * ctx->cfg.max_batch);
-    if (rc) {                                           // out of memory: back to one call per pass for good
-        ctx->fuse = ctx->fuse_ok = 0;
-        const int rc2 = alloc_workspaces(ctx, ctx->cfg.max_batch);
-        // (should even that fail the context has no workspaces left: cap == 0, and check_ready refuses every call)
-        return rc2 ? rc2 : rc;
-    }
-    return XB_OK;
-}
-
-XB_API int xb_reserve_pairing(xb_ctx *ctx)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = flush_held(ctx)) return rc;
-    if (!ctx->fuse_ok) return XB_OK;                    // this context does not pair calls: every call runs on its own
-    const int rc = reserve_pairing(ctx);
-    if (rc == XB_OK) ctx->fuse = 1;                     // from now on an asynchronous basecall may be held back for its partner
-    return rc;                                          // (XB_ERR_NOMEM: no room for a pair; the context carries on unpaired)
-}
-
-XB_API int xb_pairing_active(const xb_ctx *ctx) { return ctx && ctx->fuse ? 1 : 0; }
-
-// what follows a call's decode on its result stream: the host pipeline's D2H copies and done event, a deferred gather
-static int call_post_actions(xb_ctx *ctx, const xb_ctx::Call &c, hipStream_t rs)
-{
-    if (c.slot >= 0) {
-        xb_ctx::Slot &sl = ctx->slots[c.slot];
-        if (int rc = copy_planes(ctx, c.out.level, sl.h, sl.d, 0, c.n, ctx->T, hipMemcpyDeviceToHost, rs)) return rc;
-        // the sync word as THIS batch left it (stream order: behind its recurrences and its decode), not as whatever batch
-        // happens to be running when the slot is collected finds it
-        XB_HIP(ctx, hipMemcpyAsync(sl.h_err, ctx->error, sizeof(unsigned), hipMemcpyDeviceToHost, rs));
-        XB_HIP(ctx, hipEventRecord(sl.done, rs));
-    }
-    if (c.after) c.after(c.after_arg);
-    return XB_OK;
-}
-
-// The asynchronous basecall of one call, or of two calls as one batch (chunks [0, a.n) = a, [a.n, a.n + b->n) = b).
-static int launch_calls(xb_ctx *ctx, const xb_ctx::Call &a, const xb_ctx::Call *b)
-{
-    const int n = a.n + (b ? b->n : 0);
-    const float *sig2 = b ? b->signal : nullptr;
-    // a pair (enqueue_call: the same level and calibration) decodes into the pair planes, which are then split
-    const Planes fused = {{ctx->fseq, ctx->flen, ctx->q_fseq, ctx->q_fmoves, ctx->u_fprobs}};
-    int8_t *d_seq = b ? ctx->fseq : a.seq;
-    int32_t *d_len = b ? ctx->flen : a.len;
-    DecodeOut out = a.out;
-    if (b) { out.qstr = ctx->q_fseq; out.moves = ctx->q_fmoves; out.probs = ctx->u_fprobs; }
-    int rc;
-    hipStream_t rs;
-    if (!ctx->knobs.overlap || !ctx->stream3 || !ctx->scores2 || !ctx->knobs.decode_async) {
-        rs = ctx->result_stream = ctx->stream;
-        ctx->last_scores = ctx->scores; ctx->last_n = n;
-        rc = run_encoder(ctx, a.signal, n, 0, ctx->scores, ctx->ld_nb, sig2, a.n);
-        if (rc) return rc;
-        rc = run_decode(ctx, ctx->scores, ctx->T, n, 0, ctx->ld_nb, a.alphabet, nullptr, d_seq, d_len, nullptr, nullptr, &out);
-        if (rc) return rc;
-    } else {
-        // asynchronous decode: the encoder of this batch writes score buffer p while the decode of the previous batch may
-        // still be reading buffer p ^ 1 on the third stream; the decode that used buffer p two calls ago must be done first
-        const int pb = (int)(ctx->batch_idx++ & 1u);
-        float *sc = pb ? ctx->scores2 : ctx->scores;
-        ctx->last_scores = sc; ctx->last_n = n;
-        rs = ctx->result_stream = ctx->stream3;
-        if (ctx->dec_pending[pb]) XB_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->dec_done[pb], 0));
-        rc = run_encoder(ctx, a.signal, n, 0, sc, ctx->ld_nb, sig2, a.n);
-        if (rc) return rc;
-        hipEvent_t enc;
-        if ((rc = next_dep(ctx, &enc))) return rc;
-        XB_HIP(ctx, hipEventRecord(enc, ctx->stream));
-        XB_HIP(ctx, hipStreamWaitEvent(ctx->stream3, enc, 0));
-        rc = run_decode(ctx, sc, ctx->T, n, 0, ctx->ld_nb, a.alphabet, nullptr, d_seq, d_len, ctx->stream3, nullptr, &out);
-        if (rc) return rc;
-    }
-    if (b) {        // the pair's rows back to where each caller wants them
-        const int level = a.out.level;
-        if ((rc = copy_planes(ctx, level, planes(a.seq, a.len, a.out), fused, 0, a.n, ctx->T, hipMemcpyDeviceToDevice, rs)))
-            return rc;
-        if ((rc = copy_planes(ctx, level, planes(b->seq, b->len, b->out), fused, a.n, b->n, ctx->T, hipMemcpyDeviceToDevice, rs)))
-            return rc;
-    }
-    if (rs == ctx->stream3) {
-        const int pb = (int)((ctx->batch_idx - 1) & 1u);
-        XB_HIP(ctx, hipEventRecord(ctx->dec_done[pb], ctx->stream3));
-        ctx->dec_pending[pb] = true;
-    }
-    if ((rc = call_post_actions(ctx, a, rs))) return rc;
-    if (b && (rc = call_post_actions(ctx, *b, rs))) return rc;
-    return XB_OK;
-}
-
-// launch a held-back call on its own (every entry point that is not the asynchronous basecall comes through here first)
-int flush_held(xb_ctx *ctx)
-{
-    if (!ctx->holding || ctx->flushing) return XB_OK;
-    ctx->flushing = true;
-    const xb_ctx::Call h = ctx->held;
-    ctx->holding = false;
-    const int rc = launch_calls(ctx, h, nullptr);
-    ctx->flushing = false;
-    if (rc) {                                   // the call itself had already returned XB_OK
-        ctx->pipeline_failed = true;
-        ctx->deferred_rc = rc;                  // ... so the next call that can return a status reports it
-    }
-    return rc;
-}
-
-// Two calls share one pass only where it produces exactly what each produces alone: the same alphabet and output level (and
-// at level >= 1 the same qscale / qoffset), different seq / qstring / probs buffers, at most 2 max_batch chunks, and the
-// level's pair planes in place (enqueue_call then makes room for the pair's workspaces).
-static bool can_pair(const xb_ctx *ctx, const xb_ctx::Call &h, const xb_ctx::Call &c)
-{
-    const DecodeOut &x = h.out, &y = c.out;
-    if (!ctx->fuse || h.n + c.n > 2 * ctx->cfg.max_batch || strcmp(h.alphabet, c.alphabet) != 0 || h.seq == c.seq) return false;
-    if (x.level != y.level) return false;
-    if (x.level >= 1 && (x.qscale != y.qscale || x.qoffset != y.qoffset || x.qstr == y.qstr || !ctx->q_fseq)) return false;
-    if (x.level == 2 && (x.probs == y.probs || !ctx->u_fprobs)) return false;
-    return true;
-}
-
-static int enqueue_call(xb_ctx *ctx, const xb_ctx::Call &c)
-{
-    if (ctx->deferred_rc) {
-        const int rc = ctx->deferred_rc;
-        ctx->deferred_rc = 0;
-        return rc;               // xb_last_error still holds the message of the launch that failed
-    }
-    if (ctx->holding) {
-        const xb_ctx::Call h = ctx->held;
-        ctx->holding = false;
-        bool pair = can_pair(ctx, h, c);
-        if (pair && h.n + c.n > ctx->cap && reserve_pairing(ctx) != XB_OK) pair = false;     // no room for both: one by one
-        if (pair) {
-            const int rc = launch_calls(ctx, h, &c);
-            if (rc) ctx->pipeline_failed = true;
-            return rc;
-        }
-        const int rc = launch_calls(ctx, h, nullptr);
-        if (rc) { ctx->pipeline_failed = true; return rc; }
-    }
-    if (ctx->fuse) {
-        ctx->held = c;
-        ctx->holding = true;
-        return XB_OK;
-    }
-    return launch_calls(ctx, c, nullptr);
-}
-
-int basecall_async(xb_ctx *ctx, const float *d_signal, int n, const char *alphabet, int8_t *seq, int32_t *len, const DecodeOut &out,
-                   int slot)
-{
-    xb_ctx::Call c;
-    c.signal = d_signal; c.n = n; c.seq = seq; c.len = len; c.slot = slot; c.out = out;
-    strcpy(c.alphabet, alphabet);
-    return enqueue_call(ctx, c);
-}
-
-XB_API int xb_basecall_chunks_dev(xb_ctx *ctx, const float *d_signal, int n, const char *alphabet, int8_t *d_seq,
-                                  int32_t *d_seq_len)
-{
-    int rc = check_ready(ctx, n);
-    if (rc) return rc;
-    if (!d_signal || !d_seq || !alphabet) return fail(ctx, XB_ERR_INVALID, "null argument");
-    if ((rc = check_alphabet(ctx, alphabet))) return rc;
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    return basecall_async(ctx, d_signal, n, alphabet, d_seq, d_seq_len, {});
-}
-
-// the blocking basecalls: through the context's staging, and back to the host
-static int basecall_host(xb_ctx *ctx, const float *signal, int n, const char *alphabet, int8_t *seq, int32_t *seq_len,
-                         const DecodeOut &o)
-{
-    int rc = check_ready(ctx, n);
-    if (rc) return rc;
-    const Planes dst = planes(seq, seq_len, o);
-    if (!signal || !has_required(dst, o.level) || !alphabet) return fail(ctx, XB_ERR_INVALID, "null argument");
-    if ((rc = check_alphabet(ctx, alphabet))) return rc;
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (o.level && (rc = ensure_staging(ctx, o.level))) return rc;
-    XB_HIP(ctx, hipMemcpyAsync(ctx->d_signal, signal, sizeof(float) * (size_t)n * ctx->cfg.chunk_len,
-                               hipMemcpyHostToDevice, ctx->stream));
-    const DecodeOut d = staging_of(ctx, o);
-    if ((rc = basecall_async(ctx, ctx->d_signal, n, alphabet, ctx->seq, ctx->seq_len, d))) return rc;
-    if ((rc = join_async_decode(ctx))) return rc;
-    if ((rc = copy_planes(ctx, o.level, dst, planes(ctx->seq, ctx->seq_len, d), 0, n, ctx->T, hipMemcpyDeviceToHost, ctx->stream)))
-        return rc;
-    return xb_synchronize(ctx);
-}
-
-XB_API int xb_basecall_chunks(xb_ctx *ctx, const float *signal, int n, const char *alphabet, int8_t *seq,
-                              int32_t *seq_len)
-{
-    return basecall_host(ctx, signal, n, alphabet, seq, seq_len, {});
-}
-
-XB_API int xb_basecall_chunks_q(xb_ctx *ctx, const float *signal, int n, const char *alphabet, float qscale, float qoffset,
-                                int8_t *seq, int8_t *qstring, uint8_t *moves, int32_t *seq_len)
-{
-    return basecall_host(ctx, signal, n, alphabet, seq, seq_len, {1, qscale, qoffset, qstring, moves});
-}
-
-XB_API int xb_basecall_chunks_ub(xb_ctx *ctx, const float *signal, int n, const char *alphabet, float qscale, float qoffset,
-                                 int8_t *seq, int8_t *qstring, uint8_t *moves, uint8_t *probs, int32_t *seq_len)
-{
-    return basecall_host(ctx, signal, n, alphabet, seq, seq_len, {2, qscale, qoffset, qstring, moves, probs});
-}
-
-// a slot's staging, lazily (most contexts -- tests, bench -- never use the host pipeline): the signal, and the planes of an
-// output level on the slot's first submission at that level
-static int ensure_slot(xb_ctx *ctx, int slot, int level)
-{
-    xb_ctx::Slot &sl = ctx->slots[slot];
-    const size_t N = ctx->cfg.max_batch, L = ctx->cfg.chunk_len;
-    if (!sl.h_signal) {
-        if (!ctx->stream_copy) XB_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream_copy, hipStreamNonBlocking));
-        XB_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&sl.h_signal), sizeof(float) * N * L, hipHostMallocDefault));
-        XB_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&sl.h_err), sizeof(unsigned), hipHostMallocDefault));
-        if (int rc = ctx->mem_ctx.alloc(ctx, &sl.d_signal, N * L)) return rc;
-        XB_HIP(ctx, hipEventCreateWithFlags(&sl.h2d, hipEventDisableTiming));
-        XB_HIP(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    }
-    for (int i = 0; i < plane_count(level); ++i) {
-        const size_t bytes = N * plane_bytes(ctx->T, ctx->cfg.n_base, i);
-        if (!sl.h.p[i]) XB_HIP(ctx, hipHostMalloc(&sl.h.p[i], bytes, hipHostMallocDefault));
-        if (!sl.d.p[i]) {
-            uint8_t *p = nullptr;
-            if (int rc = ctx->mem_ctx.alloc(ctx, &p, bytes)) return rc;
-            sl.d.p[i] = p;
-        }
-    }
-    return level ? ensure_staging(ctx, level) : XB_OK;
-}
-
-static int submit_chunks(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet, const DecodeOut &o)
-{
-    int rc = check_ready(ctx, n);
-    if (rc) return rc;
-    if (slot < 0 || slot >= XB_PIPELINE_SLOTS || !signal || !alphabet) return fail(ctx, XB_ERR_INVALID, "bad slot / null argument");
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = ensure_slot(ctx, slot, o.level))) return rc;
-    xb_ctx::Slot &sl = ctx->slots[slot];
-    if (sl.busy) return fail(ctx, XB_ERR_STATE, "slot %d was submitted and not collected", slot);
-    const size_t bytes = sizeof(float) * (size_t)n * ctx->cfg.chunk_len;
-    memcpy(sl.h_signal, signal, bytes);                       // the caller's buffer is free again on return
-    XB_HIP(ctx, hipMemcpyAsync(sl.d_signal, sl.h_signal, bytes, hipMemcpyHostToDevice, ctx->stream_copy));
-    XB_HIP(ctx, hipEventRecord(sl.h2d, ctx->stream_copy));
-    XB_HIP(ctx, hipStreamWaitEvent(ctx->stream, sl.h2d, 0));
-    if ((rc = check_alphabet(ctx, alphabet))) return rc;
-    // the D2H copies of the results, the error-word snapshot and the slot's done event follow the launch of this call
-    // (call_post_actions) -- which may be held back until the next submit so that the two batches share one pass
-    DecodeOut d = o;
-    d.qstr = static_cast<int8_t *>(sl.d.p[2]); d.moves = static_cast<uint8_t *>(sl.d.p[3]); d.probs = static_cast<uint8_t *>(sl.d.p[4]);
-    rc = basecall_async(ctx, sl.d_signal, n, alphabet, static_cast<int8_t *>(sl.d.p[0]), static_cast<int32_t *>(sl.d.p[1]), d, slot);
-    if (rc) return rc;
-    sl.n = n;
-    sl.busy = true;
-    sl.level = o.level;
-    return XB_OK;
-}
-
-XB_API int xb_submit_chunks(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet)
-{
-    return submit_chunks(ctx, slot, signal, n, alphabet, {});
-}
-
-XB_API int xb_submit_chunks_q(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet, float qscale,
-                              float qoffset)
-{
-    return submit_chunks(ctx, slot, signal, n, alphabet, {1, qscale, qoffset});
-}
-
-XB_API int xb_submit_chunks_ub(xb_ctx *ctx, int slot, const float *signal, int n, const char *alphabet, float qscale,
-                               float qoffset)
-{
-    return submit_chunks(ctx, slot, signal, n, alphabet, {2, qscale, qoffset});
-}
-
-// collects the planes of an output level: a submission at that level or above (below: XB_ERR_STATE)
-static int collect_chunks(xb_ctx *ctx, int slot, int level, const Planes &dst)
-{
-    static const char *const none_in_flight[3] = {"slot %d has nothing in flight", "slot %d has no submission with qualities in flight",
-                                                  "slot %d has no submission with letter probabilities in flight"};
-    if (!ctx) return XB_ERR_INVALID;
-    if (slot < 0 || slot >= XB_PIPELINE_SLOTS || !has_required(dst, level)) return fail(ctx, XB_ERR_INVALID, "bad slot / null argument");
-    xb_ctx::Slot &sl = ctx->slots[slot];
-    if (!sl.busy || sl.level < level) return fail(ctx, XB_ERR_STATE, none_in_flight[level], slot);
-    XB_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->holding && ctx->held.slot == slot) (void)flush_held(ctx);      // a failure shows as pipeline_failed below
-    XB_HIP(ctx, hipEventSynchronize(sl.done));
-    sl.busy = false;
-    for (int i = 0; i < plane_count(level); ++i)
-        if (dst.p[i]) memcpy(dst.p[i], sl.h.p[i], (size_t)sl.n * plane_bytes(ctx->T, ctx->cfg.n_base, i));
-    // the persistent recurrence reports a lost rendezvous through the sync word (snapshot taken behind this batch):
-    // results would be garbage.  The word is not cleared while another batch is in flight -- that batch fails too (it ran
-    // on a device in an unknown state) -- and is reset once the pipeline has drained.  The data word is not looked at: a
-    // refused label of some loss call says nothing about this batch, and the next synchronising call reports it.
-    if (*sl.h_err != 0) ctx->pipeline_failed = true;
-    if (ctx->pipeline_failed) {
-        bool any_busy = false;
-        for (auto &s2 : ctx->slots) any_busy = any_busy || s2.busy;
-        if (!any_busy) {
-            (void)sync_all(ctx);
-            (void)hipMemset(ctx->error, 0, sizeof(unsigned));
-            ctx->pipeline_failed = false;
-        }
-        const xb::DeviceStatus lost = xb::decode_status(xb::SYNC_LOST, 0u);
-        return fail(ctx, lost.code, "%s", lost.message);
-    }
-    return XB_OK;
-}
-
-XB_API int xb_collect_chunks_ub(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len, int8_t *qstring, uint8_t *moves,
-                                uint8_t *probs)
-{
-    return collect_chunks(ctx, slot, 2, {{seq, seq_len, qstring, moves, probs}});
-}
-
-XB_API int xb_collect_chunks_q(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len, int8_t *qstring, uint8_t *moves)
-{
-    return collect_chunks(ctx, slot, 1, {{seq, seq_len, qstring, moves, nullptr}});
-}
-
-XB_API int xb_collect_chunks(xb_ctx *ctx, int slot, int8_t *seq, int32_t *seq_len)
-{
-    return collect_chunks(ctx, slot, 0, {{seq, seq_len, nullptr, nullptr, nullptr}});
 }
 
 XB_API int xb_set_profiling(xb_ctx *ctx, int on)

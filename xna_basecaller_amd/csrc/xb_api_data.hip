@@ -1,8 +1,8 @@
 // xb_api_data.hip -- the ctc-data tools of the C ABI: template mapping, ctc labels, the UB tally, the barcode distance, DTW segmentation, spliced
-// augmentation, synthetic spiking and fully synthetic chunks, and the validation loss with its gradient.  Each has a _dev form on
-// device pointers and a host-pointer form that stages through xb_ctx::staging (Staging, xb_ctx.h); the forms that take label
-// rows check and stage them as the trainers' steps do (label_batch_check, LabelBatch, xb_ctx.h).
-#include "xb_ctx.h"
+// augmentation, synthetic spiking and fully synthetic chunks.  Each has a _dev form on device pointers and a host-pointer form
+// that stages through xb_ctx::staging (Staging, xb_ctx.h); the forms that take label rows check and stage them as the trainers'
+// steps do (label_batch_check, LabelBatch, xb_ctx.h).
+#include "xb_api_priv.h"        // basecall_async, for xb_ctc_chunks
 
 namespace {
 
@@ -984,122 +984,6 @@ XB_API int xb_synth_chunks(xb_ctx *ctx, const float *signal, const uint8_t *targ
 {
     return spike_host(ctx, SPIKE_WHOLE, {n, N, Lt, first_index, seed, ubs_mask, prop, var_prop, pad, dist_rows, phi, noise_std, variable_noise},
                       {signal, targets, lengths, breakpoints}, {out_signal, out_targets, spiked, med, mad, status});
-}
-
-// ---- the validation loss (xb_ctc_loss, xb_validate_chunks): RAW scores where they lie, the labels as references.npy holds them ----
-namespace {
-
-// what both forms refuse before any device work: the batch, T, then the label batch (targets: the host form's rows, null in the
-// _dev forms); *ld = the row stride of the scores' layout
-int loss_args(xb_ctx *ctx, const char *who, int T, int n, int has_blank, const uint8_t *targets, int Lt, const int32_t *lengths, int *ld)
-{
-    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, XB_ERR_INVALID, "%s: batch %d outside [1, max_batch=%d]", who, n, ctx->cfg.max_batch);
-    if (T < 1 || T > ctx->T) return fail(ctx, XB_ERR_INVALID, "%s: T=%d outside [1, %d]", who, T, ctx->T);
-    if (int rc = label_batch_check(ctx, who, targets, n, Lt, lengths)) return rc;
-    *ld = has_blank ? ctx->S * (ctx->cfg.n_base + 1) : ctx->O;
-    return XB_OK;
-}
-
-}  // namespace
-
-XB_API int xb_ctc_loss_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const uint8_t *d_targets, int Lt,
-                           const int32_t *d_target_lengths, float *d_loss, float *d_logz)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    if (!d_scores || !d_targets || !d_target_lengths || !d_loss) return fail(ctx, XB_ERR_INVALID, "xb_ctc_loss: null device pointer");
-    int ld = 0;
-    if (int rc = loss_args(ctx, "xb_ctc_loss", T, n, has_blank, nullptr, Lt, nullptr, &ld)) return rc;
-    if (int rc = enter(ctx, true)) return rc;
-    return ctc_loss_run(ctx, "xb_ctc_loss", d_scores, T, n, has_blank ? 1 : 0, ld, d_targets, Lt, d_target_lengths, d_loss, d_logz);
-}
-
-XB_API int xb_ctc_loss(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, const uint8_t *targets, int Lt,
-                       const int32_t *target_lengths, float *loss, float *logz)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    if (!scores || !targets || !target_lengths || !loss) return fail(ctx, XB_ERR_INVALID, "xb_ctc_loss: null host pointer");
-    int ld = 0;
-    if (int rc = loss_args(ctx, "xb_ctc_loss", T, n, has_blank, targets, Lt, target_lengths, &ld)) return rc;
-    if (int rc = enter(ctx, false)) return rc;
-    const size_t N = (size_t)n;
-    Staging st{ctx};
-    const LabelBatch lb(st, n, Lt);
-    const auto d_logz = st.take<float>(N);
-    if (int rc = st.ready()) return rc;
-    XB_HIP(ctx, hipMemcpyAsync(ctx->scores, scores, sizeof(float) * (size_t)T * N * ld, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = lb.upload(ctx, targets, target_lengths)) return rc;
-    if (int rc = ctc_loss_run(ctx, "xb_ctc_loss", ctx->scores, T, n, has_blank ? 1 : 0, ld, lb.targets, Lt, lb.len, lb.loss, d_logz)) return rc;
-    XB_HIP(ctx, hipMemcpyAsync(loss, lb.loss, N * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (logz) XB_HIP(ctx, hipMemcpyAsync(logz, d_logz, N * 4, hipMemcpyDeviceToHost, ctx->stream));
-    return xb_synchronize(ctx);
-}
-
-// the loss with d loss / d scores (the contract is in the public header)
-XB_API int xb_ctc_loss_grad_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, const uint8_t *d_targets, int Lt,
-                                const int32_t *d_target_lengths, float loss_clip, int mean, float *d_loss, float *d_grad)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    if (!d_scores || !d_targets || !d_target_lengths || !d_loss || !d_grad)
-        return fail(ctx, XB_ERR_INVALID, "xb_ctc_loss_grad: null device pointer");
-    int ld = 0;
-    if (int rc = loss_args(ctx, "xb_ctc_loss_grad", T, n, has_blank, nullptr, Lt, nullptr, &ld)) return rc;
-    if (int rc = enter(ctx, true)) return rc;
-    return ctc_grad_run(ctx, "xb_ctc_loss_grad", d_scores, T, n, has_blank ? 1 : 0, ld, d_targets, Lt, d_target_lengths, loss_clip, mean,
-                        d_loss, d_grad);
-}
-
-XB_API int xb_ctc_loss_grad(xb_ctx *ctx, const float *scores, int T, int n, int has_blank, const uint8_t *targets, int Lt,
-                            const int32_t *target_lengths, float loss_clip, int mean, float *loss, float *grad)
-{
-    if (!ctx) return XB_ERR_INVALID;
-    if (!scores || !targets || !target_lengths || !loss || !grad) return fail(ctx, XB_ERR_INVALID, "xb_ctc_loss_grad: null host pointer");
-    int ld = 0;
-    if (int rc = loss_args(ctx, "xb_ctc_loss_grad", T, n, has_blank, targets, Lt, target_lengths, &ld)) return rc;
-    if (int rc = enter(ctx, false)) return rc;
-    const size_t N = (size_t)n, cells = (size_t)T * N * ld;
-    Staging st{ctx};
-    const LabelBatch lb(st, n, Lt);
-    const auto d_grad = st.take<float>(cells);
-    if (int rc = st.ready()) return rc;
-    XB_HIP(ctx, hipMemcpyAsync(ctx->scores, scores, sizeof(float) * cells, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = lb.upload(ctx, targets, target_lengths)) return rc;
-    if (int rc = ctc_grad_run(ctx, "xb_ctc_loss_grad", ctx->scores, T, n, has_blank ? 1 : 0, ld, lb.targets, Lt, lb.len, loss_clip, mean,
-                              lb.loss, d_grad))
-        return rc;
-    XB_HIP(ctx, hipMemcpyAsync(loss, lb.loss, N * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(grad, d_grad, sizeof(float) * cells, hipMemcpyDeviceToHost, ctx->stream));
-    return xb_synchronize(ctx);
-}
-
-// validate_one_step's device half: signal -> encoder (blank-less scores) -> Viterbi decode, as xb_basecall_chunks runs them, then the
-// loss from the scores the decode read
-XB_API int xb_validate_chunks(xb_ctx *ctx, const float *signal, int n, const char *alphabet, const uint8_t *targets, int Lt,
-                              const int32_t *target_lengths, int8_t *seq, int32_t *seq_len, float *loss)
-{
-    int rc = check_ready(ctx, n);
-    if (rc) return rc;
-    if (!signal || !alphabet || !targets || !target_lengths || !seq || !seq_len || !loss)
-        return fail(ctx, XB_ERR_INVALID, "xb_validate_chunks: null argument");
-    if ((rc = check_alphabet(ctx, alphabet))) return rc;
-    int ld = 0;
-    if ((rc = loss_args(ctx, "xb_validate_chunks", ctx->T, n, 0, targets, Lt, target_lengths, &ld))) return rc;
-    // nothing held back may pair with this call: its scores are read where the encoder left them, as a batch of their own
-    if ((rc = enter(ctx, false))) return rc;
-    const size_t N = (size_t)n, W = (size_t)ctx->T;
-    Staging st{ctx};
-    const LabelBatch lb(st, n, Lt);
-    if ((rc = st.ready())) return rc;
-    XB_HIP(ctx, hipMemcpyAsync(ctx->d_signal, signal, sizeof(float) * N * ctx->cfg.chunk_len, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = lb.upload(ctx, targets, target_lengths))) return rc;
-    if ((rc = basecall_async(ctx, ctx->d_signal, n, alphabet, ctx->seq, ctx->seq_len, {}))) return rc;
-    if ((rc = join_async_decode(ctx))) return rc;
-    if (!ctx->last_scores || ctx->last_n != n) return fail(ctx, XB_ERR_STATE, "xb_validate_chunks: the pass of %d chunks left no scores of its own", n);
-    if ((rc = ctc_loss_run(ctx, "xb_validate_chunks", ctx->last_scores, ctx->T, n, 0, ctx->ld_nb, lb.targets, Lt, lb.len, lb.loss, nullptr)))
-        return rc;
-    XB_HIP(ctx, hipMemcpyAsync(seq, ctx->seq, N * W, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(seq_len, ctx->seq_len, N * 4, hipMemcpyDeviceToHost, ctx->stream));
-    XB_HIP(ctx, hipMemcpyAsync(loss, lb.loss, N * 4, hipMemcpyDeviceToHost, ctx->stream));
-    return xb_synchronize(ctx);
 }
 
 }  // extern "C"

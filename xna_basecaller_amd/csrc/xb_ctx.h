@@ -1,12 +1,12 @@
-// xb_ctx.h -- the context behind the C ABI, shared by the translation units that implement it: xb_api.hip (context lifetime, weight
-// upload, the execution of the encoder's plans, decode, pairing, the host pipeline, and the housekeeping every entry point
-// shares: the call prologue `enter`, the status words), xb_api_data.hip (the ctc-data tools and the losses), xb_head.hip (the
-// head's gradient and trainer, and the step tail every trainer ends in), xb_lstm_train.hip (the training recurrence), xb_train_gemm.hip (the fp32 products of training), xb_conv_train.hip (the convolutions' training) and xb_top.hip (the
-// trainers of the head with the top LSTM layers, and of every layer); xb_comm.hip
-// reaches a context through the C ABI and xb_internal_defer_after only.  The host arithmetic xb_api.hip acts on lives in three headers without HIP that are
-// checked on their own: xb_schedule.h (the knobs and the planner of the encoder schedule), xb_pack.h (the forms a weight
-// tensor is uploaded in) and xb_status.h (the device status words).  Below the context: `grow`, the view of its one staging
-// buffer (Staging) and the label batch every loss and training call takes (label_batch_check, LabelBatch).  Private to csrc/.
+// xb_ctx.h -- the context behind the C ABI, shared by the translation units that implement it.  Inference: xb_api.hip (the
+// context core: lifetime, weights, and what every entry point shares -- the call prologue `enter`, the status words, the
+// workspaces), xb_run_encoder.hip (executes the encoder's plans), xb_api_scores.hip (every call on a score tensor),
+// xb_api_basecall.hip (pairing, basecalls, host pipeline), xb_api_data.hip (the ctc-data tools); xb_api_priv.h holds what only
+// these share.  Training: xb_head.hip (the head's trainer and the step tail every trainer ends in), xb_lstm_train.hip,
+// xb_train_gemm.hip, xb_conv_train.hip, xb_top.hip (the trainers of the top LSTM layers and of every layer).  xb_comm.hip reaches
+// a context through the C ABI and xb_internal_defer_after only.  The host arithmetic lives in three headers without HIP that are
+// checked on their own: xb_schedule.h, xb_pack.h, xb_status.h.  Below the context: `grow`, the view of its one staging buffer
+// (Staging) and the label batch every loss and training call takes (label_batch_check, LabelBatch).  Private to csrc/.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -421,13 +421,14 @@ inline int launched(const xb_ctx *ctx, const char *who)
     return XB_OK;
 }
 
-// the core (xb_api.hip) as the ctc-data tools call it; none is exported (the library is built with hidden visibility)
+// the core (xb_api.hip) as the other translation units call it; none is exported (the library is built with hidden visibility)
 int check_ready(xb_ctx *ctx, int n);     // a context with weights and room for a batch of n
 int check_alphabet(xb_ctx *ctx, const char *alphabet);
 int join_async_decode(xb_ctx *ctx);      // flush_held, then the main stream waits for decodes in flight on the third stream
 // The entry of a call, after its own checks: the context's device, nothing held back, the main stream behind decodes in flight
 // beside it.  dev: the call leaves its results to the main stream (every _dev form), named after a held call was launched.
 int enter(xb_ctx *ctx, bool dev);
+// the loss runners (xb_api_scores.hip) and the encoder's (xb_run_encoder.hip), as the trainers call them too
 int ctc_loss_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int n, int has_blank, int ld, const uint8_t *d_targets,
                  int Lt, const int32_t *d_len, float *d_loss, float *d_logz);
 int ctc_grad_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int n, int has_blank, int ld, const uint8_t *d_targets,
@@ -435,8 +436,3 @@ int ctc_grad_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int
 int encoder_run(xb_ctx *ctx, const float *d_signal, int n, float *d_scores, int ldc);   // blank-less scores (T, n, ldc), main stream
 // the convolutions and the first `layers` (0 .. 5) LSTM layers of the same pass; the output lies in x_hi / x_lo [layers & 1]
 int encoder_bottom_run(xb_ctx *ctx, const float *d_signal, int n, int layers);
-// ... and two from inside its extern "C" block, beside the pairing logic: flush_held launches a held-back asynchronous basecall;
-// basecall_async makes one of n chunks at d_signal into device outputs (seq, len, out), of pipeline slot `slot` or none
-extern "C" int flush_held(xb_ctx *ctx);
-extern "C" int basecall_async(xb_ctx *ctx, const float *d_signal, int n, const char *alphabet, int8_t *seq, int32_t *len,
-                              const DecodeOut &out, int slot = -1);

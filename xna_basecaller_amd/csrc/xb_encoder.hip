@@ -604,7 +604,7 @@ __global__ __launch_bounds__(GTHREADS) void gemm8r_kernel(xb::GemmParams p)
 //     runs under the other's MFMA clusters; the hardware interleaves the two main loops.
 //   * B (the weights) never touches LDS.  With the waves side by side in N no two waves share a B row, so each wave
 //     loads its own fragments straight into registers from a FRAGMENT-MAJOR weight image built once on the host
-//     (xb_api.hip: fragment_major): [k-tile][32-row block][piece][lane][16 B], i.e. every wave-instruction reads 1 KiB of
+//     (xb_pack.h: fragment_major): [k-tile][32-row block][piece][lane][16 B], i.e. every wave-instruction reads 1 KiB of
 //     consecutive bytes.  LDS carries only the A tile (shared by the four waves): 16 ds_read_b128 per wave and k-tile
 //     instead of 28, no ds_write at all.
 //   * TWO k-tiles of both operands are in flight (24 KiB per wave):
@@ -739,7 +739,7 @@ __global__ __launch_bounds__(G4_THREADS, 2) void gemm4p_kernel(xb::GemmParams p)
     // profiles/r05_mfma_shape_ubench.txt; MI355X_MICROARCH.md, DVFS give-back item 7).  A wave's 128 x 64 outputs are 8 x 4 tiles of
     // 16x16; a k-tile is ONE k-step of 32; A fragment of a 16-row tile: row (lane & 15), cell (lane >> 4) of the row (the LDS image
     // and its swizzle are unchanged); the weight image's four pieces of a 32-row block are (hi, lo) x (rows 0-15, 16-31) with lane
-    // l = row (l & 15), k 8 (l >> 4) .. + 8 (xb_api.hip: fragment_major).
+    // l = row (l & 15), k 8 (l >> 4) .. + 8 (xb_pack.h: fragment_major).
     // The k-tile's barrier then sits between its third and fourth MFMA phase instead of at its top, and the first fragments of
     // tile t + 1 are requested behind it: their LDS latency runs under the fourth phase's 24 MFMAs.
     constexpr bool S16 = NSPLIT == 3;
@@ -1079,7 +1079,7 @@ hipError_t launch_gemm4p_ns(const xb::GemmParams &p, hipStream_t stream)
     size_t lds = (size_t)3 * (NSPLIT == 1 ? 1 : 2) * 128 * 64;             // [3 stages][parts][128 rows x 64 B]
     if (p.one_per_cu) {
         // a launch that shares the chip with the recurrence: more than half of a CU's LDS keeps it to ONE workgroup per CU
-        // (half the memory traffic per CU on the recurrence's L2 / fabric), see xb_api.hip run_lstm_layer
+        // (half the memory traffic per CU on the recurrence's L2 / fabric), see xb_run_encoder.hip run_lstm_layer
         lds = 96 * 1024;
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm4p_kernel<EPI, NSPLIT>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

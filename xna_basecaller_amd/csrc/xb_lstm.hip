@@ -106,7 +106,7 @@ __device__ unsigned long long g_lstm_stamps[10];   // 0..7 cycle sums, 8 = early
 // the gin tile is requested a whole group-step ahead: a launch holds twice the chunks at the same residency.
 // YALT = true (NSPLIT 2 or 3 only): the layer output y carries the OTHER second part than the exchange image -- the fp16
 // residual when the recurrence itself runs on q8 images (NSPLIT 2), the q8 image when it runs on residuals (NSPLIT 3) -- because
-// the GEMM that consumes y runs in the other arithmetic (mixed-precision encoders: xb_api.hip stage_nsplit).  The extra
+// the GEMM that consumes y runs in the other arithmetic (mixed-precision encoders: xb_run_encoder.hip set_stage_arithmetic).  The extra
 // staging rows live in piece buffer 1, which is idle between the last piece's closing barrier and the next group-step's
 // piece-1 requests.
 template <int KS, int NSPLIT, bool DUAL, bool YALT = false>

@@ -1,6 +1,6 @@
 // xb_schedule.h -- the encoder's host scheduler as plain arithmetic: the environment knobs of a context (Knobs,
 // knobs_from_env), the plan of one LSTM layer's recurrence and of the GEMM that consumes it (plan_layer), and the batch up to
-// which two calls pair (pair_capacity).  No HIP: xb_api.hip executes the plans, tools/host_logic_main.cpp and
+// which two calls pair (pair_capacity).  No HIP: xb_run_encoder.hip executes the plans, tools/host_logic_main.cpp and
 // tests/test_schedule_host.py check them without a GPU.  Also the one definition of the recurrence's group geometry, which
 // xb_lstm.hip includes.
 #pragma once

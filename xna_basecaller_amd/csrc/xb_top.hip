@@ -1,6 +1,6 @@
 // xb_top.hip -- training the CRF head together with the top L LSTM layers, everything below them frozen: `bonito train -F` at
 // --num-unfreeze-top 2 .. 6 with --no-amp.  The frozen bottom is the inference encoder's own pass, cut off after 5 - L LSTM
-// layers (encoder_bottom_run, xb_api.hip) and joined into fp32; from there on a step is the chain tests/toptrain_dev.py
+// layers (encoder_bottom_run, xb_run_encoder.hip) and joined into fp32; from there on a step is the chain tests/toptrain_dev.py
 // composes -- the fp32 products of xb_train_gemm.hip, the training recurrence of xb_lstm_train.hip, xb_ctc_loss_grad, the norm and
 // AdamW of xb_head.hip -- on the buffers csrc/xb_top_plan.h lays out, in one call.  Three small kernels of its own: the join of
 // the two fp16 planes, an exact transpose, the sum of a layer's two biases.  xb_full_train_begin opens the same trainer at L = 5
