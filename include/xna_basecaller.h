@@ -225,8 +225,11 @@ XB_API int xb_crf_logz_dev(xb_ctx *ctx, const float *d_scores, int T, int n, int
  * specification is the "CRF beam search" section of oracle/xna_oracle.c, against which the kernel is bit-exact.  PARITY UNPINNED.
  *   scores    (T, n, C) fp32; has_blank = 0: C = S * n_base and the stay score is the context's blank_score (what the
  *             reference passes); has_blank = 1: the stay score is column 0 of every state row.
- *   beam_width 1..32; beam_cut > 0 (candidates below max - log(beam_cut) are dropped; <= 0: no cut); qscale / qoffset =
- *             koi's scale / offset on the phred value.  States: at most 1024 (the limit of the scans).
+ *   beam_width 1..32; beam_cut >= 1 (candidates below max - log(beam_cut) are dropped; <= 0: no cut; inside (0, 1) the
+ *             logarithm is negative, no candidate can reach the threshold and the beam would be empty: XB_ERR_INVALID);
+ *             qscale / qoffset = koi's scale / offset on the phred value.  States: at most 1024 (the limit of the scans).
+ *             The scores must be finite: a NaN compares below every threshold and empties the beam in the same way, and
+ *             that is NOT checked -- the results of such a call are undefined.
  *   sequence, qstring (n, T) int8: the base character alphabet[1 + base] / the quality character (33 + q, q in 1..50) at the
  *             blocks that emit a base, 0 elsewhere (koi.decode.to_str drops the zeros); moves (n, T) uint8 1 = a base is
  *             emitted in this block (moves[0] is always 1); score (n) [optional] the log-sum path score of the result.

@@ -19,6 +19,7 @@ from .oracle import (  # noqa: F401
     ctc_logz,
     beam_search,
     log_beam_cut,
+    BEAM_CENSUS,
     conv1d_silu,
     lstm,
     linear_crf,

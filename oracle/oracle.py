@@ -49,6 +49,7 @@ def lib():
         _lib.xo_num_threads.restype = C.c_int
         _lib.xo_ctc_logz.restype = C.c_int
         _lib.xo_beam_search.restype = C.c_int
+        _lib.xo_beam_census_columns.restype = C.c_int
     return _lib
 
 
@@ -311,22 +312,40 @@ def log_beam_cut(beam_cut):
     return float(np.float32(math.log(beam_cut))) if beam_cut > 0 else float(np.finfo(np.float32).max)
 
 
-def beam_search(scores, alphabet, state_len, beam_width=32, beam_cut=100.0, scale=1.0, offset=0.0, blank_score=None):
+# the columns of xo_beam_search's census (xna_oracle.c: enum XO_BC_*), per chunk
+BEAM_CENSUS = ("blocks", "bisect", "ten_guesses", "merges", "multi", "clash", "far", "tie", "short", "best_moved", "post_zero",
+               "q1", "q50", "start_tied")
+
+
+def beam_search(scores, alphabet, state_len, beam_width=32, beam_cut=100.0, scale=1.0, offset=0.0, blank_score=None,
+                want_census=False):
     """
     koi.decode.beam_search as called at crf/basecall.py:43-46, restated (xna_oracle.c: "CRF beam search"; parity unpinned).
     scores (T, N, C) fp32 with or without the blank column.  Returns dict: 'sequence', 'qstring' (N, T) int8 (ASCII at the
-    emitting blocks, 0 elsewhere), 'moves' (N, T) uint8, 'score' (N,) float32.
+    emitting blocks, 0 elsewhere), 'moves' (N, T) uint8, 'score' (N,) float32; with want_census also 'census' (N, K) int32,
+    how often each chunk took each branch, and 'census_columns' = BEAM_CENSUS, its K column names.
+    beam_cut <= 0 switches the cut off; a cut inside (0, 1) has a negative logarithm, no candidate can reach max - log(cut) and
+    the beam would be empty: ValueError.
     """
+    if 0.0 < beam_cut < 1.0:
+        raise ValueError("beam_cut %g inside (0, 1): no candidate can reach it" % beam_cut)
     n_base = len(alphabet) - 1
     scores, T, N, S, E, has_blank, blank = _decode_args(scores, n_base, state_len, blank_score)
     d = decode(scores, n_base, state_len, blank_score=blank_score, want=("alpha", "beta", "logz"))
     out = {"sequence": np.zeros((N, T), dtype=np.int8), "qstring": np.zeros((N, T), dtype=np.int8),
            "moves": np.zeros((N, T), dtype=np.uint8), "score": np.zeros((N,), dtype=np.float32)}
+    census = None
+    if want_census:
+        assert lib().xo_beam_census_columns() == len(BEAM_CENSUS)
+        census = np.zeros((N, len(BEAM_CENSUS)), dtype=np.int32)
     rc = lib().xo_beam_search(_p(scores), C.c_int(T), C.c_int(N), C.c_int(n_base), C.c_int(state_len), C.c_int(has_blank),
                               C.c_float(blank), _p(d["alpha"]), _p(d["beta"]), _p(d["logz"]), C.c_int(int(beam_width)),
                               C.c_float(log_beam_cut(beam_cut)), C.c_float(scale), C.c_float(offset),
                               C.c_char_p(alphabet.encode("ascii")), _p(out["sequence"], i8p), _p(out["qstring"], i8p),
-                              out["moves"].ctypes.data_as(C.POINTER(C.c_uint8)), _p(out["score"]))
+                              out["moves"].ctypes.data_as(C.POINTER(C.c_uint8)), _p(out["score"]),
+                              _p(census, i32p))
     if rc:
         raise ValueError("xo_beam_search failed (%d)" % rc)
+    if want_census:
+        out["census"], out["census_columns"] = census, BEAM_CENSUS
     return out

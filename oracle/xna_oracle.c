@@ -1033,7 +1033,15 @@ XO_API int xo_ctc_logz(const float *scores, int T, int N, int C, const int32_t *
  *                * qscale + qoffset, clamped to [1, 50], character (int)(33.5 + q).
  *   outputs      sequence (N, T) int8: alphabet[1 + base] at the blocks that emit (moves = 1), else 0; qstring (N, T) int8 the
  *                quality character at the same blocks; moves (N, T) uint8; score (N) the path score of element 0 [optional].
+ *   census       (N, XO_BEAM_CENSUS) int32 [optional]: how often a chunk took each branch of the above, so that a test can
+ *                demand of its inputs that they reach the branch it was written for (columns: enum below, names in
+ *                oracle.py: BEAM_CENSUS).  Counting changes no other output.  A candidate is "alive" above -1e30 (a merged-away
+ *                candidate holds -FLT_MAX, and with no cut stays in the beam): the `far` and `tie` columns count merges of two
+ *                alive candidates only.
  */
+enum { XO_BC_BLOCKS, XO_BC_BISECT, XO_BC_TEN, XO_BC_MERGES, XO_BC_MULTI, XO_BC_CLASH, XO_BC_FAR, XO_BC_TIE, XO_BC_SHORT,
+       XO_BC_BEST_MOVED, XO_BC_POST_ZERO, XO_BC_Q1, XO_BC_Q50, XO_BC_START_TIED, XO_BEAM_CENSUS };
+XO_API int xo_beam_census_columns(void) { return XO_BEAM_CENSUS; }
 #define XO_BEAM_MAX 32
 #define XO_CRC_SEED 0x12345678u
 #define XO_HASH_BITS 4096
@@ -1061,7 +1069,7 @@ static int xo_cmp_desc(const void *a, const void *b)
 XO_API int xo_beam_search(const float *scores, int T, int N, int nb, int sl, int has_blank, float blank,
                           const float *alpha, const float *beta, const float *logz,
                           int beam_width, float log_beam_cut, float qscale, float qoffset, const char *alphabet,
-                          int8_t *sequence, int8_t *qstring, uint8_t *moves, float *score_out)
+                          int8_t *sequence, int8_t *qstring, uint8_t *moves, float *score_out, int32_t *census)
 {
     const int S = (int)ipow(nb, sl), E = nb + 1;
     const int Cin = has_blank ? S * E : S * nb;
@@ -1076,6 +1084,8 @@ XO_API int xo_beam_search(const float *scores, int T, int N, int nb, int sl, int
         int fs[XO_BEAM_MAX], cs[XO_BEAM_MAX * 8], cp[XO_BEAM_MAX * 8];
         uint8_t cstay[XO_BEAM_MAX * 8], present[XO_HASH_BITS];
         float fsc[XO_BEAM_MAX], csc[XO_BEAM_MAX * 8];
+        uint8_t claims[XO_BEAM_MAX * 8];
+        int32_t cen[XO_BEAM_CENSUS] = {0};
         /* history: state, prev, stay per (block, element) */
         int32_t *hst = (int32_t *)malloc(sizeof(int32_t) * (size_t)(T + 1) * W);
         uint8_t *hprev = (uint8_t *)malloc((size_t)(T + 1) * W), *hstay = (uint8_t *)malloc((size_t)(T + 1) * W);
@@ -1095,6 +1105,9 @@ XO_API int xo_beam_search(const float *scores, int T, int N, int nb, int sl, int
             for (int s_ = 0; s_ < S; ++s_) sorted[s_] = BETA(0, s_);
             qsort(sorted, (size_t)S, sizeof(float), xo_cmp_desc);
             thr = sorted[W];
+            int tied = 0;
+            for (int s_ = 0; s_ < S; ++s_) tied += BETA(0, s_) >= thr;
+            cen[XO_BC_START_TIED] = tied > W;
         }
         int Wc = 0;
         for (int s_ = 0; s_ < S && Wc < W; ++s_)
@@ -1110,6 +1123,8 @@ XO_API int xo_beam_search(const float *scores, int T, int N, int nb, int sl, int
             const float *row = scores + ((size_t)t * N + n) * Cin;
             float max_score = -3.402823466e+38f;
             memset(present, 0, sizeof(present));
+            memset(claims, 0, sizeof(claims));
+            ++cen[XO_BC_BLOCKS];
             int nc = 0;
             for (int p = 0; p < Wc; ++p)
                 for (int b = 0; b < nb; ++b) {
@@ -1131,10 +1146,17 @@ XO_API int xo_beam_search(const float *scores, int T, int N, int nb, int sl, int
                 max_score = v > max_score ? v : max_score;
                 if (present[fh[p] % XO_HASH_BITS]) {
                     const int latest = st % nb;
+                    int matched = 0;
                     for (int q = 0; q < Wc; ++q) {
                         const int ti = q * nb + latest;
                         if (ch[si] == ch[ti]) {
                             const float f = xo_lse2(csc[si], csc[ti]);
+                            const int alive = csc[si] > -1e30f && csc[ti] > -1e30f;
+                            ++cen[XO_BC_MERGES];
+                            cen[XO_BC_MULTI] += ++matched == 2;
+                            cen[XO_BC_CLASH] += ++claims[ti] == 2;
+                            cen[XO_BC_FAR] += alive && fabsf(csc[si] - csc[ti]) >= 17.0f;
+                            cen[XO_BC_TIE] += alive && csc[si] == csc[ti];
                             if (csc[si] > csc[ti]) { csc[si] = f; csc[ti] = -3.402823466e+38f; }
                             else { csc[ti] = f; csc[si] = -3.402823466e+38f; }
                             max_score = f > max_score ? f : max_score;
@@ -1148,6 +1170,7 @@ XO_API int xo_beam_search(const float *scores, int T, int N, int nb, int sl, int
 #define XO_COUNT() do { count = 0; for (int c_ = 0; c_ < nc; ++c_) count += csc[c_] >= cutoff; } while (0)
             XO_COUNT();
             if (count > W) {
+                ++cen[XO_BC_BISECT];
                 const int minw = (W * 8) / 10;
                 float lo = cutoff, hi_s = max_score;
                 int guesses = 1;
@@ -1157,7 +1180,7 @@ XO_API int xo_beam_search(const float *scores, int T, int N, int nb, int sl, int
                     XO_COUNT();
                     ++guesses;
                 }
-                if (guesses == 10) { cutoff = hi_s; XO_COUNT(); }
+                if (guesses == 10) { cutoff = hi_s; XO_COUNT(); ++cen[XO_BC_TEN]; }
                 count = count < W ? count : W;
             }
 #undef XO_COUNT
@@ -1170,10 +1193,12 @@ XO_API int xo_beam_search(const float *scores, int T, int N, int nb, int sl, int
                     ++w;
                 }
             Wc = w;
+            cen[XO_BC_SHORT] += Wc < W;
             if (t == T - 1) {       /* the best element becomes element 0 (first maximum) */
                 int best = 0;
                 for (int i = 1; i < Wc; ++i) if (fsc[i] > fsc[best]) best = i;
                 if (best != 0) {
+                    ++cen[XO_BC_BEST_MOVED];
                     const size_t o = (size_t)T * W;
                     uint32_t th = fh[0]; fh[0] = fh[best]; fh[best] = th;
                     int ts = fs[0]; fs[0] = fs[best]; fs[best] = ts;
@@ -1210,6 +1235,7 @@ XO_API int xo_beam_search(const float *scores, int T, int N, int nb, int sl, int
 #undef XO_POST
             p = p > 1.0f ? 1.0f : p;
             p = p < 0.0f ? 0.0f : p;
+            cen[XO_BC_POST_ZERO] += !(p > 0.0f);
             prob[t] = p > 0.0f ? xo_expf_i(0.4f * xo_logf_i(p)) : 0.0f;
         }
         /* ---- sequence and quality string at the emitting blocks ---- */
@@ -1229,6 +1255,8 @@ XO_API int xo_beam_search(const float *scores, int T, int N, int nb, int sl, int
             float q = e > 0.0f ? xo_logf_i(e) * -4.3429448190325175f : 3.402823466e+38f;
             q = q * qscale;
             q = q + qoffset;
+            cen[XO_BC_Q1] += q < 1.0f;
+            cen[XO_BC_Q50] += q > 50.0f;
             q = q < 1.0f ? 1.0f : q;
             q = q > 50.0f ? 50.0f : q;
             sq[t] = (int8_t)alphabet[1 + path[t] % nb];
@@ -1236,6 +1264,7 @@ XO_API int xo_beam_search(const float *scores, int T, int N, int nb, int sl, int
         }
 #undef BETA
 #undef ALPHA
+        if (census) memcpy(census + (size_t)n * XO_BEAM_CENSUS, cen, sizeof(cen));
         free(hst); free(hprev); free(hstay); free(path); free(prob); free(sorted);
     }
     return err;

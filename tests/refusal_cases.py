@@ -8,8 +8,8 @@ signal chunks or a (T, n, C) score tensor refuse, with the exact status and the 
   EXCLUDED     exported names that match FAMILIES and have no rows, with the reason.
 
 The context: 6 bases, state length 3 (216 states), features 32, window 19, stride 5, chunks of 200 samples (T = 40), at most 4
-chunks.  Every row returns before any kernel is launched, except xb_basecall_chunks_beam's beam and alphabet rows: that call
-checks what its beam search needs after its encoder pass (of valid chunks) has been launched.
+chunks.  Every row returns before any kernel is launched, except xb_basecall_chunks_beam's beam (width and cut) and alphabet
+rows: that call checks what its beam search needs after its encoder pass (of valid chunks) has been launched.
 
 The symbolic argument values: None is a null pointer; SHORT_LENGTH and HIGH_LABEL are the label batch with its first length
 below the state length, or its first label above n_base; every pointer not named is a buffer large enough for the call."""
@@ -72,6 +72,7 @@ ALPHABET_SHORT = "alphabet needs %d symbols" % (NB + 1)
 ALPHABET_MISSING = "alphabet is required when seq is requested"
 NO_OUTPUT = "no output requested"
 BAD_SLOT = "bad slot / null argument"
+BEAM_CUT = "beam_cut 0.5 inside (0, 1): no candidate can reach it"
 
 
 def batch(n, who=""):
@@ -158,6 +159,7 @@ for fn in ("xb_beam_search", "xb_beam_search_dev"):
     nulls(fn, ("scores", "sequence", "qstring", "moves"), null_word(fn))
     for w in (0, 33):
         row(fn, "beam width %d" % w, {"beam_width": w}, INVALID, "beam_width %d outside [1, 32]" % w)
+    row(fn, "beam cut inside (0, 1)", {"beam_cut": 0.5}, INVALID, BEAM_CUT)
     row(fn, "alphabet short", {"alphabet": ALPHABET[:-1]}, INVALID, ALPHABET_SHORT)
     row(fn, "alphabet missing", {"alphabet": None}, INVALID, ALPHABET_SHORT)
 
@@ -167,6 +169,7 @@ ranges(fn, ctx="loaded", with_T=False)
 nulls(fn, ("signal", "sequence", "qstring", "moves", "alphabet"), "null argument", "loaded")
 for w in (0, 33):
     row(fn, "beam width %d" % w, {"beam_width": w}, INVALID, "beam_width %d outside [1, 32]" % w, "loaded")
+row(fn, "beam cut inside (0, 1)", {"beam_cut": 0.5}, INVALID, BEAM_CUT, "loaded")
 row(fn, "alphabet short", {"alphabet": ALPHABET[:-1]}, INVALID, ALPHABET_SHORT, "loaded")
 
 for fn, planes in (("xb_basecall_chunks", ()), ("xb_basecall_chunks_dev", ()), ("xb_basecall_chunks_q", ("qstring",)),

@@ -6,8 +6,9 @@ restatement that merges hypotheses by their actual state sequences instead of CR
 alignment of tiny problems (with a beam that holds every hypothesis the search is exact: its score is the best sequence's
 log-sum over alignments), (c) structural properties; the host pipeline around the operator with a stand-in model.
 GPU tier -- xb_beam_search / xb_basecall_chunks_beam bit-equal to the oracle for n_base 4 / 5 / 6, several state lengths, beam
-widths and cuts (including the no-cut mode whose left-over duplicates force the one-merge-at-a-time path), and the Model-level
-compute_scores / basecall on a blank-less model.
+widths and cuts on Gaussian scores, and the Model-level compute_scores / basecall on a blank-less model.  Every state length, the
+tile edges, ties and the branches these scores never take (the one-merge-at-a-time path among them): tests/test_gpu_beam.py on
+the cases of tests/beam_cases.py.
 """
 import importlib
 import itertools
@@ -17,6 +18,7 @@ import numpy as np
 import pytest
 
 import oracle
+from beam_cases import _beam_py
 from conftest import make_config, random_scores
 
 FLT_MAX = float(np.finfo(np.float32).max)
@@ -30,59 +32,6 @@ def _scores(T, N, nb, sl, seed, gain=3.0):
 
 def _strings(plane):
     return [bytes(r[r != 0].astype(np.uint8)).decode() for r in plane]
-
-
-def _beam_py(M, beta, nb, sl, W, log_cut):
-    """float64 restatement of the search for one chunk; hypotheses are keyed by their state sequence (no hashes).
-    M (T, S, E) with the stay score in column 0; returns (score, path states (T,), moves (T,))."""
-    T, S, hi = M.shape[0], nb ** sl, nb ** (sl - 1)
-    thr = sorted(beta[0], reverse=True)[W] if W < S else -math.inf
-    front = [((s,), s, 0.0) for s in range(S) if beta[0][s] >= thr][:W]
-    hist = [[(s, 0, False) for (_, s, _) in front]]
-    for t in range(T):
-        cands = []
-        for p, (key, st, score) in enumerate(front):
-            for b in range(nb):
-                j, k = (st % hi) * nb + b, st // hi
-                cands.append([key + (j,), j, score + M[t, j, 1 + k] + beta[t + 1][j], p, False])
-        for p, (key, st, score) in enumerate(front):
-            cands.append([key, st, score + M[t, st, 0] + beta[t + 1][st], p, True])
-            si = len(cands) - 1
-            for q in range(len(front)):
-                ti = q * nb + st % nb
-                if cands[ti][0] == key:
-                    a, b = cands[si][2], cands[ti][2]
-                    f = max(a, b) + (math.log1p(math.exp(-abs(a - b))) if abs(a - b) < 17.0 else 0.0)
-                    if a > b:
-                        cands[si][2], cands[ti][2] = f, -FLT_MAX
-                    else:
-                        cands[ti][2], cands[si][2] = f, -FLT_MAX
-        mx = max(c[2] for c in cands)
-        cutoff = mx - log_cut
-        count = sum(c[2] >= cutoff for c in cands)
-        if count > W:
-            lo, hi_s, guesses = cutoff, mx, 1
-            while (count > W or count < (W * 8) // 10) and guesses < 10:
-                if count > W:
-                    lo, cutoff = cutoff, (cutoff + hi_s) / 2
-                else:
-                    hi_s, cutoff = cutoff, (cutoff + lo) / 2
-                count = sum(c[2] >= cutoff for c in cands)
-                guesses += 1
-            if guesses == 10:
-                cutoff = hi_s
-        kept = [c for c in cands if c[2] >= cutoff][:W]
-        if t == T - 1:
-            best = max(range(len(kept)), key=lambda i: (kept[i][2], -i))
-            kept[0], kept[best] = kept[best], kept[0]
-        hist.append([(c[1], c[3], c[4]) for c in kept])
-        front = [(c[0], c[1], c[2] - beta[t + 1][c[1]]) for c in kept]
-    path, moves, el = [0] * T, [0] * T, 0
-    for t in range(T, 0, -1):
-        st, prev, stay = hist[t][el]
-        path[t - 1], moves[t - 1], el = st, 0 if stay else 1, prev
-    moves[0] = 1
-    return front[0][2], path, moves
 
 
 @pytest.mark.parametrize("nb,sl,W,cut", [(4, 3, 32, 100.0), (6, 2, 8, 100.0), (5, 3, 32, 4.0), (4, 2, 5, 1e6), (6, 3, 32, 100.0)])
@@ -219,7 +168,8 @@ GPU_CASES = [
     (6, 3, 100, 3, 7, 3.0, False),
     (6, 2, 64, 2, 1, 100.0, True),
     (4, 2, 90, 3, 32, 100.0, False),          # 16 states: fewer states than beam elements
-    (5, 2, 150, 4, 32, 0.0, False),           # no cut: merged-away duplicates stay in the beam -> colliding hashes
+    (5, 2, 150, 4, 32, 0.0, False),           # no cut: merged-away duplicates stay in the beam (6880 merges, but with 5 bases no
+                                              # stay matches two steps and no two stays claim one: beam_cases.py's nocut-4 rows do)
     (6, 3, 120, 3, 32, 1e30, True),
 ]
 

@@ -73,6 +73,8 @@ def compute_scores(model, batch, beam_width=32, beam_cut=100.0, scale=1.0, offse
         if own is None or float(own) != float(blank_score):
             raise ValueError("beam search uses the model's fixed blank score (%r); blank_score=%r was asked for"
                              % (own, blank_score))
+        if 0.0 < beam_cut < 1.0:
+            raise ValueError("beam_cut %g inside (0, 1): no candidate can reach it" % beam_cut)
         if reverse:
             scores = model.seqdist.reverse_complement(model(batch))
             res = model.beam_search(scores, beam_width, beam_cut, scale, offset)

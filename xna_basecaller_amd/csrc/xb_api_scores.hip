@@ -398,6 +398,10 @@ int run_beam(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, in
     const xb_config &c = ctx->cfg;
     if (beam_width < 1 || beam_width > xb::BEAM_MAX_WIDTH)
         return fail(ctx, XB_ERR_INVALID, "beam_width %d outside [1, %d]", beam_width, xb::BEAM_MAX_WIDTH);
+    // log(beam_cut) < 0: the maximum itself is below max - log(beam_cut), the front would be empty and the trace-back read history
+    // that nobody wrote
+    if (beam_cut > 0.0f && beam_cut < 1.0f)
+        return fail(ctx, XB_ERR_INVALID, "beam_cut %g inside (0, 1): no candidate can reach it", (double)beam_cut);
     if (ctx->S > xb::BEAM_MAX_STATES) return fail(ctx, XB_ERR_INVALID, "beam search supports at most %d states", xb::BEAM_MAX_STATES);
     if (!alphabet || (int)strlen(alphabet) < c.n_base + 1) return fail(ctx, XB_ERR_INVALID, "alphabet needs %d symbols", c.n_base + 1);
     if (!ctx->beam_hist) {

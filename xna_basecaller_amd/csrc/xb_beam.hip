@@ -4,7 +4,8 @@
 // koi 0.0.5 is absent from the reference tree; the algorithm is the one ONT publishes for this decoder (back guide, CRC-32C
 // sequence hashes, stay / step merging, beam cut by bisection, k-mer posterior qualities), generalised to the n_base-ary state
 // table of crf/model.py:31-36.  Its specification is the header of the same section in oracle/xna_oracle.c; this kernel is
-// written independently against that specification and is checked bit for bit (tests/test_gpu_beam.py).  PARITY UNPINNED.
+// written independently against that specification and is checked bit for bit (tests/test_gpu_beam.py on the cases of
+// tests/beam_cases.py, whose branch coverage tests/test_beam_cases_host.py proves on the CPU; tests/test_beam.py).  PARITY UNPINNED.
 //
 // MI355X mapping: a beam of 32 elements and its 32 * (n_base + 1) candidates are less than one wave's worth of work and the
 // blocks of a chunk are strictly sequential, so a chunk is ONE wave (a 64-thread workgroup): no workgroup barriers on the
@@ -12,7 +13,7 @@
 // LDS.  512 chunks = 512 waves spread over all 256 CUs; the history (state, previous element, stay flag per block and element)
 // goes to HBM and is read back tile by tile for the trace-back.  A block's score row and back-guide row are fetched one block
 // ahead by LDS-DMA (global_load_lds, no staging registers) into a double buffer, so the per-candidate gathers are LDS reads and
-// the rows' HBM latency is off the block's dependency chain (PRE = false: direct gathers, for rows that do not fit in LDS).
+// the rows' HBM latency is off the block's dependency chain.  Both images always fit (launch_beam_search).
 // Floating-point contract as in xb_decode.hip (built with -ffp-contract=off).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -87,10 +88,9 @@ __device__ __forceinline__ void dma_to_lds(const float *g, float *lds_wave_base,
                                          (__attribute__((address_space(3))) void *)lds_wave_base, 4, 0, 0);
 }
 
-template <bool PRE>
 __global__ __launch_bounds__(64) void beam_kernel(xb::BeamParams p)
 {
-    extern __shared__ __attribute__((aligned(16))) float pre_smem[];      // PRE: [2][row image | back-guide image]
+    extern __shared__ __attribute__((aligned(16))) float pre_smem[];      // [2][row image | back-guide image]
     __shared__ uint32_t crc_tab[256];
     __shared__ uint32_t f_hash[BW], f_info[BW];
     __shared__ int f_state[BW];
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(64) void beam_kernel(xb::BeamParams p)
             if (j < S) dma_to_lds(bt + j, dst + i, p.beta_vec16 != 0);
         }
     };
-    if (PRE) prefetch(0, 0);
+    prefetch(0, 0);
 
     // ---- start: the states whose back guide is among the W best
     float thr = NEG_MAX;
@@ -192,17 +192,11 @@ __global__ __launch_bounds__(64) void beam_kernel(xb::BeamParams p)
     // ---- blocks
     float sc[4];
     for (int t = 0; t < T; ++t) {
-        const float *row, *b1;
-        if (PRE) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // block t's images have landed (requested a block ago)
-            wave_sync();
-            row = pre_smem + (size_t)(t & 1) * p.pre_stride;
-            b1 = row + p.beta_off;
-            if (t + 1 < T) prefetch(t + 1, (t + 1) & 1);
-        } else {
-            row = p.scores + ((size_t)t * N + n) * p.ld;
-            b1 = beta + (size_t)(t + 1) * sstride;
-        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // block t's images have landed (requested a block ago)
+        wave_sync();
+        const float *row = pre_smem + (size_t)(t & 1) * p.pre_stride;
+        const float *b1 = row + p.beta_off;
+        if (t + 1 < T) prefetch(t + 1, (t + 1) & 1);
         const int nstep = Wc * nb, nc = nstep + Wc;
         // every lane builds its (up to) four candidates level by level, so that the four chains of dependent LDS reads
         // (element -> state table -> score / back guide, and the four CRC table steps) are in flight together
@@ -461,7 +455,9 @@ hipError_t launch_beam_search(const BeamParams &p, hipStream_t stream)
     if (p.W < 1 || p.W > BEAM_MAX_WIDTH || p.S < 1 || p.S > BEAM_MAX_STATES || p.S > 65535 || p.nb < 2 || p.nb > 7 || p.T < 1 ||
         p.N < 1)
         return hipErrorInvalidValue;
-    // the double buffer of (score row, back-guide row) images; rows that do not fit are gathered from memory directly
+    // the double buffer of (score row, back-guide row) images.  The largest is 4 bases at state length 5 with the blank column:
+    // 2 * (1024 * 5 + 1024) floats = 48 KB, of the 96 KB the kernel's other LDS leaves to it -- BEAM_MAX_STATES would have to grow
+    // before a row failed to fit, and then this refuses rather than read past the images
     BeamParams q = p;
     const int cin = p.has_blank ? p.S * (p.nb + 1) : p.S * p.nb;
     q.row_vec16 = (p.ld % 4 == 0 && p.ld >= ((cin + 3) & ~3) && reinterpret_cast<uintptr_t>(p.scores) % 16 == 0) ? 1 : 0;
@@ -470,12 +466,9 @@ hipError_t launch_beam_search(const BeamParams &p, hipStream_t stream)
     q.beta_off = (q.row_floats + 3) & ~3;
     q.pre_stride = (q.beta_off + p.S + 3) & ~3;
     const size_t lds = sizeof(float) * 2 * (size_t)q.pre_stride;
-    if (lds <= 96 * 1024) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&beam_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(beam_kernel<true>, dim3(p.N), dim3(64), lds, stream, q);
-    } else {
-        hipLaunchKernelGGL(beam_kernel<false>, dim3(p.N), dim3(64), 0, stream, q);
-    }
+    if (lds > 96 * 1024) return hipErrorInvalidValue;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&beam_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(beam_kernel, dim3(p.N), dim3(64), lds, stream, q);
     return hipGetLastError();
 }
 
