@@ -1,11 +1,11 @@
 """The CTC lattice kernels at every width up to 2048 positions: the table of cases, their builders and the helpers the CTC
 tests share (no device; tests/test_ctc_wide_host.py is the CPU tier, tests/test_gpu_ctc_wide.py the GPU tier).
 
-ctc_scan_kernel (xb_decode.hip) and ctc_loss_kernel (xb_ctc.hip) put lattice position l on thread l % threads and keep up to 8
-positions per thread, slot k = l // threads.  A case is (nb, sl, np, T): np positions, a label row of Lt = np + sl - 1 labels,
-T time steps.  Position l is unreachable before step l, so a full-width case takes T = np + 1 .. np + 4 (the row's end cell is
-live in the last steps only, and T runs through all residues of the kernels' 4-deep prefetch ring).  Every case holds three
-chunks: the full row, a chunk of about half the positions that ends one past a multiple of 256 (a wide band of live cells in a
+ctc_scan_kernel and ctc_loss_kernel (xb_ctc.hip) put lattice position l on thread l % threads and keep up to 8 positions per
+thread, slot k = l // threads.  A case is (nb, sl, np, T): np positions, a label row of Lt = np + sl - 1 labels, T time steps.
+Position l is unreachable before step l, so a full-width case takes T = np + 1 .. np + 4 (the row's end cell is live in the last
+steps only, and T runs through all residues of the kernels' 4-deep prefetch ring).  Every case holds three chunks: the full row,
+a chunk of about half the positions (from 256 positions on it ends one past a multiple of 256: a wide band of live cells in a
 launch sized for the full row), and a chunk of exactly sl labels (one position)."""
 import collections
 
@@ -16,7 +16,7 @@ import oracle
 from conftest import random_scores
 
 BLANK = 2.0
-THREADS = 256                       # ctc_scan_kernel's workgroup: the slot of position l is l // THREADS
+THREADS = 256                       # the widest workgroup (every row above 128 positions): the slot of position l is l // THREADS
 PMAX = 8                            # positions per thread at most, in both kernels
 ZERO = np.float32(-1e38)            # seqdist's Log.zero / Max.zero
 
@@ -30,8 +30,8 @@ _LOSS_EXTRA = [(64, 3), (65, 4), (128, 1), (129, 2)]
 # the other geometries: six bases, the shortest and the longest state
 _GEOMETRY = [Case(6, 3, 1025, 1029), Case(5, 2, 513, 515), Case(4, 5, 513, 516)]
 
-SCAN_CASES = [Case(4, 3, n, n + d) for n, d in _SCAN_MAIN] + _GEOMETRY
-LOSS_CASES = [Case(4, 3, n, n + d) for n, d in _LOSS_EXTRA] + SCAN_CASES
+LOSS_CASES = [Case(4, 3, n, n + d) for n, d in _LOSS_EXTRA + _SCAN_MAIN] + _GEOMETRY
+SCAN_CASES = LOSS_CASES             # the scan follows the loss's launch rule: one table
 PROPERTY_POSITIONS = [257, 513, 1025, 2048]          # the single-path and the infeasible batches (nb 4, sl 3)
 F64_POSITIONS = [513, 1025, 2048]                    # the main-table rows the oracle is held against float64 at
 
@@ -142,8 +142,8 @@ def stay_sum(x, targets, b, nb, sl):
 
 
 def loss_launch(np_, override=None):
-    """launch_ctc_loss's arithmetic (xb_ctc.hip): (threads, the PMAX of the instantiation) for np positions under an
-    XB_CTC_LOSS_THREADS of `override`."""
+    """ctc_launch's arithmetic (xb_ctc_lattice.h) restated: (threads, the PMAX of the instantiation) for np positions under an
+    XB_CTC_LOSS_THREADS of `override` (the loss and gradient calls; the scans take the rule alone)."""
     threads = 64 if np_ <= 64 else (128 if np_ <= 128 else 256)
     if override in (64, 128, 256) and override * PMAX >= np_:
         threads = override

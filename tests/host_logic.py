@@ -1,5 +1,6 @@
 """ctypes view of libxnacall.so's non-public host-logic exports (xb_internal_*, csrc/xb_api.hip): the encoder's planner
-(csrc/xb_schedule.h), the weight packer (csrc/xb_pack.h) and the decoder of the device status words (csrc/xb_status.h).  None
+(csrc/xb_schedule.h), the weight packer (csrc/xb_pack.h), the decoder of the device status words (csrc/xb_status.h) and the
+CTC lattice kernels' column and launch rules (csrc/xb_ctc_lattice.h).  None
 of them touches the device or needs a context, so the tests that use this module run without a GPU."""
 import ctypes as C
 
@@ -58,6 +59,9 @@ def lib():
         so.xb_internal_i8_limbs.argtypes = [vp, ip, ip, vp, vp, vp]
         so.xb_internal_i8_limbs.restype = None
         so.xb_internal_decode_status.argtypes = [C.c_uint, C.c_uint, C.POINTER(C.c_char_p)]
+        so.xb_internal_ctc_columns.argtypes = [vp, ip, ip, ip, ip, ip, vp, vp, vp]
+        so.xb_internal_ctc_columns.restype = None
+        so.xb_internal_ctc_launch.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(C.c_size_t)]
         _cached = so
     return _cached
 
@@ -105,6 +109,23 @@ def decode_status(sync_word, data_word):
     msg = C.c_char_p()
     code = lib().xb_internal_decode_status(sync_word, data_word, C.byref(msg))
     return code, (msg.value.decode() if msg.value is not None else None)
+
+
+def ctc_columns(labels, nb, sl, has_blank=True):
+    """The lattice kernels' column rule (csrc/xb_ctc_lattice.h) over label rows (n, Lt): (stay, move, post), each (n, Lt - sl + 1)
+    int32; cell l is position l's stay column, the move column into it and that column in the posteriors' layout."""
+    labels = np.ascontiguousarray(labels, dtype=np.uint8)
+    n, Lt = labels.shape
+    out = [np.full((n, Lt - sl + 1), -1, np.int32) for _ in range(3)]
+    lib().xb_internal_ctc_columns(labels.ctypes.data, n, Lt, nb, sl, int(has_blank), *[o.ctypes.data for o in out])
+    return tuple(out)
+
+
+def ctc_launch(positions, override=None, chains=False):
+    """The lattice kernels' launch (csrc/xb_ctc_lattice.h) for rows of `positions` positions: (threads, PMAX, LDS bytes)."""
+    threads, lds = C.c_int(), C.c_size_t()
+    pmax = lib().xb_internal_ctc_launch(positions, 0 if override is None else override, int(chains), C.byref(threads), C.byref(lds))
+    return threads.value, pmax, lds.value
 
 
 def _f32(a):

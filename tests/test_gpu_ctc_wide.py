@@ -1,10 +1,11 @@
 """GPU: the CTC lattice kernels at every width up to 2048 positions (the table is tests/ctc_wide_cases.py; its CPU tier,
 tests/test_ctc_wide_host.py, says what the reference is worth there).
 
-ctc_scan_kernel (xb_ctc_logz, xb_ctc_alignments) and ctc_loss_kernel (xb_ctc_loss, xb_validate_chunks) put position l on thread
-l % threads, slot l // threads, up to 8 slots.  Every slot holds a live position somewhere in the table, both sides of
-64 / 65, 128 / 129, 256 / 257, 512 / 513 and 1024 / 1025 occur, and 2048 is the limit; ctc_loss_kernel<1>, <2>, <4> and <8> each
-run in both score layouts, by the rule ctc_loss_threads and under XB_CTC_LOSS_THREADS.  The contract is bit-equality: with
+ctc_scan_kernel (xb_ctc_logz, xb_ctc_alignments) and ctc_loss_kernel (xb_ctc_loss, xb_validate_chunks), both in xb_ctc.hip on
+one pair of sweeps, put position l on thread l % threads, slot l // threads, up to 8 slots.  Every slot holds a live position
+somewhere in the table, both sides of 64 / 65, 128 / 129, 256 / 257, 512 / 513 and 1024 / 1025 occur, and 2048 is the limit;
+the PMAX 1, 2, 4 and 8 instantiations of both run by the rule ctc_loss_threads, ctc_loss_kernel's in both score layouts and
+under XB_CTC_LOSS_THREADS too.  The contract is bit-equality: with
 oracle.ctc_logz for the scans, with the host composition (xb_crf_logz, `scores - logz / T`, oracle.ctc_logz, `-(logz / length)`)
 for the loss, and, without any oracle, with the float32 running sum of a single path's scores and with Log.zero for a row that
 has no path."""
@@ -28,22 +29,23 @@ def _context(nb, sl, T, N):
     return ctx
 
 
-def _same(what, got, ref, lens, sl):
+def _same(what, got, ref, lens, sl, np_):
     """Bit-equality of a per-chunk vector (N,) or a per-cell array (T, N, positions); the message names the chunk, the first
-    differing position and its slot."""
+    differing position and its slot in the launch a row of np_ positions gets by the rule."""
     assert got.shape == ref.shape and got.dtype == ref.dtype, (what, got.shape, ref.shape)
     if np.array_equal(got, ref):
         return
+    threads = W.loss_launch(np_)[0]
     if got.ndim == 1:
         b = int(np.flatnonzero(got != ref)[0])
         l = int(lens[b]) - sl
-        pytest.fail("%s: chunk %d (end position %d, slot %d): %r, reference %r" % (what, b, l, l // W.THREADS, got[b], ref[b]))
+        pytest.fail("%s: chunk %d (end position %d, slot %d): %r, reference %r" % (what, b, l, l // threads, got[b], ref[b]))
     bad = np.argwhere(got != ref)
     b = int(bad[:, 1].min())
     l = int(bad[bad[:, 1] == b][:, 2].min())
     t = int(bad[(bad[:, 1] == b) & (bad[:, 2] == l)][:, 0].min())
     pytest.fail("%s: chunk %d, first differing position %d (slot %d), first at step %d: %r, reference %r; %d cells differ, in slots %s"
-                % (what, b, l, l // W.THREADS, t, got[t, b, l], ref[t, b, l], len(bad), sorted(set((bad[:, 2] // W.THREADS).tolist()))))
+                % (what, b, l, l // threads, t, got[t, b, l], ref[t, b, l], len(bad), sorted(set((bad[:, 2] // threads).tolist()))))
 
 
 def _main_case(np_):
@@ -57,16 +59,16 @@ def test_scans_are_the_oracles_bit_for_bit(c):
     ctx = _context(c.nb, c.sl, c.T, 3)
     ref = oracle.ctc_logz(sc, targets, lens, c.nb, c.sl, want_grads=True)
     got = ctx.ctc_logz(sc, targets, lens, want_grads=True)
-    _same("logz", got["logz"], ref["logz"], lens, c.sl)
-    _same("stay", got["stay"], ref["stay"], lens, c.sl)
-    _same("move", got["move"], ref["move"], lens, c.sl)
+    _same("logz", got["logz"], ref["logz"], lens, c.sl, c.np)
+    _same("stay", got["stay"], ref["stay"], lens, c.sl, c.np)
+    _same("move", got["move"], ref["move"], lens, c.sl, c.np)
     del got
-    _same("logz of the forward sweep alone", ctx.ctc_logz(sc, targets, lens)["logz"], ref["logz"], lens, c.sl)
+    _same("logz of the forward sweep alone", ctx.ctc_logz(sc, targets, lens)["logz"], ref["logz"], lens, c.sl, c.np)
     del ref
     refm = oracle.ctc_logz(sc, targets, lens, c.nb, c.sl, semiring="max", want_grads=True)
     al, best = ctx.ctc_alignments(sc, targets, lens)
-    _same("best score", best, refm["logz"], lens, c.sl)
-    _same("alignment", al, refm["stay"], lens, c.sl)
+    _same("best score", best, refm["logz"], lens, c.sl, c.np)
+    _same("alignment", al, refm["stay"], lens, c.sl, c.np)
     ctx.close()
 
 
@@ -78,22 +80,22 @@ def test_scan_of_a_single_path_and_of_no_path(np_):
     sc, targets, lens = W.build_single_path(np_)
     ctx = _context(NB, SL, np_ - 1, 2)
     want = np.array([W.diagonal_sum(sc, targets, 0, NB, SL, np_ - 1), W.stay_sum(sc, targets, 1, NB, SL)], np.float32)
-    _same("single path, logz", ctx.ctc_logz(sc, targets, lens)["logz"], want, lens, SL)
-    _same("single path, logz beside the gradients", ctx.ctc_logz(sc, targets, lens, want_grads=True)["logz"], want, lens, SL)
+    _same("single path, logz", ctx.ctc_logz(sc, targets, lens)["logz"], want, lens, SL, np_)
+    _same("single path, logz beside the gradients", ctx.ctc_logz(sc, targets, lens, want_grads=True)["logz"], want, lens, SL, np_)
     al, best = ctx.ctc_alignments(sc, targets, lens)
-    _same("single path, best score", best, want, lens, SL)
+    _same("single path, best score", best, want, lens, SL, np_)
     diagonal = np.zeros((np_ - 1, 2, np_), np.float32)
     diagonal[np.arange(np_ - 1), 0, np.arange(np_ - 1)] = 1.0
     diagonal[:, 1, 0] = 1.0
-    _same("single path, alignment", al, diagonal, lens, SL)
+    _same("single path, alignment", al, diagonal, lens, SL, np_)
 
     sc, targets, lens = W.build_infeasible(np_)
     want = np.array([W.ZERO, W.diagonal_sum(sc, targets, 1, NB, SL, np_ - 2)], np.float32)
     assert want[1] > -1e30
-    _same("no path, logz", ctx.ctc_logz(sc, targets, lens)["logz"], want, lens, SL)
+    _same("no path, logz", ctx.ctc_logz(sc, targets, lens)["logz"], want, lens, SL, np_)
     al, best = ctx.ctc_alignments(sc, targets, lens)
-    _same("no path, best score", best, want, lens, SL)
-    _same("no path, the neighbour's alignment", al[:, 1:, :], diagonal[:np_ - 2, :1, :], lens[1:], SL)
+    _same("no path, best score", best, want, lens, SL, np_)
+    _same("no path, the neighbour's alignment", al[:, 1:, :], diagonal[:np_ - 2, :1, :], lens[1:], SL, np_)
     ctx.close()
 
 
@@ -116,8 +118,8 @@ def test_loss_is_the_host_composition_bit_for_bit(c):
         assert np.all(ref_logz > -1e30)
         loss, logz = ctx.ctc_loss(sc, targets, lens, has_blank=hb, want_logz=True)
         print("%s <%d threads, PMAX %d>: max |loss - ref| = %g" % ((what,) + W.loss_launch(c.np) + (np.abs(loss - ref).max(),)))
-        _same(what + ", logz", logz, ref_logz, lens, c.sl)
-        _same(what + ", loss", loss, ref, lens, c.sl)
+        _same(what + ", logz", logz, ref_logz, lens, c.sl, c.np)
+        _same(what + ", loss", loss, ref, lens, c.sl, c.np)
         # the one-position chunk without the oracle: the running sum of its stay scores, blank-less T additions of `blank - c`
         x, cn = W.normalised(ctx, sc, c.nb, hb)
         assert logz[2] == W.stay_sum(x, targets, 2, c.nb, c.sl)
@@ -145,8 +147,8 @@ def test_loss_threads_override_returns_the_same_bits(monkeypatch, np_, value, th
         monkeypatch.setenv("XB_CTC_LOSS_THREADS", str(value))        # the library reads it on every call
         loss1, logz1 = ctx.ctc_loss(sc, targets, lens, has_blank=hb, want_logz=True)
         what = "%s, %d threads" % ("with blank" if hb else "blank-less", value)
-        _same(what + ", logz", logz1, logz0, lens, c.sl)
-        _same(what + ", loss", loss1, loss0, lens, c.sl)
+        _same(what + ", logz", logz1, logz0, lens, c.sl, c.np)
+        _same(what + ", loss", loss1, loss0, lens, c.sl, c.np)
     ctx.close()
 
 
@@ -163,16 +165,16 @@ def test_loss_of_a_single_path_and_of_no_path(np_):
         if not hb:
             assert want[1] == W.running_sum(np.full(np_ - 1, np.float32(W.BLANK) - cn[1], np.float32))
         loss, logz = ctx.ctc_loss(sc, targets.astype(np.uint8), lens, has_blank=hb, want_logz=True)
-        _same(what + ", single path, logz", logz, want, lens, SL)
-        _same(what + ", single path, loss", loss, -(want / lens.astype(np.float32)), lens, SL)
+        _same(what + ", single path, logz", logz, want, lens, SL, np_)
+        _same(what + ", single path, loss", loss, -(want / lens.astype(np.float32)), lens, SL, np_)
 
         sc, targets, lens = W.build_infeasible(np_, with_blank=hb)
         x, cn = W.normalised(ctx, sc, NB, hb)
         want = np.array([W.ZERO, W.diagonal_sum(x, targets, 1, NB, SL, np_ - 2)], np.float32)
         assert want[1] > -1e30
         loss, logz = ctx.ctc_loss(sc, targets.astype(np.uint8), lens, has_blank=hb, want_logz=True)
-        _same(what + ", no path, logz", logz, want, lens, SL)
-        _same(what + ", no path, loss", loss, -(want / lens.astype(np.float32)), lens, SL)
+        _same(what + ", no path, logz", logz, want, lens, SL, np_)
+        _same(what + ", no path, loss", loss, -(want / lens.astype(np.float32)), lens, SL, np_)
         assert loss[0] == -(W.ZERO / np.float32(np_ + SL - 1))
     ctx.close()
 
@@ -182,7 +184,7 @@ def test_device_form_at_2048_positions_validates_on_the_device():
     kernel's own label check strides over the row, so a bad label at an index a thread reaches in its fifth round and later must
     still be seen, and one beyond the chunk's length must not."""
     c = _main_case(2048)
-    N, Lt = 3, c.np + SL - 1
+    N, Lt, np_ = 3, c.np + SL - 1, c.np
     assert Lt == 2050
     ctx = _context(NB, SL, c.T, N)
     nbl, targets, lens = W.build(c, with_blank=False)
@@ -201,15 +203,15 @@ def test_device_form_at_2048_positions_validates_on_the_device():
 
     def correct_call_matches():
         run(d_t, d_l)
-        _same("device form, logz", d_logz.cpu().numpy(), ref_logz, lens, SL)
-        _same("device form, loss", d_loss.cpu().numpy(), ref, lens, SL)
+        _same("device form, logz", d_logz.cpu().numpy(), ref_logz, lens, SL, np_)
+        _same("device form, loss", d_loss.cpu().numpy(), ref, lens, SL, np_)
 
     correct_call_matches()
     assert lens[1] < 1500 < lens[0]
     beyond = targets.copy()
     beyond[1, 1500] = beyond[1, Lt - 1] = beyond[2, 1024] = NB + 1          # beyond these chunks' lengths: not read
     run(torch.from_numpy(beyond).to(dev), d_l)
-    _same("labels beyond the length, loss", d_loss.cpu().numpy(), ref, lens, SL)
+    _same("labels beyond the length, loss", d_loss.cpu().numpy(), ref, lens, SL, np_)
 
     def with_label(i):
         t = targets.copy()
@@ -239,7 +241,7 @@ def test_device_form_at_2048_positions_validates_on_the_device():
 def test_validate_chunks_with_a_2050_wide_row():
     """xb_validate_chunks where the label row is as wide as the API takes it: the loss is xb_ctc_loss of the encoder's own
     blank-less scores, the calls are xb_basecall_chunks' (what tests/test_gpu_valloss.py asserts at 12 labels)."""
-    F, L, N, Lt = 32, 10250, 2, 2050
+    F, L, N, Lt, np_ = 32, 10250, 2, 2050, 2048
     alphabet = "NACGT"
     ctx = _lib.Context(0, NB, SL, F, 19, 5, 5.0, W.BLANK, L, N)
     assert ctx.T == Lt
@@ -253,5 +255,5 @@ def test_validate_chunks_with_a_2050_wide_row():
     assert np.all(want_logz > -1e30)                         # T = 2050 steps reach position 2047
     seq, slen, loss = ctx.validate_chunks(x, alphabet, targets, lens)
     assert np.array_equal(seq, want_seq) and np.array_equal(slen, want_lens)
-    _same("loss", loss, want, lens, SL)
+    _same("loss", loss, want, lens, SL, np_)
     ctx.close()

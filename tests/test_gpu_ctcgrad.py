@@ -4,7 +4,8 @@ The contract is bit-equality (np.array_equal) of loss and gradient with the nump
 tests/test_ctcgrad_host.py establishes on the CPU -- in the host form and the _dev form, in both score layouts, and with the
 host composition the device call replaces (model.seqdist.ctc_loss(numpy scores, want_grad=True)).  The shapes: tests/test_ctc.py's
 GPU_CASES, a batch of one on a larger context, label rows built to collide (positions that share a score column must add up in
-ascending position, the same bytes on every run), 2048 positions, clipping, a stash bound that forces several launches, two calls
+ascending position, the same bytes on every run), the first width of every instantiation and both sides of every step of the
+thread rule, 2048 positions, clipping, a stash bound that forces several launches, two calls
 in a row, the refusals, and the torch.autograd surface.  A chunk without a path (T < length - state_len: the header's
 precondition, unspecified values) is left out of the comparison; GPU_CASES' 5-90-4-300 holds such chunks."""
 import numpy as np
@@ -14,7 +15,7 @@ import torch.nn.functional as F
 
 import ctcgrad_ref as G
 from conftest import make_config, random_scores
-from ctc_wide_cases import BLANK, label_rows
+from ctc_wide_cases import BLANK, half_positions, label_rows
 from test_ctc import GPU_CASES
 from xna_basecaller_amd import _lib
 
@@ -136,6 +137,20 @@ def test_colliding_label_rows(nb):
                     _same("the host route's loss", value, ref[0], ok)
                 else:
                     assert abs(float(value) - float(ref[0].mean(dtype=np.float32))) < 1e-6
+
+
+@pytest.mark.parametrize("npos", [64, 65, 128, 129, 257, 513, 1025])
+def test_every_instantiation_and_thread_count_boundary(npos):
+    """ctc_grad_kernel<1> at 64 threads, <2> at 64 -> 128, <1> -> <2> at 128 -> 256 threads, and the first row of <2>, <4> and <8>
+    at 256: the full row beside a chunk of about half its positions, both with a path (T = positions + 2)."""
+    nb, sl, N = 4, 3, 2
+    T, Lt = npos + 2, npos + sl - 1
+    targets, lens = label_rows(np.random.default_rng(npos), N, Lt, nb, sl, lens=[Lt, half_positions(npos) + sl - 1], dtype=np.uint8)
+    assert G.has_path(T, lens, sl).all()
+    ctx = _context(nb, sl, T, N)
+    for hb in (True, False):
+        _check(ctx, _scores(T, N, nb, sl, hb, npos), targets, lens, nb, sl, hb)
+    ctx.close()
 
 
 def test_2048_positions():

@@ -466,7 +466,7 @@ extern "C" __attribute__((visibility("default"))) int xb_internal_defer_after(xb
 }
 
 // The host logic on its own, for the CPU tests (tests/host_logic.py): the planner and the knobs of xb_schedule.h, the packer
-// of xb_pack.h, the decoder of xb_status.h.  None touches the device or needs a context.  Not part of the public header.
+// of xb_pack.h, the decoder of xb_status.h, the lattice rules of xb_ctc_lattice.h.  None touches the device or needs a context.  Not part of the public header.
 #define XB_INTERNAL extern "C" __attribute__((visibility("default")))
 XB_INTERNAL void xb_internal_knobs_from_env(xb::Knobs *out) { *out = xb::knobs_from_env(); }
 XB_INTERNAL int xb_internal_pair_capacity(int F, int cu_count, int lstm_wide) { return xb::pair_capacity(F, cu_count, lstm_wide); }
@@ -526,6 +526,28 @@ XB_INTERNAL void xb_internal_i8_limbs(const float *w, int rows, int cols, int8_t
     memcpy(d1, a.data(), a.size());
     memcpy(d0, b.data(), b.size());
     memcpy(scale, c.data(), c.size() * sizeof(float));
+}
+// the lattice kernels' column rule over n label rows of Lt labels: stay, move, post: (n, Lt - sl + 1), cell l = position l's
+// stay column, the move column into it and that column in the posteriors' layout
+XB_INTERNAL void xb_internal_ctc_columns(const uint8_t *labels, int n, int Lt, int nb, int sl, int has_blank, int32_t *stay, int32_t *move,
+                                         int32_t *post)
+{
+    const int np = Lt - (sl - 1);
+    for (int b = 0; b < n; ++b)
+        for (int l = 0; l < np; ++l) {
+            int cs, cm, cp;
+            if (has_blank) xb::ctc_columns<true>(labels + (size_t)b * Lt, l, nb, sl, cs, cm, cp);
+            else xb::ctc_columns<false>(labels + (size_t)b * Lt, l, nb, sl, cs, cm, cp);
+            stay[(size_t)b * np + l] = cs; move[(size_t)b * np + l] = cm; post[(size_t)b * np + l] = cp;
+        }
+}
+// -> the PMAX instantiation (0: refused); *threads, *lds_bytes: the rest of xb::ctc_launch
+XB_INTERNAL int xb_internal_ctc_launch(int positions, int threads_override, int chains, int *threads, size_t *lds_bytes)
+{
+    const xb::CtcLaunch L = xb::ctc_launch(positions, threads_override, chains != 0);
+    if (threads) *threads = L.threads;
+    if (lds_bytes) *lds_bytes = L.lds;
+    return L.pmax;
 }
 #undef XB_INTERNAL
 

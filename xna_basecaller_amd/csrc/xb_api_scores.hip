@@ -119,25 +119,38 @@ int copy_planes(xb_ctx *ctx, int level, const Planes &dst, const Planes &src, in
     return XB_OK;
 }
 
+// what the loss and its gradient tell the lattice kernels alike: the scores, the labels, logZ_crf where the Log forward scan of
+// run_decode leaves it, and the experiments' workgroup size
+static xb::CtcLossParams ctc_loss_params(xb_ctx *ctx, const float *d_scores, int T, int n, int has_blank, int ld,
+                                         const uint8_t *d_targets, int Lt, const int32_t *d_len, float *d_loss, float *d_logz)
+{
+    const xb_config &c = ctx->cfg;
+    xb::CtcLossParams p{};
+    p.scores = d_scores; p.T = T; p.N = n; p.ld = ld; p.has_blank = has_blank; p.blank = c.blank_score;
+    p.nb = c.n_base; p.sl = c.state_len; p.targets = d_targets; p.Lt = Lt; p.tlen = d_len;
+    p.logz_crf = ctx->logz; p.loss = d_loss; p.logz = d_logz; p.error = ctx->error_data;
+    if (const char *e = getenv("XB_CTC_LOSS_THREADS")) p.threads = atoi(e);
+    return p;
+}
+
+static int ctc_launched(xb_ctx *ctx, const char *who, hipError_t e)
+{
+    if (e == hipSuccess) return XB_OK;
+    return fail(ctx, e == hipErrorInvalidValue ? XB_ERR_INVALID : XB_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+}
+
 // The validation loss of n chunks from device-resident RAW scores (T, n, ld), for xb_ctc_loss and xb_validate_chunks: the Log
 // forward scan leaves logZ_crf in the decode's own (max_batch) buffer, the CTC forward scan of the labels reads it there.  Two
 // launches on the main stream, nothing waited for; the callers have checked n, T, the pointers and the width (label_batch_check).
 int ctc_loss_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int n, int has_blank, int ld, const uint8_t *d_targets,
                  int Lt, const int32_t *d_len, float *d_loss, float *d_logz)
 {
-    const xb_config &c = ctx->cfg;
     ScanOut so;
     so.logz = ctx->logz;
     if (int rc = run_decode(ctx, d_scores, T, n, has_blank, ld, nullptr, nullptr, nullptr, nullptr, nullptr, &so)) return rc;
-    xb::CtcLossParams p{};
-    p.scores = d_scores; p.T = T; p.N = n; p.ld = ld; p.has_blank = has_blank; p.blank = c.blank_score;
-    p.nb = c.n_base; p.sl = c.state_len; p.targets = d_targets; p.Lt = Lt; p.tlen = d_len;
-    p.logz_crf = ctx->logz; p.loss = d_loss; p.logz = d_logz; p.error = ctx->error_data;
-    if (const char *e = getenv("XB_CTC_LOSS_THREADS")) p.threads = atoi(e);
+    const xb::CtcLossParams p = ctc_loss_params(ctx, d_scores, T, n, has_blank, ld, d_targets, Lt, d_len, d_loss, d_logz);
     StageScope sc(ctx, XB_STAGE_DECODE, 1);
-    hipError_t e = xb::launch_ctc_loss(p, ctx->stream);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorInvalidValue ? XB_ERR_INVALID : XB_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
-    return XB_OK;
+    return ctc_launched(ctx, who, xb::launch_ctc_loss(p, ctx->stream));
 }
 
 // The loss and d loss / d scores of n chunks from device-resident RAW scores (T, n, ld), for xb_ctc_loss_grad and the trainers'
@@ -157,11 +170,7 @@ int ctc_grad_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int
     so.logz = ctx->logz; so.post = ctx->qbuf;
     if (int rc = run_decode(ctx, d_scores, T, n, has_blank, ld, nullptr, nullptr, nullptr, nullptr, nullptr, &so)) return rc;
     xb::CtcGradParams q{};
-    xb::CtcLossParams &p = q.l;
-    p.scores = d_scores; p.T = T; p.N = n; p.ld = ld; p.has_blank = has_blank; p.blank = c.blank_score;
-    p.nb = c.n_base; p.sl = c.state_len; p.targets = d_targets; p.Lt = Lt; p.tlen = d_len;
-    p.logz_crf = ctx->logz; p.loss = d_loss; p.error = ctx->error_data;
-    if (const char *e = getenv("XB_CTC_LOSS_THREADS")) p.threads = atoi(e);
+    q.l = ctc_loss_params(ctx, d_scores, T, n, has_blank, ld, d_targets, Lt, d_len, d_loss, nullptr);
     q.post = ctx->qbuf; q.ldq = (ctx->S * (c.n_base + 1) + 3) & ~3;
     q.stash = static_cast<float *>(ctx->ctcgrad.stash.p); q.slot = slot;
     q.loss_clip = loss_clip; q.mean = mean ? 1 : 0;
@@ -169,12 +178,9 @@ int ctc_grad_run(xb_ctx *ctx, const char *who, const float *d_scores, int T, int
     for (size_t first = 0; first < (size_t)n; first += per_launch) {
         q.first = (int)first;
         q.count = (int)std::min<size_t>(per_launch, (size_t)n - first);
-        hipError_t e = xb::launch_ctc_grad(q, ctx->stream);
-        if (e != hipSuccess) return fail(ctx, e == hipErrorInvalidValue ? XB_ERR_INVALID : XB_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+        if (int rc = ctc_launched(ctx, who, xb::launch_ctc_grad(q, ctx->stream))) return rc;
     }
-    hipError_t e = xb::launch_ctc_grad_fill(q, ctx->stream);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorInvalidValue ? XB_ERR_INVALID : XB_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
-    return XB_OK;
+    return ctc_launched(ctx, who, xb::launch_ctc_grad_fill(q, ctx->stream));
 }
 
 // the device-pointer decodes: labels (level 0 only), the bases and the outputs of o's level, on the main stream
@@ -304,26 +310,6 @@ XB_API int xb_crf_logz(xb_ctx *ctx, const float *scores, int T, int n, int has_b
     return xb_crf_scans(ctx, scores, T, n, has_blank, nullptr, nullptr, logz, nullptr);
 }
 
-// prepare_ctc_scores' gather columns (crf/model.py:102-116) for n targets of Lt labels: np = Lt - (sl - 1) positions
-static void ctc_indices(const int32_t *targets, int n, int Lt, int nb, int sl, std::vector<int32_t> &stay, std::vector<int32_t> &move)
-{
-    const int np = Lt - (sl - 1), E = nb + 1;
-    stay.assign((size_t)n * np, 0);
-    move.assign((size_t)n * (np > 1 ? np - 1 : 1), 0);
-    for (int b = 0; b < n; ++b) {
-        for (int l = 0; l < np; ++l) {
-            int64_t st = 0;
-            for (int i = 0; i < sl; ++i) {
-                const int v = std::max(targets[(size_t)b * Lt + l + i] - 1, 0);        // torch.clamp(targets - 1, 0)
-                st += (int64_t)v * ipow(nb, sl - i - 1);
-            }
-            stay[(size_t)b * np + l] = (int32_t)(st * E);
-        }
-        for (int l = 0; l + 1 < np; ++l)
-            move[(size_t)b * (np - 1) + l] = stay[(size_t)b * np + l + 1] + std::max(targets[(size_t)b * Lt + l] - 1, 0) + 1;
-    }
-}
-
 static int run_ctc(xb_ctx *ctx, const float *scores, int T, int n, const int32_t *targets, int Lt, const int32_t *tlen,
                    int semiring, float *logz, float *gstay, float *gmove)
 {
@@ -343,14 +329,12 @@ static int run_ctc(xb_ctx *ctx, const float *scores, int T, int n, const int32_t
                 return fail(ctx, XB_ERR_INVALID, "targets[%d][%d] = %d outside [0, n_base = %d]", b, l, targets[(size_t)b * Lt + l], nb);
     }
     if (int rcj = enter(ctx, true)) return rcj;             // (a host form that has always named the main stream)
-    std::vector<int32_t> stay, move;
-    ctc_indices(targets, n, Lt, nb, sl, stay, move);
+    const std::vector<uint8_t> labels(targets, targets + (size_t)n * Lt);      // the kernels' label type; every value is in [0, nb]
     const size_t nm = np > 1 ? np - 1 : 1;
     // per-call device scratch (a training-side operator: sizes follow the targets, not the context), freed on every return
-    DevBuf b_stay, b_move, b_len, b_alpha, b_gs, b_gm;
+    DevBuf b_lab, b_len, b_alpha, b_gs, b_gm;
     const bool grads = gstay || gmove;
-    if (int rc = b_stay.alloc(ctx, sizeof(int32_t) * stay.size())) return rc;
-    if (int rc = b_move.alloc(ctx, sizeof(int32_t) * move.size())) return rc;
+    if (int rc = b_lab.alloc(ctx, labels.size())) return rc;
     if (int rc = b_len.alloc(ctx, sizeof(int32_t) * (size_t)n)) return rc;
     if (grads) {
         if (int rc = b_alpha.alloc(ctx, sizeof(float) * (size_t)n * (T + 1) * np)) return rc;
@@ -358,17 +342,17 @@ static int run_ctc(xb_ctx *ctx, const float *scores, int T, int n, const int32_t
         if (gmove)
             if (int rc = b_gm.alloc(ctx, sizeof(float) * (size_t)T * n * nm)) return rc;
     }
-    int32_t *d_stay = static_cast<int32_t *>(b_stay.p), *d_move = static_cast<int32_t *>(b_move.p), *d_len = static_cast<int32_t *>(b_len.p);
+    uint8_t *d_lab = static_cast<uint8_t *>(b_lab.p);
+    int32_t *d_len = static_cast<int32_t *>(b_len.p);
     float *d_alpha = static_cast<float *>(b_alpha.p), *d_gs = static_cast<float *>(b_gs.p), *d_gm = static_cast<float *>(b_gm.p);
     hipStream_t st = ctx->stream;
-    XB_HIP(ctx, hipMemcpyAsync(d_stay, stay.data(), sizeof(int32_t) * stay.size(), hipMemcpyHostToDevice, st));
-    XB_HIP(ctx, hipMemcpyAsync(d_move, move.data(), sizeof(int32_t) * move.size(), hipMemcpyHostToDevice, st));
+    XB_HIP(ctx, hipMemcpyAsync(d_lab, labels.data(), labels.size(), hipMemcpyHostToDevice, st));
     XB_HIP(ctx, hipMemcpyAsync(d_len, tlen, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
     if (int rc = stage_scores(ctx, scores, T, n, C)) return rc;
     if (d_gs) XB_HIP(ctx, hipMemsetAsync(d_gs, 0, sizeof(float) * (size_t)T * n * np, st));
     if (d_gm) XB_HIP(ctx, hipMemsetAsync(d_gm, 0, sizeof(float) * (size_t)T * n * nm, st));
     xb::CtcParams p{};
-    p.scores = ctx->scores; p.T = T; p.N = n; p.C = C; p.stay_idx = d_stay; p.move_idx = d_move; p.n = np; p.tlen = d_len;
+    p.scores = ctx->scores; p.T = T; p.N = n; p.C = C; p.targets = d_lab; p.Lt = Lt; p.nb = nb; p.tlen = d_len;
     p.sl = sl; p.semiring = semiring; p.alpha = d_alpha; p.logz = ctx->logz; p.gstay = d_gs; p.gmove = d_gm; p.error = ctx->error_data;
     XB_HIP(ctx, xb::launch_ctc_scan(p, st));
     if (logz) XB_HIP(ctx, hipMemcpyAsync(logz, ctx->logz, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, st));

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "xb_ctc_lattice.h"
 #include "xb_ctc_split.h"
 
 namespace xb {
@@ -41,31 +42,27 @@ struct DecodeParams {
 hipError_t launch_crf_decode(const DecodeParams &p, hipStream_t stream);
 int decode_lanes_per_state(int S, int N);   // 1, 2 or 4 lanes serve one CRF state (env XB_DECODE_LPS overrides for tests)
 
-// ---------------------------------------------------------------- CTC-CRF loss scans (xb_decode.hip)
-// seqdist.ctc_simple logZ over the stay / move lattice of the targets (crf/model.py:102-135): position l of n = Lt - sl + 1,
-// stay[t][l] = scores[t][b][stay_idx[b][l]], move[t][l] = scores[t][b][move_idx[b][l]] (l -> l + 1).
+// ---------------------------------------------------------------- the CTC lattice (xb_ctc.hip; its pure rules: xb_ctc_lattice.h)
+// CTC-CRF loss scans: seqdist.ctc_simple logZ over the stay / move lattice of the targets (crf/model.py:102-135) on scores as
+// they are given.  Position l of Lt - sl + 1 reads the columns ctc_columns<true> derives from the labels.
 struct CtcParams {
     const float *scores;         // (T, N, C) fp32 with the blank column
     int T, N, C;
-    const int32_t *stay_idx;     // (N, n)
-    const int32_t *move_idx;     // (N, n - 1)
-    int n;
+    const uint8_t *targets;      // (N, Lt) CTC labels 1 .. nb (0 reads as base 0), checked by the caller
+    int Lt, nb, sl;
     const int32_t *tlen;         // (N) target lengths (in bases); positions in use = tlen + 1 - sl
-    int sl;
     int semiring;                // 0 Log, 1 Max
-    float *alpha;                // (N, T + 1, n) workspace, required for gstay / gmove
+    float *alpha;                // N slots of (T + 1) (Lt - sl + 1) floats, workspace, required for gstay / gmove
     float *logz;                 // (N) or nullptr
-    float *gstay;                // (T, N, n) or nullptr: Log: d logZ / d stay; Max: the one-hot alignment (zeroed by the caller)
+    float *gstay;                // (T, N, n) or nullptr, n = Lt - sl + 1: Log: d logZ / d stay; Max: the one-hot alignment (zeroed by the caller)
     float *gmove;                // (T, N, n - 1) or nullptr (Log only)
     unsigned *error;             // the context's data word: xb::DATA_SCAN_LENGTH (xb_status.h) ORed in when a target length is out of range
 };
 hipError_t launch_ctc_scan(const CtcParams &p, hipStream_t stream);
-int ctc_max_positions();
 
-// ---------------------------------------------------------------- CTC-CRF validation loss (xb_ctc.hip)
-// The forward Log scan of the same lattice on the encoder's own scores: RAW scores in either layout, the labels as
-// references.npy holds them; the gather columns and the normalisation (s - logz_crf / T) are the kernel's (the contract is in
-// the public header: xb_ctc_loss).
+// CTC-CRF validation loss: the forward Log sweep of the same lattice on the encoder's own scores.  RAW scores in either layout,
+// the labels as references.npy holds them; the normalisation (s - logz_crf / T) is the kernel's (the contract is in the public
+// header: xb_ctc_loss).
 struct CtcLossParams {
     const float *scores;         // (T, N, ld) fp32 RAW scores
     int T, N, ld, has_blank;
@@ -78,9 +75,8 @@ struct CtcLossParams {
     float *loss;                 // (N) -logz_ctc / tlen
     float *logz;                 // (N) or nullptr: logz_ctc
     unsigned *error;             // the context's data word: xb::DATA_LOSS_LABEL (xb_status.h) ORed in when a target length or a label inside it is out of range
-    int threads;                 // 0 = the rule ctc_loss_threads; 64, 128, 256 (experiments: XB_CTC_LOSS_THREADS)
+    int threads;                 // 0 = the rule ctc_loss_threads; 64, 128, 256 (experiments: XB_CTC_LOSS_THREADS): ctc_launch's override
 };
-int ctc_loss_threads(int positions);       // threads per chunk for a label row that gives `positions` lattice positions
 hipError_t launch_ctc_loss(const CtcLossParams &p, hipStream_t stream);
 
 // The loss with d loss / d scores (the contract is in the public header: xb_ctc_loss_grad).  launch_ctc_grad runs the lattice
